@@ -23,6 +23,13 @@ roofline : the dominant kernel (k_trace_pw) is bound by no bandwidth and no ALU:
            hbm_counter_frac (bytes that reach the fabric, PMC), ta_busy_frac, valu_issue_frac, wave_waiting_frac, active_lane_frac.
 cpu_baseline: the scalar oracle (oracle/, a port of the shader) timed on this host's cores on a bounded sample of the same frame;
 parity_check: those very rows rendered by the GPU and compared bit for bit (the oracle is the checker, never the product).
+
+A plain run sets up, warms up, times --steps steps and prints the result line (value, ms_per_step, config and the work counters
+of the timed steps). --full adds everything else: the device self-test, HIP events around the timed traversal launches and the
+roofline they feed, per_step_dispatch, cpu_baseline with parity_check, and in_flight_check.
+--dump-outputs DIR writes what the timed steps computed: the progressive fp32 frame after the last timed step, as a caller of
+rt_render_frames receives it (DIR/frame.npy, H x W x RGBA; above 64 MB a fixed, seeded sample of its pixels instead). The
+scene and the camera depend on the arguments alone, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -71,6 +78,12 @@ def main():
                          "traversal gets cheaper per ray the more paths share a dispatch (Sponza 1080p, ms per step with 1 / 2 / 4 / 10 / 20 "
                          "frames in one dispatch: 117 / 113.5 / 103.9 / 99.4 / 98.8). The steps of a run are split into equal groups of "
                          "at most that many. 1 = every step its own dispatch and its own gather")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: device self-test, roofline (HIP events in the timed region), per_step_dispatch, "
+                         "cpu_baseline with parity_check, in_flight_check; --no-profile, --per-step-dispatches, --cpu-seconds and "
+                         "--no-in-flight-check shape these and act with --full only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the timed steps computed (after the last timed step) to DIR/frame.npy, float32 H x W x RGBA")
     args = ap.parse_args()
 
     import numpy as np
@@ -83,7 +96,7 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
-    if not args.no_build:
+    if not args.no_build and not build_is_current(ge):
         ge.build()  # mtime check under a file lock: one rank compiles if anything is stale, the others wait for it
     from ray_tracer_amd import engine, scenes, tiling
 
@@ -110,7 +123,7 @@ def main():
     pc = cam(W, H, raysPerPixel=args.spp, progressive=1, singleRender=0)
 
     r = engine.Renderer(local)
-    if r.selftest() != 0x0F:
+    if args.full and r.selftest() != 0x0F:
         raise SystemExit("device deterministic-math self-test failed")
     for kv in filter(None, args.tune.split(",")):
         k, v = kv.split("=")
@@ -177,14 +190,18 @@ def main():
 
     run(0, args.warmup)
     r.reset_counters()
-    r.set_profiling(not args.no_profile)
+    profile = args.full and not args.no_profile
+    r.set_profiling(profile)
     fence()
     t0 = time.perf_counter()
     run(args.warmup, args.steps)
     fence()
     dt = time.perf_counter() - t0
-    trace_ms, trace_launches = r.trace_time_ms()
-    busy_ms = r.trace_busy_ms() if not args.no_profile else 0.0
+    if args.dump_outputs and rank == 0:
+        # what the timed steps computed, before anything below renders on into the same frame
+        dump_outputs(args.dump_outputs, (frame if multi else strip).to("cpu", copy=True).numpy())
+    trace_ms, trace_launches = r.trace_time_ms() if args.full else (0.0, 0)
+    busy_ms = r.trace_busy_ms() if profile else 0.0
     r.set_profiling(False)
     cnt = r.counters()
     timed_pipeline = r.last_pipeline()   # of the timed region (the legs below may run in the other one)
@@ -192,7 +209,7 @@ def main():
     # The same steps, one dispatch (and one gather) per step: what a host that presents every frame gets.
     per_step = None
     frames_rendered = args.warmup + args.steps   # progressive frames the image holds by now
-    if args.per_step_dispatches > 0:
+    if args.full and args.per_step_dispatches > 0:
         k2 = args.per_step_dispatches
         fif_saved, fif = fif, 1
         run(args.warmup + args.steps, 1)   # untimed: the first dispatch of another shape (allocations, pipeline choice)
@@ -255,84 +272,85 @@ def main():
         }
         if per_step:
             out["per_step_dispatch"] = per_step
-        # The kernel's roofline. `bound` names the unit the counters show busiest; achieved / peak / frac are the rate of that unit.
-        rf = {"kernel": tkern + ("" if tkern == "k_trace_pw" else " (traversal + shading in one kernel)"),
-              "bound": "vector-memory pipeline (16-byte gathers through the texture addresser and the L1 tags); latency- and divergence-limited: neither HBM nor MFMA nor VALU is near its peak",
-              "achieved": None, "peak": None, "unit": "GB/s", "frac": None, "traffic": None,
-              "achieved_is": "L1 look-ups per second x 16 B: look-ups per executed ray (PMC counters of the same binary) x executed rays / time with a traversal launch running (HIP events, live)",
-              "peak_is": "1.39 look-ups per clock and CU (tools/gather_bench.hip on this chip: a 64-lane dwordx4 gather costs the CU 46 clocks, L2-resident table) x 256 CUs x 2.4 GHz x 16 B",
-              "launches": sum_launches, "avg_launch_ms": avg_launch_ms,
-              "launch_overlap": sum_trace_ms / sum_busy_ms if sum_busy_ms > 0 else None,
-              "trace_busy_share_of_step": (sum_busy_ms / world) / (dt * 1e3) if sum_busy_ms > 0 else None,
-              "algorithmic_bytes_per_launch": alg_bytes / launches,
-              "algorithmic_gbps": alg_gbps, "algorithmic_frac": (alg_gbps / 8000.0) if alg_gbps else None,
-              "algorithmic_is": "SURVEY 8(d): 32 B per box test + 36 B per triangle test + 100 B per hit, counted by the kernel, per launch / average launch duration, against 8 TB/s of HBM. Mostly served by LDS / L1 / L2, so it can exceed 1: it says how much traversal work per second the kernel does, not how busy HBM is (hbm_counter_frac does). With the dispatch in parts on several streams the launches overlap (launch_overlap) and share the GPU, so a launch's duration is longer than the kernel would need alone"}
-        out["roofline"] = rf
-        # What the hardware counters say about the same kernel: separate rocprofv3 --pmc passes of this very command
-        # (tools/profile_round.sh -> profiles/), since PMC counters cannot be read from inside the process. The file is
-        # stamped with a hash of the kernel sources; a stamp that no longer matches the tree is flagged, not hidden.
-        cfile = os.path.join(ROOT, "profiles", f"counters_{tkern}_{args.scene}_{W}x{H}_{args.spp}spp.json")
-        if world == 1 and os.path.exists(cfile):
-            with open(cfile) as f:
-                pm = json.load(f)
-            rf["counters_source"] = os.path.relpath(cfile, ROOT)
-            rf["counters_stale"] = pm.get("source_sha") != kernel_source_sha()
-            rf["traffic"] = pm.get("traffic_bytes_per_launch")
-            if rf["traffic"] and pm.get("kernel_ms_under_profiler"):
-                # both from the profiled run (its own launch count and durations), per launch like everything else here
-                rf["hbm_counter_gbps"] = rf["traffic"] / (pm["kernel_ms_under_profiler"] * 1e-3) / 1e9
-                rf["hbm_counter_frac"] = rf["hbm_counter_gbps"] / 8000.0
-            for k in ("ta_busy_frac", "valu_issue_frac", "active_lane_frac", "wave_waiting_frac", "l1_lookups_per_ray", "effective_clock_ghz"):
-                if k in pm:
-                    rf[k] = pm[k]
-            if pm.get("l1_lookups_per_ray") and sum_busy_ms > 0:
-                lookups_per_s = pm["l1_lookups_per_ray"] * tot["raysTraced"] / (sum_busy_ms * 1e-3) / world
-                rf["achieved"] = lookups_per_s * 16.0 / 1e9
-                rf["achieved_from"] = "PMC look-ups per ray x live ray rate"
-        rf["peak"] = GATHER_PEAK_LOOKUPS_PER_CLK_CU * 256 * 2.4e9 * 16.0 / 1e9
-        if rf["achieved"] is None and sum_busy_ms > 0:
-            # no counters of this workload in profiles/ (another scene, size or GPU count): the look-ups the traversal's own work
-            # counters imply when none is served from LDS — four 16-byte loads per pair of child boxes, three per triangle, five per
-            # ray (its record in, its hit out): an upper bound of the traversal's share, per GPU
-            est = 2.0 * (tot["boxTests"] - tot["skippedBoxTests"]) + 3.0 * tot["triTests"] + 5.0 * tot["raysTraced"]
-            rf["achieved"] = est / (sum_busy_ms * 1e-3) / world * 16.0 / 1e9
-            rf["achieved_from"] = "estimate from the kernel's work counters (2 look-ups per box test, 3 per triangle test, 5 per ray; upper bound: the top levels' pairs come from LDS)"
-        if rf["achieved"] is not None:
-            rf["frac"] = rf["achieved"] / rf["peak"]
-        if world == 1:
-            # a streaming copy measured on this very box (1 GiB, read + write), next to the nominal 8 TB/s
-            rf["measured_copy_gbps"] = r.copy_bandwidth_gbps(1 << 30, 5)
-        if world == 1 and args.cpu_seconds > 0:
-            out["cpu_baseline"], ref_rows, tile = cpu_baseline(scene, pc, W, H, args)
-            # the rows the oracle has just rendered are the rows of the bench frame at frameCount 0: render them on the
-            # GPU with the same constants and compare, bit for bit (the oracle is the checker here, never the product)
-            # ... through both pipelines (the timed groups run in one of them, small tiles in the other)
-            same, max_rel = True, 0.0
-            for pipe in (0, 1):
-                r.set_tuning("pipeline", pipe)
+        if args.full:
+            # The kernel's roofline. `bound` names the unit the counters show busiest; achieved / peak / frac are the rate of that unit.
+            rf = {"kernel": tkern + ("" if tkern == "k_trace_pw" else " (traversal + shading in one kernel)"),
+                  "bound": "vector-memory pipeline (16-byte gathers through the texture addresser and the L1 tags); latency- and divergence-limited: neither HBM nor MFMA nor VALU is near its peak",
+                  "achieved": None, "peak": None, "unit": "GB/s", "frac": None, "traffic": None,
+                  "achieved_is": "L1 look-ups per second x 16 B: look-ups per executed ray (PMC counters of the same binary) x executed rays / time with a traversal launch running (HIP events, live)",
+                  "peak_is": "1.39 look-ups per clock and CU (tools/gather_bench.hip on this chip: a 64-lane dwordx4 gather costs the CU 46 clocks, L2-resident table) x 256 CUs x 2.4 GHz x 16 B",
+                  "launches": sum_launches, "avg_launch_ms": avg_launch_ms,
+                  "launch_overlap": sum_trace_ms / sum_busy_ms if sum_busy_ms > 0 else None,
+                  "trace_busy_share_of_step": (sum_busy_ms / world) / (dt * 1e3) if sum_busy_ms > 0 else None,
+                  "algorithmic_bytes_per_launch": alg_bytes / launches,
+                  "algorithmic_gbps": alg_gbps, "algorithmic_frac": (alg_gbps / 8000.0) if alg_gbps else None,
+                  "algorithmic_is": "SURVEY 8(d): 32 B per box test + 36 B per triangle test + 100 B per hit, counted by the kernel, per launch / average launch duration, against 8 TB/s of HBM. Mostly served by LDS / L1 / L2, so it can exceed 1: it says how much traversal work per second the kernel does, not how busy HBM is (hbm_counter_frac does). With the dispatch in parts on several streams the launches overlap (launch_overlap) and share the GPU, so a launch's duration is longer than the kernel would need alone"}
+            out["roofline"] = rf
+            # What the hardware counters say about the same kernel: separate rocprofv3 --pmc passes of this very command
+            # (tools/profile_round.sh -> profiles/), since PMC counters cannot be read from inside the process. The file is
+            # stamped with a hash of the kernel sources; a stamp that no longer matches the tree is flagged, not hidden.
+            cfile = os.path.join(ROOT, "profiles", f"counters_{tkern}_{args.scene}_{W}x{H}_{args.spp}spp.json")
+            if world == 1 and os.path.exists(cfile):
+                with open(cfile) as f:
+                    pm = json.load(f)
+                rf["counters_source"] = os.path.relpath(cfile, ROOT)
+                rf["counters_stale"] = pm.get("source_sha") != kernel_source_sha()
+                rf["traffic"] = pm.get("traffic_bytes_per_launch")
+                if rf["traffic"] and pm.get("kernel_ms_under_profiler"):
+                    # both from the profiled run (its own launch count and durations), per launch like everything else here
+                    rf["hbm_counter_gbps"] = rf["traffic"] / (pm["kernel_ms_under_profiler"] * 1e-3) / 1e9
+                    rf["hbm_counter_frac"] = rf["hbm_counter_gbps"] / 8000.0
+                for k in ("ta_busy_frac", "valu_issue_frac", "active_lane_frac", "wave_waiting_frac", "l1_lookups_per_ray", "effective_clock_ghz"):
+                    if k in pm:
+                        rf[k] = pm[k]
+                if pm.get("l1_lookups_per_ray") and sum_busy_ms > 0:
+                    lookups_per_s = pm["l1_lookups_per_ray"] * tot["raysTraced"] / (sum_busy_ms * 1e-3) / world
+                    rf["achieved"] = lookups_per_s * 16.0 / 1e9
+                    rf["achieved_from"] = "PMC look-ups per ray x live ray rate"
+            rf["peak"] = GATHER_PEAK_LOOKUPS_PER_CLK_CU * 256 * 2.4e9 * 16.0 / 1e9
+            if rf["achieved"] is None and sum_busy_ms > 0:
+                # no counters of this workload in profiles/ (another scene, size or GPU count): the look-ups the traversal's own work
+                # counters imply when none is served from LDS — four 16-byte loads per pair of child boxes, three per triangle, five per
+                # ray (its record in, its hit out): an upper bound of the traversal's share, per GPU
+                est = 2.0 * (tot["boxTests"] - tot["skippedBoxTests"]) + 3.0 * tot["triTests"] + 5.0 * tot["raysTraced"]
+                rf["achieved"] = est / (sum_busy_ms * 1e-3) / world * 16.0 / 1e9
+                rf["achieved_from"] = "estimate from the kernel's work counters (2 look-ups per box test, 3 per triangle test, 5 per ray; upper bound: the top levels' pairs come from LDS)"
+            if rf["achieved"] is not None:
+                rf["frac"] = rf["achieved"] / rf["peak"]
+            if world == 1:
+                # a streaming copy measured on this very box (1 GiB, read + write), next to the nominal 8 TB/s
+                rf["measured_copy_gbps"] = r.copy_bandwidth_gbps(1 << 30, 5)
+            if world == 1 and args.cpu_seconds > 0:
+                out["cpu_baseline"], ref_rows, tile = cpu_baseline(scene, pc, W, H, args)
+                # the rows the oracle has just rendered are the rows of the bench frame at frameCount 0: render them on the
+                # GPU with the same constants and compare, bit for bit (the oracle is the checker here, never the product)
+                # ... through both pipelines (the timed groups run in one of them, small tiles in the other)
+                same, max_rel = True, 0.0
+                for pipe in (0, 1):
+                    r.set_tuning("pipeline", pipe)
+                    r.reset_counters()
+                    pc.frameCount = 0
+                    gpu_rows = r.render(pc, W, H, **tile)
+                    same = same and bool(np.array_equal(gpu_rows.view(np.uint32), ref_rows.view(np.uint32)))
+                    with np.errstate(all="ignore"):
+                        rel = np.abs(gpu_rows - ref_rows) / np.maximum(np.abs(ref_rows), 1e-6)
+                    max_rel = max(max_rel, float(np.nanmax(rel)) if rel.size else 0.0)
+                r.set_tuning("pipeline", -1)
+                out["parity_check"] = {"rows": tile["nRows"], "pixels": int(tile["nRows"] * W), "spp": args.spp, "equal": same,
+                                       "max_rel": max_rel, "pipelines": ["multi-kernel", "fused"],
+                                       "against": "oracle (scalar restatement of raytrace.comp), same rows, frameCount 0"}
+            if world == 1 and not multi and not args.no_in_flight_check:
+                # the frame the timed groups left behind (warm-up + steps, several steps per dispatch) against the same steps
+                # dispatched one by one: bit for bit, or the run fails
                 r.reset_counters()
-                pc.frameCount = 0
-                gpu_rows = r.render(pc, W, H, **tile)
-                same = same and bool(np.array_equal(gpu_rows.view(np.uint32), ref_rows.view(np.uint32)))
-                with np.errstate(all="ignore"):
-                    rel = np.abs(gpu_rows - ref_rows) / np.maximum(np.abs(ref_rows), 1e-6)
-                max_rel = max(max_rel, float(np.nanmax(rel)) if rel.size else 0.0)
-            r.set_tuning("pipeline", -1)
-            out["parity_check"] = {"rows": tile["nRows"], "pixels": int(tile["nRows"] * W), "spp": args.spp, "equal": same,
-                                   "max_rel": max_rel, "pipelines": ["multi-kernel", "fused"],
-                                   "against": "oracle (scalar restatement of raytrace.comp), same rows, frameCount 0"}
-        if world == 1 and not multi and not args.no_in_flight_check:
-            # the frame the timed groups left behind (warm-up + steps, several steps per dispatch) against the same steps
-            # dispatched one by one: bit for bit, or the run fails
-            r.reset_counters()
-            solo = torch.zeros((H, W, 4), dtype=torch.float32, device=f"cuda:{local}")
-            for i in range(frames_rendered):
-                pc.frameCount = i
-                r.render(pc, W, H, out_ptr=solo.data_ptr(), sync=True)
-            same = bool(torch.equal(solo.view(torch.int32), strip.view(torch.int32)))
-            out["in_flight_check"] = {"equal": same, "frames": frames_rendered,
-                                      "what": "the progressive image after all steps, rendered in groups (steps in flight), equals the one rendered one dispatch per step"}
-            del solo
+                solo = torch.zeros((H, W, 4), dtype=torch.float32, device=f"cuda:{local}")
+                for i in range(frames_rendered):
+                    pc.frameCount = i
+                    r.render(pc, W, H, out_ptr=solo.data_ptr(), sync=True)
+                same = bool(torch.equal(solo.view(torch.int32), strip.view(torch.int32)))
+                out["in_flight_check"] = {"equal": same, "frames": frames_rendered,
+                                          "what": "the progressive image after all steps, rendered in groups (steps in flight), equals the one rendered one dispatch per step"}
+                del solo
         if args.check and multi:
             # the same frames rendered by one process must equal the stitched strips bit for bit
             r.reset_counters()
@@ -354,6 +372,17 @@ def main():
         dist.destroy_process_group()
 
 
+def build_is_current(ge):
+    """True when build() would compile nothing: the library is newer than everything it is built from and the oracle's make
+    target is up to date. Then build() is not called at all, so a run on a tree that build() has prepared writes nothing into it
+    (not even build()'s lock file) and needs no write access to it."""
+    import subprocess
+    if ge._stale(ge.LIB, ge.SOURCES + ge.HEADERS + [os.path.abspath(ge.__file__)]):
+        return False
+    q = subprocess.run(["make", "-q", "-C", os.path.join(ROOT, "oracle")], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return q.returncode == 0
+
+
 def kernel_source_sha():
     """Hash of the sources the traversal kernels are built from (the stamp tools/pmc_roofline.py puts into profiles/)."""
     import hashlib
@@ -362,6 +391,26 @@ def kernel_source_sha():
         with open(os.path.join(ROOT, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
+
+
+DUMP_BUDGET_BYTES = 64_000_000 - 4096   # 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, img):
+    """DIR/frame.npy: the fp32 frame (H x W x RGBA) as the timed steps left it. A frame above the budget is replaced by a fixed,
+    seeded sample of its pixels: DIR/frame_sample.npy (n x RGBA, float32) and DIR/frame_sample_pixels.npy (their row-major
+    pixel indices, float64 holds them exactly)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes <= DUMP_BUDGET_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), img)
+        return
+    px = img.reshape(-1, img.shape[-1])
+    n = min(len(px), DUMP_BUDGET_BYTES // (px.itemsize * px.shape[1] + 8))
+    idx = np.sort(np.random.default_rng(0).choice(len(px), size=n, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(out_dir, "frame_sample_pixels.npy"), idx.astype(np.float64))
 
 
 def cpu_baseline(scene, pc, W, H, args):

@@ -1,20 +1,20 @@
 """The C ABI from compiled hosts.
 
 * include/rt_amd.h is a plain C header (gcc -std=c99) as well as a C++ one;
-* its structs are the reference's structs: src/vk_engine.h's own definitions (read from /root/reference at test time, where
-  that exists — it does not travel to the GPU box) compiled with the vendored glm next to rt_amd.h, every size and every
-  field offset compared by the compiler;
+* its structs are the reference's structs: every size and every field offset of src/vk_engine.h's own definitions (compiled
+  with the glm the reference vendors; recorded in tests/golden/reference_struct_layout.json by tools/reference_layout.py)
+  compared with rt_amd.h's by the compiler;
 * tests/abi_smoke.cpp, a C++ program that follows INTEGRATION.md's call sequence (no Python, no torch), gives the frames
   the ctypes path gives, bit for bit, and runs the multi-GPU calls (rt_comm_* / rt_gather_strips over RCCL) on one rank."""
+import json
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+LAYOUT = os.path.join(ROOT, "tests", "golden", "reference_struct_layout.json")
 
 STRUCTS = {   # struct -> fields whose offsets are compared
     "Sphere": ["position", "radius", "materialIndex"],
@@ -38,25 +38,21 @@ def test_header_is_plain_c(tmp_path):
     assert p.returncode == 0, p.stderr
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "src", "vk_engine.h")), reason="the reference tree is not on this machine")
 def test_structs_equal_the_references_own_header(tmp_path):
-    """The reference's struct definitions, taken from its header as it lies there, against include/rt_amd.h."""
-    text = open(os.path.join(REF, "src", "vk_engine.h"), encoding="utf-8-sig").read()
-    bodies = []
-    for name in STRUCTS:
-        m = re.search(r"^struct %s \{.*?^\};" % name, text, flags=re.S | re.M)
-        assert m, f"struct {name} not found in the reference's header"
-        bodies.append(m.group(0))
+    """The sizes and field offsets of the reference's struct definitions, as its header compiles, against include/rt_amd.h."""
+    with open(LAYOUT) as f:
+        ref = json.load(f)
     checks = []
     for name, fields in STRUCTS.items():
-        checks.append(f'static_assert(sizeof(ref::{name}) == sizeof(::{name}), "sizeof {name}");')
+        assert name in ref and ref[name]["sizeof"] > 0, f"struct {name} not recorded"
+        checks.append(f'static_assert(sizeof(::{name}) == {ref[name]["sizeof"]}, "sizeof {name}");')
         for f in fields:
-            checks.append(f'static_assert(offsetof(ref::{name}, {f}) == offsetof(::{name}, {f}), "{name}.{f}");')
+            assert f in ref[name]["offsets"], f"{name}.{f} not recorded"
+            checks.append(f'static_assert(offsetof(::{name}, {f}) == {ref[name]["offsets"][f]}, "{name}.{f}");')
     src = tmp_path / "layout.cpp"
-    src.write_text("#include <sys/types.h>\n#include <cstddef>\n#include <glm/glm.hpp>\n#include \"rt_amd.h\"\nnamespace ref {\n"
-                   + "\n".join(bodies) + "\n}\n" + "\n".join(checks) + "\nint main() { return 0; }\n")
-    p = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wno-invalid-offsetof", "-I", os.path.join(ROOT, "include"),
-                        "-I", os.path.join(REF, "third_party", "glm"), str(src)], capture_output=True, text=True)
+    src.write_text("#include <sys/types.h>\n#include <cstddef>\n#include \"rt_amd.h\"\n" + "\n".join(checks) + "\nint main() { return 0; }\n")
+    p = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wno-invalid-offsetof", "-I", os.path.join(ROOT, "include"), str(src)],
+                       capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-3000:]
 
 

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "2",
-                        "--width", "480", "--height", "270", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--width", "480", "--height", "270", "--cpu-seconds", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -45,7 +45,7 @@ def test_one_rank_job_through_rccl_stitches_the_single_process_frame():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--spp", "2",
                         "--scene", "cornell", "--width", "320", "--height", "181", "--cpu-seconds", "0",
-                        "--force-collective", "--check"], capture_output=True, text=True, timeout=600, env=env)
+                        "--force-collective", "--check", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["check_tiled_equals_single"] is True
@@ -63,11 +63,36 @@ def test_four_rank_rehearsal_on_one_gpu_stitches_the_single_process_frame():
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
                         "--master-port", "29561", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "7", "--warmup", "1",
                         "--spp", "2", "--scene", "bunny", "--width", "320", "--height", "181", "--cpu-seconds", "0",
-                        "--backend", "gloo", "--frames-in-flight", "4", "--check"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--backend", "gloo", "--frames-in-flight", "4", "--check", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["check_tiled_equals_single"] is True
     assert d["n_gpus"] == 4 and d["steps"] == 7 and d["config"]["frames_in_flight"] == 4 and d["value"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_frame_of_the_timed_steps(tmp_path):
+    """A plain run (no --full) prints the headline fields and none of --full's, and --dump-outputs writes the frame the timed
+    steps left. The same arguments with the steps grouped otherwise (one dispatch per step) dump the same bits."""
+    import numpy as np
+    frames = []
+    for fif in ("0", "1"):
+        out = tmp_path / f"fif{fif}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--spp", "2",
+                            "--scene", "bunny", "--width", "320", "--height", "181", "--frames-in-flight", fif, "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "Mrays/s" and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["higher_is_better"] is True and d["dtype"] == "f32" and "workload" in d["config"]
+        for k in ("roofline", "cpu_baseline", "parity_check", "in_flight_check", "per_step_dispatch"):
+            assert k not in d, k
+        img = np.load(out / "frame.npy")
+        assert img.dtype == np.float32 and img.shape == (181, 320, 4) and np.isfinite(img).all() and img[..., :3].max() > 0
+        frames.append(img)
+    assert np.array_equal(frames[0].view(np.uint32), frames[1].view(np.uint32))
 
 
 def test_scripts_parse():
@@ -78,3 +103,4 @@ def test_scripts_parse():
         py_compile.compile(f, doraise=True)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT)
     assert p.returncode == 0 and "--per-step-dispatches" in p.stdout
+    assert "--full" in p.stdout and "--dump-outputs" in p.stdout

@@ -3,7 +3,7 @@
 # usage: tools/ab_libs.sh "<names: base pre ...>" [bench.py arguments]     (librt_amd_<name>.so from tools/build_variant.sh; "head" = the tree's)
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
 names=$1; shift
-args=${*:---steps 20 --warmup 5}
+args="--full ${*:---steps 20 --warmup 5}"   # --full: the roofline line's launch figures
 mkdir -p gpurun_out
 for pass in 1 2; do
   for n in $names; do
