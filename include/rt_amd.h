@@ -290,7 +290,9 @@ int  rt_upload_scene(rt_ctx* ctx, const RtSceneArrays* scene);
  * compares with 0, :509); bump — the decoded texel is a height and the interpolated normal is tilted by the height steps to the
  * next texel of the row and of the column along the triangle's dP/du, dP/dv (rt_bump_normal). A slot < 0 or beyond the uploaded
  * table binds nothing. A scene that binds one of the three is rendered by the multi-kernel pipeline (k_shade_maps,
- * k_trace_pw_alpha) whatever "pipeline" says; one whose emissive material has an alpha map traces its light queries in full.
+ * k_trace_pw_alpha) whatever "pipeline" says, unless "fused_maps" is 1 (rt_set_tuning): then it picks its pipeline as any other
+ * scene does and the fused one runs k_render_fused_maps. One whose emissive material has an alpha map traces its light queries
+ * in full.
  * Borrowed for the call; n = 0 removes all textures. */
 typedef struct RtTexture {
     uint32_t width, height;
@@ -363,6 +365,9 @@ int  rt_get_trace_busy_ms(rt_ctx* ctx, double* msOut);
  *   "pipeline"       -1 (default) pick by tile size, 0 = multi-kernel wavefront pipeline
  *                    (k_trace_pw + k_shade per round), 1 = wave-private fused pipeline
  *                    (k_render_fused: every wave runs the stages on its own 8x8 pixel blocks)
+ *   "fused_maps"     0 (default): a scene that binds an alpha, metalness or bump map takes the multi-kernel pipeline whatever
+ *                    "pipeline" says; 1: it picks its pipeline like any other scene, and the fused one reads the maps
+ *                    (k_render_fused_maps: one configuration for every such scene, as k_trace_pw_alpha)
  *   "fused_below_pixels"  paths of a dispatch (tile pixels x frames) below which -1 picks the fused pipeline
  *   "fused_below_box_tests"  ... and box tests per ray (measured on the context's earlier dispatches of
  *                    the scene, copied back without waiting) below which it does so at any size

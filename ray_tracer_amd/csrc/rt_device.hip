@@ -139,6 +139,7 @@ struct rt_ctx {
     int pixelRefill = 0;    // fused pipeline: free lanes at which a wave reserves new pixels (64 = a block at a time, 0 = by ray length)
     int batchPixels = 0;    // fused pipeline: pixels per wave-private block (0 = chosen per launch)
     int batchFixed = 80;    // ... and the fixed part of a block's cost in the chooser, in pixel units
+    int fusedMaps = 0;      // 1: a scene that binds an alpha, metalness or bump map may take the fused pipeline (k_render_fused_maps); 0: multi-kernel only
     int lastBatchPixels = 0;
     DevBuf probeBuf;        // framebuffer of the ray-cost probe
     int probe = 1;          // measure an unknown scene with a small dispatch before its first big one
@@ -315,11 +316,16 @@ uint32_t fused_batch_pixels(const rt_ctx* c, uint32_t nPixels, uint32_t waves, u
     return best;
 }
 
-template <int STACK, bool OVF, bool CULL>
+// MAPS: k_render_fused_maps<PIX> (a scene that binds an alpha, metalness or bump map; launch_fused), whose one configuration is
+// <24, true, *, true>: everything but the kernel is the same
+template <int STACK, bool OVF, bool CULL, bool MAPS = false>
 int launch_fused_t(rt_ctx* c, const FrameParams& fp, float4* fb) {
+    static_assert(!MAPS || (STACK == 24 && OVF && CULL), "k_render_fused_maps is built for 24 LDS entries, the overflow buffer and culling");
     int perCU = c->blocksPerCU;
     if (perCU <= 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_render_fused<STACK, OVF, false, CULL>, RT_BLOCK, 0) != hipSuccess || perCU <= 0) perCU = 4;
+        const hipError_t e = MAPS ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_render_fused_maps<false>, RT_BLOCK, 0)
+                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_render_fused<STACK, OVF, false, CULL>, RT_BLOCK, 0);
+        if (e != hipSuccess || perCU <= 0) perCU = 4;
     }
     const uint32_t resident = (uint32_t)perCU * (uint32_t)c->numCUs;
     const uint32_t nSlots = fp.nFrames > 1u ? ((fp.nPixels + 63u) / 64u) * 64u * fp.nFrames : fp.nPixels;  // rt_render_frames: frames are more slots of the same tile (rt_kernels.hip.h: frame_slot)
@@ -346,7 +352,8 @@ int launch_fused_t(rt_ctx* c, const FrameParams& fp, float4* fb) {
     const uint32_t nBatches = g ? ((nSlots + g - 1) / g + batchPixels / g - 1) / (batchPixels / g) : (nSlots + batchPixels - 1) / batchPixels;
     const uint32_t blocks = std::max(1u, std::min((nBatches + (RT_BLOCK / RT_WAVE) - 1) / (RT_BLOCK / RT_WAVE), resident));
     uint32_t* overflow = nullptr;
-    if (OVF) {
+    // (the maps kernel runs with its overflow buffer compiled in whatever the depth: none is needed up to 24 levels)
+    if (OVF && (!MAPS || c->maxLeafDepth > (uint32_t)STACK)) {
         int rc = dev_alloc(c, c->overflowBuf, (size_t)(c->maxLeafDepth - STACK) * resident * RT_BLOCK * 4);
         if (rc) return rc;
         overflow = (uint32_t*)c->overflowBuf.p;
@@ -366,9 +373,15 @@ int launch_fused_t(rt_ctx* c, const FrameParams& fp, float4* fb) {
     FusedArgs fa{c->q.counts + 5, fb, (DevCounters*)c->counterBuf.p, overflow, (uint32_t)c->refill, (uint32_t)c->wSetupFused, wLeaf, fastLanes, batchPixels, g, (uint32_t)c->fastShare, waveTimes, pixelRefill};
     c->lastBatchPixels = (int)batchPixels;
     const FusedKernArgs ka{c->sc, c->ps, fp, fa};
-    snprintf(c->lastKernel, sizeof c->lastKernel, "k_render_fused<%d, %s, %s, %s>", STACK, OVF ? "true" : "false", c->pixStats ? "true" : "false", CULL ? "true" : "false");
-    if (c->pixStats) hipLaunchKernelGGL((k_render_fused<STACK, OVF, true, CULL>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
-    else hipLaunchKernelGGL((k_render_fused<STACK, OVF, false, CULL>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
+    if (MAPS) {
+        snprintf(c->lastKernel, sizeof c->lastKernel, "k_render_fused_maps<%s>", c->pixStats ? "true" : "false");
+        if (c->pixStats) hipLaunchKernelGGL((k_render_fused_maps<true>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
+        else hipLaunchKernelGGL((k_render_fused_maps<false>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
+    } else {
+        snprintf(c->lastKernel, sizeof c->lastKernel, "k_render_fused<%d, %s, %s, %s>", STACK, OVF ? "true" : "false", c->pixStats ? "true" : "false", CULL ? "true" : "false");
+        if (c->pixStats) hipLaunchKernelGGL((k_render_fused<STACK, OVF, true, CULL>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
+        else hipLaunchKernelGGL((k_render_fused<STACK, OVF, false, CULL>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
+    }
     RT_HIP(c, hipGetLastError());
     return 0;
 }
@@ -387,7 +400,8 @@ int launch_fused(rt_ctx* c, const FrameParams& fp, float4* fb) {
     }
     const uint32_t d = c->maxLeafDepth, cap = (uint32_t)c->ldsStackCap;
     int rc;
-    if (c->cull) {
+    if (c->sc.mapFlags) rc = launch_fused_t<24, true, true, true>(c, fp, fb);  // a bound map (fused_maps): one kernel, any depth, any objects
+    else if (c->cull) {
         if (d <= 8) rc = launch_fused_t<8, false, true>(c, fp, fb);
         else if (cap < 16) rc = launch_fused_t<8, true, true>(c, fp, fb);
         else if (d <= 16) rc = launch_fused_t<16, false, true>(c, fp, fb);
@@ -1257,9 +1271,9 @@ int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t hei
     const bool bigScene = (uint64_t)c->sc.nodeCount * 32u + (uint64_t)c->sc.triCount * 48u > (4ull << 20);
     const bool shortButMissing = shortRays && bigScene && c->boxPerRay >= 25.0 && nSlots >= (10u << 20);
     c->lastPipeline = c->pipeline >= 0 ? c->pipeline : (((double)nSlots < sizeLimit || (shortRays && !shortButMissing)) ? 1 : 0);
-    // a scene that binds a metalness, alpha or bump map: the kernels that read them belong to the multi-kernel pipeline
-    // (k_shade_maps, k_trace_pw_alpha), whatever "pipeline" asks for
-    if (c->sc.mapFlags) c->lastPipeline = 0;
+    // a scene that binds a metalness, alpha or bump map: the multi-kernel pipeline's kernels that read them (k_shade_maps,
+    // k_trace_pw_alpha), whatever "pipeline" asks for — unless "fused_maps" lets it choose as usual (k_render_fused_maps)
+    if (c->sc.mapFlags && !c->fusedMaps) c->lastPipeline = 0;
     if (c->lastPipeline == 1) {  // wave-private fused pipeline: one launch for the whole dispatch
         rc = launch_fused(c, fp, fb);
         if (!rc && nFrames > 1u) {
@@ -1604,6 +1618,7 @@ int rt_set_tuning(rt_ctx* c, const char* key, int value) {
     else if (k == "mask_identity") { c->maskIdentity = value != 0; }
     else if (k == "fast_share") { if (value < 0 || value > 16) return c->fail("fast_share: 0..16"); c->fastShare = value; }
     else if (k == "scatter") { if (value != -1 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return c->fail("scatter: -1 (auto), 0, 1, 2, 4, 8 or 16"); c->scatter = value; }
+    else if (k == "fused_maps") { if (value < 0 || value > 1) return c->fail("fused_maps: 0 (map scenes take the multi-kernel pipeline) or 1 (they choose as usual)"); c->fusedMaps = value; }
     else if (k == "pixel_refill") { if (value < 0 || value > (int)RT_WAVE) return c->fail("pixel_refill must be 0 (by ray length) .. 64"); c->pixelRefill = value; }
     else if (k == "batch_pixels") { if (value < 0 || value > (int)RT_WAVE) return c->fail("batch_pixels must be 0 (auto) .. 64"); c->batchPixels = value; }
     else if (k == "batch_fixed") { if (value < 0 || value > 4096) return c->fail("batch_fixed out of range"); c->batchFixed = value; }

@@ -43,6 +43,9 @@
 #ifndef RT_SHADE_IDENT
 #define RT_SHADE_IDENT 1   // reconstruct_hit: no matrix loads / transforms for identity-transform objects hit by a plain ray
 #endif
+#ifndef RT_FUSED_MAPS_BLOCKS
+#define RT_FUSED_MAPS_BLOCKS 4   // k_render_fused_maps: work-groups per CU it is built for (__launch_bounds__)
+#endif
 #define RT_BLOCK 256
 #define RT_LEAF_BIT 0x80000000u
 #define RT_HIT_NONE 0xffffffffu
@@ -125,7 +128,7 @@ struct DevScene {
     uint32_t texCount;
     // The other three map slots (declared semantics: include/rt_det_math.h). mats[3 m + 2].z / .w carry metalnessIndex / bumpIndex,
     // objAlpha[object] the alpha map of the object's material and its sampler (slot | clamp << 8; 0xffffffff = none); mapFlags says
-    // which kinds the scene binds at all (RT_MAP_*): the kernels that read them are separate ones (k_shade_maps, k_trace_pw_alpha)
+    // which kinds the scene binds at all (RT_MAP_*): the kernels that read them are separate ones (k_shade_maps, k_trace_pw_alpha, k_render_fused_maps)
     const uint32_t* objAlpha;
     uint32_t mapFlags;
     float cullOriginLimit;   // rays that start farther out than this (max |origin component|) skip nothing: the padding of the world-space
@@ -714,7 +717,7 @@ struct WaveTotals {
 // ROOMY: the kernel is built for five work-groups per CU (96 registers per lane): a light query's tE rides in a register there
 // (-2 % on the bench frame). With the 80 registers of six work-groups per CU, and in the fused kernel, one more live register
 // means one more spill: measured there, it loses (Cornell + bunny +3 %, C5 at 4K +1 %).
-// ALPHA: triangle hits are looked up in their object's alpha map before they count (alpha_cut; k_trace_pw_alpha only).
+// ALPHA: triangle hits are looked up in their object's alpha map before they count (alpha_cut; k_trace_pw_alpha, k_render_fused_maps).
 template <int STACK, bool OVF, bool PIX, bool STATS, bool LOCAL, bool CULL, int HOT = 0, bool ROOMY = false, bool ALPHA = false>
 __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& ps, const TracePwArgs& ta, uint32_t* stack, uint32_t* ovf,
                                            size_t ovfStride, const uint32_t* localList, uint32_t n, WaveTotals& wt, const uint2* metaLds,
@@ -1375,7 +1378,7 @@ struct ShadeArgs {
 // of this diffuse bounce have to be traced — a light query that emitter_min_t2 answers is not; bit 2: the main ray needs no
 // traversal, its hit record is already there: the kept camera hit), refRays (the shader's
 // calculateIntersections calls for this segment), nPaths (1 if a sample finished), emitTests (primitives emitter_min_t2 tested).
-// MAPS (k_shade_maps): the scene binds a metalness or a bump map
+// MAPS (k_shade_maps, k_render_fused_maps): the scene binds a metalness or a bump map
 template <bool MAPS = false>
 __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& ps, const FrameParams& fp, uint32_t slot, bool& alive,
                                            uint32_t& auxMask, uint32_t& refRays, uint32_t& nPaths, uint32_t& emitTests, bool withMask = true) {
@@ -1773,148 +1776,18 @@ struct FusedKernArgs {  // the whole kernel-argument segment, so that it can be 
 
 template <int STACK, bool OVF, bool PIX, bool CULL>
 __global__ __launch_bounds__(RT_BLOCK, 5) void k_render_fused(FusedKernArgs ka) {
-    const DevScene& sc = ka.sc;
-    const PathState& ps = ka.ps;
-    const FrameParams& fp = ka.fp;
-    const FusedArgs& fa = ka.fa;
-    __shared__ uint32_t s_stack[(RT_BLOCK / RT_WAVE) * (STACK + 1) * RT_WAVE];
-    __shared__ uint32_t s_list[RT_BLOCK / RT_WAVE][3 * RT_WAVE];
-    __shared__ float4 s_box[64];  // DevScene::maskBox (the objects of the mask's window that can be ruled out): the rays' object masks are computed from here (reach_mask_from)
-    __shared__ uint2 s_meta[RT_META_LDS];
-    const uint32_t nBox = CULL ? sc.reachCount : 0u;
-    if (CULL && threadIdx.x < 2u * nBox) s_box[threadIdx.x] = sc.maskBox[threadIdx.x];
-    fill_meta_lds(sc, s_meta);
-    const uint32_t wv = threadIdx.x / RT_WAVE;
-    uint32_t* stack = s_stack + wv * (STACK + 1) * RT_WAVE + (threadIdx.x & (RT_WAVE - 1));
-    uint32_t* list = s_list[wv];
-    uint32_t* ovf = OVF ? fa.overflow + (size_t)blockIdx.x * RT_BLOCK + threadIdx.x : nullptr;
-    const size_t ovfStride = (size_t)gridDim.x * RT_BLOCK;
-    const TracePwArgs ta{nullptr, nullptr, nullptr, fa.refill, 0u, fa.wSetup, fa.wLeaf, fa.fastLanes, fa.fastShare, nullptr, nullptr, fa.counters, nullptr, nullptr, fa.overflow};
-    WaveTotals wt;
-    uint32_t refTot = 0, pathTot = 0, segTot = 0, emitTot = 0;
-    const unsigned long long tKernelStart = fa.waveTimes ? wall_clock64() : 0ull;
-    // scatter = g > 0: batchPixels is a multiple of g and a block is batchPixels / g chunks of g slots, nBatches apart
-    const uint32_t nBatches = fa.scatter ? ((fp.nPixels + fa.scatter - 1) / fa.scatter + fa.batchPixels / fa.scatter - 1) / (fa.batchPixels / fa.scatter)
-                                         : ((fp.nFrames > 1u ? ((fp.nPixels + 63u) >> 6) * 64u * fp.nFrames : fp.nPixels) + fa.batchPixels - 1) / fa.batchPixels;
-
-    // A lane keeps a pixel until all its samples are done, then resolves it and takes the next one: when `pixelRefill`
-    // of the wave's lanes are free (or all of them), the wave reserves that many slots with one atomic. The wave stays
-    // populated until the tile runs out, instead of draining to its slowest pixel once per block.
-    const uint32_t nSlots = fp.nFrames > 1u ? ((fp.nPixels + 63u) >> 6) * 64u * fp.nFrames : fp.nPixels;  // nFrames > 1 comes with scatter = 0
-    const uint32_t total = fa.scatter ? nBatches * fa.batchPixels : nSlots;
-    const uint32_t refillAt = min(max(fa.pixelRefill, 1u), fa.batchPixels);
-    uint32_t slot = 0;
-    bool valid = false, alive = false, exhausted = false;
-    uint32_t auxMask = 0;  // bit 0: the pixel's path has a NEE ray in flight, bit 1: a cosine probe
-    for (;;) {
-        const bool mine = lane_id() < fa.batchPixels && !alive;
-        const unsigned long long mF = __ballot(mine);
-        const uint32_t take = __popcll(mF);
-        if (!exhausted && take >= refillAt) {
-            uint32_t base = 0;
-            if (lane_id() == 0) base = atomicAdd(fa.batchHead, take);
-            base = __shfl(base, 0, RT_WAVE);
-            if (base >= total) exhausted = true;
-            else if (mine) {
-                // Frame constants and the shading tables are re-read from the kernel-argument segment where they are used
-                // (the asm makes the pointers opaque, so the loads cannot be hoisted): held across the traversal loop they
-                // cost ~60 scalar registers of a kernel that has none to spare.
-                const FusedKernArgs* kq = opaque_kernarg<FusedKernArgs>();
-                const FrameParams* fq = &kq->fp;
-                const DevScene* sq = &kq->sc;
-                if (valid && fq->nFrames == 1u) resolve_pixel(ps, *fq, fa.rgba, slot);  // several frames: k_blend_frames, afterwards
-                const uint32_t a = base + lanes_below(mF);
-                uint32_t ns = a;
-                if (fa.scatter) {
-                    // a block's pixels are spread over the whole tile (chunks of `scatter` consecutive slots, nBatches chunks
-                    // apart), so that all blocks cost about the same when every wave gets just one of them
-                    const uint32_t ch = a / fa.scatter, perBlock = fa.batchPixels / fa.scatter;
-                    ns = ((ch % perBlock) * nBatches + ch / perBlock) * fa.scatter + a % fa.scatter;
-                }
-                valid = a < total && ns < nSlots && (fq->nFrames == 1u || slot_in_tile(*fq, ns) < fq->nPixels);
-                slot = ns;
-                auxMask = 0;
-                if (valid) {
-                    init_path(*sq, ps, *fq, slot);
-                    alive = fp.samples > 0;
-                }
-            }
-        }
-        const unsigned long long mA = __ballot(alive);
-        if (mA == 0) {
-            if (exhausted) break;
-            continue;
-        }
-        const unsigned long long mM = __ballot(alive && !(auxMask & 4u));  // bit 2: the kept camera hit stands in for the main ray
-        const unsigned long long mL = __ballot(alive && (auxMask & 1u)), mC = __ballot(alive && (auxMask & 2u));
-        const uint32_t nM = __popcll(mM), nL = __popcll(mL), nC = __popcll(mC);
-        if (alive) {
-            if (!(auxMask & 4u)) list[lanes_below(mM)] = (slot << 2) | RAY_MAIN;
-            if (auxMask & 1u) list[nM + lanes_below(mL)] = (slot << 2) | RAY_NEE;
-            if (auxMask & 2u) list[nM + nL + lanes_below(mC)] = (slot << 2) | RAY_PROBE;
-        }
-        const uint32_t nRays = nM + nL + nC;
-        __threadfence_block();  // the rays written by shade_path / init_path are read by other lanes of this wave
-        trace_wave<STACK, OVF, PIX, false, true, CULL>(sc, ps, ta, stack, ovf, ovfStride, list, nRays, wt, s_meta);
-        __threadfence_block();  // ... and so are the hit records
-        if (alive) {
-            bool nowAlive = false;
-            uint32_t refRays = 0, nPaths = 0;
-            const FusedKernArgs* kq = opaque_kernarg<FusedKernArgs>();
-            const FrameParams* fq = &kq->fp;
-            const DevScene* sq = &kq->sc;
-            shade_path(*sq, ps, *fq, slot, nowAlive, auxMask, refRays, nPaths, emitTot, false);
-            segTot++;
-            if (CULL && nowAlive && nBox) {
-                // the new rays' object masks (sphere_seed), here rather than inside shade_path: its registers are spilling already
-                float4 sd;
-                if (!(auxMask & 4u)) {
-                    sd = ps.hit(RAY_MAIN)[slot];
-                    sd.z = __uint_as_float(reach_mask_from(s_box, nBox, f4xyz(ps.rayO()[slot]), f4xyz(ps.rayD()[slot]), sc.cullOriginLimit));
-                    ps.hit(RAY_MAIN)[slot] = sd;
-                }
-                if (auxMask & 1u) {
-                    sd = ps.hit(RAY_NEE)[slot];
-                    sd.z = __uint_as_float(reach_mask_from(s_box, nBox, f4xyz(ps.auxO()[slot]), f4xyz(ps.auxDL()[slot]), sc.cullOriginLimit));
-                    ps.hit(RAY_NEE)[slot] = sd;
-                }
-                if (auxMask & 2u) {
-                    sd = ps.hit(RAY_PROBE)[slot];
-                    sd.z = __uint_as_float(reach_mask_from(s_box, nBox, f4xyz(ps.auxO()[slot]), f4xyz(ps.auxDC()[slot]), sc.cullOriginLimit));
-                    ps.hit(RAY_PROBE)[slot] = sd;
-                }
-            }
-            alive = nowAlive;
-            auxMask = nowAlive ? auxMask : 0u;
-            refTot += refRays;
-            pathTot += nPaths;
-        }
-    }
-    if (valid) {  // the pixels that finished after the tile ran out
-        const FusedKernArgs* kq = opaque_kernarg<FusedKernArgs>();
-        if (kq->fp.nFrames == 1u) resolve_pixel(ps, kq->fp, fa.rgba, slot);
-    }
-
-    if (fa.waveTimes && lane_id() == 0) {  // phase_stats: when did this wave run out of blocks?
-        const size_t w = (size_t)blockIdx.x * (RT_BLOCK / RT_WAVE) + threadIdx.x / RT_WAVE;
-        fa.waveTimes[2 * w] = tKernelStart;
-        fa.waveTimes[2 * w + 1] = wall_clock64();
-    }
-    unsigned long long wb = wave_sum_u64(wt.totBox), wtri = wave_sum_u64(wt.totTri);
-    uint32_t wr = wave_sum_u32(wt.totRays), wh = wave_sum_u32(wt.totHits);
-    uint32_t wRef = wave_sum_u32(refTot), wP = wave_sum_u32(pathTot), wS = wave_sum_u32(segTot), wE = wave_sum_u32(emitTot);
-    const unsigned long long wskip = CULL ? wave_sum_u64(wt.totSkipBox) : 0ull;
-    if (lane_id() == 0 && (wr | wP | wS)) {
-        if (CULL && wskip) atomicAdd(&fa.counters->skippedBoxTests, wskip);
-        if (wE) atomicAdd(&fa.counters->emitterTests, (unsigned long long)wE);
-        atomicAdd(&fa.counters->boxTests, wb);
-        atomicAdd(&fa.counters->triTests, wtri);
-        atomicAdd(&fa.counters->raysTraced, (unsigned long long)wr);
-        atomicAdd(&fa.counters->raysHit, (unsigned long long)wh);
-        atomicAdd(&fa.counters->raysReference, (unsigned long long)wRef);
-        atomicAdd(&fa.counters->paths, (unsigned long long)wP);
-        atomicAdd(&fa.counters->segments, (unsigned long long)wS);
-    }
+    constexpr bool ALPHA = false, MAPS = false;
+#include "rt_fused_body.hip.inc"
+}
+// The fused pipeline of a scene that binds an alpha, metalness or bump map (DevScene::mapFlags): one configuration for every
+// such scene, the one k_trace_pw_alpha has — 24 stack entries in LDS with the overflow buffer behind them, object culling
+// compiled in, no top-level table — so two instantiations (PIX: heat maps). The traversal reads the alpha maps (alpha_cut),
+// shading the metalness and bump maps (shade_path<true>); the rays' object masks are still computed in the body.
+template <bool PIX>
+__global__ __launch_bounds__(RT_BLOCK, RT_FUSED_MAPS_BLOCKS) void k_render_fused_maps(FusedKernArgs ka) {
+    constexpr int STACK = 24;
+    constexpr bool OVF = true, CULL = true, ALPHA = true, MAPS = true;
+#include "rt_fused_body.hip.inc"
 }
 
 // ---------------------------------------------------------------- rt_trace_rays support
