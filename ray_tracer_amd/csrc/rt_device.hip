@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -64,7 +65,8 @@ struct rt_ctx {
     std::vector<RootInfo> rootOf;             // per reference node; idx = ~0u unless a mesh root
 
     // path state
-    DevBuf stateBuf, queueBuf, fbBuf, counterBuf, scratchBuf, overflowBuf, overflowBufSide[RT_MAX_LANES - 1];
+    DevBuf stateBuf, queueBuf, fbBuf, counterBuf, scratchBuf;
+    DevBuf overflowBuf[RT_MAX_LANES];     // per part (curLane): the traversal stack entries beyond LDS
     // Multi-kernel pipeline in `lanes` independent parts (render_impl): the paths of a dispatch are split into contiguous slot
     // ranges, each with its own queues, counters and stream, so that one part's k_shade and the tail of its k_trace_pw launch
     // run under the other part's traversal. Part 0 is the ctx stream itself; the others fork from it and join it.
@@ -115,8 +117,8 @@ struct rt_ctx {
     double segPerPath = -1.0;             // path segments per pixel sample of this scene, from the same snapshots (< 0: not measured yet)
     unsigned long long snapSeg = 0, snapPaths = 0;
     int refill = 8;         // k_trace_pw: idle lanes that trigger a refill
-    bool refillMkSet = false, wSetupSet = false;  // given explicitly (else by the scene's ray length, launch_pw_t)
-    int refillMk = 16;      // the same for k_trace_pw over the global queue when set by hand ("mk_refill"); automatic: 12 for long rays, 16 otherwise (launch_pw_t)
+    bool refillMkSet = false, wSetupSet = false;  // given explicitly (else by the scene's ray length, launch_trace)
+    int refillMk = 16;      // the same for k_trace_pw over the global queue when set by hand ("mk_refill"); automatic: 12 for long rays, 16 otherwise (launch_trace)
     int chunk = 256;        // k_trace_pw: most queue entries reserved per atomic
     int ldsStackCap = 24;   // k_trace_pw: LDS stack entries per lane (8, 16 or 24); deeper BVHs use the overflow buffer
     int fastLanes = 32;     // k_trace_pw: lanes at interior nodes that skip the full vote (4K Sponza: 24 -> 32 is -2 %, 1080p: equal)
@@ -231,10 +233,51 @@ int ensure_state(rt_ctx* c, uint32_t nPixels) {
     return 0;
 }
 
+template <int N> using Stack = std::integral_constant<int, N>;
+
+// The traversal kernel's stack for a BVH of depth d and at most `cap` LDS entries per lane: f(Stack<STACK>, bool_constant<OVF>,
+// bool_constant<CULL>), OVF: the deeper entries in the overflow buffer. Only the multi-kernel pipeline has a 20-entry kernel.
+// (tests/test_instantiations.py makes a scene for each depth bucket of these rows)
+template <bool ALLOW20, typename F>
+auto with_stack(uint32_t d, uint32_t cap, bool cull, F&& f) {
+    using Yes = std::true_type; using No = std::false_type;
+    auto go = [&](auto S, auto O) { return cull ? f(S, O, Yes{}) : f(S, O, No{}); };
+    if (d <= 8) return go(Stack<8>{}, No{});
+    if (cap < 16) return go(Stack<8>{}, Yes{});
+    if (d <= 16) return go(Stack<16>{}, No{});
+    if (cap < 24) return go(Stack<16>{}, Yes{});
+    if constexpr (ALLOW20) { if (d <= 20) return go(Stack<20>{}, No{}); }
+    if (d <= 24) return go(Stack<24>{}, No{});
+    return go(Stack<24>{}, Yes{});
+}
+
+// A kernel to launch, the one whose occupancy sizes the grid (no heat maps, no phase statistics), its stack, and its name as a
+// demangler prints it (rt_last_kernel; tests/test_instantiations.py compares it with `nm -C`)
+template <typename K> struct KernelChoice { K kernel, occupancy; int stack; bool ovf; char name[sizeof rt_ctx::lastKernel]; };
+using TracePwChoice = KernelChoice<void (*)(DevScene, PathState, TracePwArgs)>;
+using FusedChoice = KernelChoice<void (*)(FusedKernArgs)>;
+
+template <typename K, typename... A>
+KernelChoice<K> kernel_choice(K kernel, K occupancy, int stack, bool ovf, const char* format, A... a) {
+    KernelChoice<K> k{kernel, occupancy, stack, ovf, ""};
+    snprintf(k.name, sizeof k.name, format, a...);
+    return k;
+}
+const char* tf(bool b) { return b ? "true" : "false"; }
+
+template <int STACK, bool OVF, bool PIX, bool STATS, bool CULL, int HOT = 0, int BLOCKS = 6>
+TracePwChoice trace_pw_kernel() {
+    return kernel_choice(k_trace_pw<STACK, OVF, PIX, STATS, CULL, HOT, BLOCKS>, k_trace_pw<STACK, OVF, false, false, CULL, HOT, BLOCKS>, STACK, OVF,
+                         "k_trace_pw<%d, %s, %s, %s, %s, %d, %d>", STACK, tf(OVF), tf(PIX), tf(STATS), tf(CULL), HOT, BLOCKS);
+}
+template <int STACK, bool OVF, bool PIX, bool CULL>
+FusedChoice fused_kernel() {
+    return kernel_choice(k_render_fused<STACK, OVF, PIX, CULL>, k_render_fused<STACK, OVF, false, CULL>, STACK, OVF,
+                         "k_render_fused<%d, %s, %s, %s>", STACK, tf(OVF), tf(PIX), tf(CULL));
+}
+
 template <int STACK, bool OVF, bool CULL>
-int launch_pw_t(rt_ctx* c, uint32_t maxRays, const TraceArgs& ta) {
-    // per-ray counters are only needed for the pixel heat maps (debug >= 0) and rt_trace_rays
-    const bool pix = c->pixStats || ta.perRayBox;
+TracePwChoice choose_trace_pw(const rt_ctx* c, bool pix) {
     // top-level pairs from LDS (k_trace_pw<HOT>): what 160 KB of LDS per CU leave beside the stacks. hot_pairs 1: six work-groups
     // per CU, 2: five (more pairs, no spills at 96 registers)
     // (the overflow-stack kernel with 16 entries in LDS keeps six work-groups AND 120 pairs: deep BVHs, see launch_trace)
@@ -243,55 +286,59 @@ int launch_pw_t(rt_ctx* c, uint32_t maxRays, const TraceArgs& ta) {
     int hotMode = (!pix && !c->phaseStats && c->sc.hotNodes > 0) ? c->hotPairs : 0;
     if (hotMode == 1 && HOT6 == 0) hotMode = 2;   // (a 24-entry stack leaves no room at six work-groups)
     if (hotMode == 2 && HOT5 == 0) hotMode = HOT6 ? 1 : 0;   // (overflow-stack instantiations: the table only beside 16-entry stacks)
+    // (if constexpr: an instantiation the tables can never select is not compiled — every kernel in the library can be
+    // launched, and tests/test_instantiations.py launches every one of them against the oracle)
+    if constexpr (HOT6 > 0) { if (hotMode == 1) return trace_pw_kernel<STACK, OVF, false, false, CULL, HOT6, 6>(); }
+    if constexpr (HOT5 > 0) { if (hotMode == 2) return trace_pw_kernel<STACK, OVF, false, false, CULL, HOT5, 5>(); }
+    if (c->phaseStats) return trace_pw_kernel<STACK, OVF, true, true, CULL>();
+    if (pix) return trace_pw_kernel<STACK, OVF, true, false, CULL>();
+    return trace_pw_kernel<STACK, OVF, false, false, CULL>();
+}
+
+template <typename K>
+uint32_t resident_blocks(const rt_ctx* c, K kernel) {
     int perCU = c->blocksPerCU;
-    if (perCU <= 0) {
-        hipError_t e;
-        e = hipErrorInvalidValue;
-        // (if constexpr: an instantiation the tables can never select is not compiled — every kernel in the library can be
-        // launched, and tests/test_instantiations.py launches every one of them against the oracle)
-        if constexpr (HOT6 > 0) { if (hotMode == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_trace_pw<STACK, OVF, false, false, CULL, HOT6, 6>, RT_BLOCK, 0); }
-        if constexpr (HOT5 > 0) { if (hotMode == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_trace_pw<STACK, OVF, false, false, CULL, HOT5, 5>, RT_BLOCK, 0); }
-        if (hotMode == 0) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_trace_pw<STACK, OVF, false, false, CULL>, RT_BLOCK, 0);
-        if (e != hipSuccess || perCU <= 0) perCU = 4;
+    if (perCU <= 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, RT_BLOCK, 0) != hipSuccess || perCU <= 0)) perCU = 4;
+    return (uint32_t)perCU * (uint32_t)c->numCUs;
+}
+
+// with_stack picks an OVF kernel only for a BVH deeper than its stack; the map kernels have the buffer at any depth. Each part of
+// a dispatch has its own: their launches run at the same time.
+int overflow_buf(rt_ctx* c, int stack, bool ovf, uint32_t resident, uint32_t** out) {
+    *out = nullptr;
+    if (!ovf || c->maxLeafDepth <= (uint32_t)stack) return 0;
+    DevBuf& ob = c->overflowBuf[c->curLane];
+    int rc = dev_alloc(c, ob, (size_t)(c->maxLeafDepth - stack) * resident * RT_BLOCK * 4);
+    if (rc) return rc;
+    *out = (uint32_t*)ob.p;
+    return 0;
+}
+
+int wave_time_buf(rt_ctx* c, uint32_t blocks, unsigned long long** out) {
+    c->waveTimesCount = (size_t)blocks * (RT_BLOCK / RT_WAVE);
+    int rc = dev_alloc(c, c->waveTimeBuf, c->waveTimesCount * 16);
+    if (rc) return rc;
+    *out = (unsigned long long*)c->waveTimeBuf.p;
+    return 0;
+}
+
+// HIP events around a traversal launch while profiling (harvest_events); the end also counts the launch
+int prof_begin(rt_ctx* c, hipStream_t stream, EventPair** ev) {
+    *ev = nullptr;
+    if (!c->profiling) return 0;
+    if (c->evUsed == c->evPool.size()) {
+        EventPair p;
+        RT_HIP(c, hipEventCreate(&p.a));
+        RT_HIP(c, hipEventCreate(&p.b));
+        c->evPool.push_back(p);
     }
-    uint32_t resident = (uint32_t)perCU * (uint32_t)c->numCUs;
-    // a part of a dispatch that runs beside the other parts' launches takes its share of the resident work-groups (curGridPct)
-    uint32_t blocks = std::min((maxRays + RT_BLOCK - 1) / RT_BLOCK, std::max(1u, (uint32_t)((uint64_t)resident * (uint32_t)c->curGridPct / 100u)));
-    uint32_t* overflow = nullptr;
-    hipStream_t stream = c->curStream ? c->curStream : c->stream;
-    uint32_t* laneCounts = c->curCounts ? c->curCounts : c->q.counts;
-    if (OVF) {
-        const size_t need = (size_t)(c->maxLeafDepth - STACK) * resident * RT_BLOCK * 4;
-        DevBuf& ob = c->curLane ? c->overflowBufSide[c->curLane - 1] : c->overflowBuf;   // launches of different parts run at the same time
-        int rc = dev_alloc(c, ob, need);
-        if (rc) return rc;
-        overflow = (uint32_t*)ob.p;
-    }
-    unsigned long long* waveTimes = nullptr;
-    if (c->phaseStats == 1 || (c->phaseStats >= 2 && c->traceLaunchesTotal == (uint64_t)(c->phaseStats - 2))) {  // 1: the last launch's waves; 2 + k: launch k's (after rt_reset_counters)
-        c->waveTimesCount = (size_t)blocks * (RT_BLOCK / RT_WAVE);
-        int rc = dev_alloc(c, c->waveTimeBuf, c->waveTimesCount * 16);
-        if (rc) return rc;
-        waveTimes = (unsigned long long*)c->waveTimeBuf.p;
-    }
-    // Long rays (the measure the pipeline choice uses) want new rays sooner and their set-up served later: idle lanes re-armed at 12
-    // instead of 16, set-up steps voted in at weight 32 instead of 16 (Sponza 81.0 -> 79.4 ms per step, C5 115.4 -> 114.1;
-    // Cornell + bunny / + dragon, short rays: +2.5 / +3.5 % with the same, so they keep 16 / 16). Knobs set by hand win.
-    const bool longRays = c->boxPerRay >= (double)c->fusedBelowBoxTests;
-    const uint32_t refillMk = c->refillMkSet ? (uint32_t)c->refillMk : (longRays ? 12u : 16u);
-    const uint32_t wSetup = c->wSetupSet ? (uint32_t)c->wSetup : (longRays ? 32u : 16u);
-    TracePwArgs pa{ta.queue, ta.count, laneCounts + 4, refillMk, (uint32_t)c->chunk, wSetup, (uint32_t)c->wLeaf, (uint32_t)c->fastLanes, (uint32_t)c->fastShare,
-                   ta.perRayBox, ta.perRayTri, ta.counters, (unsigned long long*)((char*)c->counterBuf.p + sizeof(DevCounters)), waveTimes, overflow, ta.countAux, ta.countAux2, ta.auxOffset};
-    {
-        const bool stats = hotMode == 0 && c->phaseStats, px = hotMode == 0 && (c->phaseStats || pix);
-        snprintf(c->lastKernel, sizeof c->lastKernel, "k_trace_pw<%d, %s, %s, %s, %s, %d, %d>", STACK, OVF ? "true" : "false", px ? "true" : "false",
-                 stats ? "true" : "false", CULL ? "true" : "false", hotMode == 1 ? HOT6 : hotMode == 2 ? HOT5 : 0, hotMode == 2 ? 5 : 6);
-    }
-    if (hotMode == 1) { if constexpr (HOT6 > 0) hipLaunchKernelGGL((k_trace_pw<STACK, OVF, false, false, CULL, HOT6, 6>), dim3(blocks), dim3(RT_BLOCK), 0, stream, c->sc, c->ps, pa); }
-    else if (hotMode == 2) { if constexpr (HOT5 > 0) hipLaunchKernelGGL((k_trace_pw<STACK, OVF, false, false, CULL, HOT5, 5>), dim3(blocks), dim3(RT_BLOCK), 0, stream, c->sc, c->ps, pa); }
-    else if (c->phaseStats) hipLaunchKernelGGL((k_trace_pw<STACK, OVF, true, true, CULL>), dim3(blocks), dim3(RT_BLOCK), 0, stream, c->sc, c->ps, pa);
-    else if (pix) hipLaunchKernelGGL((k_trace_pw<STACK, OVF, true, false, CULL>), dim3(blocks), dim3(RT_BLOCK), 0, stream, c->sc, c->ps, pa);
-    else hipLaunchKernelGGL((k_trace_pw<STACK, OVF, false, false, CULL>), dim3(blocks), dim3(RT_BLOCK), 0, stream, c->sc, c->ps, pa);
+    *ev = &c->evPool[c->evUsed++];
+    RT_HIP(c, hipEventRecord((*ev)->a, stream));
+    return 0;
+}
+int prof_end(rt_ctx* c, hipStream_t stream, EventPair* ev) {
+    if (ev) RT_HIP(c, hipEventRecord(ev->b, stream));
+    c->traceLaunchesTotal++;
     return 0;
 }
 
@@ -316,18 +363,15 @@ uint32_t fused_batch_pixels(const rt_ctx* c, uint32_t nPixels, uint32_t waves, u
     return best;
 }
 
-// MAPS: k_render_fused_maps<PIX> (a scene that binds an alpha, metalness or bump map; launch_fused), whose one configuration is
-// <24, true, *, true>: everything but the kernel is the same
-template <int STACK, bool OVF, bool CULL, bool MAPS = false>
-int launch_fused_t(rt_ctx* c, const FrameParams& fp, float4* fb) {
-    static_assert(!MAPS || (STACK == 24 && OVF && CULL), "k_render_fused_maps is built for 24 LDS entries, the overflow buffer and culling");
-    int perCU = c->blocksPerCU;
-    if (perCU <= 0) {
-        const hipError_t e = MAPS ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_render_fused_maps<false>, RT_BLOCK, 0)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_render_fused<STACK, OVF, false, CULL>, RT_BLOCK, 0);
-        if (e != hipSuccess || perCU <= 0) perCU = 4;
-    }
-    const uint32_t resident = (uint32_t)perCU * (uint32_t)c->numCUs;
+// The whole dispatch in one launch of k_render_fused, or of k_render_fused_maps for a scene that binds a map (fused_maps)
+int launch_fused(rt_ctx* c, const FrameParams& fp, float4* fb) {
+    EventPair* ev;
+    int rc = prof_begin(c, c->stream, &ev);
+    if (rc) return rc;
+    const FusedChoice k = c->sc.mapFlags  // one kernel, any depth, any objects: <24, true, *, true>
+        ? kernel_choice(c->pixStats ? k_render_fused_maps<true> : k_render_fused_maps<false>, k_render_fused_maps<false>, 24, true, "k_render_fused_maps<%s>", tf(c->pixStats))
+        : with_stack<false>(c->maxLeafDepth, (uint32_t)c->ldsStackCap, c->cull, [&](auto S, auto O, auto C) { return c->pixStats ? fused_kernel<S, O, true, C>() : fused_kernel<S, O, false, C>(); });
+    const uint32_t resident = resident_blocks(c, k.occupancy);
     const uint32_t nSlots = fp.nFrames > 1u ? ((fp.nPixels + 63u) / 64u) * 64u * fp.nFrames : fp.nPixels;  // rt_render_frames: frames are more slots of the same tile (rt_kernels.hip.h: frame_slot)
     // Pixels are replaced as they finish when rays are long (Sponza -7 %, its 1/2 and 1/4 tiles -8 % and -11 %: the wave no
     // longer drains to its slowest pixel once per block) and when a wave gets fewer than five blocks (Cornell + bunny /
@@ -351,103 +395,22 @@ int launch_fused_t(rt_ctx* c, const FrameParams& fp, float4* fb) {
     if (g) batchPixels = std::min((uint32_t)RT_WAVE, (batchPixels + g - 1) / g * g);
     const uint32_t nBatches = g ? ((nSlots + g - 1) / g + batchPixels / g - 1) / (batchPixels / g) : (nSlots + batchPixels - 1) / batchPixels;
     const uint32_t blocks = std::max(1u, std::min((nBatches + (RT_BLOCK / RT_WAVE) - 1) / (RT_BLOCK / RT_WAVE), resident));
-    uint32_t* overflow = nullptr;
-    // (the maps kernel runs with its overflow buffer compiled in whatever the depth: none is needed up to 24 levels)
-    if (OVF && (!MAPS || c->maxLeafDepth > (uint32_t)STACK)) {
-        int rc = dev_alloc(c, c->overflowBuf, (size_t)(c->maxLeafDepth - STACK) * resident * RT_BLOCK * 4);
-        if (rc) return rc;
-        overflow = (uint32_t*)c->overflowBuf.p;
-    }
+    uint32_t* overflow;
+    if ((rc = overflow_buf(c, k.stack, k.ovf, resident, &overflow))) return rc;
     RT_HIP(c, hipMemsetAsync(c->q.counts + 5, 0, 4, c->stream));
     // lanes at interior nodes that make the wave skip the vote: long rays (Sponza: 157 box tests per ray) want the interior step
     // to wait for more lanes (40: -4 %); 24 for short rays and until the scene is measured
     const uint32_t fastLanes = c->fastLanesSet ? (uint32_t)c->fastLanes : (c->boxPerRay >= (double)c->fusedBelowBoxTests ? 40u : 24u);
     const uint32_t wLeaf = (uint32_t)c->wLeafFused;
     unsigned long long* waveTimes = nullptr;
-    if (c->phaseStats) {
-        c->waveTimesCount = (size_t)blocks * (RT_BLOCK / RT_WAVE);
-        int rc = dev_alloc(c, c->waveTimeBuf, c->waveTimesCount * 16);
-        if (rc) return rc;
-        waveTimes = (unsigned long long*)c->waveTimeBuf.p;
-    }
+    if (c->phaseStats && (rc = wave_time_buf(c, blocks, &waveTimes))) return rc;
     FusedArgs fa{c->q.counts + 5, fb, (DevCounters*)c->counterBuf.p, overflow, (uint32_t)c->refill, (uint32_t)c->wSetupFused, wLeaf, fastLanes, batchPixels, g, (uint32_t)c->fastShare, waveTimes, pixelRefill};
     c->lastBatchPixels = (int)batchPixels;
     const FusedKernArgs ka{c->sc, c->ps, fp, fa};
-    if (MAPS) {
-        snprintf(c->lastKernel, sizeof c->lastKernel, "k_render_fused_maps<%s>", c->pixStats ? "true" : "false");
-        if (c->pixStats) hipLaunchKernelGGL((k_render_fused_maps<true>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
-        else hipLaunchKernelGGL((k_render_fused_maps<false>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
-    } else {
-        snprintf(c->lastKernel, sizeof c->lastKernel, "k_render_fused<%d, %s, %s, %s>", STACK, OVF ? "true" : "false", c->pixStats ? "true" : "false", CULL ? "true" : "false");
-        if (c->pixStats) hipLaunchKernelGGL((k_render_fused<STACK, OVF, true, CULL>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
-        else hipLaunchKernelGGL((k_render_fused<STACK, OVF, false, CULL>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
-    }
+    memcpy(c->lastKernel, k.name, sizeof k.name);
+    hipLaunchKernelGGL(k.kernel, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
     RT_HIP(c, hipGetLastError());
-    return 0;
-}
-
-int launch_fused(rt_ctx* c, const FrameParams& fp, float4* fb) {
-    EventPair* ev = nullptr;
-    if (c->profiling) {
-        if (c->evUsed == c->evPool.size()) {
-            EventPair p;
-            RT_HIP(c, hipEventCreate(&p.a));
-            RT_HIP(c, hipEventCreate(&p.b));
-            c->evPool.push_back(p);
-        }
-        ev = &c->evPool[c->evUsed++];
-        RT_HIP(c, hipEventRecord(ev->a, c->stream));
-    }
-    const uint32_t d = c->maxLeafDepth, cap = (uint32_t)c->ldsStackCap;
-    int rc;
-    if (c->sc.mapFlags) rc = launch_fused_t<24, true, true, true>(c, fp, fb);  // a bound map (fused_maps): one kernel, any depth, any objects
-    else if (c->cull) {
-        if (d <= 8) rc = launch_fused_t<8, false, true>(c, fp, fb);
-        else if (cap < 16) rc = launch_fused_t<8, true, true>(c, fp, fb);
-        else if (d <= 16) rc = launch_fused_t<16, false, true>(c, fp, fb);
-        else if (cap < 24) rc = launch_fused_t<16, true, true>(c, fp, fb);
-        else if (d <= 24) rc = launch_fused_t<24, false, true>(c, fp, fb);
-        else rc = launch_fused_t<24, true, true>(c, fp, fb);
-    }
-    else if (d <= 8) rc = launch_fused_t<8, false, false>(c, fp, fb);
-    else if (cap < 16) rc = launch_fused_t<8, true, false>(c, fp, fb);
-    else if (d <= 16) rc = launch_fused_t<16, false, false>(c, fp, fb);
-    else if (cap < 24) rc = launch_fused_t<16, true, false>(c, fp, fb);
-    else if (d <= 24) rc = launch_fused_t<24, false, false>(c, fp, fb);
-    else rc = launch_fused_t<24, true, false>(c, fp, fb);
-    if (rc) return rc;
-    if (ev) RT_HIP(c, hipEventRecord(ev->b, c->stream));
-    c->traceLaunchesTotal++;
-    return 0;
-}
-
-// k_trace_pw_alpha<PIX>: 24 stack entries in LDS and the overflow buffer behind them, object culling compiled in, no top-level
-// table — one kernel for every scene that binds an alpha map (launch_pw_t's launch, without its choices)
-int launch_pw_alpha(rt_ctx* c, uint32_t maxRays, const TraceArgs& ta) {
-    const bool pix = c->pixStats || ta.perRayBox;
-    int perCU = c->blocksPerCU;
-    if (perCU <= 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_trace_pw_alpha<false>, RT_BLOCK, 0) != hipSuccess || perCU <= 0)) perCU = 4;
-    const uint32_t resident = (uint32_t)perCU * (uint32_t)c->numCUs;
-    const uint32_t blocks = std::min((maxRays + RT_BLOCK - 1) / RT_BLOCK, std::max(1u, (uint32_t)((uint64_t)resident * (uint32_t)c->curGridPct / 100u)));
-    hipStream_t stream = c->curStream ? c->curStream : c->stream;
-    uint32_t* laneCounts = c->curCounts ? c->curCounts : c->q.counts;
-    uint32_t* overflow = nullptr;
-    if (c->maxLeafDepth > 24u) {
-        const size_t need = (size_t)(c->maxLeafDepth - 24u) * resident * RT_BLOCK * 4;
-        DevBuf& ob = c->curLane ? c->overflowBufSide[c->curLane - 1] : c->overflowBuf;
-        int rc = dev_alloc(c, ob, need);
-        if (rc) return rc;
-        overflow = (uint32_t*)ob.p;
-    }
-    const bool longRays = c->boxPerRay >= (double)c->fusedBelowBoxTests;
-    const uint32_t refillMk = c->refillMkSet ? (uint32_t)c->refillMk : (longRays ? 12u : 16u);
-    const uint32_t wSetup = c->wSetupSet ? (uint32_t)c->wSetup : (longRays ? 32u : 16u);
-    TracePwArgs pa{ta.queue, ta.count, laneCounts + 4, refillMk, (uint32_t)c->chunk, wSetup, (uint32_t)c->wLeaf, (uint32_t)c->fastLanes, (uint32_t)c->fastShare,
-                   ta.perRayBox, ta.perRayTri, ta.counters, (unsigned long long*)((char*)c->counterBuf.p + sizeof(DevCounters)), nullptr, overflow, ta.countAux, ta.countAux2, ta.auxOffset};
-    snprintf(c->lastKernel, sizeof c->lastKernel, "k_trace_pw_alpha<%s>", pix ? "true" : "false");
-    if (pix) hipLaunchKernelGGL((k_trace_pw_alpha<true>), dim3(blocks), dim3(RT_BLOCK), 0, stream, c->sc, c->ps, pa);
-    else hipLaunchKernelGGL((k_trace_pw_alpha<false>), dim3(blocks), dim3(RT_BLOCK), 0, stream, c->sc, c->ps, pa);
-    return 0;
+    return prof_end(c, c->stream, ev);
 }
 
 template <int STACK>
@@ -461,22 +424,13 @@ void launch_v0_t(rt_ctx* c, uint32_t maxRays, const TraceArgs& ta) {
 int launch_trace(rt_ctx* c, uint32_t maxRays, const TraceArgs& ta) {
     if (maxRays == 0) return 0;
     hipStream_t stream = c->curStream ? c->curStream : c->stream;
-    EventPair* ev = nullptr;
-    if (c->profiling) {
-        if (c->evUsed == c->evPool.size()) {
-            EventPair p;
-            RT_HIP(c, hipEventCreate(&p.a));
-            RT_HIP(c, hipEventCreate(&p.b));
-            c->evPool.push_back(p);
-        }
-        ev = &c->evPool[c->evUsed++];
-        RT_HIP(c, hipEventRecord(ev->a, stream));
-    }
+    EventPair* ev;
+    int rc = prof_begin(c, stream, &ev);
+    if (rc) return rc;
     const uint32_t d = c->maxLeafDepth;
-    int rc = 0;
-    if (c->sc.mapFlags & RT_MAP_ALPHA) {  // a bound alpha map: the one traversal kernel that reads it (any depth, any objects)
-        rc = launch_pw_alpha(c, maxRays, ta);
-    } else if (c->traceVariant == 0) {  // one ray per lane, whole stack in LDS
+    const bool pix = c->pixStats || ta.perRayBox;  // per-ray counters are only needed for the pixel heat maps (debug >= 0) and rt_trace_rays
+    const bool alpha = c->sc.mapFlags & RT_MAP_ALPHA;  // a bound alpha map: the one traversal kernel that reads it (any depth, any objects)
+    if (!alpha && c->traceVariant == 0) {  // one ray per lane, whole stack in LDS
         if (d <= 8) launch_v0_t<8>(c, maxRays, ta);
         else if (d <= 16) launch_v0_t<16>(c, maxRays, ta);
         else if (d <= 24) launch_v0_t<24>(c, maxRays, ta);
@@ -487,30 +441,33 @@ int launch_trace(rt_ctx* c, uint32_t maxRays, const TraceArgs& ta) {
         // BVHs deeper than 24: 16 entries in LDS, the rest in the overflow buffer (the stack only holds far siblings and is rarely
         // that deep), which leaves room for 120 top-level pairs beside six work-groups per CU: C5 at 4K 474 -> 468 ms per step,
         // flattened 471 -> 462, 1080p 117.5 -> 115.6 (Cornell + dragon: level)
-        const bool tableWanted = c->hotPairs && c->sc.hotNodes > 0 && !c->phaseStats && !(c->pixStats || ta.perRayBox);  // (launch_pw_t's condition)
+        const bool tableWanted = c->hotPairs && c->sc.hotNodes > 0 && !c->phaseStats && !pix;  // (choose_trace_pw's condition)
         const uint32_t cap = (d > 24u && c->ldsStackCap >= 24 && tableWanted) ? 16u : (uint32_t)c->ldsStackCap;
-        if (c->cull) {
-            if (d <= 8) rc = launch_pw_t<8, false, true>(c, maxRays, ta);
-            else if (cap < 16) rc = launch_pw_t<8, true, true>(c, maxRays, ta);
-            else if (d <= 16) rc = launch_pw_t<16, false, true>(c, maxRays, ta);
-            else if (cap < 24) rc = launch_pw_t<16, true, true>(c, maxRays, ta);
-            else if (d <= 20) rc = launch_pw_t<20, false, true>(c, maxRays, ta);
-            else if (d <= 24) rc = launch_pw_t<24, false, true>(c, maxRays, ta);
-            else rc = launch_pw_t<24, true, true>(c, maxRays, ta);
-        }
-        else if (d <= 8) rc = launch_pw_t<8, false, false>(c, maxRays, ta);
-        else if (cap < 16) rc = launch_pw_t<8, true, false>(c, maxRays, ta);
-        else if (d <= 16) rc = launch_pw_t<16, false, false>(c, maxRays, ta);
-        else if (cap < 24) rc = launch_pw_t<16, true, false>(c, maxRays, ta);
-        else if (d <= 20) rc = launch_pw_t<20, false, false>(c, maxRays, ta);
-        else if (d <= 24) rc = launch_pw_t<24, false, false>(c, maxRays, ta);
-        else rc = launch_pw_t<24, true, false>(c, maxRays, ta);
+        const TracePwChoice k = alpha
+            ? kernel_choice(pix ? k_trace_pw_alpha<true> : k_trace_pw_alpha<false>, k_trace_pw_alpha<false>, 24, true, "k_trace_pw_alpha<%s>", tf(pix))
+            : with_stack<true>(d, cap, c->cull, [&](auto S, auto O, auto C) { return choose_trace_pw<S, O, C>(c, pix); });
+        const uint32_t resident = resident_blocks(c, k.occupancy);
+        // a part of a dispatch that runs beside the other parts' launches takes its share of the resident work-groups (curGridPct)
+        const uint32_t blocks = std::min((maxRays + RT_BLOCK - 1) / RT_BLOCK, std::max(1u, (uint32_t)((uint64_t)resident * (uint32_t)c->curGridPct / 100u)));
+        uint32_t* overflow;
+        if ((rc = overflow_buf(c, k.stack, k.ovf, resident, &overflow))) return rc;
+        unsigned long long* waveTimes = nullptr;
+        const bool times = c->phaseStats == 1 || (c->phaseStats >= 2 && c->traceLaunchesTotal == (uint64_t)(c->phaseStats - 2));  // 1: the last launch's waves; 2 + k: launch k's (after rt_reset_counters)
+        if (!alpha && times && (rc = wave_time_buf(c, blocks, &waveTimes))) return rc;
+        // Long rays (the measure the pipeline choice uses) want new rays sooner and their set-up served later: idle lanes re-armed at 12
+        // instead of 16, set-up steps voted in at weight 32 instead of 16 (Sponza 81.0 -> 79.4 ms per step, C5 115.4 -> 114.1;
+        // Cornell + bunny / + dragon, short rays: +2.5 / +3.5 % with the same, so they keep 16 / 16). Knobs set by hand win.
+        const bool longRays = c->boxPerRay >= (double)c->fusedBelowBoxTests;
+        const uint32_t refillMk = c->refillMkSet ? (uint32_t)c->refillMk : (longRays ? 12u : 16u);
+        const uint32_t wSetup = c->wSetupSet ? (uint32_t)c->wSetup : (longRays ? 32u : 16u);
+        uint32_t* laneCounts = c->curCounts ? c->curCounts : c->q.counts;
+        const TracePwArgs pa{ta.queue, ta.count, laneCounts + 4, refillMk, (uint32_t)c->chunk, wSetup, (uint32_t)c->wLeaf, (uint32_t)c->fastLanes, (uint32_t)c->fastShare,
+                             ta.perRayBox, ta.perRayTri, ta.counters, (unsigned long long*)((char*)c->counterBuf.p + sizeof(DevCounters)), waveTimes, overflow, ta.countAux, ta.countAux2, ta.auxOffset};
+        memcpy(c->lastKernel, k.name, sizeof k.name);
+        hipLaunchKernelGGL(k.kernel, dim3(blocks), dim3(RT_BLOCK), 0, stream, c->sc, c->ps, pa);
     }
-    if (rc) return rc;
     RT_HIP(c, hipGetLastError());
-    if (ev) RT_HIP(c, hipEventRecord(ev->b, stream));
-    c->traceLaunchesTotal++;
-    return 0;
+    return prof_end(c, stream, ev);
 }
 
 void poll_ray_cost(rt_ctx* c);
@@ -644,7 +601,7 @@ void rt_destroy(rt_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& b : c->sceneBufs) dev_free(b);
     for (DevBuf* b : {&c->matBuf, &c->sphereBuf, &c->sphereMatBuf, &c->objInvBuf, &c->objFwdBuf, &c->objMetaBuf, &c->objBoxBuf, &c->objSkipBuf, &c->maskBoxBuf, &c->emitBuf, &c->emitPreBuf, &c->texelBuf, &c->texInfoBuf, &c->triUVBuf, &c->objTreeBuf, &c->objCostBuf, &c->objAlphaBuf, &c->stateBuf,
-                      &c->queueBuf, &c->fbBuf, &c->counterBuf, &c->scratchBuf, &c->overflowBuf, &c->waveTimeBuf, &c->probeBuf})
+                      &c->queueBuf, &c->fbBuf, &c->counterBuf, &c->scratchBuf, &c->waveTimeBuf, &c->probeBuf})
         dev_free(*b);
     (void)rt_comm_destroy(c);
     dev_free(c->gatherBuf);
@@ -659,8 +616,8 @@ void rt_destroy(rt_ctx* c) {
         if (c->joinEvent[l]) (void)hipEventDestroy(c->joinEvent[l]);
         if (c->pollEventSide[l]) (void)hipEventDestroy(c->pollEventSide[l]);
         if (c->sideStream[l]) (void)hipStreamDestroy(c->sideStream[l]);
-        dev_free(c->overflowBufSide[l]);
     }
+    for (DevBuf& b : c->overflowBuf) dev_free(b);
     if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
     delete c;
 }
