@@ -343,6 +343,34 @@ int  rt_read_rgba8_srgb(rt_ctx* ctx, uint8_t* hostOut, size_t nBytes);
  * each), for kernel-level parity tests. Synchronous. */
 int  rt_trace_rays(rt_ctx* ctx, uint32_t n, const float* origins, const float* dirs, RtHit* hitsOut);
 
+/* First-hit AOVs: one pass over the rows y = row0 + k*rowStride, k in [0,nRows) of a width x height image, as rt_render has
+ * them. It shoots each pixel's camera ray (origin camInfo.pos, the direction every sample of the pixel starts with in
+ * rt_render: the reference does not jitter, raytrace.comp:547-556) and writes calculateIntersections' closest hit for it into
+ * per-pixel planes: the same record, bit for bit, as rt_trace_rays returns for that ray, with the counts of rayTraceParams and
+ * alpha maps cutting hits out as in rendering. Each non-NULL field holds nRows*width*4 elements; pixel (k, x) starts at
+ * (k*width + x)*4, the order of rt_render's d_rgba. */
+typedef struct RtAovBuffers {
+    float*    normalDepth; /* xyz: hit normal as RtHit has it (unit, turned towards the side the ray came from, bump-tilted where
+                            * a bump map binds); w: hit dst along the unit camera ray. Miss: (0, 0, 0, RT_MISS_DST) */
+    float*    position;    /* xyz: hit point (world); w: 1 on a hit. Miss: all 0 */
+    float*    albedo;      /* rgb: the material's albedo; a triangle hit whose material binds an uploaded albedo map multiplies it
+                            * by the texel as the diffuse branch of shading does. Spheres are untextured. a: 1 on a hit. Miss: all 0 */
+    float*    rayDir;      /* xyz: the camera ray's direction; w: 0 */
+    uint32_t* ids;         /* x: object index, or sphere index; y: triangle index (0 for spheres); z: material index;
+                            * w: bit 0 hit, bit 1 sphere, bit 2 frontFace. Miss: (~0u, ~0u, ~0u, 0) */
+} RtAovBuffers;
+/* Asynchronous on the ctx stream, like rt_render, and checked like it (geometry, rows, scene, counts). d_out: device planes
+ * (NULL fields are skipped), or NULL: the ctx keeps all five (rt_read_aovs). The pass runs the ordinary traversal kernel
+ * (rt_last_kernel names it) and changes nothing a later rt_render produces: not the ctx framebuffer nor its progressive
+ * history, not the pipeline, parts or ray-cost choices. Its traversal work goes to boxTests, triTests, skippedBoxTests,
+ * raysTraced, raysHit and traceLaunches of rt_get_counters, from a counter block of its own that the ray-cost measurement
+ * never reads; rt_reset_counters clears it. */
+int  rt_render_aovs(rt_ctx* ctx, const PushConstants* pc, uint32_t width, uint32_t height,
+                    uint32_t row0, uint32_t rowStride, uint32_t nRows, const RtAovBuffers* d_out);
+/* copies the ctx-owned planes of the last rt_render_aovs(…, NULL) to the non-NULL host fields (nPixels = nRows*width of that
+ * pass); blocks */
+int  rt_read_aovs(rt_ctx* ctx, const RtAovBuffers* hostOut, size_t nPixels);
+
 int  rt_get_counters(rt_ctx* ctx, RtCounters* out);
 int  rt_reset_counters(rt_ctx* ctx);
 /* When enabled, every traversal-kernel launch is bracketed by HIP events on

@@ -97,6 +97,11 @@ class RtHit(C.Structure):
                 ("boxTests", C.c_uint32), ("triTests", C.c_uint32)]
 
 
+class RtAovBuffers(C.Structure):
+    _fields_ = [("normalDepth", C.c_void_p), ("position", C.c_void_p), ("albedo", C.c_void_p), ("rayDir", C.c_void_p),
+                ("ids", C.c_void_p)]
+
+
 # every symbol include/rt_amd.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 _vp = C.c_void_p
@@ -142,6 +147,8 @@ SYMBOLS = {
     "rt_read_rgba_f32": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
     "rt_read_rgba8_srgb": (C.c_int, [_vp, _P(C.c_uint8), C.c_size_t]),
     "rt_trace_rays": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), _P(C.c_float), _P(RtHit)]),
+    "rt_render_aovs": (C.c_int, [_vp, _P(PushConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(RtAovBuffers)]),
+    "rt_read_aovs": (C.c_int, [_vp, _P(RtAovBuffers), C.c_size_t]),
     "rt_get_counters": (C.c_int, [_vp, _P(RtCounters)]),
     "rt_reset_counters": (C.c_int, [_vp]),
     "rt_set_profiling": (C.c_int, [_vp, C.c_int]),

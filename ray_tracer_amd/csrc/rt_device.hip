@@ -149,6 +149,12 @@ struct rt_ctx {
     DevBuf waveTimeBuf;     // phase_stats: per-wave start/end clocks of the last k_trace_pw launch
     size_t waveTimesCount = 0;
     bool pixStats = false;  // this dispatch needs per-pixel box/triangle counts (debug heat maps)
+    // first-hit AOV passes (rt_render_aovs): the ctx-owned planes of the last pass into them, and a counter block of their own, which
+    // rt_get_counters adds to the rendering counters and the ray-cost snapshots never see
+    DevBuf aovBuf, aovCounterBuf;
+    uint32_t aovPixels = 0;
+    bool aovValid = false;
+    uint64_t aovLaunches = 0;
 
     int fail(const std::string& m) { error = m; return -1; }
     int hip(hipError_t e, const char* what) {
@@ -590,6 +596,8 @@ int rt_create(int device, rt_ctx** out) {
     if (hipEventCreateWithFlags(&c->pollEvent, hipEventDisableTiming) != hipSuccess) { c->pollEvent = nullptr; rt_destroy(c); return -6; }
     if (dev_alloc(c, c->counterBuf, sizeof(DevCounters) + 256) != 0) { rt_destroy(c); return -7; }
     (void)hipMemsetAsync(c->counterBuf.p, 0, sizeof(DevCounters) + 256, c->stream);
+    if (dev_alloc(c, c->aovCounterBuf, sizeof(DevCounters)) != 0) { rt_destroy(c); return -7; }
+    (void)hipMemsetAsync(c->aovCounterBuf.p, 0, sizeof(DevCounters), c->stream);
     (void)hipStreamSynchronize(c->stream);
     *out = c;
     return 0;
@@ -601,7 +609,7 @@ void rt_destroy(rt_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& b : c->sceneBufs) dev_free(b);
     for (DevBuf* b : {&c->matBuf, &c->sphereBuf, &c->sphereMatBuf, &c->objInvBuf, &c->objFwdBuf, &c->objMetaBuf, &c->objBoxBuf, &c->objSkipBuf, &c->maskBoxBuf, &c->emitBuf, &c->emitPreBuf, &c->texelBuf, &c->texInfoBuf, &c->triUVBuf, &c->objTreeBuf, &c->objCostBuf, &c->objAlphaBuf, &c->stateBuf,
-                      &c->queueBuf, &c->fbBuf, &c->counterBuf, &c->scratchBuf, &c->waveTimeBuf, &c->probeBuf})
+                      &c->queueBuf, &c->fbBuf, &c->counterBuf, &c->scratchBuf, &c->waveTimeBuf, &c->probeBuf, &c->aovBuf, &c->aovCounterBuf})
         dev_free(*b);
     (void)rt_comm_destroy(c);
     dev_free(c->gatherBuf);
@@ -1130,16 +1138,50 @@ extern "C" {
 }  // extern "C"
 
 namespace {
+// The checks rt_render and rt_render_aovs share: the tile's geometry, an uploaded scene, the counts of rayTraceParams
+int check_tile(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride, uint32_t nRows,
+               const char* fn) {
+    if (width == 0 || height == 0 || rowStride == 0) return c->fail(std::string(fn) + ": bad image geometry");
+    if (nRows && (uint64_t)row0 + (uint64_t)(nRows - 1) * rowStride >= height) return c->fail(std::string(fn) + ": rows exceed the image");
+    if (!c->sc.nodes) return c->fail(std::string(fn) + " before rt_upload_scene");
+    const RayTracerData& td = pc->rayTraceParams;
+    if (td.sphereCount > c->sc.sphereCount) return c->fail("rayTraceParams.sphereCount exceeds the uploaded spheres");
+    if (td.objectCount > c->sc.objectCount) return c->fail("rayTraceParams.objectCount exceeds the uploaded objects");
+    return 0;
+}
+
+// The scene of a dispatch: the uploaded one with the counts of rayTraceParams
+DevScene dispatch_scene(const rt_ctx* c, const RayTracerData& td) {
+    DevScene sc = c->sc;
+    sc.sphereCount = td.sphereCount;
+    sc.objectCount = td.objectCount;
+    if (sc.objectCount < c->sc.objectCount) { sc.reachCount = 0; sc.objTreeLevels = 0; }  // a dispatch with fewer objects than were uploaded: no masks, no object hierarchy
+    return sc;
+}
+
+// The camera and tile of a dispatch (host side of raytrace.comp:547-556; primary_dir is the device side)
+FrameParams frame_camera(const rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
+                         uint32_t nRows, uint32_t nPixels) {
+    FrameParams fp{};
+    memcpy(fp.camRot, pc->camInfo.cameraRotation, 64);
+    memcpy(fp.camPos, pc->camInfo.pos, 12);
+    fp.planeHeight = pc->camInfo.nearPlane * rt_tan(rt_radians(pc->camInfo.fov * 0.5f)) * 2.f;
+    fp.planeWidth = fp.planeHeight * pc->camInfo.aspectRatio;
+    fp.bottomLeft[0] = -fp.planeWidth / 2.f;
+    fp.bottomLeft[1] = -fp.planeHeight / 2.f;
+    fp.bottomLeft[2] = 0.1f;
+    fp.tiled = (c->tileSlots && (width % 8u) == 0u) ? 1u : 0u;
+    fp.width = width; fp.height = height; fp.row0 = row0; fp.rowStride = rowStride; fp.nRows = nRows; fp.nPixels = nPixels;
+    return fp;
+}
+
 // rt_render (nFrames = 1) and rt_render_frames
 int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
                 uint32_t nRows, uint32_t nFrames, float* d_rgba) {
     if (!c || !pc) return -1;
-    if (width == 0 || height == 0 || rowStride == 0) return c->fail("rt_render: bad image geometry");
-    if (nRows && (uint64_t)row0 + (uint64_t)(nRows - 1) * rowStride >= height) return c->fail("rt_render: rows exceed the image");
-    if (!c->sc.nodes) return c->fail("rt_render before rt_upload_scene");
+    int rc = check_tile(c, pc, width, height, row0, rowStride, nRows, "rt_render");
+    if (rc) return rc;
     const RayTracerData& td = pc->rayTraceParams;
-    if (td.sphereCount > c->sc.sphereCount) return c->fail("rayTraceParams.sphereCount exceeds the uploaded spheres");
-    if (td.objectCount > c->sc.objectCount) return c->fail("rayTraceParams.objectCount exceeds the uploaded objects");
     if (td.bounceLimit >= (1u << 28) - 1u) return c->fail("rayTraceParams.bounceLimit needs more than 28 bits");
     const uint64_t np64 = (uint64_t)nRows * width;
     if ((np64 + 63) / 64 * 64 * nFrames >= (1ull << 30)) return c->fail("tile too large (slot ids are 30 bits)");
@@ -1147,7 +1189,7 @@ int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t hei
     RT_HIP(c, hipSetDevice(c->device));
     if (nPixels == 0) return 0;
 
-    int rc = ensure_state(c, nFrames > 1u ? (nPixels + 63u) / 64u * 64u * nFrames : nPixels);
+    rc = ensure_state(c, nFrames > 1u ? (nPixels + 63u) / 64u * 64u * nFrames : nPixels);
     if (rc) return rc;
     float4* fb = (float4*)d_rgba;
     if (!fb) {
@@ -1160,16 +1202,7 @@ int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t hei
     }
 
     // ---- per-frame constants (host side of raytrace.comp:547-564)
-    FrameParams fp{};
-    memcpy(fp.camRot, pc->camInfo.cameraRotation, 64);
-    memcpy(fp.camPos, pc->camInfo.pos, 12);
-    fp.planeHeight = pc->camInfo.nearPlane * rt_tan(rt_radians(pc->camInfo.fov * 0.5f)) * 2.f;
-    fp.planeWidth = fp.planeHeight * pc->camInfo.aspectRatio;
-    fp.bottomLeft[0] = -fp.planeWidth / 2.f;
-    fp.bottomLeft[1] = -fp.planeHeight / 2.f;
-    fp.bottomLeft[2] = 0.1f;
-    fp.tiled = (c->tileSlots && (width % 8u) == 0u) ? 1u : 0u;
-    fp.width = width; fp.height = height; fp.row0 = row0; fp.rowStride = rowStride; fp.nRows = nRows; fp.nPixels = nPixels;
+    FrameParams fp = frame_camera(c, pc, width, height, row0, rowStride, nRows, nPixels);
     uint32_t lol = pc->frameCount;
     fp.startingSeed = (uint32_t)(rt_random(&lol) * 23892183.f);
     fp.samples = td.singleRender ? td.sampleLimit : td.raysPerPixel;
@@ -1184,10 +1217,7 @@ int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t hei
     fp.env = pc->environment;
 
     c->pixStats = td.debug >= 0;
-    DevScene sc = c->sc;
-    sc.sphereCount = td.sphereCount;
-    sc.objectCount = td.objectCount;
-    if (sc.objectCount < c->sc.objectCount) { sc.reachCount = 0; sc.objTreeLevels = 0; }  // a dispatch with fewer objects than were uploaded: no masks, no object hierarchy
+    DevScene sc = dispatch_scene(c, td);
     // c->sc holds this dispatch's counts while the launches are built; whatever way the function is left, the uploaded scene comes back
     struct SceneGuard {
         rt_ctx* c; DevScene saved;
@@ -1452,17 +1482,83 @@ int rt_trace_rays(rt_ctx* c, uint32_t n, const float* origins, const float* dirs
     return harvest_events(c);
 }
 
+int rt_render_aovs(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
+                   uint32_t nRows, const RtAovBuffers* d_out) {
+    if (!c || !pc) return -1;
+    int rc = check_tile(c, pc, width, height, row0, rowStride, nRows, "rt_render_aovs");
+    if (rc) return rc;
+    const uint64_t np64 = (uint64_t)nRows * width;
+    if (np64 >= (1ull << 30)) return c->fail("rt_render_aovs: tile too large (slot ids are 30 bits)");
+    const uint32_t nPixels = (uint32_t)np64;
+    RT_HIP(c, hipSetDevice(c->device));
+    if (nPixels == 0) return 0;
+    // The pass's rays live in path-state slots [0, nPixels) and its ray count in the first part's counters: the ctx stream orders it
+    // after a dispatch still in flight (whose parts join the ctx stream before it ends). Growing the path state frees the old one,
+    // so that waits for the device first.
+    if (c->capacity < nPixels || !c->stateBuf.p) RT_HIP(c, hipStreamSynchronize(c->stream));
+    if ((rc = ensure_state(c, nPixels))) return rc;
+    AovOut out;
+    if (d_out) {
+        out = AovOut{(float4*)d_out->normalDepth, (float4*)d_out->position, (float4*)d_out->albedo, (float4*)d_out->rayDir, (uint4*)d_out->ids};
+    } else {
+        if ((rc = dev_alloc(c, c->aovBuf, (size_t)nPixels * sizeof(float4) * 5))) return rc;
+        float4* p = (float4*)c->aovBuf.p;
+        out = AovOut{p, p + nPixels, p + 2 * (size_t)nPixels, p + 3 * (size_t)nPixels, (uint4*)(p + 4 * (size_t)nPixels)};
+        c->aovPixels = nPixels;
+        c->aovValid = true;
+    }
+    FrameParams fp = frame_camera(c, pc, width, height, row0, rowStride, nRows, nPixels);
+    fp.nFrames = 1;
+    // launch_trace reads what the dispatches leave behind: this pass gets its scene counts, no per-pixel statistics (a heat-map
+    // render leaves pixStats set) and no phase statistics, and its launch is counted apart; everything comes back afterwards
+    struct PassGuard {
+        rt_ctx* c; DevScene sc; bool pixStats; int phaseStats; uint64_t launches;
+        ~PassGuard() {
+            c->aovLaunches += c->traceLaunchesTotal - launches;
+            c->sc = sc; c->pixStats = pixStats; c->phaseStats = phaseStats; c->traceLaunchesTotal = launches;
+        }
+    } guard{c, c->sc, c->pixStats, c->phaseStats, c->traceLaunchesTotal};
+    c->sc = dispatch_scene(c, pc->rayTraceParams);
+    c->pixStats = false;
+    c->phaseStats = 0;
+    const uint32_t blocks = (nPixels + RT_BLOCK - 1) / RT_BLOCK;
+    hipLaunchKernelGGL(k_aov_rays, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, c->ps, fp);
+    hipLaunchKernelGGL(k_init_counts, dim3(1), dim3(64), 0, c->stream, c->q.counts, nPixels);
+    RT_HIP(c, hipGetLastError());
+    const TraceArgs ta{nullptr, c->q.counts, nullptr, nullptr, (DevCounters*)c->aovCounterBuf.p};
+    if ((rc = launch_trace(c, nPixels, ta))) return rc;
+    hipLaunchKernelGGL(k_aov_resolve, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, c->ps, fp, out);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rt_read_aovs(rt_ctx* c, const RtAovBuffers* out, size_t nPixels) {
+    if (!c || !out) return -1;
+    if (!c->aovValid) return c->fail("no ctx-owned AOV planes: rt_render_aovs was never called with d_out = NULL");
+    if (nPixels != (size_t)c->aovPixels) return c->fail("rt_read_aovs: size mismatch");
+    RT_HIP(c, hipSetDevice(c->device));
+    const float4* p = (const float4*)c->aovBuf.p;
+    void* const dst[5] = {out->normalDepth, out->position, out->albedo, out->rayDir, out->ids};
+    for (int k = 0; k < 5; k++)
+        if (dst[k]) RT_HIP(c, hipMemcpyAsync(dst[k], p + (size_t)k * nPixels, nPixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int rt_get_counters(rt_ctx* c, RtCounters* out) {
     if (!c || !out) return -1;
     RT_HIP(c, hipSetDevice(c->device));
-    DevCounters h;
+    DevCounters h, a;
     RT_HIP(c, hipMemcpyAsync(&h, c->counterBuf.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipMemcpyAsync(&a, c->aovCounterBuf.p, sizeof(a), hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    out->boxTests = h.boxTests; out->triTests = h.triTests; out->raysTraced = h.raysTraced; out->raysHit = h.raysHit;
+    // the AOV passes' block holds traversal work only (rt_render_aovs)
+    out->boxTests = h.boxTests + a.boxTests; out->triTests = h.triTests + a.triTests;
+    out->raysTraced = h.raysTraced + a.raysTraced; out->raysHit = h.raysHit + a.raysHit;
     out->raysReference = h.raysReference; out->paths = h.paths; out->segments = h.segments;
-    out->traceLaunches = c->traceLaunchesTotal;
+    out->traceLaunches = c->traceLaunchesTotal + c->aovLaunches;
     out->emitterTests = h.emitterTests;
-    out->skippedBoxTests = h.skippedBoxTests;
+    out->skippedBoxTests = h.skippedBoxTests + a.skippedBoxTests;
     if (c->phaseStats) {
         unsigned long long ps[21];
         RT_HIP(c, hipMemcpy(ps, (char*)c->counterBuf.p + sizeof(DevCounters), sizeof(ps), hipMemcpyDeviceToHost));
@@ -1500,11 +1596,12 @@ int rt_reset_counters(rt_ctx* c) {
     RT_HIP(c, hipStreamSynchronize(c->stream));
     poll_ray_cost(c);  // a snapshot of the last dispatch's counters has arrived by now: what it says about the scene's rays is kept
     RT_HIP(c, hipMemsetAsync(c->counterBuf.p, 0, sizeof(DevCounters) + 256, c->stream));
+    RT_HIP(c, hipMemsetAsync(c->aovCounterBuf.p, 0, sizeof(DevCounters), c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     c->snapPending = false;
     c->snapBox = 0; c->snapRays = 0; c->snapSeg = 0; c->snapPaths = 0;
     int rc = harvest_events(c);
-    c->traceMs = 0.0; c->traceLaunches = 0; c->traceLaunchesTotal = 0;
+    c->traceMs = 0.0; c->traceLaunches = 0; c->traceLaunchesTotal = 0; c->aovLaunches = 0;
     c->traceSpans.clear();
     return rc;
 }

@@ -1822,6 +1822,56 @@ __global__ __launch_bounds__(RT_BLOCK) void k_seed_rays(DevScene sc, PathState p
     if (i < n) ps.hit(RAY_MAIN)[i] = sphere_seed(sc, f4xyz(ps.rayO()[i]), f4xyz(ps.rayD()[i]));
 }
 
+// ---------------------------------------------------------------- first-hit AOVs (rt_render_aovs)
+// One pass of a tile's camera rays through the ordinary traversal, and the hit records turned into per-pixel planes. Slot i is the
+// pixel slot_to_pixel gives it (8x8 blocks per wave, as k_raygen), so the rays of a wave are coherent in the traversal.
+struct AovOut { float4 *normalDepth, *position, *albedo, *rayDir; uint4* ids; };  // NULL: plane not wanted; pixel (k, x) at k * width + x
+
+// the camera ray every sample of the pixel starts with (init_path) and its sphere seed (k_seed_rays)
+__global__ __launch_bounds__(RT_BLOCK) void k_aov_rays(DevScene sc, PathState ps, FrameParams fp) {
+    const uint32_t slot = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (slot >= fp.nPixels) return;
+    uint32_t gx, gy, krow;
+    slot_to_pixel(fp, slot, gx, gy, krow);
+    const rt_vec3 ro = rt_v3(fp.camPos[0], fp.camPos[1], fp.camPos[2]), rd = primary_dir(fp, gx, gy);
+    ps.rayO()[slot] = mk4(ro, 0.f);
+    ps.rayD()[slot] = mk4(rd, 0.f);
+    ps.hit(RAY_MAIN)[slot] = sphere_seed(sc, ro, rd);
+}
+
+// The traversal's {dst, object, triangle} -> the RtHit fields of k_hit_details (reconstruct_hit<true>: bump-tilted normals) and
+// the albedo the diffuse branch of shade_path would use; one 16-byte store per plane and pixel, in pixel order
+__global__ __launch_bounds__(RT_BLOCK) void k_aov_resolve(DevScene sc, PathState ps, FrameParams fp, AovOut out) {
+    const uint32_t slot = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (slot >= fp.nPixels) return;
+    uint32_t gx, gy, krow;
+    slot_to_pixel(fp, slot, gx, gy, krow);
+    const size_t px = (size_t)krow * fp.width + gx;
+    const rt_vec3 ro = f4xyz(ps.rayO()[slot]), rd = f4xyz(ps.rayD()[slot]);
+    const float4 hm = ps.hit(RAY_MAIN)[slot];
+    const uint32_t obj = __float_as_uint(hm.y), tri = __float_as_uint(hm.z);
+    float4 normalDepth = make_float4(0.f, 0.f, 0.f, hm.x), position = make_float4(0.f, 0.f, 0.f, 0.f), albedo = position;
+    uint4 ids = make_uint4(RT_HIT_NONE, RT_HIT_NONE, RT_HIT_NONE, 0u);
+    if (obj != RT_HIT_NONE) {
+        const bool sphere = (obj & RT_HIT_SPHERE) != 0u;
+        const FullHit f = reconstruct_hit<true>(sc, ro, rd, obj, tri);
+        const float4* mp = rt_global(sc.mats) + 3 * f.materialIndex;
+        const float4 mA = mp[0];
+        rt_vec3 a = rt_v3(mA.x, mA.y, mA.z);
+        const uint32_t texSlot = __float_as_uint(mp[2].y);   // albedoIndex; 0xffffffff (-1) = none
+        if (texSlot < sc.texCount && !sphere) a = rt_mul(a, albedo_texel(sc, texSlot, tri, obj, ro, rd));
+        normalDepth = mk4(f.normal, hm.x);
+        position = mk4(f.hitPoint, 1.f);
+        albedo = mk4(a, 1.f);
+        ids = make_uint4(obj & ~RT_HIT_SPHERE, sphere ? 0u : tri, f.materialIndex, 1u | (sphere ? 2u : 0u) | (f.frontFace ? 4u : 0u));
+    }
+    if (out.normalDepth) out.normalDepth[px] = normalDepth;
+    if (out.position) out.position[px] = position;
+    if (out.albedo) out.albedo[px] = albedo;
+    if (out.rayDir) out.rayDir[px] = mk4(rd, 0.f);
+    if (out.ids) out.ids[px] = ids;
+}
+
 // ---------------------------------------------------------------- misc kernels
 // start of a multi-kernel dispatch: n active paths and n rays in buffer 0, nothing in buffer 1, work counter 0
 __global__ void k_init_counts(uint32_t* counts, uint32_t n) {

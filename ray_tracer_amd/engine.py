@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtCounters, RtHit, RtPlacement,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAovBuffers, RtCounters, RtHit, RtPlacement,
                     RtSceneArrays, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -222,6 +222,7 @@ class Renderer:
         self._frameNumber = 0
         self._scene = None
         self._shape = None
+        self._aov_shape = None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -353,6 +354,43 @@ class Renderer:
                     "rt_trace_rays")
         return hits
 
+    def render_aovs(self, pc, width, height, row0=0, rowStride=1, nRows=None, out_ptrs=None, sync=True):
+        """First-hit planes of the tile's camera rays (rt_render_aovs), for the rows render() would render. Returns the dict of
+        aovs_to_numpy, arrays shaped (nRows, width[, 3]); with `out_ptrs` (device pointers keyed by the RtAovBuffers field names,
+        e.g. a torch tensor's data_ptr(); planes left out are not written) the pass writes there and returns None."""
+        if nRows is None:
+            nRows = (height - row0 + rowStride - 1) // rowStride
+        d = None
+        if out_ptrs is not None:
+            unknown = set(out_ptrs) - set(AOV_PLANES)
+            if unknown:
+                raise KeyError(f"not an RtAovBuffers field: {sorted(unknown)}")
+            d = RtAovBuffers(**{k: v for k, v in out_ptrs.items() if v})
+        self.fill_counts(pc)
+        self._check(self._l.rt_render_aovs(self._h, C.byref(pc), width, height, row0, rowStride, nRows,
+                                           C.byref(d) if d is not None else None), "rt_render_aovs")
+        if d is None:
+            self._aov_shape = (nRows, width)
+        if not sync:
+            return None
+        self.sync()
+        return None if d is not None else self.read_aovs()
+
+    def read_aovs(self):
+        """The context's own planes of the last render_aovs() without `out_ptrs` (rt_read_aovs), as aovs_to_numpy gives them."""
+        n, w = self._aov_shape or (0, 0)
+        planes = {k: np.empty((n, w, 4), np.uint32 if k == "ids" else np.float32) for k in AOV_PLANES}
+        b = RtAovBuffers(**{k: v.ctypes.data for k, v in planes.items()})
+        self._check(self._l.rt_read_aovs(self._h, C.byref(b), n * w), "rt_read_aovs")
+        return aovs_to_numpy(planes)
+
+    def pick(self, pc, width, height, x, y):
+        """What the camera ray of pixel (x, y) hits: one row of render_aovs(), the record at x (scalars and 3-vectors)."""
+        if not (0 <= x < width and 0 <= y < height):
+            raise ValueError(f"pixel ({x}, {y}) is outside the {width} x {height} image")
+        a = self.render_aovs(pc, width, height, row0=y, rowStride=1, nRows=1)
+        return {k: (v[0, x].copy() if v.ndim == 3 else v[0, x].item()) for k, v in a.items()}
+
     def counters(self):
         c = RtCounters()
         self._check(self._l.rt_get_counters(self._h, C.byref(c)), "rt_get_counters")
@@ -448,6 +486,18 @@ class Renderer:
         g = C.c_double()
         self._check(self._l.rt_measure_copy_bandwidth(self._h, nbytes, iters, C.byref(g)), "copy bandwidth")
         return g.value
+
+
+AOV_PLANES = ("normalDepth", "position", "albedo", "rayDir", "ids")   # the fields of RtAovBuffers
+
+
+def aovs_to_numpy(planes):
+    """The five (nRows, width, 4) planes of rt_render_aovs (float32, ids uint32) -> named arrays shaped (nRows, width[, 3])."""
+    nd, ids = planes["normalDepth"], planes["ids"]
+    return dict(depth=nd[..., 3].copy(), normal=nd[..., :3].copy(), position=planes["position"][..., :3].copy(),
+                albedo=planes["albedo"][..., :3].copy(), ray_dir=planes["rayDir"][..., :3].copy(), object=ids[..., 0].copy(),
+                triangle=ids[..., 1].copy(), material=ids[..., 2].copy(), hit=(ids[..., 3] & 1) != 0,
+                sphere=(ids[..., 3] & 2) != 0, front_face=(ids[..., 3] & 4) != 0)
 
 
 def hits_to_numpy(hits):

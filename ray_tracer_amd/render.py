@@ -63,6 +63,9 @@ def build_parser():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="several processes: nccl (= RCCL, one GPU per rank); gloo lets all ranks share --device (rehearsal on one GPU)")
     ap.add_argument("--out", help="PNG (8-bit sRGB) or .npy (fp32 RGBA) output file")
+    ap.add_argument("--aov-out", metavar="FILE.npz",
+                    help="also write the first-hit planes of the camera rays (Renderer.render_aovs: depth, normal, position, albedo, "
+                         "ray_dir, object, triangle, material, hit, sphere, front_face) to this .npz")
     # Ray Tracer Info panel
     ap.add_argument("--progressive", action="store_true")
     ap.add_argument("--frames-in-flight", type=int, default=1,
@@ -137,6 +140,22 @@ def srgb8(img):
     return (np.concatenate([rgb, v[..., 3:]], axis=-1) * 255.0 + 0.5).astype(np.uint8)
 
 
+def gather_planes(planes, height, world, rank, on):
+    """Each rank's rows of the AOV planes -> the whole image's on rank 0 (None elsewhere), through tiling.gather_frame. The
+    planes travel as int32 (uint32 ids) and uint8 (flags) tensors, which every backend gathers."""
+    import torch
+    from . import tiling
+    out = {}
+    for k, a in planes.items():
+        wire = a.view(np.int32) if a.dtype == np.uint32 else a.view(np.uint8) if a.dtype == np.bool_ else a
+        strip = torch.from_numpy(np.ascontiguousarray(wire)).to(on)
+        frame = torch.zeros((height,) + tuple(strip.shape[1:]), dtype=strip.dtype, device=on) if rank == 0 else None
+        tiling.gather_frame(strip, frame, height, world, rank)
+        if rank == 0:
+            out[k] = frame.cpu().numpy().view(a.dtype)
+    return out if rank == 0 else None
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -177,8 +196,11 @@ def main(argv=None):
         frames += 1
         if not args.progressive and not args.single_render:
             break  # every further dispatch would be this very frame again (frameCount does not advance)
+    aovs = r.render_aovs(pc, W, H, **tile) if args.aov_out else None
+    on = f"cuda:{device}" if args.backend == "nccl" else "cpu"
+    if world > 1 and aovs is not None:
+        aovs = gather_planes(aovs, H, world, rank, on)
     if world > 1 and img is not None:   # strips -> frame on rank 0
-        on = f"cuda:{device}" if args.backend == "nccl" else "cpu"
         strip = torch.from_numpy(img).to(on)
         frame = torch.zeros((H, W, 4), dtype=torch.float32, device=on) if rank == 0 else None
         tiling.gather_frame(strip, frame, H, world, rank)
@@ -200,6 +222,9 @@ def main(argv=None):
                 from PIL import Image
                 Image.fromarray((srgb8(img) if world > 1 else r.read_rgba8_srgb())[..., :3]).save(args.out)
             print("wrote", args.out)
+        if aovs is not None:
+            np.savez(args.aov_out, **aovs)
+            print("wrote", args.aov_out)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -95,6 +95,13 @@ class InteractiveSession:
         self.frameTime = (time.perf_counter() - t0) * 1e3
         return img
 
+    # ---- what is under the cursor: the camera ray of pixel (x, y) with the session's current camera (Renderer.pick)
+    def pick(self, x, y):
+        """The first hit of pixel (x, y): object / sphere, triangle and material index, depth, normal, point and albedo. The
+        index feeds the editors below (set_object, set_sphere, set_material); nothing of the progressive image changes."""
+        self._rotation()
+        return self.r.pick(self.pc, self.W, self.H, int(x), int(y))
+
     # ---- the editors and their "Update Buffer" buttons (:1536-1618)
     def _arrays(self):
         if self._edited is None:
