@@ -371,6 +371,34 @@ int  rt_render_aovs(rt_ctx* ctx, const PushConstants* pc, uint32_t width, uint32
  * pass); blocks */
 int  rt_read_aovs(rt_ctx* ctx, const RtAovBuffers* hostOut, size_t nPixels);
 
+/* Edge-avoiding a-trous denoiser over a whole width x height frame (the spatial filter of SVGF, Schied et al. 2017, after
+ * Dammertz et al. 2010; DESIGN.md, "Denoising"). Pixel p is filtered when ids.w & 1 (a hit), ids.z < the material count and
+ * that material's emissionStrength == 0, all in the ctx's current material table; every other pixel (misses, emitters) is kept:
+ * copied bit for bit and never anyone's neighbour. The filter demodulates e = rgb / max(albedo, 1e-3), estimates the luminance
+ * variance over the 5 x 5 window and the depth gradient, runs `iterations` edge-stopping passes with steps 1, 2, 4, ... and
+ * remodulates; alpha is copied. */
+typedef struct RtDenoiseParams {
+    uint32_t iterations;      /* K: a-trous passes, 0..10 (pass k steps 2^k pixels); 0 copies the frame */
+    float    sigmaLuminance;  /* σl > 0 */
+    float    sigmaNormal;     /* σn >= 0 (0: normals do not stop the filter) */
+    float    sigmaDepth;      /* σz > 0 */
+} RtDenoiseParams;
+void rt_denoise_params_default(RtDenoiseParams* p);          /* 5, 4, 128, 1 (SVGF's published values) */
+/* Asynchronous on the ctx stream. d_rgba: the noisy RGBA fp32 frame on the device, or NULL: the ctx framebuffer, whose last
+ * rt_render / rt_render_frames(…, NULL) must have been the whole frame (row0 0, rowStride 1, nRows = height). d_aovs: device
+ * planes of rt_render_aovs's layout (normalDepth, albedo and ids are read; the other fields are ignored), or NULL: the ctx
+ * planes of the last rt_render_aovs(…, NULL), which must also have covered the whole frame. params NULL: the defaults. d_out:
+ * the denoised RGBA fp32 frame, not overlapping the inputs, or NULL: a ctx-owned plane (rt_read_denoised_rgba_f32). Needs an
+ * uploaded scene (the material table). Its work planes are its own; it changes no counter, no ray-cost figure, none of
+ * rt_last_kernel / rt_last_parts / rt_last_pipeline and not the progressive history of the ctx framebuffer. */
+int  rt_denoise(rt_ctx* ctx, uint32_t width, uint32_t height, const float* d_rgba, const RtAovBuffers* d_aovs,
+                const RtDenoiseParams* params, float* d_out);
+/* copies the ctx-owned output of the last rt_denoise(…, NULL) (nFloats = width*height*4 of that call); blocks */
+int  rt_read_denoised_rgba_f32(rt_ctx* ctx, float* hostOut, size_t nFloats);
+/* rt_denoise of host arrays (rgba and out: width*height*4 floats; aovs: host planes as above); blocks */
+int  rt_denoise_host(rt_ctx* ctx, uint32_t width, uint32_t height, const float* rgba, const RtAovBuffers* aovs,
+                     const RtDenoiseParams* params, float* out);
+
 int  rt_get_counters(rt_ctx* ctx, RtCounters* out);
 int  rt_reset_counters(rt_ctx* ctx);
 /* When enabled, every traversal-kernel launch is bracketed by HIP events on

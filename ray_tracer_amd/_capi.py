@@ -102,6 +102,10 @@ class RtAovBuffers(C.Structure):
                 ("ids", C.c_void_p)]
 
 
+class RtDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigmaLuminance", C.c_float), ("sigmaNormal", C.c_float), ("sigmaDepth", C.c_float)]
+
+
 # every symbol include/rt_amd.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 _vp = C.c_void_p
@@ -149,6 +153,10 @@ SYMBOLS = {
     "rt_trace_rays": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), _P(C.c_float), _P(RtHit)]),
     "rt_render_aovs": (C.c_int, [_vp, _P(PushConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(RtAovBuffers)]),
     "rt_read_aovs": (C.c_int, [_vp, _P(RtAovBuffers), C.c_size_t]),
+    "rt_denoise_params_default": (None, [_P(RtDenoiseParams)]),
+    "rt_denoise": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _P(RtAovBuffers), _P(RtDenoiseParams), _vp]),
+    "rt_read_denoised_rgba_f32": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
+    "rt_denoise_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _P(RtAovBuffers), _P(RtDenoiseParams), _vp]),
     "rt_get_counters": (C.c_int, [_vp, _P(RtCounters)]),
     "rt_reset_counters": (C.c_int, [_vp]),
     "rt_set_profiling": (C.c_int, [_vp, C.c_int]),

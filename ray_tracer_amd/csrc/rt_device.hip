@@ -33,6 +33,11 @@ struct EventPair { hipEvent_t a, b; };
 #define RT_MAX_LANES 4
 #define RT_FRAMES_MAX_SLOTS (24ull << 20)   // default for the paths of one multi-frame dispatch (ten 1080p frames or three 4K frames: 5.8 GB of path state)
 struct RootInfo { uint32_t idx, cnt; float lo[3], hi[3]; uint32_t triFirst, triTotal; };  // triTotal = ~0u: the mesh's triangles are not one contiguous range
+// the rows y = row0 + k*rowStride, k in [0,nRows) of a width x height image
+struct RowsOf {
+    uint32_t width = 0, height = 0, row0 = 0, rowStride = 0, nRows = 0;
+    bool whole(uint32_t w, uint32_t h) const { return width == w && height == h && row0 == 0 && rowStride == 1 && nRows == h; }
+};
 
 }  // namespace
 
@@ -155,6 +160,12 @@ struct rt_ctx {
     uint32_t aovPixels = 0;
     bool aovValid = false;
     uint64_t aovLaunches = 0;
+    // the rows of the image the ctx framebuffer and the ctx AOV planes hold (rt_denoise reads them only as a whole frame)
+    RowsOf fbRows, aovRows;
+    // the denoiser (rt_denoise): its work planes, the staging planes of rt_denoise_host and the ctx-owned output
+    DevBuf dnWorkBuf, dnHostBuf, dnOutBuf;
+    size_t dnOutPixels = 0;
+    bool dnValid = false;
 
     int fail(const std::string& m) { error = m; return -1; }
     int hip(hipError_t e, const char* what) {
@@ -609,7 +620,8 @@ void rt_destroy(rt_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& b : c->sceneBufs) dev_free(b);
     for (DevBuf* b : {&c->matBuf, &c->sphereBuf, &c->sphereMatBuf, &c->objInvBuf, &c->objFwdBuf, &c->objMetaBuf, &c->objBoxBuf, &c->objSkipBuf, &c->maskBoxBuf, &c->emitBuf, &c->emitPreBuf, &c->texelBuf, &c->texInfoBuf, &c->triUVBuf, &c->objTreeBuf, &c->objCostBuf, &c->objAlphaBuf, &c->stateBuf,
-                      &c->queueBuf, &c->fbBuf, &c->counterBuf, &c->scratchBuf, &c->waveTimeBuf, &c->probeBuf, &c->aovBuf, &c->aovCounterBuf})
+                      &c->queueBuf, &c->fbBuf, &c->counterBuf, &c->scratchBuf, &c->waveTimeBuf, &c->probeBuf, &c->aovBuf, &c->aovCounterBuf,
+                      &c->dnWorkBuf, &c->dnHostBuf, &c->dnOutBuf})
         dev_free(*b);
     (void)rt_comm_destroy(c);
     dev_free(c->gatherBuf);
@@ -1199,6 +1211,7 @@ int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t hei
         c->fbPixels = nPixels;
         fb = (float4*)c->fbBuf.p;
         c->fbValid = true;
+        c->fbRows = RowsOf{width, height, row0, rowStride, nRows};
     }
 
     // ---- per-frame constants (host side of raytrace.comp:547-564)
@@ -1506,6 +1519,7 @@ int rt_render_aovs(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t 
         out = AovOut{p, p + nPixels, p + 2 * (size_t)nPixels, p + 3 * (size_t)nPixels, (uint4*)(p + 4 * (size_t)nPixels)};
         c->aovPixels = nPixels;
         c->aovValid = true;
+        c->aovRows = RowsOf{width, height, row0, rowStride, nRows};
     }
     FrameParams fp = frame_camera(c, pc, width, height, row0, rowStride, nRows, nPixels);
     fp.nFrames = 1;
@@ -1541,6 +1555,145 @@ int rt_read_aovs(rt_ctx* c, const RtAovBuffers* out, size_t nPixels) {
     void* const dst[5] = {out->normalDepth, out->position, out->albedo, out->rayDir, out->ids};
     for (int k = 0; k < 5; k++)
         if (dst[k]) RT_HIP(c, hipMemcpyAsync(dst[k], p + (size_t)k * nPixels, nPixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+}  // extern "C"
+
+namespace {
+// The checks rt_denoise and rt_denoise_host share: geometry, parameters, an uploaded scene (its material table says which hits
+// are emitters)
+int check_denoise(rt_ctx* c, uint32_t width, uint32_t height, const RtDenoiseParams& p, const char* fn) {
+    const std::string f(fn);
+    if (width == 0 || height == 0) return c->fail(f + ": bad image geometry");
+    if ((uint64_t)width * height >= (1ull << 30) || height > 65535u * 16u) return c->fail(f + ": image too large");
+    if (p.iterations > 10) return c->fail(f + ": iterations must be 0..10");
+    if (!(std::isfinite(p.sigmaLuminance) && p.sigmaLuminance > 0.f)) return c->fail(f + ": sigmaLuminance must be finite and > 0");
+    if (!(std::isfinite(p.sigmaNormal) && p.sigmaNormal >= 0.f)) return c->fail(f + ": sigmaNormal must be finite and >= 0");
+    if (!(std::isfinite(p.sigmaDepth) && p.sigmaDepth > 0.f)) return c->fail(f + ": sigmaDepth must be finite and > 0");
+    if (!c->sc.nodes) return c->fail(f + " before rt_upload_scene");
+    return 0;
+}
+
+std::string not_whole(const char* what, const RowsOf& r, uint32_t width, uint32_t height) {
+    char m[256];
+    snprintf(m, sizeof(m), "rt_denoise: %s: rows %u + k*%u, k < %u of a %u x %u image, not the whole %u x %u frame", what, r.row0,
+             r.rowStride, r.nRows, r.width, r.height, width, height);
+    return m;
+}
+
+bool overlap(const void* a, const void* b, size_t bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+}  // namespace
+
+extern "C" {
+
+void rt_denoise_params_default(RtDenoiseParams* p) {
+    if (p) *p = RtDenoiseParams{5u, 4.f, 128.f, 1.f};
+}
+
+int rt_denoise(rt_ctx* c, uint32_t width, uint32_t height, const float* d_rgba, const RtAovBuffers* d_aovs, const RtDenoiseParams* params,
+               float* d_out) {
+    if (!c) return -1;
+    RtDenoiseParams p;
+    rt_denoise_params_default(&p);
+    if (params) p = *params;
+    int rc = check_denoise(c, width, height, p, "rt_denoise");
+    if (rc) return rc;
+    const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
+    const float4* rgba = (const float4*)d_rgba;
+    if (!rgba) {
+        if (!c->fbValid) return c->fail("rt_denoise: no ctx-owned framebuffer: rt_render was never called with d_rgba = NULL");
+        if (!c->fbRows.whole(width, height)) return c->fail(not_whole("the ctx framebuffer", c->fbRows, width, height));
+        rgba = (const float4*)c->fbBuf.p;
+    }
+    const float4 *nd, *albedo;
+    const uint4* ids;
+    if (!d_aovs) {
+        if (!c->aovValid) return c->fail("rt_denoise: no ctx-owned AOV planes: rt_render_aovs was never called with d_out = NULL");
+        if (!c->aovRows.whole(width, height)) return c->fail(not_whole("the ctx AOV planes", c->aovRows, width, height));
+        const float4* a = (const float4*)c->aovBuf.p;   // rt_render_aovs's order: normalDepth, position, albedo, rayDir, ids
+        nd = a;
+        albedo = a + 2 * n;
+        ids = (const uint4*)(a + 4 * n);
+    } else {
+        if (!d_aovs->normalDepth || !d_aovs->albedo || !d_aovs->ids) return c->fail("rt_denoise: d_aovs needs the normalDepth, albedo and ids planes");
+        nd = (const float4*)d_aovs->normalDepth;
+        albedo = (const float4*)d_aovs->albedo;
+        ids = (const uint4*)d_aovs->ids;
+    }
+    if (d_out)
+        for (const void* in : {(const void*)rgba, (const void*)nd, (const void*)albedo, (const void*)ids})
+            if (overlap(d_out, in, bytes)) return c->fail("rt_denoise: d_out overlaps an input");
+    RT_HIP(c, hipSetDevice(c->device));
+    // growing a plane frees the old one, which a denoise still in flight may be using
+    const size_t workBytes = 2 * bytes + n * sizeof(float2);
+    if ((p.iterations && c->dnWorkBuf.bytes < workBytes) || (!d_out && c->dnOutBuf.bytes < bytes)) RT_HIP(c, hipStreamSynchronize(c->stream));
+    float4* out = (float4*)d_out;
+    if (!out) {
+        if ((rc = dev_alloc(c, c->dnOutBuf, bytes))) return rc;
+        out = (float4*)c->dnOutBuf.p;
+        c->dnOutPixels = n;
+        c->dnValid = true;
+    }
+    if (p.iterations == 0) {
+        RT_HIP(c, hipMemcpyAsync(out, rgba, bytes, hipMemcpyDeviceToDevice, c->stream));
+        return 0;
+    }
+    if ((rc = dev_alloc(c, c->dnWorkBuf, workBytes))) return rc;
+    float4* const work[2] = {(float4*)c->dnWorkBuf.p, (float4*)c->dnWorkBuf.p + n};
+    const DenoiseFrame f{rgba, nd, albedo, ids, (float2*)(work[1] + n), width, height};
+    const dim3 grid((width + 15u) / 16u, (height + 15u) / 16u), block(RT_DN_BLOCK);
+    hipLaunchKernelGGL(k_dn_demod, grid, block, 0, c->stream, f, c->sc.mats, c->sc.materialCount, work[0]);
+    hipLaunchKernelGGL(k_dn_variance, grid, block, 0, c->stream, f, (const float4*)work[0], work[1]);
+    for (uint32_t k = 0; k < p.iterations; k++) {   // pass k reads work[1 - k % 2] and writes work[k % 2], the last one `out`
+        const float4* in = work[1 - (k & 1u)];
+        if (k + 1 < p.iterations)
+            hipLaunchKernelGGL(k_dn_atrous<false>, grid, block, 0, c->stream, f, in, work[k & 1u], (float4*)nullptr, 1 << k, p.sigmaLuminance,
+                               p.sigmaNormal, p.sigmaDepth);
+        else
+            hipLaunchKernelGGL(k_dn_atrous<true>, grid, block, 0, c->stream, f, in, (float4*)nullptr, out, 1 << k, p.sigmaLuminance,
+                               p.sigmaNormal, p.sigmaDepth);
+    }
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rt_read_denoised_rgba_f32(rt_ctx* c, float* out, size_t nFloats) {
+    if (!c || !out) return -1;
+    if (!c->dnValid) return c->fail("no ctx-owned denoised frame: rt_denoise was never called with d_out = NULL");
+    if (nFloats != c->dnOutPixels * 4) return c->fail("rt_read_denoised_rgba_f32: size mismatch");
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipMemcpyAsync(out, c->dnOutBuf.p, nFloats * 4, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int rt_denoise_host(rt_ctx* c, uint32_t width, uint32_t height, const float* rgba, const RtAovBuffers* aovs, const RtDenoiseParams* params,
+                    float* out) {
+    if (!c) return -1;
+    RtDenoiseParams p;
+    rt_denoise_params_default(&p);
+    if (params) p = *params;
+    int rc = check_denoise(c, width, height, p, "rt_denoise_host");
+    if (rc) return rc;
+    if (!rgba || !out) return c->fail("rt_denoise_host: rgba and out are required");
+    if (!aovs || !aovs->normalDepth || !aovs->albedo || !aovs->ids) return c->fail("rt_denoise_host: aovs needs the normalDepth, albedo and ids planes");
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    RT_HIP(c, hipSetDevice(c->device));
+    if (c->dnHostBuf.bytes < 5 * bytes) RT_HIP(c, hipStreamSynchronize(c->stream));
+    if ((rc = dev_alloc(c, c->dnHostBuf, 5 * bytes))) return rc;
+    char* d = (char*)c->dnHostBuf.p;   // rgba, normalDepth, albedo, ids, out
+    const void* src[4] = {rgba, aovs->normalDepth, aovs->albedo, aovs->ids};
+    for (int k = 0; k < 4; k++) RT_HIP(c, hipMemcpyAsync(d + k * bytes, src[k], bytes, hipMemcpyHostToDevice, c->stream));
+    RtAovBuffers planes{};
+    planes.normalDepth = (float*)(d + bytes);
+    planes.albedo = (float*)(d + 2 * bytes);
+    planes.ids = (uint32_t*)(d + 3 * bytes);
+    if ((rc = rt_denoise(c, width, height, (const float*)d, &planes, &p, (float*)(d + 4 * bytes)))) return rc;
+    RT_HIP(c, hipMemcpyAsync(out, d + 4 * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }

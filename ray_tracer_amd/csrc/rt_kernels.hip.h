@@ -1872,6 +1872,133 @@ __global__ __launch_bounds__(RT_BLOCK) void k_aov_resolve(DevScene sc, PathState
     if (out.ids) out.ids[px] = ids;
 }
 
+// ---------------------------------------------------------------- a-trous denoiser (rt_denoise)
+// The spatial filter of SVGF over a whole frame and its first-hit planes ("Denoising"). One lane per pixel, a wave per
+// 8x8 block and a work-group of four waves per 16x16 block, so a tap row of a wave is 8 records of 16 B. The work planes hold
+// (e.rgb, v) per pixel; v < 0 marks a kept pixel (a miss or an emitter), which is never a neighbour. Each launch reads only what
+// an earlier launch on the stream wrote, so no work-group waits for another.
+#define RT_DN_BLOCK 256
+struct DenoiseFrame {
+    const float4* rgba;         // the noisy frame; pixel (x, y) at y * width + x
+    const float4* normalDepth;  // rt_render_aovs's planes of the same frame
+    const float4* albedo;
+    const uint4* ids;
+    float2* grad;               // the depth gradient of each filtered pixel (k_dn_variance)
+    uint32_t width, height;
+};
+
+__device__ __forceinline__ bool dn_pixel(const DenoiseFrame& f, uint32_t& x, uint32_t& y) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    x = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u);
+    y = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
+    return x < f.width && y < f.height;
+}
+__device__ __forceinline__ float dn_luminance(float4 e) { return (0.2126f * e.x + 0.7152f * e.y) + 0.0722f * e.z; }
+__device__ __forceinline__ float dn_h(int i) { return i == 0 ? 0.375f : (i == 1 || i == -1) ? 0.25f : 0.0625f; }   // (1, 4, 6, 4, 1) / 16
+
+// e = rgb / max(albedo, 1e-3) with v = 0 for a filtered pixel (a hit on a material with emissionStrength == 0), (0, 0, 0, -1) kept
+__global__ __launch_bounds__(RT_DN_BLOCK) void k_dn_demod(DenoiseFrame f, const float4* mats, uint32_t materialCount, float4* work) {
+    uint32_t x, y;
+    if (!dn_pixel(f, x, y)) return;
+    const size_t p = (size_t)y * f.width + x;
+    const uint4 id = f.ids[p];
+    float4 r = make_float4(0.f, 0.f, 0.f, -1.f);
+    if ((id.w & 1u) && id.z < materialCount && rt_global(mats)[3 * id.z + 1].w == 0.f) {
+        const float4 c = f.rgba[p], a = f.albedo[p];
+        r = make_float4(c.x / rt_max(a.x, 1e-3f), c.y / rt_max(a.y, 1e-3f), c.z / rt_max(a.z, 1e-3f), 0.f);
+    }
+    work[p] = r;
+}
+
+// v = the variance of the luminance over the filtered pixels of the 5x5 window (mean first, then the mean squared deviation: fp32
+// mean(l^2) - mean(l)^2 cancels), and the depth gradient: per axis the forward or backward difference to a filtered neighbour,
+// the smaller in magnitude (the forward one on a tie), 0 without either
+__global__ __launch_bounds__(RT_DN_BLOCK) void k_dn_variance(DenoiseFrame f, const float4* work, float4* out) {
+    uint32_t x, y;
+    if (!dn_pixel(f, x, y)) return;
+    const size_t p = (size_t)y * f.width + x;
+    const float4 e = work[p];
+    if (e.w < 0.f) { out[p] = e; return; }
+    const uint32_t x0 = x >= 2u ? x - 2u : 0u, x1 = x + 2u < f.width ? x + 2u : f.width - 1u;
+    const uint32_t y0 = y >= 2u ? y - 2u : 0u, y1 = y + 2u < f.height ? y + 2u : f.height - 1u;
+    float sum = 0.f, n = 0.f;
+    for (uint32_t qy = y0; qy <= y1; qy++)
+        for (uint32_t qx = x0; qx <= x1; qx++) {
+            const float4 q = work[(size_t)qy * f.width + qx];
+            if (q.w >= 0.f) { sum += dn_luminance(q); n += 1.f; }
+        }
+    const float mu = sum / n;
+    float ss = 0.f;
+    for (uint32_t qy = y0; qy <= y1; qy++)
+        for (uint32_t qx = x0; qx <= x1; qx++) {
+            const float4 q = work[(size_t)qy * f.width + qx];
+            if (q.w >= 0.f) { const float d = dn_luminance(q) - mu; ss += d * d; }
+        }
+    const float z = f.normalDepth[p].w;
+    auto diff = [&](bool hasF, size_t qf, bool hasB, size_t qb) {
+        hasF = hasF && work[qf].w >= 0.f;
+        hasB = hasB && work[qb].w >= 0.f;
+        const float fd = hasF ? f.normalDepth[qf].w - z : 0.f, bd = hasB ? z - f.normalDepth[qb].w : 0.f;
+        return hasF && hasB ? (rt_abs(bd) < rt_abs(fd) ? bd : fd) : hasF ? fd : bd;
+    };
+    f.grad[p] = make_float2(diff(x + 1u < f.width, p + 1, x > 0u, p - 1), diff(y + 1u < f.height, p + f.width, y > 0u, p - f.width));
+    out[p] = make_float4(e.x, e.y, e.z, ss / n);
+}
+
+// One a-trous pass with step s: taps p + s * (i, j), i, j in [-2, 2], inside the image and filtered, weighted
+// h_i h_j max(0, n_p.n_q)^sn exp(-|z_p - z_q| / (sz |g.(s i, s j)| + 1e-4 z_p) - |l_p - l_q| / (sl sqrt(v_p) + 1e-4));
+// e' = sum w e / sum w, v' = sum w^2 v / (sum w)^2. LAST remodulates, e' * max(albedo, 1e-3) with the input's alpha, into rgbaOut
+// and copies kept pixels there.
+template <bool LAST>
+__global__ __launch_bounds__(RT_DN_BLOCK) void k_dn_atrous(DenoiseFrame f, const float4* in, float4* out, float4* rgbaOut, int step,
+                                                           float sigmaL, float sigmaN, float sigmaZ) {
+    uint32_t x, y;
+    if (!dn_pixel(f, x, y)) return;
+    const size_t p = (size_t)y * f.width + x;
+    const float4 c = in[p];
+    if (c.w < 0.f) {
+        if (LAST) rgbaOut[p] = f.rgba[p];
+        else out[p] = c;
+        return;
+    }
+    const float4 ndp = f.normalDepth[p];
+    const float2 g = f.grad[p];
+    const rt_vec3 np = f4xyz(ndp);
+    const float lp = dn_luminance(c), lumDen = sigmaL * rt_sqrt(c.w) + 1e-4f, zEps = 1e-4f * ndp.w;
+    float sw = 0.f, sv = 0.f;
+    rt_vec3 se = rt_v3(0.f, 0.f, 0.f);
+#pragma unroll
+    for (int j = -2; j <= 2; j++) {
+        const int qy = (int)y + step * j;
+        if (qy < 0 || qy >= (int)f.height) continue;
+#pragma unroll
+        for (int i = -2; i <= 2; i++) {
+            const int qx = (int)x + step * i;
+            if (qx < 0 || qx >= (int)f.width) continue;
+            const size_t q = (size_t)qy * f.width + (uint32_t)qx;
+            const float4 e = in[q];
+            if (e.w < 0.f) continue;
+            const float4 ndq = f.normalDepth[q];
+            float w = dn_h(i) * dn_h(j);
+            if (sigmaN != 0.f) w = w * rt_pow(rt_max(0.f, rt_dot(np, f4xyz(ndq))), sigmaN);
+            const float dz = rt_abs(ndp.w - ndq.w);
+            const float az = dz == 0.f ? 0.f : dz / (sigmaZ * rt_abs(g.x * (float)(step * i) + g.y * (float)(step * j)) + zEps);
+            const float al = rt_abs(lp - dn_luminance(e)) / lumDen;
+            w = w * rt_exp2(-(az + al) * 1.44269504088896341f);
+            sw += w;
+            se = rt_add(se, rt_scale(f4xyz(e), w));
+            sv += (w * w) * e.w;
+        }
+    }
+    const rt_vec3 ep = rt_v3(se.x / sw, se.y / sw, se.z / sw);
+    if (LAST) {
+        const float4 a = f.albedo[p];
+        rgbaOut[p] = make_float4(ep.x * rt_max(a.x, 1e-3f), ep.y * rt_max(a.y, 1e-3f), ep.z * rt_max(a.z, 1e-3f), f.rgba[p].w);
+    } else {
+        out[p] = mk4(ep, sv / (sw * sw));
+    }
+}
+
 // ---------------------------------------------------------------- misc kernels
 // start of a multi-kernel dispatch: n active paths and n rays in buffer 0, nothing in buffer 1, work counter 0
 __global__ void k_init_counts(uint32_t* counts, uint32_t n) {

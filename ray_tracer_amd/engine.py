@@ -18,8 +18,8 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAovBuffers, RtCounters, RtHit, RtPlacement,
-                    RtSceneArrays, RtTexture, Sphere, Triangle, TrianglePoint)
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit,
+                    RtPlacement, RtSceneArrays, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
 
@@ -384,6 +384,32 @@ class Renderer:
         self._check(self._l.rt_read_aovs(self._h, C.byref(b), n * w), "rt_read_aovs")
         return aovs_to_numpy(planes)
 
+    def denoise(self, frame=None, aovs=None, iterations=5, sigma_luminance=4.0, sigma_normal=128.0, sigma_depth=1.0):
+        """The edge-aware a-trous denoiser (rt_denoise; DESIGN.md, "Denoising") of a whole frame: an (H, W, 4) float32 array.
+        Without `frame` and `aovs` it filters the context's own frame (the last render() into it) with the context's own planes
+        (the last render_aovs() without out_ptrs), both of the whole image. Otherwise `frame` is an (H, W, 4) float32 array and
+        `aovs` the dict render_aovs() returns for the same image, and the call goes through rt_denoise_host."""
+        p = RtDenoiseParams(int(iterations), float(sigma_luminance), float(sigma_normal), float(sigma_depth))
+        if frame is None and aovs is None:
+            H, W = self._aov_shape or (0, 0)
+            self._check(self._l.rt_denoise(self._h, W, H, None, None, C.byref(p), None), "rt_denoise")
+            out = np.empty((H, W, 4), np.float32)
+            self._check(self._l.rt_read_denoised_rgba_f32(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size),
+                        "rt_read_denoised_rgba_f32")
+            return out
+        if frame is None or aovs is None:
+            raise ValueError("denoise() takes both a frame and its AOV planes, or neither (the context's own)")
+        frame = np.ascontiguousarray(frame, np.float32)
+        H, W = frame.shape[:2]
+        if frame.shape != (H, W, 4) or aovs["depth"].shape != (H, W):
+            raise ValueError(f"frame {frame.shape} and planes {aovs['depth'].shape}: not one (H, W, 4) frame and its (H, W) planes")
+        planes = numpy_to_aovs(aovs)
+        b = RtAovBuffers(**{k: v.ctypes.data for k, v in planes.items()})
+        out = np.empty_like(frame)
+        self._check(self._l.rt_denoise_host(self._h, W, H, frame.ctypes.data, C.byref(b), C.byref(p), out.ctypes.data),
+                    "rt_denoise_host")
+        return out
+
     def pick(self, pc, width, height, x, y):
         """What the camera ray of pixel (x, y) hits: one row of render_aovs(), the record at x (scalars and 3-vectors)."""
         if not (0 <= x < width and 0 <= y < height):
@@ -498,6 +524,20 @@ def aovs_to_numpy(planes):
                 albedo=planes["albedo"][..., :3].copy(), ray_dir=planes["rayDir"][..., :3].copy(), object=ids[..., 0].copy(),
                 triangle=ids[..., 1].copy(), material=ids[..., 2].copy(), hit=(ids[..., 3] & 1) != 0,
                 sphere=(ids[..., 3] & 2) != 0, front_face=(ids[..., 3] & 4) != 0)
+
+
+def numpy_to_aovs(a):
+    """The inverse of aovs_to_numpy: the named arrays of render_aovs() -> the five (H, W, 4) planes of RtAovBuffers."""
+    shape = a["depth"].shape + (4,)
+    planes = {k: np.zeros(shape, np.uint32 if k == "ids" else np.float32) for k in AOV_PLANES}
+    planes["normalDepth"][..., :3], planes["normalDepth"][..., 3] = a["normal"], a["depth"]
+    planes["position"][..., :3], planes["position"][..., 3] = a["position"], a["hit"]
+    planes["albedo"][..., :3], planes["albedo"][..., 3] = a["albedo"], a["hit"]
+    planes["rayDir"][..., :3] = a["ray_dir"]
+    ids = planes["ids"]
+    ids[..., 0], ids[..., 1], ids[..., 2] = a["object"], a["triangle"], a["material"]
+    ids[..., 3] = a["hit"].astype(np.uint32) | (a["sphere"].astype(np.uint32) << 1) | (a["front_face"].astype(np.uint32) << 2)
+    return planes
 
 
 def hits_to_numpy(hits):

@@ -66,6 +66,9 @@ def build_parser():
     ap.add_argument("--aov-out", metavar="FILE.npz",
                     help="also write the first-hit planes of the camera rays (Renderer.render_aovs: depth, normal, position, albedo, "
                          "ray_dir, object, triangle, material, hit, sphere, front_face) to this .npz")
+    ap.add_argument("--denoise", action="store_true",
+                    help="write the frame through the edge-aware a-trous denoiser (Renderer.denoise, defaults; DESIGN.md, "
+                         "\"Denoising\") to --out; it runs the first-hit AOV pass itself unless --aov-out did")
     # Ray Tracer Info panel
     ap.add_argument("--progressive", action="store_true")
     ap.add_argument("--frames-in-flight", type=int, default=1,
@@ -196,7 +199,8 @@ def main(argv=None):
         frames += 1
         if not args.progressive and not args.single_render:
             break  # every further dispatch would be this very frame again (frameCount does not advance)
-    aovs = r.render_aovs(pc, W, H, **tile) if args.aov_out else None
+    denoise = args.denoise and img is not None
+    aovs = r.render_aovs(pc, W, H, **tile) if args.aov_out or denoise else None
     on = f"cuda:{device}" if args.backend == "nccl" else "cpu"
     if world > 1 and aovs is not None:
         aovs = gather_planes(aovs, H, world, rank, on)
@@ -205,6 +209,10 @@ def main(argv=None):
         frame = torch.zeros((H, W, 4), dtype=torch.float32, device=on) if rank == 0 else None
         tiling.gather_frame(strip, frame, H, world, rank)
         img = frame.cpu().numpy() if rank == 0 else None
+    if denoise and world == 1:
+        img = r.denoise()   # the context's own frame and planes
+    elif denoise and rank == 0:
+        img = r.denoise(img, aovs)   # the gathered frame and planes
     dt = time.perf_counter() - t0
     c = r.counters()
     if world > 1:
@@ -220,9 +228,9 @@ def main(argv=None):
                 np.save(args.out, img)
             else:
                 from PIL import Image
-                Image.fromarray((srgb8(img) if world > 1 else r.read_rgba8_srgb())[..., :3]).save(args.out)
+                Image.fromarray((srgb8(img) if world > 1 or denoise else r.read_rgba8_srgb())[..., :3]).save(args.out)
             print("wrote", args.out)
-        if aovs is not None:
+        if args.aov_out:
             np.savez(args.aov_out, **aovs)
             print("wrote", args.aov_out)
     if world > 1:
