@@ -23,9 +23,13 @@
 
 namespace {
 
-struct DevBuf {
+struct DevBuf {  // device memory that belongs to whoever holds this: move-only, freed with it
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
 
 struct EventPair { hipEvent_t a, b; };
@@ -42,131 +46,123 @@ struct RowsOf {
 }  // namespace
 
 struct rt_ctx {
-    int device = 0;
-    hipStream_t ownStream = nullptr;
-    hipStream_t stream = nullptr;
     std::string error;
-
+    // ---- resources: device, streams, events, buffers, communicator, and the host's view of what the buffers hold. Written by
+    // rt_create, the upload / update entry points, the ensure / allocate helpers and rt_destroy.
+    int device = 0, numCUs = 256;
+    hipStream_t ownStream = nullptr, stream = nullptr;  // rt_set_stream: the ctx stream is the caller's or the ctx's own
     // scene
     DevScene sc{};
     std::vector<DevBuf> sceneBufs;
-    DevBuf texelBuf, texInfoBuf, triUVBuf;
-    DevBuf objTreeBuf, objCostBuf;
-    int objTreeMin = 48;    // rt_set_tuning("object_tree_min"): general-transform objects from which the object hierarchy is built (0 = never)
+    DevBuf texelBuf, texInfoBuf, triUVBuf, objTreeBuf, objCostBuf;
     DevBuf matBuf, sphereBuf, sphereMatBuf, objInvBuf, objFwdBuf, objMetaBuf, objBoxBuf, objSkipBuf, maskBoxBuf, emitBuf, emitPreBuf;
     // host copies of what the emitter list is derived from (rebuild_emitters)
     std::vector<RayMaterial> hostMats;
     std::vector<uint32_t> hostSphereMat, hostObjMat, hostObjRoot, hostObjSampler;
     DevBuf objAlphaBuf;     // per object: its material's alpha map and sampler (refresh_maps)
+    uint32_t maxLeafDepth = 0;
+    std::vector<uint32_t> nodeRemap;          // reference node index -> device node index
+    std::vector<RootInfo> rootOf;             // per reference node; idx = ~0u unless a mesh root
+    bool cull = false;      // kernels with the object-skipping code (CULL) for this scene
     // multi-GPU (rt_comm_*): this rank's RCCL communicator, a staging buffer on the gathering rank
     ncclComm_t comm = nullptr;
     int commRanks = 0, commRank = 0;
     DevBuf gatherBuf;
-    int framesPerLaunch = 0; // rt_render_frames: most frames of a tile rendered by one launch (0 = as many as fit)
-    int cameraReuse = 1;    // rt_set_tuning("camera_reuse", 0): trace the camera ray of every sample
-    int lightQueries = 1;   // rt_set_tuning("light_queries", 0): trace every NEE ray and cosine probe in full
-    uint32_t maxLeafDepth = 0;
-    std::vector<uint32_t> nodeRemap;          // reference node index -> device node index
-    std::vector<RootInfo> rootOf;             // per reference node; idx = ~0u unless a mesh root
-
     // path state
     DevBuf stateBuf, queueBuf, fbBuf, counterBuf, scratchBuf;
-    DevBuf overflowBuf[RT_MAX_LANES];     // per part (curLane): the traversal stack entries beyond LDS
-    // Multi-kernel pipeline in `lanes` independent parts (render_impl): the paths of a dispatch are split into contiguous slot
+    DevBuf overflowBuf[RT_MAX_LANES];     // per part (Dispatch::part): the traversal stack entries beyond LDS
+    // Multi-kernel pipeline in `lanes` independent parts (render_parts): the paths of a dispatch are split into contiguous slot
     // ranges, each with its own queues, counters and stream, so that one part's k_shade and the tail of its k_trace_pw launch
     // run under the other part's traversal. Part 0 is the ctx stream itself; the others fork from it and join it.
     hipStream_t sideStream[RT_MAX_LANES - 1] = {};
     hipEvent_t forkEvent = nullptr, joinEvent[RT_MAX_LANES - 1] = {}, pollEventSide[RT_MAX_LANES - 1] = {};
-    bool lanesSet = false;                // "lanes" given explicitly: no automatic fall-back to one part
-    int lanes = 3;                        // rt_set_tuning("lanes", 1..RT_MAX_LANES)
-    uint32_t lanesMinSlots = 1u << 20;    // dispatches of fewer paths than this stay in one part
-    hipStream_t curStream = nullptr;      // the stream and counters of the part whose launches are being built (launch_trace)
-    uint32_t* curCounts = nullptr;
-    int curLane = 0;
-    int lastParts = 1;                    // parts the last multi-kernel dispatch ran in (rt_last_parts)
-    int curGridPct = 100;                 // share of the resident work-groups a k_trace_pw launch of the current part takes
-    int laneGridPct = 0;                  // rt_set_tuning("lane_grid_pct"): that share while a dispatch runs in several parts (0 = by the parts' size: 50, 40 below 1.2 M paths per part)
     uint32_t capacity = 0;  // pixels the state buffers hold
-    PathState ps{};
-    Queues q{};
+    PathState ps{}; Queues q{};
     uint32_t* hostCounts = nullptr;  // pinned, 4 words
-    uint32_t fbPixels = 0;
-    bool fbValid = false;
-
-    // profiling of the traversal kernel
+    uint32_t fbPixels = 0; bool fbValid = false;
+    // profiling of the traversal kernel (rt_set_profiling switches it; prof_begin takes events from the pool, harvest_events returns them)
     bool profiling = false;
     std::vector<EventPair> evPool;
     size_t evUsed = 0;
-    double traceMs = 0.0;
-    uint64_t traceLaunches = 0;
     hipEvent_t profBase = nullptr;                         // recorded when profiling is switched on: the origin of traceSpans
-    std::vector<std::pair<float, float>> traceSpans;       // [start, end) of every bracketed launch, ms since profBase (rt_get_trace_busy_ms)
-    uint64_t traceLaunchesTotal = 0;
-
-    // tuning (rt_set_tuning)
-    int traceVariant = 1;   // 0 = one-ray-per-lane k_trace, 1 = persistent waves k_trace_pw
-    int pipeline = -1;      // 0 = multi-kernel wavefront pipeline, 1 = wave-private fused pipeline (k_render_fused), -1 = by tile size
-    int lastPipeline = 0;   // what the last rt_render used
-    char lastKernel[96] = "";  // the traversal kernel instantiation of the last launch, as a demangler prints it (rt_last_kernel)
-    uint32_t fusedBelowPixels = 4000000;  // auto: dispatches of fewer paths than this use the fused pipeline — scaled down to 1.5 M as the rays get longer
-                                          // (render_impl: sizeLimit). Sponza, 8 spp, ms per step with 1 / 2 / 4 / 10 frames of 1080p in one dispatch
-                                          // (round 3, multi-kernel in three parts): fused 113.8 / 109.4 / 107.4 / 105, multi-kernel 103.4 / 90.7 / 84.7 / 79.5
-    uint32_t fusedBelowBoxTests = 70;     // auto: ... and so do scenes whose rays are short (EXECUTED box tests per ray, measured), with one exception (render_impl)
     // box tests per ray of this scene, from counter snapshots copied back asynchronously after each dispatch
     DevCounters* snap = nullptr;          // pinned
     hipEvent_t snapEvent = nullptr;
     hipEvent_t pollEvent = nullptr;       // multi-kernel pipeline: the active-path count on its way back (never waited for)
-    bool snapPending = false;
-    unsigned long long snapBox = 0, snapRays = 0;  // counters at the previous snapshot
-    double boxPerRay = -1.0;              // < 0: not measured yet
-    double segPerPath = -1.0;             // path segments per pixel sample of this scene, from the same snapshots (< 0: not measured yet)
-    unsigned long long snapSeg = 0, snapPaths = 0;
-    int refill = 8;         // k_trace_pw: idle lanes that trigger a refill
-    bool refillMkSet = false, wSetupSet = false;  // given explicitly (else by the scene's ray length, launch_trace)
-    int refillMk = 16;      // the same for k_trace_pw over the global queue when set by hand ("mk_refill"); automatic: 12 for long rays, 16 otherwise (launch_trace)
-    int chunk = 256;        // k_trace_pw: most queue entries reserved per atomic
-    int ldsStackCap = 24;   // k_trace_pw: LDS stack entries per lane (8, 16 or 24); deeper BVHs use the overflow buffer
-    int fastLanes = 32;     // k_trace_pw: lanes at interior nodes that skip the full vote (4K Sponza: 24 -> 32 is -2 %, 1080p: equal)
-    int wSetup = 16, wLeaf = 16; // k_trace_pw: vote weights in eighths (interior = 8); the set-up weight when set by hand ("mk_w_setup"), automatic: 32 for long rays, 16 otherwise
-    int blocksPerCU = 0;    // k_trace_pw: 0 = occupancy query
-    int numCUs = 256;
-    int phaseStats = 0;     // diagnostic: k_trace_pw counts rounds / active lanes per phase
-    int tileSlots = 1;      // slots follow 8x8 pixel blocks instead of rows
-    bool wLeafSet = false;
-    bool fastLanesSet = false;  // fast_lanes given explicitly: it then also applies to the fused pipeline
-    int wSetupFused = 16, wLeafFused = 24;  // vote weights of the fused pipeline (short private lists: leaves and set-ups sooner)
-    double bvhBuildMs = 0.0; // last rt_bvh_build
-    int fastShare = 10;     // sixteenths of the live lanes that suffice to skip the vote (0 = fixed count only): -1..-2 % everywhere
-    bool cull = false;      // kernels with the object-skipping code (CULL) for this scene
-    int maskIdentity = 0;   // identity-transform objects in the rays' object masks too (rt_update_objects reads it)
-    int scatter = -1;       // fused pipeline: blocks made of chunks of this many slots from all over the tile; 0 = neighbouring pixels; -1 = auto
-    uint64_t framesMaxSlots = RT_FRAMES_MAX_SLOTS;  // most paths of one multi-frame dispatch (rt_render_frames)
-    int hotPairs = 2;       // k_trace_pw: child pairs of the meshes' top levels from LDS. 0 = off, 1 = as many as fit beside the stacks of
-                            // six work-groups per CU, 2 = of five (Sponza, 21-entry stacks, ten frames in flight: 90.4 / 90.6 / 88.7 ms per step)
-    int pixelRefill = 0;    // fused pipeline: free lanes at which a wave reserves new pixels (64 = a block at a time, 0 = by ray length)
-    int batchPixels = 0;    // fused pipeline: pixels per wave-private block (0 = chosen per launch)
-    int batchFixed = 80;    // ... and the fixed part of a block's cost in the chooser, in pixel units
-    int fusedMaps = 0;      // 1: a scene that binds an alpha, metalness or bump map may take the fused pipeline (k_render_fused_maps); 0: multi-kernel only
-    int lastBatchPixels = 0;
     DevBuf probeBuf;        // framebuffer of the ray-cost probe
-    int probe = 1;          // measure an unknown scene with a small dispatch before its first big one
-    bool inProbe = false;
     DevBuf waveTimeBuf;     // phase_stats: per-wave start/end clocks of the last k_trace_pw launch
-    size_t waveTimesCount = 0;
-    bool pixStats = false;  // this dispatch needs per-pixel box/triangle counts (debug heat maps)
     // first-hit AOV passes (rt_render_aovs): the ctx-owned planes of the last pass into them, and a counter block of their own, which
     // rt_get_counters adds to the rendering counters and the ray-cost snapshots never see
     DevBuf aovBuf, aovCounterBuf;
-    uint32_t aovPixels = 0;
-    bool aovValid = false;
-    uint64_t aovLaunches = 0;
+    uint32_t aovPixels = 0; bool aovValid = false;
     // the rows of the image the ctx framebuffer and the ctx AOV planes hold (rt_denoise reads them only as a whole frame)
     RowsOf fbRows, aovRows;
     // the denoiser (rt_denoise): its work planes, the staging planes of rt_denoise_host and the ctx-owned output
     DevBuf dnWorkBuf, dnHostBuf, dnOutBuf;
-    size_t dnOutPixels = 0;
-    bool dnValid = false;
+    size_t dnOutPixels = 0; bool dnValid = false;
 
+    // ---- tuning: what rt_set_tuning writes, each "given explicitly" flag beside the knob it qualifies. Nothing else assigns to it.
+    struct Tuning {
+        int objTreeMin = 48;    // rt_set_tuning("object_tree_min"): general-transform objects from which the object hierarchy is built (0 = never)
+        int framesPerLaunch = 0; // rt_render_frames: most frames of a tile rendered by one launch (0 = as many as fit)
+        uint64_t framesMaxSlots = RT_FRAMES_MAX_SLOTS;  // most paths of one multi-frame dispatch (rt_render_frames)
+        int cameraReuse = 1;    // rt_set_tuning("camera_reuse", 0): trace the camera ray of every sample
+        int lightQueries = 1;   // rt_set_tuning("light_queries", 0): trace every NEE ray and cosine probe in full
+        int lanes = 3;                        // rt_set_tuning("lanes", 1..RT_MAX_LANES)
+        bool lanesSet = false;                // "lanes" given explicitly: no automatic fall-back to one part
+        uint32_t lanesMinSlots = 1u << 20;    // dispatches of fewer paths than this stay in one part
+        int laneGridPct = 0;                  // rt_set_tuning("lane_grid_pct"): share of the resident work-groups a k_trace_pw launch takes while a dispatch runs in several parts (0 = by the parts' size: 50, 40 below 1.2 M paths per part)
+        int traceVariant = 1;   // 0 = one-ray-per-lane k_trace, 1 = persistent waves k_trace_pw
+        int pipeline = -1;      // 0 = multi-kernel wavefront pipeline, 1 = wave-private fused pipeline (k_render_fused), -1 = by tile size
+        uint32_t fusedBelowPixels = 4000000;  // auto: dispatches of fewer paths than this use the fused pipeline — scaled down to 1.5 M as the rays get longer
+                                              // (choose_pipeline: sizeLimit). Sponza, 8 spp, ms per step with 1 / 2 / 4 / 10 frames of 1080p in one dispatch
+                                              // (round 3, multi-kernel in three parts): fused 113.8 / 109.4 / 107.4 / 105, multi-kernel 103.4 / 90.7 / 84.7 / 79.5
+        uint32_t fusedBelowBoxTests = 70;     // auto: ... and so do scenes whose rays are short (EXECUTED box tests per ray, measured), with one exception (choose_pipeline)
+        int refill = 8;         // k_trace_pw: idle lanes that trigger a refill
+        int refillMk = 16;      // the same for k_trace_pw over the global queue when set by hand ("mk_refill"); automatic: 12 for long rays, 16 otherwise (launch_trace)
+        bool refillMkSet = false;  // given explicitly (else by the scene's ray length, launch_trace)
+        int chunk = 256;        // k_trace_pw: most queue entries reserved per atomic
+        int ldsStackCap = 24;   // k_trace_pw: LDS stack entries per lane (8, 16 or 24); deeper BVHs use the overflow buffer
+        int fastLanes = 32;     // k_trace_pw: lanes at interior nodes that skip the full vote (4K Sponza: 24 -> 32 is -2 %, 1080p: equal)
+        bool fastLanesSet = false;  // fast_lanes given explicitly: it then also applies to the fused pipeline
+        int wSetup = 16, wLeaf = 16; // k_trace_pw: vote weights in eighths (interior = 8); the set-up weight when set by hand ("mk_w_setup"), automatic: 32 for long rays, 16 otherwise
+        bool wSetupSet = false, wLeafSet = false;  // given explicitly (the set-up weight else by the scene's ray length, launch_trace)
+        int wSetupFused = 16, wLeafFused = 24;  // vote weights of the fused pipeline (short private lists: leaves and set-ups sooner)
+        int blocksPerCU = 0;    // k_trace_pw: 0 = occupancy query
+        int phaseStats = 0;     // diagnostic: k_trace_pw counts rounds / active lanes per phase
+        int tileSlots = 1;      // slots follow 8x8 pixel blocks instead of rows
+        int fastShare = 10;     // sixteenths of the live lanes that suffice to skip the vote (0 = fixed count only): -1..-2 % everywhere
+        int maskIdentity = 0;   // identity-transform objects in the rays' object masks too (rt_update_objects reads it)
+        int scatter = -1;       // fused pipeline: blocks made of chunks of this many slots from all over the tile; 0 = neighbouring pixels; -1 = auto
+        int hotPairs = 2;       // k_trace_pw: child pairs of the meshes' top levels from LDS. 0 = off, 1 = as many as fit beside the stacks of
+                                // six work-groups per CU, 2 = of five (Sponza, 21-entry stacks, ten frames in flight: 90.4 / 90.6 / 88.7 ms per step)
+        int pixelRefill = 0;    // fused pipeline: free lanes at which a wave reserves new pixels (64 = a block at a time, 0 = by ray length)
+        int batchPixels = 0;    // fused pipeline: pixels per wave-private block (0 = chosen per launch)
+        int batchFixed = 80;    // ... and the fixed part of a block's cost in the chooser, in pixel units
+        int fusedMaps = 0;      // 1: a scene that binds an alpha, metalness or bump map may take the fused pipeline (k_render_fused_maps); 0: multi-kernel only
+        int probe = 1;          // measure an unknown scene with a small dispatch before its first big one
+    } tune;
+
+    // ---- measured on earlier dispatches. Written by poll_ray_cost, request_ray_cost, probe_ray_cost, measured_new_scene and rt_reset_counters only.
+    struct Measured {
+        bool snapPending = false;
+        unsigned long long snapBox = 0, snapRays = 0, snapSeg = 0, snapPaths = 0;  // counters at the previous snapshot
+        double boxPerRay = -1.0;              // < 0: not measured yet
+        double segPerPath = -1.0;             // path segments per pixel sample of this scene, from the same snapshots (< 0: not measured yet)
+    } meas;
+
+    // ---- reports: written by the launch functions, harvest_events and rt_bvh_build, zeroed by rt_reset_counters, read by rt_last_* / rt_get_*.
+    struct Reports {
+        int lastPipeline = 0;   // what the last rt_render used
+        int lastParts = 1;                    // parts the last multi-kernel dispatch ran in (rt_last_parts)
+        char lastKernel[96] = "";  // the traversal kernel instantiation of the last launch, as a demangler prints it (rt_last_kernel)
+        size_t waveTimesCount = 0;
+        double traceMs = 0.0;
+        uint64_t traceLaunches = 0;
+        std::vector<std::pair<float, float>> traceSpans;       // [start, end) of every bracketed launch, ms since profBase (rt_get_trace_busy_ms)
+        uint64_t traceLaunchesTotal = 0, aovLaunches = 0;      // traversal launches of the rendering dispatches and of the AOV passes
+        double bvhBuildMs = 0.0; // last rt_bvh_build
+    } rep;
     int fail(const std::string& m) { error = m; return -1; }
     int hip(hipError_t e, const char* what) {
         if (e == hipSuccess) return 0;
@@ -185,15 +181,11 @@ namespace {
 
 int dev_alloc(rt_ctx* c, DevBuf& b, size_t bytes) {
     if (b.p && b.bytes >= bytes) return 0;
-    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; }
+    b.release();
     if (bytes == 0) bytes = 256;
     RT_HIP(c, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
     return 0;
-}
-void dev_free(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.bytes = 0;
 }
 
 int upload(rt_ctx* c, DevBuf& b, const void* src, size_t bytes) {
@@ -250,6 +242,32 @@ int ensure_state(rt_ctx* c, uint32_t nPixels) {
     return 0;
 }
 
+// What the launch functions need to know about the dispatch (or pass) they launch for. Whoever starts one builds it and hands it
+// down; the context keeps the buffers, the tuning and the measured statistics, and nothing of a dispatch.
+struct Dispatch {
+    DevScene sc;         // the uploaded scene with the counts of rayTraceParams (dispatch_scene)
+    bool pixStats;       // per-pixel box/triangle counts are wanted (debug heat maps)
+    int phaseStats;      // rt_set_tuning("phase_stats") as it holds for this dispatch (0 for the probe and the AOV pass)
+    int pipeline;        // rt_set_tuning("pipeline") as it holds for this dispatch (the probe: 1)
+    bool profiled;       // its traversal launches are bracketed by events (prof_begin)
+    bool probe;          // the ray-cost probe: no probe of its own, no trace in rt_last_pipeline
+    uint64_t* launches;  // the counter its traversal launches are added to (null: not counted)
+    // the part of a multi-kernel dispatch being launched; everything else is one part
+    hipStream_t stream;
+    uint32_t* counts;    // the part's counter block
+    int part;            // which overflow buffer
+    int gridPct;         // share of the resident work-groups a k_trace_pw launch of this part takes
+};
+// A dispatch in one part: the ctx stream, the first counter block (which ensure_state makes), the whole grid
+Dispatch one_part(rt_ctx* c, const DevScene& sc, bool pixStats) {
+    return Dispatch{sc, pixStats, c->tune.phaseStats, c->tune.pipeline, c->profiling, false, &c->rep.traceLaunchesTotal, c->stream, c->q.counts, 0, 100};
+}
+
+// Paths of a dispatch. Several frames in one dispatch: the paths are {64 tile slots} x {frames} (FrameParams::nFrames; rt_kernels.hip.h:
+// frame_slot), in either pipeline
+uint64_t frame_slots(uint64_t nPixels) { return (nPixels + 63) / 64 * 64; }
+uint64_t dispatch_slots(uint64_t nPixels, uint32_t nFrames) { return nFrames > 1u ? frame_slots(nPixels) * nFrames : nPixels; }
+
 template <int N> using Stack = std::integral_constant<int, N>;
 
 // The traversal kernel's stack for a BVH of depth d and at most `cap` LDS entries per lane: f(Stack<STACK>, bool_constant<OVF>,
@@ -270,7 +288,7 @@ auto with_stack(uint32_t d, uint32_t cap, bool cull, F&& f) {
 
 // A kernel to launch, the one whose occupancy sizes the grid (no heat maps, no phase statistics), its stack, and its name as a
 // demangler prints it (rt_last_kernel; tests/test_instantiations.py compares it with `nm -C`)
-template <typename K> struct KernelChoice { K kernel, occupancy; int stack; bool ovf; char name[sizeof rt_ctx::lastKernel]; };
+template <typename K> struct KernelChoice { K kernel, occupancy; int stack; bool ovf; char name[sizeof rt_ctx::Reports::lastKernel]; };
 using TracePwChoice = KernelChoice<void (*)(DevScene, PathState, TracePwArgs)>;
 using FusedChoice = KernelChoice<void (*)(FusedKernArgs)>;
 
@@ -294,37 +312,37 @@ FusedChoice fused_kernel() {
 }
 
 template <int STACK, bool OVF, bool CULL>
-TracePwChoice choose_trace_pw(const rt_ctx* c, bool pix) {
+TracePwChoice choose_trace_pw(const rt_ctx* c, const Dispatch& d, bool pix) {
     // top-level pairs from LDS (k_trace_pw<HOT>): what 160 KB of LDS per CU leave beside the stacks. hot_pairs 1: six work-groups
     // per CU, 2: five (more pairs, no spills at 96 registers)
     // (the overflow-stack kernel with 16 entries in LDS keeps six work-groups AND 120 pairs: deep BVHs, see launch_trace)
     constexpr int HOT6 = OVF ? (STACK == 16 ? 120 : 0) : STACK == 8 ? 192 : STACK == 16 ? 136 : STACK == 20 ? 72 : 0;
     constexpr int HOT5 = OVF ? 0 : STACK == 24 ? 80 : STACK == 20 ? 144 : 192;
-    int hotMode = (!pix && !c->phaseStats && c->sc.hotNodes > 0) ? c->hotPairs : 0;
+    int hotMode = (!pix && !d.phaseStats && d.sc.hotNodes > 0) ? c->tune.hotPairs : 0;
     if (hotMode == 1 && HOT6 == 0) hotMode = 2;   // (a 24-entry stack leaves no room at six work-groups)
     if (hotMode == 2 && HOT5 == 0) hotMode = HOT6 ? 1 : 0;   // (overflow-stack instantiations: the table only beside 16-entry stacks)
     // (if constexpr: an instantiation the tables can never select is not compiled — every kernel in the library can be
     // launched, and tests/test_instantiations.py launches every one of them against the oracle)
     if constexpr (HOT6 > 0) { if (hotMode == 1) return trace_pw_kernel<STACK, OVF, false, false, CULL, HOT6, 6>(); }
     if constexpr (HOT5 > 0) { if (hotMode == 2) return trace_pw_kernel<STACK, OVF, false, false, CULL, HOT5, 5>(); }
-    if (c->phaseStats) return trace_pw_kernel<STACK, OVF, true, true, CULL>();
+    if (d.phaseStats) return trace_pw_kernel<STACK, OVF, true, true, CULL>();
     if (pix) return trace_pw_kernel<STACK, OVF, true, false, CULL>();
     return trace_pw_kernel<STACK, OVF, false, false, CULL>();
 }
 
 template <typename K>
 uint32_t resident_blocks(const rt_ctx* c, K kernel) {
-    int perCU = c->blocksPerCU;
+    int perCU = c->tune.blocksPerCU;
     if (perCU <= 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, RT_BLOCK, 0) != hipSuccess || perCU <= 0)) perCU = 4;
     return (uint32_t)perCU * (uint32_t)c->numCUs;
 }
 
 // with_stack picks an OVF kernel only for a BVH deeper than its stack; the map kernels have the buffer at any depth. Each part of
 // a dispatch has its own: their launches run at the same time.
-int overflow_buf(rt_ctx* c, int stack, bool ovf, uint32_t resident, uint32_t** out) {
+int overflow_buf(rt_ctx* c, const Dispatch& d, int stack, bool ovf, uint32_t resident, uint32_t** out) {
     *out = nullptr;
     if (!ovf || c->maxLeafDepth <= (uint32_t)stack) return 0;
-    DevBuf& ob = c->overflowBuf[c->curLane];
+    DevBuf& ob = c->overflowBuf[d.part];
     int rc = dev_alloc(c, ob, (size_t)(c->maxLeafDepth - stack) * resident * RT_BLOCK * 4);
     if (rc) return rc;
     *out = (uint32_t*)ob.p;
@@ -332,17 +350,17 @@ int overflow_buf(rt_ctx* c, int stack, bool ovf, uint32_t resident, uint32_t** o
 }
 
 int wave_time_buf(rt_ctx* c, uint32_t blocks, unsigned long long** out) {
-    c->waveTimesCount = (size_t)blocks * (RT_BLOCK / RT_WAVE);
-    int rc = dev_alloc(c, c->waveTimeBuf, c->waveTimesCount * 16);
+    c->rep.waveTimesCount = (size_t)blocks * (RT_BLOCK / RT_WAVE);
+    int rc = dev_alloc(c, c->waveTimeBuf, c->rep.waveTimesCount * 16);
     if (rc) return rc;
     *out = (unsigned long long*)c->waveTimeBuf.p;
     return 0;
 }
 
 // HIP events around a traversal launch while profiling (harvest_events); the end also counts the launch
-int prof_begin(rt_ctx* c, hipStream_t stream, EventPair** ev) {
+int prof_begin(rt_ctx* c, const Dispatch& d, EventPair** ev) {
     *ev = nullptr;
-    if (!c->profiling) return 0;
+    if (!d.profiled) return 0;
     if (c->evUsed == c->evPool.size()) {
         EventPair p;
         RT_HIP(c, hipEventCreate(&p.a));
@@ -350,12 +368,12 @@ int prof_begin(rt_ctx* c, hipStream_t stream, EventPair** ev) {
         c->evPool.push_back(p);
     }
     *ev = &c->evPool[c->evUsed++];
-    RT_HIP(c, hipEventRecord((*ev)->a, stream));
+    RT_HIP(c, hipEventRecord((*ev)->a, d.stream));
     return 0;
 }
-int prof_end(rt_ctx* c, hipStream_t stream, EventPair* ev) {
-    if (ev) RT_HIP(c, hipEventRecord(ev->b, stream));
-    c->traceLaunchesTotal++;
+int prof_end(rt_ctx* c, const Dispatch& d, EventPair* ev) {
+    if (ev) RT_HIP(c, hipEventRecord(ev->b, d.stream));
+    if (d.launches) ++*d.launches;
     return 0;
 }
 
@@ -367,29 +385,29 @@ int prof_end(rt_ctx* c, hipStream_t stream, EventPair* ev) {
 // longest ray and the shading step do not shrink with the block); beyond two blocks per wave the
 // dynamic hand-out evens the waves out by itself and whole 8x8 blocks are best.
 uint32_t fused_batch_pixels(const rt_ctx* c, uint32_t nPixels, uint32_t waves, uint32_t evenBelow) {
-    if (c->batchPixels > 0) return (uint32_t)std::min(c->batchPixels, (int)RT_WAVE);
+    if (c->tune.batchPixels > 0) return (uint32_t)std::min(c->tune.batchPixels, (int)RT_WAVE);
     if (((uint64_t)nPixels + RT_WAVE - 1) / RT_WAVE > (uint64_t)evenBelow * waves) return RT_WAVE;
     uint32_t best = RT_WAVE;
     uint64_t bestCost = ~0ull;
     for (uint32_t b = RT_WAVE; b >= 16; b--) {
         const uint64_t nb = (nPixels + b - 1) / b;
         const uint64_t rounds = (nb + waves - 1) / waves;
-        const uint64_t cost = rounds * (uint64_t)((uint32_t)c->batchFixed + b);
+        const uint64_t cost = rounds * (uint64_t)((uint32_t)c->tune.batchFixed + b);
         if (cost < bestCost) { bestCost = cost; best = b; }
     }
     return best;
 }
 
 // The whole dispatch in one launch of k_render_fused, or of k_render_fused_maps for a scene that binds a map (fused_maps)
-int launch_fused(rt_ctx* c, const FrameParams& fp, float4* fb) {
+int launch_fused(rt_ctx* c, const Dispatch& d, const FrameParams& fp, float4* fb) {
     EventPair* ev;
-    int rc = prof_begin(c, c->stream, &ev);
+    int rc = prof_begin(c, d, &ev);
     if (rc) return rc;
-    const FusedChoice k = c->sc.mapFlags  // one kernel, any depth, any objects: <24, true, *, true>
-        ? kernel_choice(c->pixStats ? k_render_fused_maps<true> : k_render_fused_maps<false>, k_render_fused_maps<false>, 24, true, "k_render_fused_maps<%s>", tf(c->pixStats))
-        : with_stack<false>(c->maxLeafDepth, (uint32_t)c->ldsStackCap, c->cull, [&](auto S, auto O, auto C) { return c->pixStats ? fused_kernel<S, O, true, C>() : fused_kernel<S, O, false, C>(); });
+    const FusedChoice k = d.sc.mapFlags  // one kernel, any depth, any objects: <24, true, *, true>
+        ? kernel_choice(d.pixStats ? k_render_fused_maps<true> : k_render_fused_maps<false>, k_render_fused_maps<false>, 24, true, "k_render_fused_maps<%s>", tf(d.pixStats))
+        : with_stack<false>(c->maxLeafDepth, (uint32_t)c->tune.ldsStackCap, c->cull, [&](auto S, auto O, auto C) { return d.pixStats ? fused_kernel<S, O, true, C>() : fused_kernel<S, O, false, C>(); });
     const uint32_t resident = resident_blocks(c, k.occupancy);
-    const uint32_t nSlots = fp.nFrames > 1u ? ((fp.nPixels + 63u) / 64u) * 64u * fp.nFrames : fp.nPixels;  // rt_render_frames: frames are more slots of the same tile (rt_kernels.hip.h: frame_slot)
+    const uint32_t nSlots = (uint32_t)dispatch_slots(fp.nPixels, fp.nFrames);  // rt_render_frames: frames are more slots of the same tile
     // Pixels are replaced as they finish when rays are long (Sponza -7 %, its 1/2 and 1/4 tiles -8 % and -11 %: the wave no
     // longer drains to its slowest pixel once per block) and when a wave gets fewer than five blocks (Cornell + bunny /
     // + dragon, rank 0's rows of 2 GPUs -3 %, of 4 GPUs -13 %); with short rays and many blocks per wave a block at a
@@ -397,10 +415,10 @@ int launch_fused(rt_ctx* c, const FrameParams& fp, float4* fb) {
     // (scenes whose paths end early — open scenes, most samples leave after a bounce or two: fewer than 2.5 segments per sample
     // against ~4 in a closed box — empty a block's lanes unevenly; there replacing pays up to eight blocks per wave:
     // tools/heuristics_table.py, 256 bunnies on a floor under the sky, one 1080p frame: 19.1 against 19.7 ms)
-    const uint64_t fewBelow = (c->segPerPath >= 0.0 && c->segPerPath < 2.5) ? 8ull : 5ull;
+    const uint64_t fewBelow = (c->meas.segPerPath >= 0.0 && c->meas.segPerPath < 2.5) ? 8ull : 5ull;
     const bool fewBlocks = ((uint64_t)nSlots + RT_WAVE - 1) / RT_WAVE < fewBelow * resident * (RT_BLOCK / RT_WAVE);
-    const uint32_t pixelRefill = c->pixelRefill > 0 ? (uint32_t)c->pixelRefill
-                               : ((c->boxPerRay >= (double)c->fusedBelowBoxTests || fewBlocks) ? 8u : (uint32_t)RT_WAVE);
+    const uint32_t pixelRefill = c->tune.pixelRefill > 0 ? (uint32_t)c->tune.pixelRefill
+                               : ((c->meas.boxPerRay >= (double)c->tune.fusedBelowBoxTests || fewBlocks) ? 8u : (uint32_t)RT_WAVE);
     // a wave that replaces its pixels one by one evens out by itself as soon as there is more than one block per wave
     const uint32_t evenBelow = pixelRefill < RT_WAVE ? 1u : 2u;
     uint32_t batchPixels = fused_batch_pixels(c, nSlots, resident * (RT_BLOCK / RT_WAVE), evenBelow);
@@ -408,96 +426,118 @@ int launch_fused(rt_ctx* c, const FrameParams& fp, float4* fb) {
     // all over the tile cost about the same (-6 % on a 1/8-height 1080p tile); with more blocks per wave the dynamic
     // hand-out balances by itself and neighbouring pixels (shared cache lines, coherent rays) are 3-8 % faster.
     const uint32_t wavesResident = resident * (RT_BLOCK / RT_WAVE);
-    const uint32_t g = fp.nFrames > 1u ? 0u : c->scatter >= 0 ? (uint32_t)c->scatter : ((((uint64_t)nSlots + RT_WAVE - 1) / RT_WAVE <= (uint64_t)evenBelow * wavesResident) ? 4u : 0u);
+    const uint32_t g = fp.nFrames > 1u ? 0u : c->tune.scatter >= 0 ? (uint32_t)c->tune.scatter : ((((uint64_t)nSlots + RT_WAVE - 1) / RT_WAVE <= (uint64_t)evenBelow * wavesResident) ? 4u : 0u);
     if (g) batchPixels = std::min((uint32_t)RT_WAVE, (batchPixels + g - 1) / g * g);
     const uint32_t nBatches = g ? ((nSlots + g - 1) / g + batchPixels / g - 1) / (batchPixels / g) : (nSlots + batchPixels - 1) / batchPixels;
     const uint32_t blocks = std::max(1u, std::min((nBatches + (RT_BLOCK / RT_WAVE) - 1) / (RT_BLOCK / RT_WAVE), resident));
     uint32_t* overflow;
-    if ((rc = overflow_buf(c, k.stack, k.ovf, resident, &overflow))) return rc;
-    RT_HIP(c, hipMemsetAsync(c->q.counts + 5, 0, 4, c->stream));
+    if ((rc = overflow_buf(c, d, k.stack, k.ovf, resident, &overflow))) return rc;
+    RT_HIP(c, hipMemsetAsync(d.counts + 5, 0, 4, d.stream));
     // lanes at interior nodes that make the wave skip the vote: long rays (Sponza: 157 box tests per ray) want the interior step
     // to wait for more lanes (40: -4 %); 24 for short rays and until the scene is measured
-    const uint32_t fastLanes = c->fastLanesSet ? (uint32_t)c->fastLanes : (c->boxPerRay >= (double)c->fusedBelowBoxTests ? 40u : 24u);
-    const uint32_t wLeaf = (uint32_t)c->wLeafFused;
+    const uint32_t fastLanes = c->tune.fastLanesSet ? (uint32_t)c->tune.fastLanes : (c->meas.boxPerRay >= (double)c->tune.fusedBelowBoxTests ? 40u : 24u);
+    const uint32_t wLeaf = (uint32_t)c->tune.wLeafFused;
     unsigned long long* waveTimes = nullptr;
-    if (c->phaseStats && (rc = wave_time_buf(c, blocks, &waveTimes))) return rc;
-    FusedArgs fa{c->q.counts + 5, fb, (DevCounters*)c->counterBuf.p, overflow, (uint32_t)c->refill, (uint32_t)c->wSetupFused, wLeaf, fastLanes, batchPixels, g, (uint32_t)c->fastShare, waveTimes, pixelRefill};
-    c->lastBatchPixels = (int)batchPixels;
-    const FusedKernArgs ka{c->sc, c->ps, fp, fa};
-    memcpy(c->lastKernel, k.name, sizeof k.name);
-    hipLaunchKernelGGL(k.kernel, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, ka);
+    if (d.phaseStats && (rc = wave_time_buf(c, blocks, &waveTimes))) return rc;
+    FusedArgs fa{d.counts + 5, fb, (DevCounters*)c->counterBuf.p, overflow, (uint32_t)c->tune.refill, (uint32_t)c->tune.wSetupFused, wLeaf, fastLanes, batchPixels, g, (uint32_t)c->tune.fastShare, waveTimes, pixelRefill};
+    const FusedKernArgs ka{d.sc, c->ps, fp, fa};
+    memcpy(c->rep.lastKernel, k.name, sizeof k.name);
+    hipLaunchKernelGGL(k.kernel, dim3(blocks), dim3(RT_BLOCK), 0, d.stream, ka);
     RT_HIP(c, hipGetLastError());
-    return prof_end(c, c->stream, ev);
+    return prof_end(c, d, ev);
 }
 
 template <int STACK>
-void launch_v0_t(rt_ctx* c, uint32_t maxRays, const TraceArgs& ta) {
+void launch_v0_t(rt_ctx* c, const Dispatch& d, uint32_t maxRays, const TraceArgs& ta) {
     uint32_t blocks = (maxRays + RT_BLOCK - 1) / RT_BLOCK;
-    snprintf(c->lastKernel, sizeof c->lastKernel, "k_trace<%d>", STACK);
-    hipLaunchKernelGGL((k_trace<STACK>), dim3(blocks), dim3(RT_BLOCK), 0, c->curStream ? c->curStream : c->stream, c->sc, c->ps, ta);
+    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_trace<%d>", STACK);
+    hipLaunchKernelGGL((k_trace<STACK>), dim3(blocks), dim3(RT_BLOCK), 0, d.stream, d.sc, c->ps, ta);
 }
 
 // the work counter (counts[4]) must be zero when this is called
-int launch_trace(rt_ctx* c, uint32_t maxRays, const TraceArgs& ta) {
+int launch_trace(rt_ctx* c, const Dispatch& d, uint32_t maxRays, const TraceArgs& ta) {
     if (maxRays == 0) return 0;
-    hipStream_t stream = c->curStream ? c->curStream : c->stream;
     EventPair* ev;
-    int rc = prof_begin(c, stream, &ev);
+    int rc = prof_begin(c, d, &ev);
     if (rc) return rc;
-    const uint32_t d = c->maxLeafDepth;
-    const bool pix = c->pixStats || ta.perRayBox;  // per-ray counters are only needed for the pixel heat maps (debug >= 0) and rt_trace_rays
-    const bool alpha = c->sc.mapFlags & RT_MAP_ALPHA;  // a bound alpha map: the one traversal kernel that reads it (any depth, any objects)
-    if (!alpha && c->traceVariant == 0) {  // one ray per lane, whole stack in LDS
-        if (d <= 8) launch_v0_t<8>(c, maxRays, ta);
-        else if (d <= 16) launch_v0_t<16>(c, maxRays, ta);
-        else if (d <= 24) launch_v0_t<24>(c, maxRays, ta);
-        else if (d <= 32) launch_v0_t<32>(c, maxRays, ta);
-        else if (d <= 48) launch_v0_t<48>(c, maxRays, ta);
-        else launch_v0_t<64>(c, maxRays, ta);
+    const uint32_t depth = c->maxLeafDepth;
+    const bool pix = d.pixStats || ta.perRayBox;  // per-ray counters are only needed for the pixel heat maps (debug >= 0) and rt_trace_rays
+    const bool alpha = d.sc.mapFlags & RT_MAP_ALPHA;  // a bound alpha map: the one traversal kernel that reads it (any depth, any objects)
+    if (!alpha && c->tune.traceVariant == 0) {  // one ray per lane, whole stack in LDS
+        if (depth <= 8) launch_v0_t<8>(c, d, maxRays, ta);
+        else if (depth <= 16) launch_v0_t<16>(c, d, maxRays, ta);
+        else if (depth <= 24) launch_v0_t<24>(c, d, maxRays, ta);
+        else if (depth <= 32) launch_v0_t<32>(c, d, maxRays, ta);
+        else if (depth <= 48) launch_v0_t<48>(c, d, maxRays, ta);
+        else launch_v0_t<64>(c, d, maxRays, ta);
     } else {  // persistent waves; at most 24 entries in LDS, deeper ones in the overflow buffer
         // BVHs deeper than 24: 16 entries in LDS, the rest in the overflow buffer (the stack only holds far siblings and is rarely
         // that deep), which leaves room for 120 top-level pairs beside six work-groups per CU: C5 at 4K 474 -> 468 ms per step,
         // flattened 471 -> 462, 1080p 117.5 -> 115.6 (Cornell + dragon: level)
-        const bool tableWanted = c->hotPairs && c->sc.hotNodes > 0 && !c->phaseStats && !pix;  // (choose_trace_pw's condition)
-        const uint32_t cap = (d > 24u && c->ldsStackCap >= 24 && tableWanted) ? 16u : (uint32_t)c->ldsStackCap;
+        const bool tableWanted = c->tune.hotPairs && d.sc.hotNodes > 0 && !d.phaseStats && !pix;  // (choose_trace_pw's condition)
+        const uint32_t cap = (depth > 24u && c->tune.ldsStackCap >= 24 && tableWanted) ? 16u : (uint32_t)c->tune.ldsStackCap;
         const TracePwChoice k = alpha
             ? kernel_choice(pix ? k_trace_pw_alpha<true> : k_trace_pw_alpha<false>, k_trace_pw_alpha<false>, 24, true, "k_trace_pw_alpha<%s>", tf(pix))
-            : with_stack<true>(d, cap, c->cull, [&](auto S, auto O, auto C) { return choose_trace_pw<S, O, C>(c, pix); });
+            : with_stack<true>(depth, cap, c->cull, [&](auto S, auto O, auto C) { return choose_trace_pw<S, O, C>(c, d, pix); });
         const uint32_t resident = resident_blocks(c, k.occupancy);
-        // a part of a dispatch that runs beside the other parts' launches takes its share of the resident work-groups (curGridPct)
-        const uint32_t blocks = std::min((maxRays + RT_BLOCK - 1) / RT_BLOCK, std::max(1u, (uint32_t)((uint64_t)resident * (uint32_t)c->curGridPct / 100u)));
+        // a part of a dispatch that runs beside the other parts' launches takes its share of the resident work-groups (Dispatch::gridPct)
+        const uint32_t blocks = std::min((maxRays + RT_BLOCK - 1) / RT_BLOCK, std::max(1u, (uint32_t)((uint64_t)resident * (uint32_t)d.gridPct / 100u)));
         uint32_t* overflow;
-        if ((rc = overflow_buf(c, k.stack, k.ovf, resident, &overflow))) return rc;
+        if ((rc = overflow_buf(c, d, k.stack, k.ovf, resident, &overflow))) return rc;
         unsigned long long* waveTimes = nullptr;
-        const bool times = c->phaseStats == 1 || (c->phaseStats >= 2 && c->traceLaunchesTotal == (uint64_t)(c->phaseStats - 2));  // 1: the last launch's waves; 2 + k: launch k's (after rt_reset_counters)
+        const bool times = d.phaseStats == 1 || (d.phaseStats >= 2 && d.launches && *d.launches == (uint64_t)(d.phaseStats - 2));  // 1: the last launch's waves; 2 + k: launch k's (after rt_reset_counters)
         if (!alpha && times && (rc = wave_time_buf(c, blocks, &waveTimes))) return rc;
         // Long rays (the measure the pipeline choice uses) want new rays sooner and their set-up served later: idle lanes re-armed at 12
         // instead of 16, set-up steps voted in at weight 32 instead of 16 (Sponza 81.0 -> 79.4 ms per step, C5 115.4 -> 114.1;
         // Cornell + bunny / + dragon, short rays: +2.5 / +3.5 % with the same, so they keep 16 / 16). Knobs set by hand win.
-        const bool longRays = c->boxPerRay >= (double)c->fusedBelowBoxTests;
-        const uint32_t refillMk = c->refillMkSet ? (uint32_t)c->refillMk : (longRays ? 12u : 16u);
-        const uint32_t wSetup = c->wSetupSet ? (uint32_t)c->wSetup : (longRays ? 32u : 16u);
-        uint32_t* laneCounts = c->curCounts ? c->curCounts : c->q.counts;
-        const TracePwArgs pa{ta.queue, ta.count, laneCounts + 4, refillMk, (uint32_t)c->chunk, wSetup, (uint32_t)c->wLeaf, (uint32_t)c->fastLanes, (uint32_t)c->fastShare,
+        const bool longRays = c->meas.boxPerRay >= (double)c->tune.fusedBelowBoxTests;
+        const uint32_t refillMk = c->tune.refillMkSet ? (uint32_t)c->tune.refillMk : (longRays ? 12u : 16u);
+        const uint32_t wSetup = c->tune.wSetupSet ? (uint32_t)c->tune.wSetup : (longRays ? 32u : 16u);
+        const TracePwArgs pa{ta.queue, ta.count, d.counts + 4, refillMk, (uint32_t)c->tune.chunk, wSetup, (uint32_t)c->tune.wLeaf, (uint32_t)c->tune.fastLanes, (uint32_t)c->tune.fastShare,
                              ta.perRayBox, ta.perRayTri, ta.counters, (unsigned long long*)((char*)c->counterBuf.p + sizeof(DevCounters)), waveTimes, overflow, ta.countAux, ta.countAux2, ta.auxOffset};
-        memcpy(c->lastKernel, k.name, sizeof k.name);
-        hipLaunchKernelGGL(k.kernel, dim3(blocks), dim3(RT_BLOCK), 0, stream, c->sc, c->ps, pa);
+        memcpy(c->rep.lastKernel, k.name, sizeof k.name);
+        hipLaunchKernelGGL(k.kernel, dim3(blocks), dim3(RT_BLOCK), 0, d.stream, d.sc, c->ps, pa);
     }
     RT_HIP(c, hipGetLastError());
-    return prof_end(c, stream, ev);
+    return prof_end(c, d, ev);
 }
 
-void poll_ray_cost(rt_ctx* c);
+// Fold in the counter snapshot of an earlier dispatch if its copy has arrived (never waits).
+void poll_ray_cost(rt_ctx* c) {
+    if (!c->meas.snapPending || hipEventQuery(c->snapEvent) != hipSuccess) return;
+    c->meas.snapPending = false;
+    const unsigned long long box = c->snap->boxTests - c->snap->skippedBoxTests, rays = c->snap->raysTraced;  // executed tests: what a ray costs the GPU
+    if (rays > c->meas.snapRays && box >= c->meas.snapBox && rays - c->meas.snapRays > 100000ull)
+        c->meas.boxPerRay = (double)(box - c->meas.snapBox) / (double)(rays - c->meas.snapRays);
+    const unsigned long long seg = c->snap->segments, paths = c->snap->paths;
+    if (paths > c->meas.snapPaths && seg >= c->meas.snapSeg && paths - c->meas.snapPaths > 100000ull) c->meas.segPerPath = (double)(seg - c->meas.snapSeg) / (double)(paths - c->meas.snapPaths);
+    c->meas.snapBox = box;
+    c->meas.snapRays = rays;
+    c->meas.snapSeg = seg;
+    c->meas.snapPaths = paths;
+}
+// Queue the next snapshot behind the dispatch just enqueued.
+void request_ray_cost(rt_ctx* c) {
+    if (c->meas.snapPending) return;
+    if (hipMemcpyAsync(c->snap, c->counterBuf.p, sizeof(DevCounters), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return;
+    if (hipEventRecord(c->snapEvent, c->stream) != hipSuccess) return;
+    c->meas.snapPending = true;
+}
+// What the measured statistics keep of the previous scene when a new one is uploaded (the stream is idle)
+void measured_new_scene(rt_ctx* c) {
+    if (c->meas.snapPending) { c->meas.snapBox = c->snap->boxTests; c->meas.snapRays = c->snap->raysTraced; c->meas.snapPending = false; }
+    c->meas.boxPerRay = -1.0;  // a new scene: its ray cost is not known yet
+}
 
 // sum finished event pairs; the stream must be idle
 int harvest_events(rt_ctx* c) {
     for (size_t i = 0; i < c->evUsed; i++) {
         float ms = 0.f;
         RT_HIP(c, hipEventElapsedTime(&ms, c->evPool[i].a, c->evPool[i].b));
-        c->traceMs += ms;
-        c->traceLaunches++;
+        c->rep.traceMs += ms;
+        c->rep.traceLaunches++;
         float t0 = 0.f;
-        if (c->profBase && hipEventElapsedTime(&t0, c->profBase, c->evPool[i].a) == hipSuccess) c->traceSpans.emplace_back(t0, t0 + ms);
+        if (c->profBase && hipEventElapsedTime(&t0, c->profBase, c->evPool[i].a) == hipSuccess) c->rep.traceSpans.emplace_back(t0, t0 + ms);
     }
     c->evUsed = 0;
     return 0;
@@ -532,7 +572,7 @@ int refresh_maps(rt_ctx* c) {
 int rebuild_emitters(rt_ctx* c) {
     c->sc.emitCount = 0; c->sc.emitSphereMask = 0; c->sc.emitMode = 0;
     { int rc = refresh_maps(c); if (rc) return rc; }
-    if (!c->lightQueries || c->hostMats.empty()) return 0;
+    if (!c->tune.lightQueries || c->hostMats.empty()) return 0;
     auto emissive = [&](uint32_t m) { return m < c->hostMats.size() && !(c->hostMats[m].emissionStrength == 0.f); };
     for (const RayMaterial& m : c->hostMats)
         for (int k = 0; k < 3; k++)
@@ -618,28 +658,19 @@ void rt_destroy(rt_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& b : c->sceneBufs) dev_free(b);
-    for (DevBuf* b : {&c->matBuf, &c->sphereBuf, &c->sphereMatBuf, &c->objInvBuf, &c->objFwdBuf, &c->objMetaBuf, &c->objBoxBuf, &c->objSkipBuf, &c->maskBoxBuf, &c->emitBuf, &c->emitPreBuf, &c->texelBuf, &c->texInfoBuf, &c->triUVBuf, &c->objTreeBuf, &c->objCostBuf, &c->objAlphaBuf, &c->stateBuf,
-                      &c->queueBuf, &c->fbBuf, &c->counterBuf, &c->scratchBuf, &c->waveTimeBuf, &c->probeBuf, &c->aovBuf, &c->aovCounterBuf,
-                      &c->dnWorkBuf, &c->dnHostBuf, &c->dnOutBuf})
-        dev_free(*b);
     (void)rt_comm_destroy(c);
-    dev_free(c->gatherBuf);
     for (auto& e : c->evPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (c->hostCounts) (void)hipHostFree(c->hostCounts);
     if (c->snap) (void)hipHostFree(c->snap);
-    if (c->snapEvent) (void)hipEventDestroy(c->snapEvent);
-    if (c->pollEvent) (void)hipEventDestroy(c->pollEvent);
-    if (c->forkEvent) (void)hipEventDestroy(c->forkEvent);
-    if (c->profBase) (void)hipEventDestroy(c->profBase);
+    for (hipEvent_t e : {c->snapEvent, c->pollEvent, c->forkEvent, c->profBase})
+        if (e) (void)hipEventDestroy(e);
     for (int l = 0; l < RT_MAX_LANES - 1; l++) {
         if (c->joinEvent[l]) (void)hipEventDestroy(c->joinEvent[l]);
         if (c->pollEventSide[l]) (void)hipEventDestroy(c->pollEventSide[l]);
         if (c->sideStream[l]) (void)hipStreamDestroy(c->sideStream[l]);
     }
-    for (DevBuf& b : c->overflowBuf) dev_free(b);
     if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
-    delete c;
+    delete c;  // every DevBuf frees itself
 }
 
 const char* rt_last_error(const rt_ctx* c) { return c ? c->error.c_str() : "null ctx"; }
@@ -770,7 +801,7 @@ int rt_update_objects(rt_ctx* c, const RenderObject* o, uint32_t n) {
                 boxOk = 6u;  // the rays' creators may rule the object out as well (bit 2)
             }
         }
-        if (isIdent && c->maskIdentity) {  // exact root box: the rays' creators could rule the object out with the traversal's own
+        if (isIdent && c->tune.maskIdentity) {  // exact root box: the rays' creators could rule the object out with the traversal's own
             wbox[2 * (size_t)i] = make_float4(r.lo[0], r.lo[1], r.lo[2], 0.f);       // slab test. Off by default: measured, the rounds
             wbox[2 * (size_t)i + 1] = make_float4(r.hi[0], r.hi[1], r.hi[2], 0.f);   // this saves are the cheap ones (profiles/README.md)
             boxOk = 4u;
@@ -816,7 +847,7 @@ int rt_update_objects(rt_ctx* c, const RenderObject* o, uint32_t n) {
     // origin is not much farther out than the objects are big: both errors grow like 6e-8 * |origin|. Rays
     // that start beyond 1e3 object scales take the reference's own route through every object.
     c->sc.cullOriginLimit = minScale < 1e300 ? (float)(minScale * 1e3) : 0.f;
-    c->cull = nGeneral >= 2 || (c->maskIdentity && c->sc.reachCount);
+    c->cull = nGeneral >= 2 || (c->tune.maskIdentity && c->sc.reachCount);
     if (!c->cull) c->sc.reachCount = 0;
     if ((rc = upload(c, c->maskBoxBuf, maskBox.data(), maskBox.size() * sizeof(float4)))) return rc;
     c->sc.maskBox = (const float4*)c->maskBoxBuf.p;
@@ -844,7 +875,7 @@ int rt_update_objects(rt_ctx* c, const RenderObject* o, uint32_t n) {
         }
         uint32_t off[RT_OBJTREE_LEVELS + 1] = {};
         uint32_t levels = 0;
-        if (c->objTreeMin > 0 && nGeneral >= (uint32_t)c->objTreeMin) {
+        if (c->tune.objTreeMin > 0 && nGeneral >= (uint32_t)c->tune.objTreeMin) {
             auto skippable = [&](uint32_t i) { return i < n && (meta[i].w & 3u) == 2u; };
             for (uint32_t k = 1; k <= (uint32_t)RT_OBJTREE_LEVELS; k++) {
                 off[k] = (uint32_t)(tree.size() / 2);
@@ -892,16 +923,11 @@ int rt_update_objects(rt_ctx* c, const RenderObject* o, uint32_t n) {
     return rebuild_emitters(c);
 }
 
-}  // extern "C"
-
-extern "C" {
-
 int rt_upload_scene(rt_ctx* c, const RtSceneArrays* s) {
     if (!c || !s) return -1;
     RT_HIP(c, hipSetDevice(c->device));
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->snapPending) { c->snapBox = c->snap->boxTests; c->snapRays = c->snap->raysTraced; c->snapPending = false; }
-    c->boxPerRay = -1.0;  // a new scene: its ray cost is not known yet
+    measured_new_scene(c);
     c->hostObjMat.clear(); c->hostObjRoot.clear(); c->hostObjSampler.clear(); c->hostSphereMat.clear(); c->hostMats.clear();
     c->sc.emitMode = 0; c->sc.emitCount = 0; c->sc.emitSphereMask = 0;
     c->sc.mapFlags = 0;
@@ -1055,8 +1081,8 @@ int rt_upload_scene(rt_ctx* c, const RtSceneArrays* s) {
         if (rcu) return rcu;
         c->sc.triUV = (const float4*)c->triUVBuf.p;
     }
-    for (auto& b : c->sceneBufs) dev_free(b);
-    c->sceneBufs.assign(5, DevBuf());
+    c->sceneBufs.clear();
+    c->sceneBufs.resize(5);
     int rc;
     if ((rc = upload(c, c->sceneBufs[0], nodes.data(), nodes.size() * sizeof(float4)))) return rc;
     if ((rc = upload(c, c->sceneBufs[1], tpos.data(), tpos.size() * sizeof(float4)))) return rc;
@@ -1084,68 +1110,6 @@ int rt_sync(rt_ctx* c) {
     RT_HIP(c, hipStreamSynchronize(c->stream));
     return harvest_events(c);
 }
-
-}  // extern "C"
-
-namespace {
-// Fold in the counter snapshot of an earlier dispatch if its copy has arrived (never waits).
-void poll_ray_cost(rt_ctx* c) {
-    if (!c->snapPending || hipEventQuery(c->snapEvent) != hipSuccess) return;
-    c->snapPending = false;
-    const unsigned long long box = c->snap->boxTests - c->snap->skippedBoxTests, rays = c->snap->raysTraced;  // executed tests: what a ray costs the GPU
-    if (rays > c->snapRays && box >= c->snapBox && rays - c->snapRays > 100000ull)
-        c->boxPerRay = (double)(box - c->snapBox) / (double)(rays - c->snapRays);
-    const unsigned long long seg = c->snap->segments, paths = c->snap->paths;
-    if (paths > c->snapPaths && seg >= c->snapSeg && paths - c->snapPaths > 100000ull) c->segPerPath = (double)(seg - c->snapSeg) / (double)(paths - c->snapPaths);
-    c->snapBox = box;
-    c->snapRays = rays;
-    c->snapSeg = seg;
-    c->snapPaths = paths;
-}
-// Queue the next snapshot behind the dispatch just enqueued.
-void request_ray_cost(rt_ctx* c) {
-    if (c->snapPending) return;
-    if (hipMemcpyAsync(c->snap, c->counterBuf.p, sizeof(DevCounters), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return;
-    if (hipEventRecord(c->snapEvent, c->stream) != hipSuccess) return;
-    c->snapPending = true;
-}
-
-// The launch parameters of both pipelines follow the scene's measured box tests per ray, which the first dispatch of a
-// scene does not have — and a single-render job (the reference's singleRender mode: all samples in one dispatch) is
-// nothing but a first dispatch. Before a big one, eight rows of the same tile are rendered once with one sample per
-// pixel into a scratch image and the counters put back: a few ms, no trace in anything the caller can read.
-int probe_ray_cost(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride, uint32_t nRows) {
-    const uint32_t rows = std::min(nRows, 8u), skip = nRows / rows;
-    PushConstants p = *pc;
-    p.rayTraceParams.singleRender = 1;
-    p.rayTraceParams.sampleLimit = 1;
-    p.rayTraceParams.progressive = 0;
-    p.rayTraceParams.debug = -1;
-    int rc = dev_alloc(c, c->probeBuf, (size_t)rows * width * sizeof(float4));
-    if (rc) return rc;
-    DevCounters before, after;
-    RT_HIP(c, hipMemcpyAsync(&before, c->counterBuf.p, sizeof(DevCounters), hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    const int pipeline = c->pipeline, lastPipeline = c->lastPipeline, lastBatch = c->lastBatchPixels;
-    const bool profiling = c->profiling; const int phaseStats = c->phaseStats;
-    const uint64_t launches = c->traceLaunchesTotal;
-    c->pipeline = 1; c->profiling = false; c->phaseStats = 0; c->inProbe = true;
-    rc = rt_render(c, &p, width, height, row0 + (skip / 2u) * rowStride, rowStride * skip, rows, (float*)c->probeBuf.p);
-    c->pipeline = pipeline; c->profiling = profiling; c->phaseStats = phaseStats; c->inProbe = false;
-    c->lastPipeline = lastPipeline; c->lastBatchPixels = lastBatch; c->traceLaunchesTotal = launches;
-    if (rc) return rc;
-    RT_HIP(c, hipMemcpyAsync(&after, c->counterBuf.p, sizeof(DevCounters), hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    RT_HIP(c, hipMemcpyAsync(c->counterBuf.p, &before, sizeof(DevCounters), hipMemcpyHostToDevice, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    c->snapPending = false;  // the probe's own snapshot request: its copy has arrived, and it is not wanted
-    if (after.raysTraced > before.raysTraced + 1000ull)
-        c->boxPerRay = (double)((after.boxTests - after.skippedBoxTests) - (before.boxTests - before.skippedBoxTests)) / (double)(after.raysTraced - before.raysTraced);
-    return 0;
-}
-}  // namespace
-
-extern "C" {
 
 }  // extern "C"
 
@@ -1182,12 +1146,225 @@ FrameParams frame_camera(const rt_ctx* c, const PushConstants* pc, uint32_t widt
     fp.bottomLeft[0] = -fp.planeWidth / 2.f;
     fp.bottomLeft[1] = -fp.planeHeight / 2.f;
     fp.bottomLeft[2] = 0.1f;
-    fp.tiled = (c->tileSlots && (width % 8u) == 0u) ? 1u : 0u;
+    fp.tiled = (c->tune.tileSlots && (width % 8u) == 0u) ? 1u : 0u;
     fp.width = width; fp.height = height; fp.row0 = row0; fp.rowStride = rowStride; fp.nRows = nRows; fp.nPixels = nPixels;
     return fp;
 }
 
-// rt_render (nFrames = 1) and rt_render_frames
+// Both pipelines give the same bits; which one is faster depends on how much a wave has to do per pixel. Small tiles
+// and scenes with short rays (few box tests per ray, measured on this context's earlier dispatches) go to the fused one.
+// 0 = multi-kernel, 1 = fused; `pipeline` is Dispatch::pipeline.
+int choose_pipeline(const rt_ctx::Tuning& t, int pipeline, double boxPerRay, const DevScene& sc, uint32_t nSlots) {
+    const bool shortRays = boxPerRay >= 0.0 && boxPerRay < (double)t.fusedBelowBoxTests;
+    // the longer the rays, the earlier the global queue of the multi-kernel pipeline pays — and with the dispatch in overlapping
+    // parts earlier than it used to (tools/size_sweep.py, one 1080p frame = 2.07 M paths, fused / multi-kernel in parts: Sponza,
+    // 153 executed box tests per ray, 113.8 / 103.4 ms; Sponza + 16 dragons 167.2 / 162.5; the klein bottle x 8, 84 tests,
+    // 70.2 / 76.6; half a frame, 1.04 M paths: 61.5 / 66.3, 91.9 / 106.8, 41.5 / 57.4): 4 M paths up to 90 tests per ray, falling
+    // to 1.5 M at 150
+    double sizeLimit = (double)t.fusedBelowPixels;
+    if (boxPerRay > 90.0) sizeLimit = std::max(0.375 * sizeLimit, sizeLimit - (boxPerRay - 90.0) * (0.625 / 60.0) * sizeLimit);
+    // (the paths of all the frames of the dispatch count: four frames of a quarter of a 4K frame are a 4K frame's worth)
+    // Short rays keep the fused pipeline at any size — unless the traversal misses the caches: a scene whose hot data (child pairs
+    // and triangle positions) exceeds one XCD's 4 MB of L2 is bound by latency even with few tests per ray, and from 10 M paths the
+    // multi-kernel pipeline's extra resident waves and overlapping parts win there too (Cornell + bunny, 33 box tests per ray, ten
+    // 1080p frames: 36.1 against 38.0 ms per frame; + dragon 36.3 against 40.1; level between four and six frames:
+    // tools/frames_sweep.py), while small scenes (bobadog, the 45-object scene)
+    // and scenes of very short rays (fewer than 25 executed tests: 232 k loose triangles on a floor) stay fused (tools/heuristics_table.py)
+    const bool bigScene = (uint64_t)sc.nodeCount * 32u + (uint64_t)sc.triCount * 48u > (4ull << 20);
+    const bool shortButMissing = shortRays && bigScene && boxPerRay >= 25.0 && nSlots >= (10u << 20);
+    const int chosen = pipeline >= 0 ? pipeline : (((double)nSlots < sizeLimit || (shortRays && !shortButMissing)) ? 1 : 0);
+    // a scene that binds a metalness, alpha or bump map: the multi-kernel pipeline's kernels that read them (k_shade_maps,
+    // k_trace_pw_alpha), whatever "pipeline" asks for — unless "fused_maps" lets it choose as usual (k_render_fused_maps)
+    return (sc.mapFlags && !t.fusedMaps) ? 0 : chosen;
+}
+
+// The parts a multi-kernel dispatch is wanted in (ensure_part_streams may grant fewer)
+int choose_parts(const rt_ctx::Tuning& t, const Dispatch& d, bool cull, double boxPerRay, uint32_t samples, uint32_t nSlots) {
+    int nLanes = (samples > 0 && nSlots >= t.lanesMinSlots) ? std::max(1, std::min(t.lanes, (int)RT_MAX_LANES)) : 1;
+    if (d.phaseStats) nLanes = 1;  // the diagnostic kernel's statistics are per launch
+    // One scene shape loses by it (tools/lanes_table.py): long rays that walk into many placed objects (C5: sixteen instanced dragons,
+    // ~190 executed box tests per ray; 116.1 ms per frame in one part against 121.2 in three at 1080p, 472 against 492 at 4K).
+    // Every placed object a ray enters costs a set-up round that reloads the ray from its path state in HBM, so that traversal
+    // competes with the other parts' k_shade for HBM instead of complementing it. Such scenes keep one part unless "lanes" was set.
+    // (from 8 M paths on: a single 1080p frame of the same scene still gains 7 % from its parts, whose launches are short against their tails)
+    if (!t.lanesSet && cull && boxPerRay >= 150.0 && nSlots >= (8u << 20)) nLanes = 1;
+    return nLanes;
+}
+// ... and the share of the resident work-groups each part's k_trace_pw launches take
+// (small parts — one 1080p frame per dispatch is three parts of 0.69 M paths — run better on 40 % grids: 101.7 -> 99.5 ms per
+// frame; the bench's ten frames per dispatch, 6.9 M paths per part, on 50 %: 77.2 against 78.6)
+int part_grid_pct(const rt_ctx::Tuning& t, int nLanes, uint32_t firstPartSlots) {
+    return nLanes > 1 ? (t.laneGridPct > 0 ? t.laneGridPct : (firstPartSlots < 1200000u ? 40 : 50)) : 100;
+}
+
+// The side streams and events of parts 1..nLanes-1, made when first needed; returns the parts there are streams for
+int ensure_part_streams(rt_ctx* c, int nLanes) {
+    for (int l = 1; l < nLanes; l++) {
+        if (!c->sideStream[l - 1]) {
+            if (hipStreamCreateWithFlags(&c->sideStream[l - 1], hipStreamNonBlocking) != hipSuccess) { c->sideStream[l - 1] = nullptr; nLanes = l; break; }
+            if (hipEventCreateWithFlags(&c->joinEvent[l - 1], hipEventDisableTiming) != hipSuccess ||
+                hipEventCreateWithFlags(&c->pollEventSide[l - 1], hipEventDisableTiming) != hipSuccess) { nLanes = l; break; }
+        }
+    }
+    if (nLanes > 1 && !c->forkEvent && hipEventCreateWithFlags(&c->forkEvent, hipEventDisableTiming) != hipSuccess) { c->forkEvent = nullptr; nLanes = 1; }
+    return nLanes;
+}
+
+// One part of a multi-kernel dispatch: what its launches are built with (d), its slots [begin, begin + n) and the state of its rounds
+struct Lane { Dispatch d; hipEvent_t poll; uint32_t begin, n, ubActive; int cur; bool pollPending, done; };
+// The slots of a dispatch in nLanes contiguous ranges of whole blocks
+void slice_parts(rt_ctx* c, const Dispatch& d, uint32_t nSlots, uint32_t nFrames, int nLanes, Lane* lane) {
+    const uint32_t unit = 256u * std::max(1u, nFrames);  // whole blocks of k_shade, whole tile blocks of all their frames
+    const uint32_t units = (nSlots + unit - 1) / unit;
+    uint32_t at = 0;
+    for (int l = 0; l < nLanes; l++) {
+        const uint32_t u = units / (uint32_t)nLanes + ((uint32_t)l < units % (uint32_t)nLanes ? 1u : 0u);
+        const uint32_t end = std::min(nSlots, at + u * unit);
+        lane[l] = Lane{d, l ? c->pollEventSide[l - 1] : c->pollEvent, at, end - at, end - at, 0, false, end == at};
+        lane[l].d.stream = l ? c->sideStream[l - 1] : c->stream; lane[l].d.counts = c->q.counts + 16 * l; lane[l].d.part = l;
+        at = end;
+    }
+    const int gridPct = part_grid_pct(c->tune, nLanes, lane[0].n);
+    for (int l = 0; l < nLanes; l++) lane[l].d.gridPct = gridPct;
+}
+
+// The rounds of the multi-kernel pipeline: the parts fork from the ctx stream, each runs traversal, then shading, until none of its
+// paths is active, and they join it again
+int render_rounds(rt_ctx* c, const FrameParams& fp, Lane* lane, int nLanes) {
+    DevCounters* dc = (DevCounters*)c->counterBuf.p;
+    int rc = 0;
+    if (nLanes > 1) {
+        RT_HIP(c, hipEventRecord(c->forkEvent, c->stream));
+        for (int l = 1; l < nLanes; l++) RT_HIP(c, hipStreamWaitEvent(lane[l].d.stream, c->forkEvent, 0));
+    }
+    // The whole dispatch is enqueued without waiting for the device (rt_amd.h: "asynchronous on the ctx stream"): every
+    // kernel reads its queue length from device memory and leaves at once when the queue is empty, so the loop may
+    // simply run to the most rounds a pixel can need, samples * (bounceLimit + 1). The active-path count is copied
+    // back now and then without ever being waited for; a copy that has arrived shrinks the grids of the launches still
+    // to be enqueued (active paths never increase, so a stale count is a valid upper bound) and ends the part at zero.
+    const uint64_t maxRounds = (uint64_t)fp.samples * ((uint64_t)fp.bounceLimit + 1);
+    for (uint64_t it = 0; it < maxRounds; it++) {
+        bool any = false;
+        for (int l = 0; l < nLanes; l++) {
+            Lane& L = lane[l];
+            if (L.done) continue;
+            any = true;
+            const hipStream_t stream = L.d.stream; uint32_t* const counts = L.d.counts;
+            const int cur = L.cur, nxt = cur ^ 1;
+            uint32_t* const active[2] = {c->q.active[0] + L.begin, c->q.active[1] + L.begin};
+            uint32_t* const rays[2] = {c->q.rays[0] + 3 * (size_t)L.begin, c->q.rays[1] + 3 * (size_t)L.begin};
+            hipLaunchKernelGGL(k_zero_counts, dim3(1), dim3(64), 0, stream, counts + nxt, counts + 2 + nxt, counts + 4, counts + 5 + nxt, counts + 7 + nxt);
+            TraceArgs ta{rays[cur], counts + 2 + cur, nullptr, nullptr, dc, counts + 5 + cur, counts + 7 + cur, L.n};
+            const uint64_t ubRays = std::min<uint64_t>((uint64_t)L.ubActive * 3, (uint64_t)L.n * 3);
+            if ((rc = launch_trace(c, L.d, (uint32_t)ubRays, ta))) break;
+            ShadeArgs sa{active[cur], counts + cur, active[nxt], rays[nxt], counts + nxt, counts + 2 + nxt, dc, counts + 5 + nxt, counts + 7 + nxt, L.n};
+            if (L.d.sc.mapFlags & (RT_MAP_METALNESS | RT_MAP_BUMP)) hipLaunchKernelGGL(k_shade_maps, dim3((L.ubActive + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, L.d.sc, c->ps, sa, fp);
+            else hipLaunchKernelGGL(k_shade, dim3((L.ubActive + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, L.d.sc, c->ps, sa, fp);
+            L.cur = nxt;
+            if (L.pollPending && hipEventQuery(L.poll) == hipSuccess) {
+                L.pollPending = false;
+                L.ubActive = std::min(L.ubActive, c->hostCounts[8 + l]);
+                if (L.ubActive == 0) { L.done = true; continue; }
+            }
+            if (!L.pollPending && (it & 7u) == 7u) {
+                if (hipMemcpyAsync(c->hostCounts + 8 + l, counts + L.cur, 4, hipMemcpyDeviceToHost, stream) == hipSuccess &&
+                    hipEventRecord(L.poll, stream) == hipSuccess)
+                    L.pollPending = true;
+            }
+        }
+        if (!any || rc) break;
+    }
+    // (a copy still in flight when the loop ends is harmless: the stream orders it before the next dispatch's own
+    // copies, and the slot is only read after the event of the copy that filled it)
+    for (int l = 1; l < nLanes; l++) {  // (also when a launch failed: nothing of this dispatch is left running beside the ctx stream)
+        RT_HIP(c, hipEventRecord(c->joinEvent[l - 1], lane[l].d.stream));
+        RT_HIP(c, hipStreamWaitEvent(c->stream, c->joinEvent[l - 1], 0));
+    }
+    return rc;
+}
+
+// The multi-kernel pipeline: the dispatch in `nLanes` independent parts: contiguous slot ranges (whole 256-slot blocks of all the frames of a tile
+// block), each with its own region of the queues, its own counters and its own stream. A pixel's path depends on nothing but
+// its slot, so the parts give the same bits as the whole; what they buy is overlap: one part's k_shade (bound by the path
+// state it streams) and the draining tail of its k_trace_pw launch run under the other part's traversal (bound by latency).
+// Part 0 runs on the ctx stream, the others fork from it after the ray generation and join it before the image is written.
+int render_parts(rt_ctx* c, const FrameParams& fp, const Dispatch& d, uint32_t nSlots, float4* fb) {
+    const int nLanes = ensure_part_streams(c, choose_parts(c->tune, d, c->cull, c->meas.boxPerRay, fp.samples, nSlots));
+    c->rep.lastParts = nLanes;
+    Lane lane[RT_MAX_LANES];
+    slice_parts(c, d, nSlots, fp.nFrames, nLanes, lane);
+    for (int l = 0; l < nLanes; l++) {
+        const Lane& L = lane[l];
+        if (!L.n) continue;
+        hipLaunchKernelGGL(k_raygen, dim3((L.n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, c->stream, d.sc, c->ps,
+                           c->q.active[0] + L.begin, c->q.rays[0] + 3 * (size_t)L.begin, fp, L.begin, L.begin + L.n);
+        // counts: [0],[1] active paths of buffer 0/1; [2],[3] main rays of buffer 0/1; [4] the traversal's work counter; [5],[6] NEE rays, [7],[8] cosine probes of buffer 0/1
+        if (fp.samples > 0) hipLaunchKernelGGL(k_init_counts, dim3(1), dim3(64), 0, c->stream, L.d.counts, L.n);
+    }
+    RT_HIP(c, hipGetLastError());
+    if (fp.samples > 0)
+        if (int rc = render_rounds(c, fp, lane, nLanes)) return rc;
+    const uint32_t blocksPix = (fp.nPixels + RT_BLOCK - 1) / RT_BLOCK;
+    if (fp.nFrames > 1u) hipLaunchKernelGGL(k_blend_frames, dim3(blocksPix), dim3(RT_BLOCK), 0, c->stream, c->ps, fp, fb);
+    else hipLaunchKernelGGL(k_resolve, dim3(blocksPix), dim3(RT_BLOCK), 0, c->stream, c->ps, fp, fb);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int probe_ray_cost(rt_ctx* c, const FrameParams& fp, const Dispatch& d);
+
+// A dispatch whose arguments are checked and whose path state and image exist: measure, choose, launch
+int render_dispatch(rt_ctx* c, const FrameParams& fp, const Dispatch& d, float4* fb) {
+    const uint32_t nSlots = (uint32_t)dispatch_slots(fp.nPixels, fp.nFrames);
+    int rc;
+    poll_ray_cost(c);
+    if (c->meas.boxPerRay < 0.0 && c->tune.probe && !d.probe && !d.sc.mapFlags && (uint64_t)fp.nPixels * fp.samples >= 8000000ull && fp.debug < 0 &&
+        (rc = probe_ray_cost(c, fp, d)))
+        return rc;
+    const int pipeline = choose_pipeline(c->tune, d.pipeline, c->meas.boxPerRay, d.sc, nSlots);
+    if (!d.probe) c->rep.lastPipeline = pipeline;
+    if (pipeline == 1) {  // wave-private fused pipeline: one launch for the whole dispatch
+        rc = launch_fused(c, d, fp, fb);
+        if (!rc && fp.nFrames > 1u) {
+            hipLaunchKernelGGL(k_blend_frames, dim3((fp.nPixels + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, c->stream, c->ps, fp, fb);
+            rc = c->hip(hipGetLastError(), "k_blend_frames");
+        }
+    } else {
+        rc = render_parts(c, fp, d, nSlots, fb);
+    }
+    if (!rc) request_ray_cost(c);
+    return rc;
+}
+
+// The launch parameters of both pipelines follow the scene's measured box tests per ray, which the first dispatch of a
+// scene does not have — and a single-render job (the reference's singleRender mode: all samples in one dispatch) is
+// nothing but a first dispatch. Before a big one, eight rows of the same tile are rendered once with one sample per
+// pixel into a scratch image and the counters put back: a few ms, no trace in anything the caller can read.
+// (fp, d: the big dispatch's. The probe's path state fits in its, and its scene counts are the same.)
+int probe_ray_cost(rt_ctx* c, const FrameParams& fp, const Dispatch& d) {
+    const uint32_t rows = std::min(fp.nRows, 8u), skip = fp.nRows / rows;
+    FrameParams p = fp;
+    p.samples = 1; p.progressive = 0; p.debug = -1; p.nFrames = 1;
+    p.row0 = fp.row0 + (skip / 2u) * fp.rowStride; p.rowStride = fp.rowStride * skip; p.nRows = rows; p.nPixels = rows * fp.width;
+    Dispatch pd = d;  // fused pipeline, no profiling, no phase statistics, launches not counted
+    pd.probe = true; pd.pipeline = 1; pd.profiled = false; pd.phaseStats = 0; pd.launches = nullptr;
+    int rc = dev_alloc(c, c->probeBuf, (size_t)rows * fp.width * sizeof(float4));
+    if (rc) return rc;
+    DevCounters before, after;
+    RT_HIP(c, hipMemcpyAsync(&before, c->counterBuf.p, sizeof(DevCounters), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    if ((rc = render_dispatch(c, p, pd, (float4*)c->probeBuf.p))) return rc;
+    RT_HIP(c, hipMemcpyAsync(&after, c->counterBuf.p, sizeof(DevCounters), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    RT_HIP(c, hipMemcpyAsync(c->counterBuf.p, &before, sizeof(DevCounters), hipMemcpyHostToDevice, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    c->meas.snapPending = false;  // the probe's own snapshot request: its copy has arrived, and it is not wanted
+    if (after.raysTraced > before.raysTraced + 1000ull)
+        c->meas.boxPerRay = (double)((after.boxTests - after.skippedBoxTests) - (before.boxTests - before.skippedBoxTests)) / (double)(after.raysTraced - before.raysTraced);
+    return 0;
+}
+
+// rt_render (nFrames = 1) and rt_render_frames: the checks, the path state and the image, then render_dispatch
 int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
                 uint32_t nRows, uint32_t nFrames, float* d_rgba) {
     if (!c || !pc) return -1;
@@ -1196,12 +1373,12 @@ int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t hei
     const RayTracerData& td = pc->rayTraceParams;
     if (td.bounceLimit >= (1u << 28) - 1u) return c->fail("rayTraceParams.bounceLimit needs more than 28 bits");
     const uint64_t np64 = (uint64_t)nRows * width;
-    if ((np64 + 63) / 64 * 64 * nFrames >= (1ull << 30)) return c->fail("tile too large (slot ids are 30 bits)");
+    if (frame_slots(np64) * nFrames >= (1ull << 30)) return c->fail("tile too large (slot ids are 30 bits)");
     const uint32_t nPixels = (uint32_t)np64;
     RT_HIP(c, hipSetDevice(c->device));
     if (nPixels == 0) return 0;
 
-    rc = ensure_state(c, nFrames > 1u ? (nPixels + 63u) / 64u * 64u * nFrames : nPixels);
+    rc = ensure_state(c, (uint32_t)dispatch_slots(nPixels, nFrames));
     if (rc) return rc;
     float4* fb = (float4*)d_rgba;
     if (!fb) {
@@ -1223,174 +1400,12 @@ int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t hei
     fp.progressive = td.progressive;
     fp.frameCount = pc->frameCount;
     fp.nFrames = nFrames;
-    fp.camReuse = (c->cameraReuse && td.debug < 0) ? 1u : 0u;
+    fp.camReuse = (c->tune.cameraReuse && td.debug < 0) ? 1u : 0u;
     fp.debug = td.debug;
     fp.boxCap = td.boxCap;
     fp.triCap = td.triangleCap;
     fp.env = pc->environment;
-
-    c->pixStats = td.debug >= 0;
-    DevScene sc = dispatch_scene(c, td);
-    // c->sc holds this dispatch's counts while the launches are built; whatever way the function is left, the uploaded scene comes back
-    struct SceneGuard {
-        rt_ctx* c; DevScene saved;
-        ~SceneGuard() { c->sc = saved; }
-    } guard{c, c->sc};
-    c->sc = sc;
-
-    const uint32_t blocksPix = (nPixels + RT_BLOCK - 1) / RT_BLOCK;
-    // several frames in one dispatch: the paths are {64 tile slots} x {frames} (FrameParams::nFrames), in either pipeline
-    const uint32_t nSlots = nFrames > 1u ? (nPixels + 63u) / 64u * 64u * nFrames : nPixels;
-    DevCounters* dc = (DevCounters*)c->counterBuf.p;
-    uint32_t* counts = c->q.counts;
-
-    // Both pipelines give the same bits; which one is faster depends on how much a wave has to do per pixel. Small tiles
-    // and scenes with short rays (few box tests per ray, measured on this context's earlier dispatches) go to the fused one.
-    poll_ray_cost(c);
-    if (c->boxPerRay < 0.0 && c->probe && !c->inProbe && !c->sc.mapFlags && (uint64_t)nPixels * fp.samples >= 8000000ull && td.debug < 0) {
-        c->sc = guard.saved;
-        if ((rc = probe_ray_cost(c, pc, width, height, row0, rowStride, nRows))) return rc;
-        c->sc = sc;
-        c->pixStats = false;
-    }
-    const bool shortRays = c->boxPerRay >= 0.0 && c->boxPerRay < (double)c->fusedBelowBoxTests;
-    // the longer the rays, the earlier the global queue of the multi-kernel pipeline pays — and with the dispatch in overlapping
-    // parts earlier than it used to (tools/size_sweep.py, one 1080p frame = 2.07 M paths, fused / multi-kernel in parts: Sponza,
-    // 153 executed box tests per ray, 113.8 / 103.4 ms; Sponza + 16 dragons 167.2 / 162.5; the klein bottle x 8, 84 tests,
-    // 70.2 / 76.6; half a frame, 1.04 M paths: 61.5 / 66.3, 91.9 / 106.8, 41.5 / 57.4): 4 M paths up to 90 tests per ray, falling
-    // to 1.5 M at 150
-    double sizeLimit = (double)c->fusedBelowPixels;
-    if (c->boxPerRay > 90.0) sizeLimit = std::max(0.375 * sizeLimit, sizeLimit - (c->boxPerRay - 90.0) * (0.625 / 60.0) * sizeLimit);
-    // (the paths of all the frames of the dispatch count: four frames of a quarter of a 4K frame are a 4K frame's worth)
-    // Short rays keep the fused pipeline at any size — unless the traversal misses the caches: a scene whose hot data (child pairs
-    // and triangle positions) exceeds one XCD's 4 MB of L2 is bound by latency even with few tests per ray, and from 10 M paths the
-    // multi-kernel pipeline's extra resident waves and overlapping parts win there too (Cornell + bunny, 33 box tests per ray, ten
-    // 1080p frames: 36.1 against 38.0 ms per frame; + dragon 36.3 against 40.1; level between four and six frames:
-    // tools/frames_sweep.py), while small scenes (bobadog, the 45-object scene)
-    // and scenes of very short rays (fewer than 25 executed tests: 232 k loose triangles on a floor) stay fused (tools/heuristics_table.py)
-    const bool bigScene = (uint64_t)c->sc.nodeCount * 32u + (uint64_t)c->sc.triCount * 48u > (4ull << 20);
-    const bool shortButMissing = shortRays && bigScene && c->boxPerRay >= 25.0 && nSlots >= (10u << 20);
-    c->lastPipeline = c->pipeline >= 0 ? c->pipeline : (((double)nSlots < sizeLimit || (shortRays && !shortButMissing)) ? 1 : 0);
-    // a scene that binds a metalness, alpha or bump map: the multi-kernel pipeline's kernels that read them (k_shade_maps,
-    // k_trace_pw_alpha), whatever "pipeline" asks for — unless "fused_maps" lets it choose as usual (k_render_fused_maps)
-    if (c->sc.mapFlags && !c->fusedMaps) c->lastPipeline = 0;
-    if (c->lastPipeline == 1) {  // wave-private fused pipeline: one launch for the whole dispatch
-        rc = launch_fused(c, fp, fb);
-        if (!rc && nFrames > 1u) {
-            hipLaunchKernelGGL(k_blend_frames, dim3(blocksPix), dim3(RT_BLOCK), 0, c->stream, c->ps, fp, fb);
-            rc = c->hip(hipGetLastError(), "k_blend_frames");
-        }
-        if (!rc) request_ray_cost(c);
-        return rc;
-    }
-    // The dispatch in `nLanes` independent parts: contiguous slot ranges (whole 256-slot blocks of all the frames of a tile
-    // block), each with its own region of the queues, its own counters and its own stream. A pixel's path depends on nothing but
-    // its slot, so the parts give the same bits as the whole; what they buy is overlap: one part's k_shade (bound by the path
-    // state it streams) and the draining tail of its k_trace_pw launch run under the other part's traversal (bound by latency).
-    // Part 0 runs on the ctx stream, the others fork from it after the ray generation and join it before the image is written.
-    int nLanes = (fp.samples > 0 && nSlots >= c->lanesMinSlots) ? std::max(1, std::min(c->lanes, (int)RT_MAX_LANES)) : 1;
-    if (c->phaseStats) nLanes = 1;  // the diagnostic kernel's statistics are per launch
-    // One scene shape loses by it (tools/lanes_table.py): long rays that walk into many placed objects (C5: sixteen instanced dragons,
-    // ~190 executed box tests per ray; 116.1 ms per frame in one part against 121.2 in three at 1080p, 472 against 492 at 4K).
-    // Every placed object a ray enters costs a set-up round that reloads the ray from its path state in HBM, so that traversal
-    // competes with the other parts' k_shade for HBM instead of complementing it. Such scenes keep one part unless "lanes" was set.
-    // (from 8 M paths on: a single 1080p frame of the same scene still gains 7 % from its parts, whose launches are short against their tails)
-    if (!c->lanesSet && c->cull && c->boxPerRay >= 150.0 && nSlots >= (8u << 20)) nLanes = 1;
-    for (int l = 1; l < nLanes; l++) {
-        if (!c->sideStream[l - 1]) {
-            if (hipStreamCreateWithFlags(&c->sideStream[l - 1], hipStreamNonBlocking) != hipSuccess) { c->sideStream[l - 1] = nullptr; nLanes = l; break; }
-            if (hipEventCreateWithFlags(&c->joinEvent[l - 1], hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&c->pollEventSide[l - 1], hipEventDisableTiming) != hipSuccess) { nLanes = l; break; }
-        }
-    }
-    if (nLanes > 1 && !c->forkEvent && hipEventCreateWithFlags(&c->forkEvent, hipEventDisableTiming) != hipSuccess) { c->forkEvent = nullptr; nLanes = 1; }
-    c->lastParts = nLanes;
-    struct Lane {
-        hipStream_t stream; uint32_t* counts; hipEvent_t poll; uint32_t begin, n, ubActive; int cur; bool pollPending, done;
-    } lane[RT_MAX_LANES];
-    {
-        const uint32_t unit = 256u * std::max(1u, nFrames);  // whole blocks of k_shade, whole tile blocks of all their frames
-        const uint32_t units = (nSlots + unit - 1) / unit;
-        uint32_t at = 0;
-        for (int l = 0; l < nLanes; l++) {
-            const uint32_t u = units / (uint32_t)nLanes + ((uint32_t)l < units % (uint32_t)nLanes ? 1u : 0u);
-            const uint32_t end = std::min(nSlots, at + u * unit);
-            lane[l] = Lane{l ? c->sideStream[l - 1] : c->stream, counts + 16 * l, l ? c->pollEventSide[l - 1] : c->pollEvent, at, end - at, end - at, 0, false, end == at};
-            at = end;
-        }
-    }
-    for (int l = 0; l < nLanes; l++) {
-        const Lane& L = lane[l];
-        if (!L.n) continue;
-        hipLaunchKernelGGL(k_raygen, dim3((L.n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, c->stream, c->sc, c->ps,
-                           c->q.active[0] + L.begin, c->q.rays[0] + 3 * (size_t)L.begin, fp, L.begin, L.begin + L.n);
-        // counts: [0],[1] active paths of buffer 0/1; [2],[3] main rays of buffer 0/1; [4] the traversal's work counter; [5],[6] NEE rays, [7],[8] cosine probes of buffer 0/1
-        if (fp.samples > 0) hipLaunchKernelGGL(k_init_counts, dim3(1), dim3(64), 0, c->stream, L.counts, L.n);
-    }
-    RT_HIP(c, hipGetLastError());
-
-    if (fp.samples > 0) {
-        if (nLanes > 1) {
-            RT_HIP(c, hipEventRecord(c->forkEvent, c->stream));
-            for (int l = 1; l < nLanes; l++) RT_HIP(c, hipStreamWaitEvent(lane[l].stream, c->forkEvent, 0));
-        }
-        // The whole dispatch is enqueued without waiting for the device (rt_amd.h: "asynchronous on the ctx stream"): every
-        // kernel reads its queue length from device memory and leaves at once when the queue is empty, so the loop may
-        // simply run to the most rounds a pixel can need, samples * (bounceLimit + 1). The active-path count is copied
-        // back now and then without ever being waited for; a copy that has arrived shrinks the grids of the launches still
-        // to be enqueued (active paths never increase, so a stale count is a valid upper bound) and ends the part at zero.
-        const uint64_t maxRounds = (uint64_t)fp.samples * ((uint64_t)fp.bounceLimit + 1);
-        struct LaneGuard {  // launch_trace builds its launches for the part named here
-            rt_ctx* c;
-            ~LaneGuard() { c->curStream = nullptr; c->curCounts = nullptr; c->curLane = 0; c->curGridPct = 100; }
-        } laneGuard{c};
-        // (small parts — one 1080p frame per dispatch is three parts of 0.69 M paths — run better on 40 % grids: 101.7 -> 99.5 ms per
-        // frame; the bench's ten frames per dispatch, 6.9 M paths per part, on 50 %: 77.2 against 78.6)
-        c->curGridPct = nLanes > 1 ? (c->laneGridPct > 0 ? c->laneGridPct : (lane[0].n < 1200000u ? 40 : 50)) : 100;
-        for (uint64_t it = 0; it < maxRounds; it++) {
-            bool any = false;
-            for (int l = 0; l < nLanes; l++) {
-                Lane& L = lane[l];
-                if (L.done) continue;
-                any = true;
-                c->curStream = L.stream; c->curCounts = L.counts; c->curLane = l;
-                const int cur = L.cur, nxt = cur ^ 1;
-                uint32_t* const active[2] = {c->q.active[0] + L.begin, c->q.active[1] + L.begin};
-                uint32_t* const rays[2] = {c->q.rays[0] + 3 * (size_t)L.begin, c->q.rays[1] + 3 * (size_t)L.begin};
-                hipLaunchKernelGGL(k_zero_counts, dim3(1), dim3(64), 0, L.stream, L.counts + nxt, L.counts + 2 + nxt, L.counts + 4, L.counts + 5 + nxt, L.counts + 7 + nxt);
-                TraceArgs ta{rays[cur], L.counts + 2 + cur, nullptr, nullptr, dc, L.counts + 5 + cur, L.counts + 7 + cur, L.n};
-                const uint64_t ubRays = std::min<uint64_t>((uint64_t)L.ubActive * 3, (uint64_t)L.n * 3);
-                if ((rc = launch_trace(c, (uint32_t)ubRays, ta))) break;
-                ShadeArgs sa{active[cur], L.counts + cur, active[nxt], rays[nxt], L.counts + nxt, L.counts + 2 + nxt, dc, L.counts + 5 + nxt, L.counts + 7 + nxt, L.n};
-                if (c->sc.mapFlags & (RT_MAP_METALNESS | RT_MAP_BUMP)) hipLaunchKernelGGL(k_shade_maps, dim3((L.ubActive + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, L.stream, c->sc, c->ps, sa, fp);
-                else hipLaunchKernelGGL(k_shade, dim3((L.ubActive + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, L.stream, c->sc, c->ps, sa, fp);
-                L.cur = nxt;
-                if (L.pollPending && hipEventQuery(L.poll) == hipSuccess) {
-                    L.pollPending = false;
-                    L.ubActive = std::min(L.ubActive, c->hostCounts[8 + l]);
-                    if (L.ubActive == 0) { L.done = true; continue; }
-                }
-                if (!L.pollPending && (it & 7u) == 7u) {
-                    if (hipMemcpyAsync(c->hostCounts + 8 + l, L.counts + L.cur, 4, hipMemcpyDeviceToHost, L.stream) == hipSuccess &&
-                        hipEventRecord(L.poll, L.stream) == hipSuccess)
-                        L.pollPending = true;
-                }
-            }
-            if (!any || rc) break;
-        }
-        // (a copy still in flight when the loop ends is harmless: the stream orders it before the next dispatch's own
-        // copies, and the slot is only read after the event of the copy that filled it)
-        for (int l = 1; l < nLanes; l++) {  // (also when a launch failed: nothing of this dispatch is left running beside the ctx stream)
-            RT_HIP(c, hipEventRecord(c->joinEvent[l - 1], lane[l].stream));
-            RT_HIP(c, hipStreamWaitEvent(c->stream, c->joinEvent[l - 1], 0));
-        }
-        if (rc) return rc;
-    }
-    if (nFrames > 1u) hipLaunchKernelGGL(k_blend_frames, dim3(blocksPix), dim3(RT_BLOCK), 0, c->stream, c->ps, fp, fb);
-    else hipLaunchKernelGGL(k_resolve, dim3(blocksPix), dim3(RT_BLOCK), 0, c->stream, c->ps, fp, fb);
-    RT_HIP(c, hipGetLastError());
-    request_ray_cost(c);
-    return 0;
+    return render_dispatch(c, fp, one_part(c, dispatch_scene(c, td), td.debug >= 0), fb);
 }
 }  // namespace
 
@@ -1413,9 +1428,9 @@ int rt_render_frames(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_
     const uint64_t np = (uint64_t)nRows * width;
     uint32_t per = 1;  // frames per dispatch
     if (nFrames > 1u && pc->rayTraceParams.debug < 0 && np > 0) {
-        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(c->framesMaxSlots, np), (1ull << 30) - 1);
-        per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nFrames, cap / ((np + 63) / 64 * 64)));
-        if (c->framesPerLaunch > 0) per = std::min(per, (uint32_t)c->framesPerLaunch);
+        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(c->tune.framesMaxSlots, np), (1ull << 30) - 1);
+        per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nFrames, cap / frame_slots(np)));
+        if (c->tune.framesPerLaunch > 0) per = std::min(per, (uint32_t)c->tune.framesPerLaunch);
     }
     PushConstants p = *pc;
     for (uint32_t f = 0; f < nFrames; f += per) {
@@ -1487,7 +1502,7 @@ int rt_trace_rays(rt_ctx* c, uint32_t n, const float* origins, const float* dirs
     RT_HIP(c, hipMemsetAsync(c->ps.statTri(), 0, (size_t)n * 4, c->stream));
     hipLaunchKernelGGL(k_seed_rays, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, c->stream, c->sc, c->ps, n);
     TraceArgs ta{nullptr, c->q.counts, prb, prt, (DevCounters*)c->counterBuf.p};
-    if ((rc = launch_trace(c, n, ta))) return rc;
+    if ((rc = launch_trace(c, one_part(c, c->sc, false), n, ta))) return rc;  // (perRayBox: the kernels with per-ray counters)
     hipLaunchKernelGGL(k_hit_details, dim3((n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, c->stream, c->sc, c->ps, n, prb, prt, dh);
     RT_HIP(c, hipGetLastError());
     RT_HIP(c, hipMemcpyAsync(hitsOut, dh, (size_t)n * sizeof(RtHit), hipMemcpyDeviceToHost, c->stream));
@@ -1523,25 +1538,16 @@ int rt_render_aovs(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t 
     }
     FrameParams fp = frame_camera(c, pc, width, height, row0, rowStride, nRows, nPixels);
     fp.nFrames = 1;
-    // launch_trace reads what the dispatches leave behind: this pass gets its scene counts, no per-pixel statistics (a heat-map
-    // render leaves pixStats set) and no phase statistics, and its launch is counted apart; everything comes back afterwards
-    struct PassGuard {
-        rt_ctx* c; DevScene sc; bool pixStats; int phaseStats; uint64_t launches;
-        ~PassGuard() {
-            c->aovLaunches += c->traceLaunchesTotal - launches;
-            c->sc = sc; c->pixStats = pixStats; c->phaseStats = phaseStats; c->traceLaunchesTotal = launches;
-        }
-    } guard{c, c->sc, c->pixStats, c->phaseStats, c->traceLaunchesTotal};
-    c->sc = dispatch_scene(c, pc->rayTraceParams);
-    c->pixStats = false;
-    c->phaseStats = 0;
+    // this pass gets its scene counts, no per-pixel statistics and no phase statistics, and its launch is counted apart
+    Dispatch d = one_part(c, dispatch_scene(c, pc->rayTraceParams), false);
+    d.phaseStats = 0; d.launches = &c->rep.aovLaunches;
     const uint32_t blocks = (nPixels + RT_BLOCK - 1) / RT_BLOCK;
-    hipLaunchKernelGGL(k_aov_rays, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, c->ps, fp);
+    hipLaunchKernelGGL(k_aov_rays, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, d.sc, c->ps, fp);
     hipLaunchKernelGGL(k_init_counts, dim3(1), dim3(64), 0, c->stream, c->q.counts, nPixels);
     RT_HIP(c, hipGetLastError());
     const TraceArgs ta{nullptr, c->q.counts, nullptr, nullptr, (DevCounters*)c->aovCounterBuf.p};
-    if ((rc = launch_trace(c, nPixels, ta))) return rc;
-    hipLaunchKernelGGL(k_aov_resolve, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, c->ps, fp, out);
+    if ((rc = launch_trace(c, d, nPixels, ta))) return rc;
+    hipLaunchKernelGGL(k_aov_resolve, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, d.sc, c->ps, fp, out);
     RT_HIP(c, hipGetLastError());
     return 0;
 }
@@ -1709,10 +1715,10 @@ int rt_get_counters(rt_ctx* c, RtCounters* out) {
     out->boxTests = h.boxTests + a.boxTests; out->triTests = h.triTests + a.triTests;
     out->raysTraced = h.raysTraced + a.raysTraced; out->raysHit = h.raysHit + a.raysHit;
     out->raysReference = h.raysReference; out->paths = h.paths; out->segments = h.segments;
-    out->traceLaunches = c->traceLaunchesTotal + c->aovLaunches;
+    out->traceLaunches = c->rep.traceLaunchesTotal + c->rep.aovLaunches;
     out->emitterTests = h.emitterTests;
     out->skippedBoxTests = h.skippedBoxTests + a.skippedBoxTests;
-    if (c->phaseStats) {
+    if (c->tune.phaseStats) {
         unsigned long long ps[21];
         RT_HIP(c, hipMemcpy(ps, (char*)c->counterBuf.p + sizeof(DevCounters), sizeof(ps), hipMemcpyDeviceToHost));
         static const char* nm[4] = {"refill", "setup", "interior", "leaf"};
@@ -1725,19 +1731,19 @@ int rt_get_counters(rt_ctx* c, RtCounters* out) {
         fprintf(stderr, "[phase_stats] trips of the set-up step's object-skipping loop: %llu (%.1f per lane and set-up step)\n", ps[20], ps[5] ? (double)ps[20] / ps[5] : 0.0);
         fprintf(stderr, "[phase_stats] lanes sitting out interior rounds: %.1f at a leaf, %.1f in set-up states, %.1f without a ray (of 64, average)\n",
                 ps[2] ? (double)ps[12] / ps[2] : 0.0, ps[2] ? (double)ps[13] / ps[2] : 0.0, ps[2] ? (double)ps[14] / ps[2] : 0.0);
-        if (c->waveTimesCount && c->waveTimeBuf.p) {  // the last k_trace_pw launch: when did its waves finish?
-            std::vector<unsigned long long> t(c->waveTimesCount * 2);
+        if (c->rep.waveTimesCount && c->waveTimeBuf.p) {  // the last k_trace_pw launch: when did its waves finish?
+            std::vector<unsigned long long> t(c->rep.waveTimesCount * 2);
             RT_HIP(c, hipMemcpy(t.data(), c->waveTimeBuf.p, t.size() * 8, hipMemcpyDeviceToHost));
             unsigned long long t0 = ~0ull, t1 = 0;
-            for (size_t w = 0; w < c->waveTimesCount; w++) { t0 = std::min(t0, t[2 * w]); t1 = std::max(t1, t[2 * w + 1]); }
-            std::vector<double> end(c->waveTimesCount);
+            for (size_t w = 0; w < c->rep.waveTimesCount; w++) { t0 = std::min(t0, t[2 * w]); t1 = std::max(t1, t[2 * w + 1]); }
+            std::vector<double> end(c->rep.waveTimesCount);
             double busy = 0;
             const double span = (double)(t1 - t0);
-            for (size_t w = 0; w < c->waveTimesCount; w++) { end[w] = (t[2 * w + 1] - t0) / span; busy += (t[2 * w + 1] - t[2 * w]) / span; }
+            for (size_t w = 0; w < c->rep.waveTimesCount; w++) { end[w] = (t[2 * w + 1] - t0) / span; busy += (t[2 * w + 1] - t[2 * w]) / span; }
             std::sort(end.begin(), end.end());
             auto q = [&](double f) { return end[std::min(end.size() - 1, (size_t)(f * end.size()))]; };
             fprintf(stderr, "[phase_stats] last launch: %zu waves, span %.3f ms (100 MHz clock), mean wave lifetime %.1f %% of it; waves finished by 10/25/50/75/90/99 %% : %.2f %.2f %.2f %.2f %.2f %.2f of the span\n",
-                    c->waveTimesCount, span / 1e5, 100.0 * busy / c->waveTimesCount, q(0.10), q(0.25), q(0.50), q(0.75), q(0.90), q(0.99));
+                    c->rep.waveTimesCount, span / 1e5, 100.0 * busy / c->rep.waveTimesCount, q(0.10), q(0.25), q(0.50), q(0.75), q(0.90), q(0.99));
         }
     }
     return 0;
@@ -1751,11 +1757,11 @@ int rt_reset_counters(rt_ctx* c) {
     RT_HIP(c, hipMemsetAsync(c->counterBuf.p, 0, sizeof(DevCounters) + 256, c->stream));
     RT_HIP(c, hipMemsetAsync(c->aovCounterBuf.p, 0, sizeof(DevCounters), c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    c->snapPending = false;
-    c->snapBox = 0; c->snapRays = 0; c->snapSeg = 0; c->snapPaths = 0;
+    c->meas.snapPending = false;
+    c->meas.snapBox = 0; c->meas.snapRays = 0; c->meas.snapSeg = 0; c->meas.snapPaths = 0;
     int rc = harvest_events(c);
-    c->traceMs = 0.0; c->traceLaunches = 0; c->traceLaunchesTotal = 0; c->aovLaunches = 0;
-    c->traceSpans.clear();
+    c->rep.traceMs = 0.0; c->rep.traceLaunches = 0; c->rep.traceLaunchesTotal = 0; c->rep.aovLaunches = 0;
+    c->rep.traceSpans.clear();
     return rc;
 }
 
@@ -1767,7 +1773,7 @@ int rt_set_profiling(rt_ctx* c, int on) {
     if (on) {
         if (!c->profBase) RT_HIP(c, hipEventCreate(&c->profBase));
         RT_HIP(c, hipEventRecord(c->profBase, c->stream));
-        c->traceSpans.clear();
+        c->rep.traceSpans.clear();
     }
     return rc;
 }
@@ -1776,7 +1782,7 @@ int rt_get_trace_busy_ms(rt_ctx* c, double* ms) {
     if (!c || !ms) return -1;
     RT_HIP(c, hipStreamSynchronize(c->stream));
     int rc = harvest_events(c);
-    std::vector<std::pair<float, float>> v = c->traceSpans;
+    std::vector<std::pair<float, float>> v = c->rep.traceSpans;
     std::sort(v.begin(), v.end());
     double busy = 0.0, end = -1e300;
     for (const auto& iv : v) {
@@ -1791,56 +1797,56 @@ int rt_get_trace_time_ms(rt_ctx* c, double* ms, uint64_t* launches) {
     if (!c) return -1;
     RT_HIP(c, hipStreamSynchronize(c->stream));
     int rc = harvest_events(c);
-    if (ms) *ms = c->traceMs;
-    if (launches) *launches = c->traceLaunches;
+    if (ms) *ms = c->rep.traceMs;
+    if (launches) *launches = c->rep.traceLaunches;
     return rc;
 }
 
-const char* rt_last_kernel(const rt_ctx* c) { return c ? c->lastKernel : ""; }
-int rt_last_parts(const rt_ctx* c) { return c ? c->lastParts : 0; }
+const char* rt_last_kernel(const rt_ctx* c) { return c ? c->rep.lastKernel : ""; }
+int rt_last_parts(const rt_ctx* c) { return c ? c->rep.lastParts : 0; }
 
 int rt_set_tuning(rt_ctx* c, const char* key, int value) {
     if (!c || !key) return -1;
     std::string k(key);
-    if (k == "pipeline") { if (value < -1 || value > 1) return c->fail("pipeline: -1 (auto), 0 or 1"); c->pipeline = value; }
-    else if (k == "probe") { c->probe = value ? 1 : 0; }
-    else if (k == "frames_max_mslots") { if (value < 1 || value > 1000) return c->fail("frames_max_mslots: 1..1000 (millions of paths per multi-frame dispatch)"); c->framesMaxSlots = (uint64_t)value << 20; }
-    else if (k == "frames_per_launch") { if (value < 0) return c->fail("frames_per_launch >= 0"); c->framesPerLaunch = value; }
-    else if (k == "camera_reuse") { c->cameraReuse = value ? 1 : 0; }
-    else if (k == "light_queries") { c->lightQueries = value ? 1 : 0; int rc = rebuild_emitters(c); if (rc) return rc; }
-    else if (k == "fused_below_box_tests") { if (value < 0) return c->fail("fused_below_box_tests >= 0"); c->fusedBelowBoxTests = (uint32_t)value; }
-    else if (k == "fused_below_pixels") { if (value < 0) return c->fail("fused_below_pixels >= 0"); c->fusedBelowPixels = (uint32_t)value; }
-    else if (k == "trace_variant") { if (value < 0 || value > 1) return c->fail("trace_variant: 0 or 1"); c->traceVariant = value; }
-    else if (k == "refill") { if (value < 1 || value > 64) return c->fail("refill: 1..64"); c->refill = value; c->refillMk = value; c->refillMkSet = true; }
-    else if (k == "hot_pairs") { if (value < 0 || value > 2) return c->fail("hot_pairs: 0, 1 (six work-groups per CU) or 2 (five)"); c->hotPairs = value; }
-    else if (k == "mk_refill") { if (value < 1 || value > 64) return c->fail("mk_refill: 1..64"); c->refillMk = value; c->refillMkSet = true; }
-    else if (k == "lds_stack") { if (value != 8 && value != 16 && value != 24) return c->fail("lds_stack: 8, 16 or 24"); c->ldsStackCap = value; }
-    else if (k == "fast_lanes") { if (value < 0 || value > 65) return c->fail("fast_lanes: 1..65 (0: back to the defaults)"); c->fastLanesSet = value != 0; c->fastLanes = value ? value : 32; }
-    else if (k == "chunk") { if (value < 1 || value > 4096) return c->fail("chunk: 1..4096"); c->chunk = value; }
-    else if (k == "w_setup") { if (value < 1 || value > 512) return c->fail("w_setup: 1..512"); c->wSetup = value; c->wSetupFused = value; c->wSetupSet = true; }
-    else if (k == "w_leaf") { if (value < 1 || value > 512) return c->fail("w_leaf: 1..512"); c->wLeaf = value; c->wLeafFused = value; c->wLeafSet = true; }
-    else if (k == "mk_w_setup") { if (value < 1 || value > 512) return c->fail("mk_w_setup: 1..512"); c->wSetup = value; c->wSetupSet = true; }
-    else if (k == "mk_w_leaf") { if (value < 1 || value > 512) return c->fail("mk_w_leaf: 1..512"); c->wLeaf = value; }
-    else if (k == "tile_slots") { c->tileSlots = value != 0; }
-    else if (k == "mask_identity") { c->maskIdentity = value != 0; }
-    else if (k == "fast_share") { if (value < 0 || value > 16) return c->fail("fast_share: 0..16"); c->fastShare = value; }
-    else if (k == "scatter") { if (value != -1 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return c->fail("scatter: -1 (auto), 0, 1, 2, 4, 8 or 16"); c->scatter = value; }
-    else if (k == "fused_maps") { if (value < 0 || value > 1) return c->fail("fused_maps: 0 (map scenes take the multi-kernel pipeline) or 1 (they choose as usual)"); c->fusedMaps = value; }
-    else if (k == "pixel_refill") { if (value < 0 || value > (int)RT_WAVE) return c->fail("pixel_refill must be 0 (by ray length) .. 64"); c->pixelRefill = value; }
-    else if (k == "batch_pixels") { if (value < 0 || value > (int)RT_WAVE) return c->fail("batch_pixels must be 0 (auto) .. 64"); c->batchPixels = value; }
-    else if (k == "batch_fixed") { if (value < 0 || value > 4096) return c->fail("batch_fixed out of range"); c->batchFixed = value; }
-    else if (k == "phase_stats") { if (value < 0) return c->fail("phase_stats >= 0"); c->phaseStats = value; }
-    else if (k == "object_tree_min") { if (value < 0) return c->fail("object_tree_min >= 0"); c->objTreeMin = value; }
-    else if (k == "lanes") { if (value < 0 || value > RT_MAX_LANES) return c->fail("lanes: 1..4 (parts of a multi-kernel dispatch, each on its own stream), 0 = automatic"); c->lanes = value ? value : 3; c->lanesSet = value != 0; }
-    else if (k == "lane_grid_pct") { if (value != 0 && (value < 10 || value > 100)) return c->fail("lane_grid_pct: 0 (by size) or 10..100"); c->laneGridPct = value; }
-    else if (k == "lanes_min_kslots") { if (value < 0) return c->fail("lanes_min_kslots >= 0"); c->lanesMinSlots = (uint32_t)value << 10; }
-    else if (k == "blocks_per_cu") { if (value < 0 || value > 8) return c->fail("blocks_per_cu: 0..8"); c->blocksPerCU = value; }
+    if (k == "pipeline") { if (value < -1 || value > 1) return c->fail("pipeline: -1 (auto), 0 or 1"); c->tune.pipeline = value; }
+    else if (k == "probe") { c->tune.probe = value ? 1 : 0; }
+    else if (k == "frames_max_mslots") { if (value < 1 || value > 1000) return c->fail("frames_max_mslots: 1..1000 (millions of paths per multi-frame dispatch)"); c->tune.framesMaxSlots = (uint64_t)value << 20; }
+    else if (k == "frames_per_launch") { if (value < 0) return c->fail("frames_per_launch >= 0"); c->tune.framesPerLaunch = value; }
+    else if (k == "camera_reuse") { c->tune.cameraReuse = value ? 1 : 0; }
+    else if (k == "light_queries") { c->tune.lightQueries = value ? 1 : 0; int rc = rebuild_emitters(c); if (rc) return rc; }
+    else if (k == "fused_below_box_tests") { if (value < 0) return c->fail("fused_below_box_tests >= 0"); c->tune.fusedBelowBoxTests = (uint32_t)value; }
+    else if (k == "fused_below_pixels") { if (value < 0) return c->fail("fused_below_pixels >= 0"); c->tune.fusedBelowPixels = (uint32_t)value; }
+    else if (k == "trace_variant") { if (value < 0 || value > 1) return c->fail("trace_variant: 0 or 1"); c->tune.traceVariant = value; }
+    else if (k == "refill") { if (value < 1 || value > 64) return c->fail("refill: 1..64"); c->tune.refill = value; c->tune.refillMk = value; c->tune.refillMkSet = true; }
+    else if (k == "hot_pairs") { if (value < 0 || value > 2) return c->fail("hot_pairs: 0, 1 (six work-groups per CU) or 2 (five)"); c->tune.hotPairs = value; }
+    else if (k == "mk_refill") { if (value < 1 || value > 64) return c->fail("mk_refill: 1..64"); c->tune.refillMk = value; c->tune.refillMkSet = true; }
+    else if (k == "lds_stack") { if (value != 8 && value != 16 && value != 24) return c->fail("lds_stack: 8, 16 or 24"); c->tune.ldsStackCap = value; }
+    else if (k == "fast_lanes") { if (value < 0 || value > 65) return c->fail("fast_lanes: 1..65 (0: back to the defaults)"); c->tune.fastLanesSet = value != 0; c->tune.fastLanes = value ? value : 32; }
+    else if (k == "chunk") { if (value < 1 || value > 4096) return c->fail("chunk: 1..4096"); c->tune.chunk = value; }
+    else if (k == "w_setup") { if (value < 1 || value > 512) return c->fail("w_setup: 1..512"); c->tune.wSetup = value; c->tune.wSetupFused = value; c->tune.wSetupSet = true; }
+    else if (k == "w_leaf") { if (value < 1 || value > 512) return c->fail("w_leaf: 1..512"); c->tune.wLeaf = value; c->tune.wLeafFused = value; c->tune.wLeafSet = true; }
+    else if (k == "mk_w_setup") { if (value < 1 || value > 512) return c->fail("mk_w_setup: 1..512"); c->tune.wSetup = value; c->tune.wSetupSet = true; }
+    else if (k == "mk_w_leaf") { if (value < 1 || value > 512) return c->fail("mk_w_leaf: 1..512"); c->tune.wLeaf = value; }
+    else if (k == "tile_slots") { c->tune.tileSlots = value != 0; }
+    else if (k == "mask_identity") { c->tune.maskIdentity = value != 0; }
+    else if (k == "fast_share") { if (value < 0 || value > 16) return c->fail("fast_share: 0..16"); c->tune.fastShare = value; }
+    else if (k == "scatter") { if (value != -1 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return c->fail("scatter: -1 (auto), 0, 1, 2, 4, 8 or 16"); c->tune.scatter = value; }
+    else if (k == "fused_maps") { if (value < 0 || value > 1) return c->fail("fused_maps: 0 (map scenes take the multi-kernel pipeline) or 1 (they choose as usual)"); c->tune.fusedMaps = value; }
+    else if (k == "pixel_refill") { if (value < 0 || value > (int)RT_WAVE) return c->fail("pixel_refill must be 0 (by ray length) .. 64"); c->tune.pixelRefill = value; }
+    else if (k == "batch_pixels") { if (value < 0 || value > (int)RT_WAVE) return c->fail("batch_pixels must be 0 (auto) .. 64"); c->tune.batchPixels = value; }
+    else if (k == "batch_fixed") { if (value < 0 || value > 4096) return c->fail("batch_fixed out of range"); c->tune.batchFixed = value; }
+    else if (k == "phase_stats") { if (value < 0) return c->fail("phase_stats >= 0"); c->tune.phaseStats = value; }
+    else if (k == "object_tree_min") { if (value < 0) return c->fail("object_tree_min >= 0"); c->tune.objTreeMin = value; }
+    else if (k == "lanes") { if (value < 0 || value > RT_MAX_LANES) return c->fail("lanes: 1..4 (parts of a multi-kernel dispatch, each on its own stream), 0 = automatic"); c->tune.lanes = value ? value : 3; c->tune.lanesSet = value != 0; }
+    else if (k == "lane_grid_pct") { if (value != 0 && (value < 10 || value > 100)) return c->fail("lane_grid_pct: 0 (by size) or 10..100"); c->tune.laneGridPct = value; }
+    else if (k == "lanes_min_kslots") { if (value < 0) return c->fail("lanes_min_kslots >= 0"); c->tune.lanesMinSlots = (uint32_t)value << 10; }
+    else if (k == "blocks_per_cu") { if (value < 0 || value > 8) return c->fail("blocks_per_cu: 0..8"); c->tune.blocksPerCU = value; }
     else return c->fail("unknown tuning key " + k);
     return 0;
 }
 
-int rt_last_pipeline(const rt_ctx* c) { return c ? c->lastPipeline : -1; }
-double rt_ray_cost(const rt_ctx* c) { return c ? c->boxPerRay : -1.0; }
+int rt_last_pipeline(const rt_ctx* c) { return c ? c->rep.lastPipeline : -1; }
+double rt_ray_cost(const rt_ctx* c) { return c ? c->meas.boxPerRay : -1.0; }
 
 // ---------------------------------------------------------------- GPU BVH build (bvh_build.hip.h)
 int rt_bvh_build(rt_ctx* c, const TrianglePoint* points, uint32_t pointCount, Triangle* triangles, float* centroids, uint32_t count,
@@ -1862,16 +1868,13 @@ int rt_bvh_build(rt_ctx* c, const TrianglePoint* points, uint32_t pointCount, Tr
     }
     const size_t nNodesMax = 2 * (size_t)count - 1;
     DevBuf bVerts, bCent, bPerm, bTmp, bHole, bNodes, bList, bCtr, bWide;
-    auto release = [&]() { for (DevBuf* b : {&bVerts, &bCent, &bPerm, &bTmp, &bHole, &bNodes, &bList, &bCtr, &bWide}) dev_free(*b); };
     const uint32_t maxChunks = (count + RT_BVH_CHUNK - 1) / RT_BVH_CHUNK;
     int rc;
     if ((rc = upload(c, bVerts, verts.data(), verts.size() * 4)) || (rc = upload(c, bCent, centroids, (size_t)count * 12)) ||
         (rc = dev_alloc(c, bPerm, (size_t)count * 4)) || (rc = dev_alloc(c, bTmp, (size_t)count * 4)) || (rc = dev_alloc(c, bHole, (size_t)count * 4)) ||
         (rc = dev_alloc(c, bNodes, nNodesMax * sizeof(BNode))) || (rc = dev_alloc(c, bList, 2 * (size_t)(count + 1) * 4)) || (rc = dev_alloc(c, bCtr, 64)) ||
-        (rc = dev_alloc(c, bWide, RT_BVH_WIDE_NODES * sizeof(WideAcc) + (size_t)RT_BVH_WIDE_NODES * maxChunks * 4))) {
-        release();
+        (rc = dev_alloc(c, bWide, RT_BVH_WIDE_NODES * sizeof(WideAcc) + (size_t)RT_BVH_WIDE_NODES * maxChunks * 4)))
         return rc;
-    }
     mark("uploaded");
     BvhBuildArgs a{(const float*)bVerts.p, (const float*)bCent.p, (uint32_t*)bPerm.p, (uint32_t*)bTmp.p, (uint32_t*)bHole.p, (BNode*)bNodes.p, (uint32_t*)bCtr.p};
     uint32_t* lists[2] = {(uint32_t*)bList.p, (uint32_t*)bList.p + (count + 1)};
@@ -1911,15 +1914,13 @@ int rt_bvh_build(rt_ctx* c, const TrianglePoint* points, uint32_t pointCount, Tr
     mark("levels done");
     uint32_t nNodes = 0;
     if (e == hipSuccess) e = hipMemcpy(&nNodes, bCtr.p, 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && (nNodes == 0 || nNodes > nNodesMax || nNodes != levelStart.back())) { release(); return c->fail("rt_bvh_build: node counter out of range"); }
+    if (e == hipSuccess && (nNodes == 0 || nNodes > nNodesMax || nNodes != levelStart.back())) return c->fail("rt_bvh_build: node counter out of range");
 
     // ---- the reference's numbering (bvh_build.hip.h): interior counts bottom-up, slots top-down, nodes written in place
     DevBuf bNum, bOut;
     uint32_t hstats[3] = {0u, 0xffffffffu, 0u};
-    if (e == hipSuccess && ((rc = dev_alloc(c, bNum, 3 * (size_t)nNodes * 4 + 64)) || (rc = dev_alloc(c, bOut, (size_t)nNodes * sizeof(BVHNode))))) {
-        release(); dev_free(bNum); dev_free(bOut);
+    if (e == hipSuccess && ((rc = dev_alloc(c, bNum, 3 * (size_t)nNodes * 4 + 64)) || (rc = dev_alloc(c, bOut, (size_t)nNodes * sizeof(BVHNode)))))
         return rc;
-    }
     std::vector<uint32_t> perm(count);
     if (e == hipSuccess) {
         uint32_t* nb = (uint32_t*)bNum.p;
@@ -1942,8 +1943,7 @@ int rt_bvh_build(rt_ctx* c, const TrianglePoint* points, uint32_t pointCount, Tr
         if (e == hipSuccess) e = hipGetLastError();
     }
     mark("numbered");
-    release();
-    dev_free(bNum); dev_free(bOut);
+    for (DevBuf* b : {&bVerts, &bCent, &bPerm, &bTmp, &bHole, &bNodes, &bList, &bCtr, &bWide, &bNum, &bOut}) b->release();  // now, not at the return: the host's part follows
     if (e != hipSuccess) return c->fail(std::string("rt_bvh_build: ") + hipGetErrorString(e));
     *nodeCountOut = nNodes;
     if (statsOut) { statsOut[0] = hstats[0]; statsOut[1] = hstats[1]; statsOut[2] = hstats[2]; }
@@ -1957,7 +1957,7 @@ int rt_bvh_build(rt_ctx* c, const TrianglePoint* points, uint32_t pointCount, Tr
         memcpy(centroids + 3 * (size_t)k2, &cOld[3 * (size_t)perm[k2]], 12);
     }
     mark("permuted");
-    c->bvhBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->rep.bvhBuildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
 
@@ -1966,7 +1966,7 @@ int rt_bvh_hook(void* ctx, const TrianglePoint* points, uint32_t pointCount, Tri
     return rt_bvh_build((rt_ctx*)ctx, points, pointCount, triangles, centroids, count, triIndex0, nodeBase, nodesOut, nodeCapacity, nodeCountOut, statsOut);
 }
 
-double rt_bvh_last_build_ms(const rt_ctx* c) { return c ? c->bvhBuildMs : 0.0; }
+double rt_bvh_last_build_ms(const rt_ctx* c) { return c ? c->rep.bvhBuildMs : 0.0; }
 
 int rt_device_selftest(rt_ctx* c, uint32_t* bitsOut) {
     if (!c || !bitsOut) return -1;
