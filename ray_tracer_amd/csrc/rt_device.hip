@@ -94,6 +94,7 @@ struct rt_ctx {
     // first-hit AOV passes (rt_render_aovs): the ctx-owned planes of the last pass into them, and a counter block of their own, which
     // rt_get_counters adds to the rendering counters and the ray-cost snapshots never see
     DevBuf aovBuf, aovCounterBuf;
+    DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
     uint32_t aovPixels = 0; bool aovValid = false;
     // the rows of the image the ctx framebuffer and the ctx AOV planes hold (rt_denoise reads them only as a whole frame)
     RowsOf fbRows, aovRows;
@@ -219,7 +220,7 @@ int ensure_state(rt_ctx* c, uint32_t nPixels) {
     if (c->capacity >= nPixels && c->stateBuf.p) return 0;
     const size_t stride4 = (((size_t)nPixels * 16) + 255) & ~(size_t)255;  // bytes per float4 array
     const size_t stride1 = (((size_t)nPixels * 4) + 255) & ~(size_t)255;
-    const int nF4 = 14, nU1 = 2;
+    const int nF4 = RT_STATE_F4_ARRAYS, nU1 = 2;
     int rc = dev_alloc(c, c->stateBuf, stride4 * nF4 + stride1 * nU1);
     if (rc) return rc;
     PathState& ps = c->ps;
@@ -649,6 +650,8 @@ int rt_create(int device, rt_ctx** out) {
     (void)hipMemsetAsync(c->counterBuf.p, 0, sizeof(DevCounters) + 256, c->stream);
     if (dev_alloc(c, c->aovCounterBuf, sizeof(DevCounters)) != 0) { rt_destroy(c); return -7; }
     (void)hipMemsetAsync(c->aovCounterBuf.p, 0, sizeof(DevCounters), c->stream);
+    if (dev_alloc(c, c->shadeStatBuf, sizeof(ShadeStatStripe) * RT_STAT_STRIPES) != 0) { rt_destroy(c); return -7; }
+    (void)hipMemsetAsync(c->shadeStatBuf.p, 0, sizeof(ShadeStatStripe) * RT_STAT_STRIPES, c->stream);
     (void)hipStreamSynchronize(c->stream);
     *out = c;
     return 0;
@@ -1257,7 +1260,7 @@ int render_rounds(rt_ctx* c, const FrameParams& fp, Lane* lane, int nLanes) {
             TraceArgs ta{rays[cur], counts + 2 + cur, nullptr, nullptr, dc, counts + 5 + cur, counts + 7 + cur, L.n};
             const uint64_t ubRays = std::min<uint64_t>((uint64_t)L.ubActive * 3, (uint64_t)L.n * 3);
             if ((rc = launch_trace(c, L.d, (uint32_t)ubRays, ta))) break;
-            ShadeArgs sa{active[cur], counts + cur, active[nxt], rays[nxt], counts + nxt, counts + 2 + nxt, dc, counts + 5 + nxt, counts + 7 + nxt, L.n};
+            ShadeArgs sa{active[cur], counts + cur, active[nxt], rays[nxt], counts + nxt, counts + 2 + nxt, (ShadeStatStripe*)c->shadeStatBuf.p, counts + 5 + nxt, counts + 7 + nxt, L.n};
             if (L.d.sc.mapFlags & (RT_MAP_METALNESS | RT_MAP_BUMP)) hipLaunchKernelGGL(k_shade_maps, dim3((L.ubActive + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, L.d.sc, c->ps, sa, fp);
             else hipLaunchKernelGGL(k_shade, dim3((L.ubActive + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, L.d.sc, c->ps, sa, fp);
             L.cur = nxt;
@@ -1280,6 +1283,8 @@ int render_rounds(rt_ctx* c, const FrameParams& fp, Lane* lane, int nLanes) {
         RT_HIP(c, hipEventRecord(c->joinEvent[l - 1], lane[l].d.stream));
         RT_HIP(c, hipStreamWaitEvent(c->stream, c->joinEvent[l - 1], 0));
     }
+    // all parts are back on the ctx stream: their k_shade launches' statistics into the counters (also after a failed launch)
+    hipLaunchKernelGGL(k_fold_shade_stats, dim3(1), dim3(RT_STAT_STRIPES), 0, c->stream, (ShadeStatStripe*)c->shadeStatBuf.p, dc);
     return rc;
 }
 

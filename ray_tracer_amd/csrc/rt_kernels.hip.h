@@ -138,12 +138,17 @@ struct DevScene {
 
 // ---------------------------------------------------------------- path state (SoA, one slot per pixel)
 enum { RAY_MAIN = 0, RAY_NEE = 1, RAY_PROBE = 2 };
+// Queue entries only (Queues::rays): a main ray whose creator's seed says nothing — no sphere in front of it and no object ruled
+// out — and therefore was not written. Its hit record is hit(RAY_MAIN) like any main ray's: ray_kind() gives the kind to index by.
+#define RAY_MAIN_BLANK 3u
+__host__ __device__ __forceinline__ uint32_t ray_kind(uint32_t id) { return (id & 3u) == RAY_MAIN_BLANK ? (uint32_t)RAY_MAIN : (id & 3u); }
 
 // 16-byte records per slot: a path touches its state through a dozen dwordx4
 // accesses instead of ~85 dword accesses (k_shade is bound by the number of
 // memory instructions in flight, not by bytes).
 // One base pointer and the array pitch instead of fifteen pointers: the kernels that shade and traverse in one
 // (k_render_fused) are short of scalar registers, and an array's address is one scalar multiply-add away.
+#define RT_STATE_F4_ARRAYS 15   // float4 arrays of a PathState (ensure_state); the two uint32 statistics arrays follow them
 struct PathState {
     float4* base;
     uint32_t pitch;       // float4 elements between consecutive arrays (>= slots, 256-byte multiple)
@@ -152,24 +157,31 @@ struct PathState {
     __host__ __device__ __forceinline__ float4* rayO() const { return arr(0); }        // main ray origin            | w: misWeight (raytrace.comp:487)
     __host__ __device__ __forceinline__ float4* rayD() const { return arr(1); }        // main ray direction         | w: RNG state bits (:564)
     __host__ __device__ __forceinline__ float4* auxO() const { return arr(2); }        // origin of the probe rays (read by the traversal only)
-    __host__ __device__ __forceinline__ float4* auxDL() const { return arr(3); }       // NEE direction              | w: cosineHemispherePDF(n, lightSample)  (:448)
-    __host__ __device__ __forceinline__ float4* auxDC() const { return arr(4); }       // cosine-sample direction    | w: cosineHemispherePDF(n, cosineSample) (:454)
-    __host__ __device__ __forceinline__ float4* hit(uint32_t kind) const { return arr(5 + kind); }  // per ray kind. From the ray's creator: {closest sphere hit, its object bits, object mask, tE of a light query or 0}; from the traversal: {dst, object bits, triangle bits, 0}
+    // auxO / auxDL / auxDC are read by the traversal only, and written only for the queries that are traced (auxO: if either is)
+    __host__ __device__ __forceinline__ float4* auxDL() const { return arr(3); }       // NEE direction
+    __host__ __device__ __forceinline__ float4* auxDC() const { return arr(4); }       // cosine-sample direction
+    // per ray kind (RAY_MAIN .. RAY_PROBE; never RAY_MAIN_BLANK: ray_kind()). From the ray's creator: {closest sphere hit, its object bits, object mask, tE of a
+    // light query or 0} — not written for a main ray of k_shade whose seed is {RT_MISS_DST, RT_HIT_NONE, all objects, 0} (seed_is_blank; the queue entry
+    // says so), nor for a sample's first main ray under camReuse (k_shade reads camHit); from the traversal: {dst, object bits, triangle bits, 0}
+    __host__ __device__ __forceinline__ float4* hit(uint32_t kind) const { return arr(5 + kind); }
     __host__ __device__ __forceinline__ float4* att() const { return arr(8); }         // attenuation                | w: bounce index j (28 bits), bit 31 = NEE results pending, bit 30 = the last bounce was specular (directLight = -1, :469,480), bits 29 / 28 = the NEE ray / the cosine probe was answered "not emissive" by its creator (no record written for it)
-    __host__ __device__ __forceinline__ float4* total() const { return arr(9); }       // totalColor                 | w: samples finished for this pixel
+    __host__ __device__ __forceinline__ float4* total() const { return arr(9); }       // totalColor                 | w: samples finished for this pixel (k_shade stores it only when its bits changed)
     // (directLight has no record: between two segments it is either about to be recomputed from the probe results — bit 31 of
     // att.w — or one of two constants: -1 after a specular bounce, bit 30, and 0 at the start of a sample)
     __host__ __device__ __forceinline__ float4* pendAlbedo() const { return arr(10); } // albedo of the previous diffuse hit | w: max(0, dot(n, lightSample)) (:460)
     __host__ __device__ __forceinline__ float4* accum() const { return arr(11); }      // sum of trace() over the pixel's samples (:572)
     __host__ __device__ __forceinline__ float4* camHit() const { return arr(12); }     // the camera ray's hit record, kept from the pixel's first sample (FrameParams::camReuse)
     __host__ __device__ __forceinline__ float4* camDir() const { return arr(13); }     // the camera ray's direction (every sample of the pixel starts with it: no jitter, raytrace.comp:541-557)
-    __host__ __device__ __forceinline__ uint32_t* statBox() const { return (uint32_t*)arr(14); }             // stats[0] of the pixel (main-path traversals only)
-    __host__ __device__ __forceinline__ uint32_t* statTri() const { return (uint32_t*)arr(14) + pitchStat; } // stats[1]
+    // the rest of what finishes the previous diffuse bounce's MIS (:443-460), next to pendAlbedo: {dot((0,-1,0), lightSample), dot((0,-1,0), cosineSample)
+    // (light_cos: lightSamplePDF's cosine, :399), cosineHemispherePDF(n, lightSample) (:448), cosineHemispherePDF(n, cosineSample) (:454)}
+    __host__ __device__ __forceinline__ float4* pendMis() const { return arr(14); }
+    __host__ __device__ __forceinline__ uint32_t* statBox() const { return (uint32_t*)arr(RT_STATE_F4_ARRAYS); }             // stats[0] of the pixel (main-path traversals only)
+    __host__ __device__ __forceinline__ uint32_t* statTri() const { return (uint32_t*)arr(RT_STATE_F4_ARRAYS) + pitchStat; } // stats[1]
 };
 
 struct Queues {
     uint32_t* active[2];  // path slots that have rays in flight
-    uint32_t* rays[2];    // slot*4 + kind
+    uint32_t* rays[2];    // slot*4 + kind (RAY_MAIN, RAY_NEE, RAY_PROBE, or RAY_MAIN_BLANK: a main ray without a seed record)
     uint32_t* counts;     // [0..1] active counts, [2..3] ray counts
 };
 
@@ -200,6 +212,18 @@ struct FrameParams {
 struct DevCounters {
     unsigned long long boxTests, triTests, raysTraced, raysHit, raysReference, paths, segments, emitterTests;
     unsigned long long skippedBoxTests;  // of boxTests: charged for objects rays were taken past (the reference tests the children of their roots), not executed
+};
+
+// k_shade's four statistics. Every 256-path block adds its share once, and a part's launch has tens of thousands of blocks in a few ms:
+// added straight to the four adjacent DevCounters fields, that is one cache line taking four atomics per block, and the blocks
+// queue up behind it (measured on the bench frame: the four atomics were 27 % of k_shade's run time). So a block adds to one of
+// RT_STAT_STRIPES copies, each in a line of its own, chosen by its index — blocks that run at the same time have neighbouring
+// indices — and k_fold_shade_stats adds the copies to DevCounters and clears them at the end of the dispatch, on the ctx stream,
+// before anything the host can enqueue to read the counters.
+#define RT_STAT_STRIPES 256u
+struct ShadeStatStripe {
+    unsigned long long raysReference, paths, segments, emitterTests;
+    unsigned long long pad[12];   // 128 bytes
 };
 
 // ---------------------------------------------------------------- address spaces of the scene tables
@@ -336,6 +360,12 @@ __device__ __forceinline__ float4 sphere_seed(const DevScene& sc, rt_vec3 ro, rt
         if (h.didHit && h.dst < best) { best = h.dst; obj = RT_HIT_SPHERE | i; }
     }
     return make_float4(best, __uint_as_float(obj), __uint_as_float(withMask ? reach_mask(sc, ro, rd) : 0xffffffffu), 0.f);
+}
+
+// A seed that says nothing: no sphere in front of the ray, no object ruled out (and no tE: sphere_seed's .w is 0). The traversal starts
+// such a ray from these constants without a record (trace_wave, set-up step; RAY_MAIN_BLANK).
+__device__ __forceinline__ bool seed_is_blank(float4 seed) {
+    return __float_as_uint(seed.y) == RT_HIT_NONE && __float_as_uint(seed.z) == 0xffffffffu;
 }
 
 struct TriHit { bool didHit, frontFace; float dst, u, v, w; };
@@ -544,14 +574,16 @@ __global__ __launch_bounds__(RT_BLOCK) void k_trace(DevScene sc, PathState ps, T
     if (live) {
         uint32_t id = ta.queue ? ta.queue[qpos] : (gid << 2);
         slot = id >> 2;
-        kind = id & 3u;
+        kind = ray_kind(id);
         rt_vec3 ro, rd;
         if (kind == RAY_MAIN) { ro = f4xyz(ps.rayO()[slot]); rd = f4xyz(ps.rayD()[slot]); }
         else { ro = f4xyz(ps.auxO()[slot]); rd = f4xyz(kind == RAY_NEE ? ps.auxDL()[slot] : ps.auxDC()[slot]); }
 
         float best = RT_MISS_DST;
         uint32_t bestObj = RT_HIT_NONE, bestTri = 0;
-        const float earlyT = ta.queue ? ps.hit(kind)[slot].w : 0.f;  // light queries: distance of the nearest emissive primitive
+        // light queries: distance of the nearest emissive primitive. (The seed's sphere hit and object mask are not used here: this kernel
+        // runs the sphere loop itself and enters every object, so a main ray without a seed record, RAY_MAIN_BLANK, only has no tE.)
+        const float earlyT = (ta.queue && (id & 3u) != RAY_MAIN_BLANK) ? ps.hit(kind)[slot].w : 0.f;
 
         for (uint32_t i = 0; i < sc.sphereCount; i++) {
             SphereHit h = sphere_intersect(sc.spheres[i], ro, rd);
@@ -881,7 +913,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                     // is "not emissive" whatever else the ray meets, so it ends here and reports no hit, which is what shade_path
                     // reads as "not emissive". tE is re-read from the ray's hit record on the rare step that finds a hit rather
                     // than held in a register through the loop. The leaf counts in full, as the shader counts it (:310).
-                    if (closer && best < ((RT_TE_REG && ROOMY) ? earlyT : ps.hit(id & 3u)[id >> 2].w)) {
+                    if (closer && best < ((RT_TE_REG && ROOMY) ? earlyT : (!LOCAL && (id & 3u) == RAY_MAIN_BLANK) ? 0.f : ps.hit(id & 3u)[id >> 2].w)) {
                         if ((int32_t)cur < 0 && cur < RT_CUR_LEAF_MAX) {  // triangles of this leaf not yet stepped through
                             const uint32_t rest = (cur >> RT_LEAF_CNT_SHIFT) & 7u;
                             if (PIX) rayTri += rest; else wt.totTri += rest;
@@ -907,7 +939,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                 //   WORLD: world-space ray again                     -> NEED
                 //   SETUP: into object `obj` with a general matrix   -> its root
                 if (cur - RT_CUR_INIT <= RT_CUR_SETUP - RT_CUR_INIT) {
-                    const uint32_t slot = id >> 2, kind = id & 3u;
+                    const uint32_t slot = id >> 2, kind = LOCAL ? (id & 3u) : ray_kind(id);  // (the fused kernels' lists hold no RAY_MAIN_BLANK)
                     rt_vec3 wo, wd;
                     if (kind == RAY_MAIN) { wo = f4xyz(ps.rayO()[slot]); wd = f4xyz(ps.rayD()[slot]); }
                     else { wo = f4xyz(ps.auxO()[slot]); wd = f4xyz(kind == RAY_NEE ? ps.auxDL()[slot] : ps.auxDC()[slot]); }
@@ -918,7 +950,9 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                     }
                     if (cur == RT_CUR_INIT) {
                         // the ray's creator already ran the sphere loop (sphere_seed)
-                        const float4 seed = STATS ? seedPre : ps.hit(kind)[slot];
+                        // ... and left a seed record, unless the seed says nothing (seed_is_blank): then the queue entry says so
+                        float4 seed = make_float4(RT_MISS_DST, __uint_as_float(RT_HIT_NONE), __uint_as_float(0xffffffffu), 0.f);
+                        if (LOCAL || (id & 3u) != RAY_MAIN_BLANK) seed = STATS ? seedPre : ps.hit(kind)[slot];
                         best = seed.x; bestObj = __float_as_uint(seed.y); bestTri = 0;
                         plain = ray_is_plain(wo, wd);
                         reach = __float_as_uint(seed.z);
@@ -1063,7 +1097,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                 fetch_next_meta();
             }
             if (cur == RT_CUR_DONE) {
-                const uint32_t slot = id >> 2, kind = id & 3u;
+                const uint32_t slot = id >> 2, kind = LOCAL ? (id & 3u) : ray_kind(id);
                 ps.hit(kind)[slot] = make_float4(best, __uint_as_float(bestObj), __uint_as_float(bestTri), 0.f);
                 if (PIX && kind == RAY_MAIN) { ps.statBox()[slot] += rayBox; ps.statTri()[slot] += rayTri; }
                 if (PIX) {
@@ -1270,12 +1304,13 @@ __device__ __forceinline__ rt_vec3 environment_light(const EnvironmentData& env,
 }
 
 // raytrace.comp:389-403 given the probe ray's closest hit
-__device__ __forceinline__ float light_sample_pdf(const DevScene& sc, float t, uint32_t obj, rt_vec3 dir) {
+// cosTheta: light_cos of the query's direction, computed by the segment that made the direction
+__device__ __forceinline__ float light_cos(rt_vec3 dir) { return rt_dot(rt_v3(0.f, -1.f, 0.f), dir); }
+__device__ __forceinline__ float light_sample_pdf(const DevScene& sc, float t, uint32_t obj, float cosTheta) {
     if (obj == RT_HIT_NONE) return 0.f;
     uint32_t m = hit_material(sc, obj);
     if (rt_global(sc.mats)[3 * m + 1].w == 0.f) return 0.f;
     float sq = t * t;
-    float cosTheta = rt_dot(rt_v3(0.f, -1.f, 0.f), dir);
     return sq / (cosTheta * 0.4444444f);
 }
 
@@ -1355,6 +1390,8 @@ __global__ __launch_bounds__(RT_BLOCK) void k_raygen(DevScene sc, PathState ps, 
     }
     init_path(sc, ps, fp, slot);
     activeOut[pos] = slot;
+    // (always with its seed record, RAY_MAIN: init_path is the fused kernels' too, and a camera ray is one record in the ~47 segments of
+    // a pixel's eight samples. k_seed_rays and k_aov_rays feed launches without a queue, which have no entry to mark: they write it as well.)
     raysOut[pos] = slot << 2;
 }
 
@@ -1366,7 +1403,7 @@ struct ShadeArgs {
     uint32_t* outRays;
     uint32_t* outActiveCount;
     uint32_t* outRayCount;
-    DevCounters* counters;
+    ShadeStatStripe* stats;   // [RT_STAT_STRIPES]
     uint32_t* outAuxCount;    // the queue's second and third piece, outRays[auxOffset ..] and outRays[2 * auxOffset ..] (TraceArgs::countAux)
     uint32_t* outAuxCount2;
     uint32_t auxOffset;
@@ -1379,7 +1416,12 @@ struct ShadeArgs {
 // traversal, its hit record is already there: the kept camera hit), refRays (the shader's
 // calculateIntersections calls for this segment), nPaths (1 if a sample finished), emitTests (primitives emitter_min_t2 tested).
 // MAPS (k_shade_maps, k_render_fused_maps): the scene binds a metalness or a bump map
-template <bool MAPS = false>
+// QUEUED (k_shade, k_shade_maps): the segment's records travel through memory between two kernels, so every record that can be
+// left out is. auxMask bit 3: the main ray's seed says nothing (no sphere hit, every object to be entered) and has no record — its
+// queue entry says so (RAY_MAIN_BLANK); a finished sample's successor reads the kept camera hit where it is (camHit) instead of a
+// copy of it in hit(RAY_MAIN); `total` is stored only when its bits changed. The fused kernels, whose records stay in the
+// wave's own cache lines and whose registers are spilling already, keep the plain form of these three spots.
+template <bool MAPS = false, bool QUEUED = false>
 __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& ps, const FrameParams& fp, uint32_t slot, bool& alive,
                                            uint32_t& auxMask, uint32_t& refRays, uint32_t& nPaths, uint32_t& emitTests, bool withMask = true) {
     bool wantAux = false;  // a diffuse bounce whose MIS the next segment finishes (raytrace.comp:443-460)
@@ -1387,8 +1429,11 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
     rt_vec3 auxOrigin = rt_v3(0, 0, 0), auxL = auxOrigin, auxC = auxOrigin;  // probe rays of this bounce (diffuse only)
     rt_vec3 auxAlbedo = auxOrigin;                                           // ... and what the next segment needs to finish its MIS
     float auxNdotL = 0.f, auxCosPdfL = 0.f, auxCosPdfC = 0.f;
+    float auxCosL = 0.f, auxCosC = 0.f;                                      // light_sample_pdf's cosine of the two directions
     const float4 sO = ps.rayO()[slot], sD = ps.rayD()[slot], sA = ps.att()[slot], sT = ps.total()[slot];
-    const float4 hM = ps.hit(RAY_MAIN)[slot];
+    // QUEUED: a sample's first segment other than the pixel's first has no record of its own, the camera ray's hit is kept in camHit
+    const float4 hM = (QUEUED && fp.camReuse && (__float_as_uint(sA.w) & 0x0fffffffu) == 0u && __float_as_uint(sT.w) != 0u) ? ps.camHit()[slot]
+                                                                                                                        : ps.hit(RAY_MAIN)[slot];
     rt_vec3 ro = f4xyz(sO), rd = f4xyz(sD);
     rt_vec3 att = f4xyz(sA), total = f4xyz(sT);
     float misW = sO.w;
@@ -1419,18 +1464,17 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
             float4 hL = make_float4(RT_MISS_DST, __uint_as_float(RT_HIT_NONE), 0.f, 0.f), hC = hL;
             if (!(jraw & 0x20000000u)) hL = ps.hit(RAY_NEE)[slot];
             if (!(jraw & 0x10000000u)) hC = ps.hit(RAY_PROBE)[slot];
-            const float4 aL = ps.auxDL()[slot], aC = ps.auxDC()[slot];
+            const float4 pM = ps.pendMis()[slot];      // {light_cos(lightSample), light_cos(cosineSample), the two cosine pdfs}
             float tL = hL.x, tC = hC.x;
             uint32_t oL = __float_as_uint(hL.y), oC = __float_as_uint(hC.y);
-            rt_vec3 dL = f4xyz(aL), dC = f4xyz(aC);
             uint32_t lm = (oL == RT_HIT_NONE) ? 0u : hit_material(sc, oL);
             float4 lmE = rt_global(sc.mats)[3 * lm + 1];
-            float realLightPDF = light_sample_pdf(sc, tL, oL, dL);
-            float cosinePDF = aL.w;
+            float realLightPDF = light_sample_pdf(sc, tL, oL, pM.x);
+            float cosinePDF = pM.z;
             float misWeight1 = realLightPDF * realLightPDF / (realLightPDF * realLightPDF + cosinePDF * cosinePDF);
             if (rt_isnan(misWeight1)) misWeight1 = 0.f;
-            float lightPDF = light_sample_pdf(sc, tC, oC, dC);
-            float realCosinePDF = aC.w;
+            float lightPDF = light_sample_pdf(sc, tC, oC, pM.y);
+            float realCosinePDF = pM.w;
             float misWeight2 = realCosinePDF * realCosinePDF / (lightPDF * lightPDF + realCosinePDF * realCosinePDF);
             if (rt_isnan(misWeight2)) misWeight2 = 0.f;
             const float4 pA = ps.pendAlbedo()[slot];   // {albedo, max(0, dot(n, lightSample))}
@@ -1514,6 +1558,7 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
                 // (the four records of the unfinished MIS are written at the end, once it is known that the path goes on and that
                 // the next segment needs them)
                 auxOrigin = origin; auxL = lightSample; auxC = cosineSample; auxAlbedo = albedo;
+                auxCosL = light_cos(lightSample); auxCosC = light_cos(cosineSample);
                 auxNdotL = rt_max(0.f, rt_dot(hit.normal, lightSample));
                 auxCosPdfL = rt_max(0.f, rt_dot(lightSample, hit.normal) * RT_INV_PI);
                 auxCosPdfC = realCosinePDF;
@@ -1569,14 +1614,16 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
     if (alive) {
         if (done && fp.camReuse) {
             // a new sample of the same pixel: the same camera ray, whose hit is known — no traversal this round (bit 2)
-            ps.hit(RAY_MAIN)[slot] = ps.camHit()[slot];
+            if (!QUEUED) ps.hit(RAY_MAIN)[slot] = ps.camHit()[slot];
             auxMask |= 4u;
         } else {
-            ps.hit(RAY_MAIN)[slot] = sphere_seed(sc, ro, rd, withMask);
+            const float4 seed = sphere_seed(sc, ro, rd, withMask);
+            if (QUEUED && seed_is_blank(seed)) auxMask |= 8u;
+            else ps.hit(RAY_MAIN)[slot] = seed;
         }
         if (wantAux) {
             float4 sL = sphere_seed(sc, auxOrigin, auxL, withMask), sC = sphere_seed(sc, auxOrigin, auxC, withMask);
-            auxMask = 3u;
+            auxMask |= 3u;
             if (sc.emitMode) {
                 // Both are light queries: only "is the closest hit emissive, and at what distance" is read from them. With
                 // tE the nearest emissive primitive on the ray: none at all, or a sphere nearer than it, answers "not
@@ -1604,17 +1651,22 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
             } else {
                 if (auxMask & 1u) ps.hit(RAY_NEE)[slot] = sL;     // the traversal's seed; an answered query needs no record (att.w bits 29 / 28)
                 if (auxMask & 2u) ps.hit(RAY_PROBE)[slot] = sC;
-                ps.auxO()[slot] = mk4(auxOrigin, 0.f);
-                ps.auxDL()[slot] = mk4(auxL, auxCosPdfL);
-                ps.auxDC()[slot] = mk4(auxC, auxCosPdfC);
+                // the directions are the traversal's alone: only those of the queries that fly
+                if (auxMask & 3u) ps.auxO()[slot] = mk4(auxOrigin, 0.f);
+                if (auxMask & 1u) ps.auxDL()[slot] = mk4(auxL, 0.f);
+                if (auxMask & 2u) ps.auxDC()[slot] = mk4(auxC, 0.f);
                 ps.pendAlbedo()[slot] = mk4(auxAlbedo, auxNdotL);
+                ps.pendMis()[slot] = make_float4(auxCosL, auxCosC, auxCosPdfL, auxCosPdfC);
             }
         }
         const uint32_t answered = wantAux ? (((auxMask & 1u) ? 0u : 0x20000000u) | ((auxMask & 2u) ? 0u : 0x10000000u)) : 0u;
         ps.rayO()[slot] = mk4(ro, misW);
         ps.rayD()[slot] = mk4u(rd, state);
         ps.att()[slot] = mk4u(att, j | (wantAux ? 0x80000000u : 0u) | (specular ? 0x40000000u : 0u) | answered);
-        ps.total()[slot] = mk4u(total, samplesDone);
+        const float4 nT = mk4u(total, samplesDone);
+        if (!QUEUED || __float_as_uint(nT.x) != __float_as_uint(sT.x) || __float_as_uint(nT.y) != __float_as_uint(sT.y) ||
+            __float_as_uint(nT.z) != __float_as_uint(sT.z) || __float_as_uint(nT.w) != __float_as_uint(sT.w))
+            ps.total()[slot] = nT;
     }
 }
 
@@ -1628,19 +1680,19 @@ __device__ __forceinline__ void shade_block(const DevScene& sc, const PathState&
     const bool live = gid < n;
 
     bool alive = false;    // path (or its successor sample) has a main ray for the next round
-    uint32_t auxMask = 0;  // ... bit 0: and a NEE ray, bit 1: and a cosine probe
+    uint32_t auxMask = 0;  // ... bit 0: and a NEE ray, bit 1: and a cosine probe (bits 2 and 3: shade_path)
     uint32_t slot = 0;
     uint32_t refRays = 0, nPaths = 0, emitTests = 0;
     bool path = live;
     if (live) {
         slot = sa.inActive[gid];
         path = slot != 0xffffffffu;  // RT_QUEUE_HOLE
-        if (path) shade_path<MAPS>(sc, ps, fp, slot, alive, auxMask, refRays, nPaths, emitTests);
+        if (path) shade_path<MAPS, true>(sc, ps, fp, slot, alive, auxMask, refRays, nPaths, emitTests);
     }
 
     // Queue compaction: ranks inside a wave from ballots, wave offsets through LDS, and ONE atomic
     // per block and queue (a single hot counter saturates near 90 atomics/us; per-wave atomics made
-    // this kernel wait on them for half of its run time).
+    // this kernel wait on them for half of its run time). The statistics go to the block's stripe (ShadeStatStripe).
     const unsigned long long mAlive = __ballot(alive), mM = __ballot(alive && !(auxMask & 4u));
     const unsigned long long mL = __ballot(alive && (auxMask & 1u)), mC = __ballot(alive && (auxMask & 2u));
     const uint32_t nAlive = __popcll(mAlive), nM = __popcll(mM), nL = __popcll(mL), nC = __popcll(mC);
@@ -1657,10 +1709,11 @@ __device__ __forceinline__ void shade_block(const DevScene& sc, const PathState&
         s_base[1] = tR ? atomicAdd(sa.outRayCount, tR) : 0u;
         s_base[2] = tX ? atomicAdd(RT_QUEUE_ORDER ? sa.outAuxCount2 : sa.outAuxCount, tX) : 0u;
         s_base[3] = tY ? atomicAdd(RT_QUEUE_ORDER ? sa.outAuxCount : sa.outAuxCount2, tY) : 0u;
-        atomicAdd(&sa.counters->raysReference, (unsigned long long)tRef);
-        atomicAdd(&sa.counters->paths, (unsigned long long)tP);
-        atomicAdd(&sa.counters->segments, (unsigned long long)tS);
-        if (tE) atomicAdd(&sa.counters->emitterTests, (unsigned long long)tE);
+        ShadeStatStripe* const st = sa.stats + (blockIdx.x & (RT_STAT_STRIPES - 1u));
+        atomicAdd(&st->raysReference, (unsigned long long)tRef);
+        if (tP) atomicAdd(&st->paths, (unsigned long long)tP);
+        atomicAdd(&st->segments, (unsigned long long)tS);
+        if (tE) atomicAdd(&st->emitterTests, (unsigned long long)tE);
     }
     __syncthreads();
     if (alive) {
@@ -1669,7 +1722,7 @@ __device__ __forceinline__ void shade_block(const DevScene& sc, const PathState&
         for (uint32_t w = 0; w < wv; w++) { baseA += s_cnt[w][0]; baseR += s_cnt[w][1]; baseX += s_cnt[w][6]; baseY += s_cnt[w][7]; }
         sa.outActive[baseA + lanes_below(mAlive)] = slot;
         // the queue's pieces: main rays, NEE rays, cosine probes
-        if (!(auxMask & 4u)) sa.outRays[baseR + lanes_below(mM)] = (slot << 2) | RAY_MAIN;
+        if (!(auxMask & 4u)) sa.outRays[baseR + lanes_below(mM)] = (slot << 2) | ((auxMask & 8u) ? RAY_MAIN_BLANK : (uint32_t)RAY_MAIN);
         if (auxMask & 1u) sa.outRays[baseX + lanes_below(mL)] = (slot << 2) | RAY_NEE;
         if (auxMask & 2u) sa.outRays[baseY + lanes_below(mC)] = (slot << 2) | RAY_PROBE;
     }
@@ -2003,6 +2056,18 @@ __global__ __launch_bounds__(RT_DN_BLOCK) void k_dn_atrous(DenoiseFrame f, const
 // start of a multi-kernel dispatch: n active paths and n rays in buffer 0, nothing in buffer 1, work counter 0
 __global__ void k_init_counts(uint32_t* counts, uint32_t n) {
     if (threadIdx.x == 0) { counts[0] = n; counts[1] = 0; counts[2] = n; counts[3] = 0; counts[4] = 0; counts[5] = 0; counts[6] = 0; counts[7] = 0; counts[8] = 0; }
+}
+// end of a multi-kernel dispatch: k_shade's striped statistics into the counters, and the stripes cleared for the next one
+__global__ __launch_bounds__(RT_STAT_STRIPES) void k_fold_shade_stats(ShadeStatStripe* stats, DevCounters* counters) {
+    ShadeStatStripe* const st = stats + threadIdx.x;
+    const unsigned long long a = wave_sum_u64(st->raysReference), b = wave_sum_u64(st->paths), c = wave_sum_u64(st->segments), d = wave_sum_u64(st->emitterTests);
+    st->raysReference = 0; st->paths = 0; st->segments = 0; st->emitterTests = 0;
+    if (lane_id() == 0) {
+        atomicAdd(&counters->raysReference, a);
+        atomicAdd(&counters->paths, b);
+        atomicAdd(&counters->segments, c);
+        atomicAdd(&counters->emitterTests, d);
+    }
 }
 __global__ void k_zero_counts(uint32_t* a, uint32_t* b, uint32_t* c, uint32_t* d, uint32_t* e) {
     if (threadIdx.x == 0) { *a = 0; *b = 0; *c = 0; *d = 0; *e = 0; }
