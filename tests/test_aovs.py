@@ -232,18 +232,7 @@ def test_parity_alpha_and_bump_maps(renderer, tmp_path):
 
 
 # ---------------------------------------------------------------- 2. camera rays against a float64 restatement
-def _camera_dirs(pc, W, H):
-    """raytrace.comp:547-556 in float64: a plane of nearPlane * tan(fov / 2) * 2 by aspectRatio times that, at depth 0.1 (not
-    nearPlane), uv = pixel / image size, dir = normalize(point), (cameraRotation * vec4(dir, 1)).xyz."""
-    cam = pc.camInfo
-    ph = np.float64(np.float32(cam.nearPlane)) * np.tan(np.radians(np.float64(np.float32(cam.fov)) * 0.5)) * 2.0
-    pw = ph * np.float64(np.float32(cam.aspectRatio))
-    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
-    u, v = x / W, y / H
-    p = np.stack([-pw / 2 + pw * u, -ph / 2 + ph * v, np.full_like(u, 0.1)], -1)
-    d = p / np.linalg.norm(p, axis=-1, keepdims=True)
-    M = np.array(list(cam.cameraRotation), np.float64).reshape(4, 4).T   # column-major
-    return d @ M[:3, :3].T + M[:3, 3]
+from brute_force import camera_dirs as _camera_dirs   # noqa: E402  (the float64 camera lives with the float64 closest-hit reference)
 
 
 @pytest.mark.gpu
