@@ -605,7 +605,7 @@ Scene make_scene(const RtSceneArrays* a, uint32_t sphereCount, uint32_t objectCo
     sc.objectCount = objectCount;
     sc.inv.resize((size_t)objectCount * 16);
     for (uint32_t i = 0; i < objectCount; i++) rt_mat4_inverse(a->objects[i].transformMatrix, &sc.inv[(size_t)i * 16]);
-    // the emitter list, by the rules of rt_device.hip's rebuild_emitters (over the UPLOADED scene: a->sphereCount / a->objectCount)
+    // the emitter list, by the rules of scene_layout.cpp's layout_emitters (over the UPLOADED scene: a->sphereCount / a->objectCount)
     auto emissive = [&](uint32_t m) { return m < a->materialCount && !(a->materials[m].emissionStrength == 0.f); };
     bool ok = lightQueries;
     for (uint32_t m = 0; m < a->materialCount && ok; m++)

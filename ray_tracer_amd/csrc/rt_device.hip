@@ -33,10 +33,8 @@ struct DevBuf {  // device memory that belongs to whoever holds this: move-only,
 };
 
 struct EventPair { hipEvent_t a, b; };
-// device-side {index,triCount} of a mesh root, keyed by its reference node index
 #define RT_MAX_LANES 4
 #define RT_FRAMES_MAX_SLOTS (24ull << 20)   // default for the paths of one multi-frame dispatch (ten 1080p frames or three 4K frames: 5.8 GB of path state)
-struct RootInfo { uint32_t idx, cnt; float lo[3], hi[3]; uint32_t triFirst, triTotal; };  // triTotal = ~0u: the mesh's triangles are not one contiguous range
 // the rows y = row0 + k*rowStride, k in [0,nRows) of a width x height image
 struct RowsOf {
     uint32_t width = 0, height = 0, row0 = 0, rowStride = 0, nRows = 0;
@@ -56,12 +54,9 @@ struct rt_ctx {
     std::vector<DevBuf> sceneBufs;
     DevBuf texelBuf, texInfoBuf, triUVBuf, objTreeBuf, objCostBuf;
     DevBuf matBuf, sphereBuf, sphereMatBuf, objInvBuf, objFwdBuf, objMetaBuf, objBoxBuf, objSkipBuf, maskBoxBuf, emitBuf, emitPreBuf;
-    // host copies of what the emitter list is derived from (rebuild_emitters)
-    std::vector<RayMaterial> hostMats;
-    std::vector<uint32_t> hostSphereMat, hostObjMat, hostObjRoot, hostObjSampler;
-    DevBuf objAlphaBuf;     // per object: its material's alpha map and sampler (refresh_maps)
+    SceneSources host;      // host copies of what the emitter list and the map flags are derived from (rebuild_emitters)
+    DevBuf objAlphaBuf;     // per object: its material's alpha map and sampler (rebuild_emitters)
     uint32_t maxLeafDepth = 0;
-    std::vector<uint32_t> nodeRemap;          // reference node index -> device node index
     std::vector<RootInfo> rootOf;             // per reference node; idx = ~0u unless a mesh root
     bool cull = false;      // kernels with the object-skipping code (CULL) for this scene
     // multi-GPU (rt_comm_*): this rank's RCCL communicator, a staging buffer on the gathering rank
@@ -197,23 +192,13 @@ int upload(rt_ctx* c, DevBuf& b, const void* src, size_t bytes) {
     return 0;
 }
 
-void pack_materials(const RayMaterial* m, uint32_t n, std::vector<float4>& out) {
-    out.resize((size_t)std::max(n, 1u) * 3);
-    for (uint32_t i = 0; i < n; i++) {
-        out[3 * i + 0] = make_float4(m[i].albedo[0], m[i].albedo[1], m[i].albedo[2], m[i].reflectance);
-        out[3 * i + 1] = make_float4(m[i].emissionColor[0], m[i].emissionColor[1], m[i].emissionColor[2], m[i].emissionStrength);
-        float ai;
-        memcpy(&ai, &m[i].albedoIndex, 4);   // bits of the int; -1 = no texture
-        float mi, bi;
-        memcpy(&mi, &m[i].metalnessIndex, 4);
-        memcpy(&bi, &m[i].bumpIndex, 4);
-        out[3 * i + 2] = make_float4(m[i].ior, ai, mi, bi);
-    }
-}
-
-// rows 0..2 of a column-major mat4
-void rows_of(const float* m, float4* out) {
-    for (int r = 0; r < 3; r++) out[r] = make_float4(m[0 + r], m[4 + r], m[8 + r], m[12 + r]);
+// upload a table and point its DevScene field at it
+template <typename T>
+int upload_table(rt_ctx* c, DevBuf& b, const std::vector<T>& v, const T*& field) {
+    int rc = upload(c, b, v.data(), v.size() * sizeof(T));
+    if (rc) return rc;
+    field = (const T*)b.p;
+    return 0;
 }
 
 int ensure_state(rt_ctx* c, uint32_t nPixels) {
@@ -544,75 +529,79 @@ int harvest_events(rt_ctx* c) {
     return 0;
 }
 
-// The emitter list of the light queries (rt_kernels.hip.h: emitter_min_t2): every triangle of every object whose material is
-// emissive, and the emissive spheres. "Emissive" is what lightSamplePDF asks (raytrace.comp:392): emissionStrength != 0.
-// The shortcut is only taken when it is cheap (at most RT_EMIT_MAX_TRIS triangles) and exact: the NEE term of a query that
-// is answered "not emissive" is emission * 0, which is 0 only while every material's emissionColor * emissionStrength is finite.
-// The metalness, alpha and bump maps (declared semantics, include/rt_det_math.h): which of them the uploaded scene binds at all
-// (DevScene::mapFlags — the kernels that read them are separate ones, picked by these bits), and every object's alpha map for the
-// traversal. Follows the texture table, the materials and the objects: called whenever one of the three is replaced.
-int refresh_maps(rt_ctx* c) {
-    const uint32_t n = (uint32_t)c->hostObjMat.size();
-    auto bound = [&](int32_t index) { return index >= 0 && (uint32_t)index < c->sc.texCount; };
-    uint32_t flags = 0;
-    std::vector<uint32_t> oa(std::max(n, 1u), 0xffffffffu);
-    for (uint32_t i = 0; i < n; i++) {
-        if (c->hostObjMat[i] >= c->hostMats.size()) continue;
-        const RayMaterial& m = c->hostMats[c->hostObjMat[i]];
-        if (bound(m.metalnessIndex)) flags |= RT_MAP_METALNESS;
-        if (bound(m.bumpIndex)) flags |= RT_MAP_BUMP;
-        if (bound(m.alphaIndex)) { flags |= RT_MAP_ALPHA; oa[i] = (uint32_t)m.alphaIndex | (c->hostObjSampler[i] == 1u ? 0x100u : 0u); }
-    }
-    int rc = upload(c, c->objAlphaBuf, oa.data(), oa.size() * 4);
+// The map flags, every object's alpha map and the emitter list of the light queries (scene_layout.h: layout_maps, layout_emitters).
+// They follow the texture table, the materials, the spheres and the objects: called whenever one of the four is replaced.
+int rebuild_emitters(rt_ctx* c) {
+    c->sc.emitCount = 0; c->sc.emitSphereMask = 0; c->sc.emitMode = 0;
+    const MapLayout maps = layout_maps(c->host, c->sc.texCount);
+    int rc = upload_table(c, c->objAlphaBuf, maps.objAlpha, c->sc.objAlpha);
     if (rc) return rc;
-    c->sc.objAlpha = (const uint32_t*)c->objAlphaBuf.p;
-    c->sc.mapFlags = flags;
+    c->sc.mapFlags = maps.mapFlags;
+    if (!c->tune.lightQueries) return 0;
+    const EmitterLayout e = layout_emitters(c->host, c->rootOf, c->sc.texCount);
+    if (!e.mode) return 0;
+    if (!e.tris.empty()) {
+        if ((rc = upload_table(c, c->emitBuf, e.tris, c->sc.emitTris))) return rc;
+    } else {
+        if ((rc = dev_alloc(c, c->emitBuf, 256))) return rc;
+        c->sc.emitTris = (const uint2*)c->emitBuf.p;
+    }
+    // the ray-independent part of every listed triangle's test, computed on the device with the traversal's own operations
+    if ((rc = dev_alloc(c, c->emitPreBuf, std::max<size_t>(e.tris.size(), 1) * 4 * sizeof(float4)))) return rc;
+    if (!e.tris.empty()) {
+        hipLaunchKernelGGL(k_emit_precompute, dim3(((uint32_t)e.tris.size() + 63u) / 64u), dim3(64), 0, c->stream, c->sc.triPos, c->sc.emitTris, (uint32_t)e.tris.size(), (float4*)c->emitPreBuf.p);
+        RT_HIP(c, hipGetLastError());
+        RT_HIP(c, hipStreamSynchronize(c->stream));  // set-up time; the renders may go to another stream later (rt_set_stream)
+    }
+    c->sc.emitPre = (const float4*)c->emitPreBuf.p;
+    c->sc.emitCount = (uint32_t)e.tris.size();
+    c->sc.emitSphereMask = e.sphereMask;
+    c->sc.emitMode = 1;
     return 0;
 }
 
-int rebuild_emitters(rt_ctx* c) {
-    c->sc.emitCount = 0; c->sc.emitSphereMask = 0; c->sc.emitMode = 0;
-    { int rc = refresh_maps(c); if (rc) return rc; }
-    if (!c->tune.lightQueries || c->hostMats.empty()) return 0;
-    auto emissive = [&](uint32_t m) { return m < c->hostMats.size() && !(c->hostMats[m].emissionStrength == 0.f); };
-    for (const RayMaterial& m : c->hostMats)
-        for (int k = 0; k < 3; k++)
-            if (!std::isfinite(m.emissionColor[k] * m.emissionStrength)) return 0;
-    uint32_t mask = 0;
-    for (size_t i = 0; i < c->hostSphereMat.size() && i < 32; i++)
-        if (emissive(c->hostSphereMat[i])) mask |= 1u << i;
-    for (size_t i = 32; i < c->hostSphereMat.size(); i++)
-        if (emissive(c->hostSphereMat[i])) return 0;  // beyond the mask (the reference has ten spheres)
-    std::vector<uint2> list;
-    for (size_t i = 0; i < c->hostObjMat.size(); i++) {
-        if (!emissive(c->hostObjMat[i])) continue;
-        { const int32_t ai = c->hostMats[c->hostObjMat[i]].alphaIndex; if (ai >= 0 && (uint32_t)ai < c->sc.texCount) return 0; }  // an emitter with holes: its list entries would need the map
-        const RootInfo& r = c->rootOf[c->hostObjRoot[i]];
-        if (r.triTotal == 0xffffffffu || list.size() + r.triTotal > (size_t)RT_EMIT_MAX_TRIS) return 0;
-        for (uint32_t t = 0; t < r.triTotal; t++) list.push_back(make_uint2((uint32_t)i, r.triFirst + t));
-    }
-    if (!list.empty()) {
-        int rc = upload(c, c->emitBuf, list.data(), list.size() * sizeof(uint2));
-        if (rc) return rc;
-    } else {
-        int rc = dev_alloc(c, c->emitBuf, 256);
-        if (rc) return rc;
-    }
-    c->sc.emitTris = (const uint2*)c->emitBuf.p;
-    {   // the ray-independent part of every listed triangle's test, computed on the device with the traversal's own operations
-        int rc = dev_alloc(c, c->emitPreBuf, std::max<size_t>(list.size(), 1) * 4 * sizeof(float4));
-        if (rc) return rc;
-        if (!list.empty()) {
-            hipLaunchKernelGGL(k_emit_precompute, dim3(((uint32_t)list.size() + 63u) / 64u), dim3(64), 0, c->stream, c->sc.triPos, c->sc.emitTris, (uint32_t)list.size(), (float4*)c->emitPreBuf.p);
-            RT_HIP(c, hipGetLastError());
-            RT_HIP(c, hipStreamSynchronize(c->stream));  // set-up time; the renders may go to another stream later (rt_set_stream)
-        }
-        c->sc.emitPre = (const float4*)c->emitPreBuf.p;
-    }
-    c->sc.emitCount = (uint32_t)list.size();
-    c->sc.emitSphereMask = mask;
-    c->sc.emitMode = 1;
-    return 0;
+// The tables that rt_upload_scene replaces after the meshes and the update entry points replace on their own. Their input has
+// been checked by the time these run: only HIP can fail here.
+int set_materials(rt_ctx* c, const RayMaterial* m, uint32_t n) {
+    int rc = upload_table(c, c->matBuf, layout_materials(m, n), c->sc.mats);
+    if (rc) return rc;
+    c->sc.materialCount = n;
+    c->host.mats.assign(m, m + n);
+    return rebuild_emitters(c);
+}
+
+int set_spheres(rt_ctx* c, const Sphere* s, uint32_t n) {
+    const SphereLayout l = layout_spheres(s, n);
+    int rc = upload_table(c, c->sphereBuf, l.spheres, c->sc.spheres);
+    if (rc) return rc;
+    if ((rc = upload_table(c, c->sphereMatBuf, l.mat, c->sc.sphereMat))) return rc;
+    c->sc.sphereCount = n;
+    c->sc.sphereTestMask = l.testMask;
+    c->host.sphereMat.assign(l.mat.begin(), l.mat.begin() + n);
+    return rebuild_emitters(c);
+}
+
+int set_objects(rt_ctx* c, const ObjectLayout& l, const RenderObject* o, uint32_t n) {
+    if (l.treeLevels && getenv("RT_DEBUG_OBJTREE")) dump_object_tree(l, n);
+    int rc;
+    if ((rc = upload_table(c, c->objInvBuf, l.inv, c->sc.objInv))) return rc;
+    if ((rc = upload_table(c, c->objFwdBuf, l.fwd, c->sc.objFwd))) return rc;
+    if ((rc = upload_table(c, c->objMetaBuf, l.meta, c->sc.objMeta))) return rc;
+    if ((rc = upload_table(c, c->objBoxBuf, l.box, c->sc.objBox))) return rc;
+    if ((rc = upload_table(c, c->maskBoxBuf, l.maskBox, c->sc.maskBox))) return rc;
+    if ((rc = upload_table(c, c->objSkipBuf, l.skipCost, c->sc.objSkipCost))) return rc;
+    if ((rc = upload_table(c, c->objTreeBuf, l.tree, c->sc.objTree))) return rc;
+    if ((rc = upload_table(c, c->objCostBuf, l.cost, c->sc.objCost))) return rc;
+    for (int k = 0; k <= RT_OBJTREE_LEVELS; k++) c->sc.objTreeOff[k] = l.treeOff[k];
+    c->sc.objTreeLevels = l.treeLevels;
+    c->sc.reachCount = l.reachCount;
+    c->sc.maskBase = l.maskBase;
+    c->sc.cullOriginLimit = l.cullOriginLimit;
+    c->cull = l.cull;
+    c->sc.objectCount = n;
+    c->host.objMat.resize(n); c->host.objRoot.resize(n); c->host.objSampler.resize(n);
+    for (uint32_t i = 0; i < n; i++) { c->host.objMat[i] = o[i].materialIndex; c->host.objRoot[i] = o[i].bvhIndex; c->host.objSampler[i] = o[i].samplerIndex; }
+    return rebuild_emitters(c);
 }
 
 }  // namespace
@@ -685,25 +674,16 @@ int rt_set_stream(rt_ctx* c, void* s) {
     return 0;
 }
 
+// The entry points that replace scene tables: check the arguments, derive the tables on the host (scene_layout.h), upload.
+// Nothing of the context is written before the layout has succeeded, so a refused input leaves it as it was.
 int rt_upload_textures(rt_ctx* c, const RtTexture* tex, uint32_t n) {
     if (!c || (!tex && n)) return -1;
-    if (n > (uint32_t)RT_MAX_TEXTURES) return c->fail("more than RT_MAX_TEXTURES textures");
+    const TextureLayout l = layout_textures(tex, n);
+    if (!l.error.empty()) return c->fail(l.error);
     RT_HIP(c, hipSetDevice(c->device));
-    std::vector<uint4> info(std::max(n, 1u), make_uint4(0u, 1u, 1u, 0u));
-    size_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (!tex[i].rgba8 || tex[i].width == 0 || tex[i].height == 0) return c->fail("texture " + std::to_string(i) + " is empty");
-        if ((uint64_t)tex[i].width * tex[i].height > (1ull << 28) || total + (size_t)tex[i].width * tex[i].height > 0xffffffffull) return c->fail("textures too large");
-        info[i] = make_uint4((uint32_t)total, tex[i].width, tex[i].height, 0u);
-        total += (size_t)tex[i].width * tex[i].height;
-    }
-    std::vector<uint32_t> texels(std::max<size_t>(total, 1), 0u);
-    for (uint32_t i = 0; i < n; i++) memcpy(&texels[info[i].x], tex[i].rgba8, (size_t)tex[i].width * tex[i].height * 4);
-    int rc = upload(c, c->texelBuf, texels.data(), texels.size() * 4);
+    int rc = upload_table(c, c->texelBuf, l.texels, c->sc.texels);
     if (rc) return rc;
-    if ((rc = upload(c, c->texInfoBuf, info.data(), info.size() * sizeof(uint4)))) return rc;
-    c->sc.texels = (const uint32_t*)c->texelBuf.p;
-    c->sc.texInfo = (const uint4*)c->texInfoBuf.p;
+    if ((rc = upload_table(c, c->texInfoBuf, l.info, c->sc.texInfo))) return rc;
     c->sc.texCount = n;
     return rebuild_emitters(c);   // (which maps are bound follows the table's size; an emitter with an alpha map leaves the emitter list)
 }
@@ -711,401 +691,55 @@ int rt_upload_textures(rt_ctx* c, const RtTexture* tex, uint32_t n) {
 int rt_update_materials(rt_ctx* c, const RayMaterial* m, uint32_t n) {
     if (!c || (!m && n)) return -1;
     RT_HIP(c, hipSetDevice(c->device));
-    std::vector<float4> packed;
-    pack_materials(m, n, packed);
-    int rc = upload(c, c->matBuf, packed.data(), packed.size() * sizeof(float4));
-    if (rc) return rc;
-    c->sc.mats = (const float4*)c->matBuf.p;
-    c->sc.materialCount = n;
-    c->hostMats.assign(m, m + n);
-    return rebuild_emitters(c);
+    return set_materials(c, m, n);
 }
 
 int rt_update_spheres(rt_ctx* c, const Sphere* s, uint32_t n) {
     if (!c || (!s && n)) return -1;
     RT_HIP(c, hipSetDevice(c->device));
-    std::vector<float4> sp(std::max(n, 1u));
-    std::vector<uint32_t> sm(std::max(n, 1u));
-    for (uint32_t i = 0; i < n; i++) {
-        sp[i] = make_float4(s[i].position[0], s[i].position[1], s[i].position[2], s[i].radius);
-        sm[i] = s[i].materialIndex;
-    }
-    int rc = upload(c, c->sphereBuf, sp.data(), sp.size() * sizeof(float4));
-    if (rc) return rc;
-    rc = upload(c, c->sphereMatBuf, sm.data(), sm.size() * 4);
-    if (rc) return rc;
-    c->sc.spheres = (const float4*)c->sphereBuf.p;
-    c->sc.sphereMat = (const uint32_t*)c->sphereMatBuf.p;
-    c->sc.sphereCount = n;
-    // spheres whose {center, radius} repeat an earlier sphere's bit for bit are not tested by the rays' creators (DevScene::sphereTestMask)
-    c->sc.sphereTestMask = 0;
-    for (uint32_t i = 0; i < std::min(n, 32u); i++) {
-        bool repeat = false;
-        for (uint32_t k = 0; k < i && !repeat; k++) repeat = memcmp(&sp[i], &sp[k], sizeof(float4)) == 0;
-        if (!repeat) c->sc.sphereTestMask |= 1u << i;
-    }
-    c->hostSphereMat.assign(sm.begin(), sm.begin() + n);
-    return rebuild_emitters(c);
+    return set_spheres(c, s, n);
 }
 
-// objects: inverse computed once on the host with the shared
-// rt_mat4_inverse, root metadata resolved against the uploaded BVH.
 int rt_update_objects(rt_ctx* c, const RenderObject* o, uint32_t n) {
     if (!c || (!o && n)) return -1;
     if (c->rootOf.empty() && n) return c->fail("rt_update_objects before rt_upload_scene");
+    const ObjectLayout l = layout_objects(o, n, c->rootOf, c->sc.materialCount, c->tune.objTreeMin, c->tune.maskIdentity);
+    if (!l.error.empty()) return c->fail(l.error);
     RT_HIP(c, hipSetDevice(c->device));
-    std::vector<float4> inv((size_t)std::max(n, 1u) * 3), fwd((size_t)std::max(n, 1u) * 3);
-    std::vector<uint4> meta(std::max(n, 1u));
-    std::vector<float4> wbox((size_t)std::max(n, 1u) * 2, make_float4(0.f, 0.f, 0.f, 0.f));
-    uint32_t nGeneral = 0;
-    double minScale = 1e300;  // smallest size-and-position scale among the padded boxes
-    for (uint32_t i = 0; i < n; i++) {
-        float im[16];
-        rt_mat4_inverse(o[i].transformMatrix, im);
-        rows_of(im, &inv[3 * (size_t)i]);
-        rows_of(o[i].transformMatrix, &fwd[3 * (size_t)i]);
-        if (o[i].bvhIndex >= c->rootOf.size()) return c->fail("object.bvhIndex out of range");
-        const RootInfo& r = c->rootOf[o[i].bvhIndex];
-        if (r.idx == 0xffffffffu) return c->fail("object.bvhIndex does not point at a mesh root of the uploaded BVH");
-        if (o[i].materialIndex >= std::max(c->sc.materialCount, 1u)) return c->fail("object.materialIndex out of range");
-        // exact identity inverse: the traversal may reuse the world-space ray (k_trace_pw)
-        static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-        bool isIdent = true;
-        for (int r4 = 0; r4 < 3; r4++) {
-            const float4& q = inv[3 * (size_t)i + r4];
-            const float qq[4] = {q.x, q.y, q.z, q.w};
-            for (int k4 = 0; k4 < 4; k4++) isIdent = isIdent && (qq[k4] == ident[r4 * 4 + k4]);
-        }
-        // World-space box of the object, padded: a ray that cannot reach it before its current closest hit cannot reach the
-        // object's root box in object space either, so the object is worth exactly the reference's two box tests on the root's
-        // children (or the root leaf's triangle tests) and no set-up. Padding 1e-3 of the box's size and position: four
-        // orders of magnitude above what the fp32 inverse and the two slab tests can disagree by.
-        uint32_t boxOk = 0;
-        nGeneral += isIdent ? 0u : 1u;
-        if (!isIdent) {
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-            bool finite = true;
-            for (int corner = 0; corner < 8; corner++) {
-                const double p[3] = {(corner & 1) ? r.hi[0] : r.lo[0], (corner & 2) ? r.hi[1] : r.lo[1], (corner & 4) ? r.hi[2] : r.lo[2]};
-                for (int d = 0; d < 3; d++) {
-                    const float* m = o[i].transformMatrix;
-                    const double w = (double)m[0 * 4 + d] * p[0] + (double)m[1 * 4 + d] * p[1] + (double)m[2 * 4 + d] * p[2] + (double)m[3 * 4 + d];
-                    finite = finite && std::isfinite(w);
-                    lo[d] = std::min(lo[d], w); hi[d] = std::max(hi[d], w);
-                }
-            }
-            for (int k4 = 0; k4 < 12; k4++) finite = finite && std::isfinite((&inv[3 * (size_t)i].x)[k4]);
-            if (finite) {
-                double pad = 1e-6;
-                for (int d = 0; d < 3; d++) pad = std::max(pad, 1e-3 * std::max(hi[d] - lo[d], std::max(std::fabs(lo[d]), std::fabs(hi[d]))));
-                minScale = std::min(minScale, pad * 1e3);
-                wbox[2 * (size_t)i] = make_float4((float)(lo[0] - pad), (float)(lo[1] - pad), (float)(lo[2] - pad), 0.f);
-                wbox[2 * (size_t)i + 1] = make_float4((float)(hi[0] + pad), (float)(hi[1] + pad), (float)(hi[2] + pad), 0.f);
-                boxOk = 6u;  // the rays' creators may rule the object out as well (bit 2)
-            }
-        }
-        if (isIdent && c->tune.maskIdentity) {  // exact root box: the rays' creators could rule the object out with the traversal's own
-            wbox[2 * (size_t)i] = make_float4(r.lo[0], r.lo[1], r.lo[2], 0.f);       // slab test. Off by default: measured, the rounds
-            wbox[2 * (size_t)i + 1] = make_float4(r.hi[0], r.hi[1], r.hi[2], 0.f);   // this saves are the cheap ones (profiles/README.md)
-            boxOk = 4u;
-        }
-        // bit 3: the matrix itself is exactly the identity as well (reconstruct_hit then applies neither matrix)
-        bool fwdIdent = isIdent;
-        for (int r4 = 0; r4 < 3; r4++) {
-            const float4& q = fwd[3 * (size_t)i + r4];
-            const float qq[4] = {q.x, q.y, q.z, q.w};
-            for (int k4 = 0; k4 < 4; k4++) fwdIdent = fwdIdent && (qq[k4] == ident[r4 * 4 + k4]);
-        }
-        meta[i] = make_uint4(r.idx, r.cnt, o[i].materialIndex, (isIdent ? 1u : 0u) | boxOk | (fwdIdent ? 8u : 0u) | ((o[i].samplerIndex & 0xffffu) << 16));
-        {   // flags and root triangle count ride in the box's w components (one fetch per object in the skipping loop)
-            const uint32_t fl = meta[i].w & 0xffffu, cn = r.cnt;
-            memcpy(&wbox[2 * (size_t)i].w, &fl, 4);
-            memcpy(&wbox[2 * (size_t)i + 1].w, &cn, 4);
-        }
-    }
-    int rc = upload(c, c->objInvBuf, inv.data(), inv.size() * sizeof(float4));
-    if (rc) return rc;
-    if ((rc = upload(c, c->objFwdBuf, fwd.data(), fwd.size() * sizeof(float4)))) return rc;
-    if ((rc = upload(c, c->objMetaBuf, meta.data(), meta.size() * sizeof(uint4)))) return rc;
-    if ((rc = upload(c, c->objBoxBuf, wbox.data(), wbox.size() * sizeof(float4)))) return rc;
-    c->sc.objBox = (const float4*)c->objBoxBuf.p;
-    // the objects a ray's creator tests for the ray's object mask, compact: {lo.xyz, position in the window} {hi.xyz, -}. The mask
-    // has 32 bits; its window starts at the first object that can be ruled out at all, so that a scene like C5 (26 identity
-    // groups, then sixteen placed dragons) has all its placed objects under the mask
-    std::vector<float4> maskBox(64, make_float4(0.f, 0.f, 0.f, 0.f));
-    c->sc.reachCount = 0;
-    uint32_t maskBase = 0;
-    while (maskBase < n && !(meta[maskBase].w & 4u)) maskBase++;
-    if (maskBase >= n) maskBase = 0;
-    c->sc.maskBase = maskBase;
-    for (uint32_t i = maskBase; i < std::min(n, maskBase + 32u); i++)
-        if (meta[i].w & 4u) {
-            const uint32_t k = c->sc.reachCount++, w = i - maskBase;
-            maskBox[2 * k] = wbox[2 * (size_t)i]; maskBox[2 * k + 1] = wbox[2 * (size_t)i + 1];
-            memcpy(&maskBox[2 * k].w, &w, 4);
-        }
-    // one general-transform object among identity ones (Sponza's emitter) does not pay for either mechanism: measured +3 % and
-    // +8..19 % on that scene; from two on they do (Cornell + model: -5..-13 %)
-    // The padding dominates the rounding of the world-space slab test and of the object-space ray only while the ray's
-    // origin is not much farther out than the objects are big: both errors grow like 6e-8 * |origin|. Rays
-    // that start beyond 1e3 object scales take the reference's own route through every object.
-    c->sc.cullOriginLimit = minScale < 1e300 ? (float)(minScale * 1e3) : 0.f;
-    c->cull = nGeneral >= 2 || (c->tune.maskIdentity && c->sc.reachCount);
-    if (!c->cull) c->sc.reachCount = 0;
-    if ((rc = upload(c, c->maskBoxBuf, maskBox.data(), maskBox.size() * sizeof(float4)))) return rc;
-    c->sc.maskBox = (const float4*)c->maskBoxBuf.p;
-    // what the reference spends on objects [0, i) when a ray misses them all: two box tests per interior root, the root's
-    // triangles per leaf root. A run of skipped objects costs the difference of two entries (trace_wave: fetch_next_meta).
-    std::vector<uint2> skipCost(33, make_uint2(0u, 0u));  // over the mask's window
-    for (uint32_t w = 0; w < 32u; w++) {
-        const uint32_t i = maskBase + w;
-        skipCost[w + 1] = skipCost[w];
-        if (i < n) {
-            if (meta[i].y == 0u) skipCost[w + 1].x += 2u;
-            else skipCost[w + 1].y += meta[i].y;
-        }
-    }
-    if ((rc = upload(c, c->objSkipBuf, skipCost.data(), skipCost.size() * sizeof(uint2)))) return rc;
-    c->sc.objSkipCost = (const uint2*)c->objSkipBuf.p;
-    {   // the hierarchy over runs of general-transform objects with a padded box (rt_kernels.hip.h: DevScene::objTree), for scenes with
-        // many of them: measured on 256 separated bunny instances (tools/heuristics_table.py) against 7 % lost on C5's sixteen
-        // overlapping dragons, which stay below the threshold (and inside the rays' object masks anyway)
-        std::vector<float4> tree;
-        std::vector<uint2> cost((size_t)n + 1, make_uint2(0u, 0u));
-        for (uint32_t i = 0; i < n; i++) {
-            cost[i + 1] = cost[i];
-            if (meta[i].y == 0u) cost[i + 1].x += 2u; else cost[i + 1].y += meta[i].y;
-        }
-        uint32_t off[RT_OBJTREE_LEVELS + 1] = {};
-        uint32_t levels = 0;
-        if (c->tune.objTreeMin > 0 && nGeneral >= (uint32_t)c->tune.objTreeMin) {
-            auto skippable = [&](uint32_t i) { return i < n && (meta[i].w & 3u) == 2u; };
-            for (uint32_t k = 1; k <= (uint32_t)RT_OBJTREE_LEVELS; k++) {
-                off[k] = (uint32_t)(tree.size() / 2);
-                const uint32_t nb = (n + (1u << k) - 1) >> k;
-                for (uint32_t b = 0; b < nb; b++) {
-                    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-                    bool ok = true;
-                    for (uint32_t i = b << k; i < ((b + 1) << k); i++) {
-                        if (!skippable(i)) { ok = false; break; }
-                        const float4 &l = wbox[2 * (size_t)i], &h = wbox[2 * (size_t)i + 1];
-                        lo[0] = std::min(lo[0], l.x); lo[1] = std::min(lo[1], l.y); lo[2] = std::min(lo[2], l.z);
-                        hi[0] = std::max(hi[0], h.x); hi[1] = std::max(hi[1], h.y); hi[2] = std::max(hi[2], h.z);
-                    }
-                    tree.push_back(ok ? make_float4(lo[0], lo[1], lo[2], 1.f) : make_float4(0.f, 0.f, 0.f, 0.f));
-                    tree.push_back(ok ? make_float4(hi[0], hi[1], hi[2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f));
-                }
-            }
-            levels = (uint32_t)RT_OBJTREE_LEVELS;
-            if (getenv("RT_DEBUG_OBJTREE")) {
-                for (uint32_t k = 1; k <= levels; k++) {
-                    const uint32_t nb = (n + (1u << k) - 1) >> k;
-                    uint32_t valid = 0;
-                    for (uint32_t b = 0; b < nb; b++) valid += tree[2 * (size_t)(off[k] + b)].w != 0.f;
-                    const float4 &l = tree[2 * (size_t)(off[k] + std::min(1u, nb - 1))], &h = tree[2 * (size_t)(off[k] + std::min(1u, nb - 1)) + 1];
-                    fprintf(stderr, "[objtree] level %u: %u blocks, %u valid; block 1: (%g %g %g)-(%g %g %g)\n", k, nb, valid, l.x, l.y, l.z, h.x, h.y, h.z);
-                }
-                for (uint32_t i = 0; i < std::min(n, 6u); i++)
-                    fprintf(stderr, "[objtree] object %u flags %x box (%g %g %g)-(%g %g %g)\n", i, meta[i].w, wbox[2 * i].x, wbox[2 * i].y, wbox[2 * i].z, wbox[2 * i + 1].x, wbox[2 * i + 1].y, wbox[2 * i + 1].z);
-            }
-        }
-        if (tree.empty()) tree.assign(2, make_float4(0.f, 0.f, 0.f, 0.f));
-        if ((rc = upload(c, c->objTreeBuf, tree.data(), tree.size() * sizeof(float4)))) return rc;
-        if ((rc = upload(c, c->objCostBuf, cost.data(), cost.size() * sizeof(uint2)))) return rc;
-        c->sc.objTree = (const float4*)c->objTreeBuf.p;
-        c->sc.objCost = (const uint2*)c->objCostBuf.p;
-        for (int k = 0; k <= RT_OBJTREE_LEVELS; k++) c->sc.objTreeOff[k] = off[k];
-        c->sc.objTreeLevels = levels;
-    }
-    c->sc.objInv = (const float4*)c->objInvBuf.p;
-    c->sc.objFwd = (const float4*)c->objFwdBuf.p;
-    c->sc.objMeta = (const uint4*)c->objMetaBuf.p;
-    c->sc.objectCount = n;
-    c->hostObjMat.resize(n); c->hostObjRoot.resize(n); c->hostObjSampler.resize(n);
-    for (uint32_t i = 0; i < n; i++) { c->hostObjMat[i] = o[i].materialIndex; c->hostObjRoot[i] = o[i].bvhIndex; c->hostObjSampler[i] = o[i].samplerIndex; }
-    return rebuild_emitters(c);
+    return set_objects(c, l, o, n);
 }
 
 int rt_upload_scene(rt_ctx* c, const RtSceneArrays* s) {
     if (!c || !s) return -1;
+    SceneLayout l = layout_scene(*s, c->tune.objTreeMin, c->tune.maskIdentity);
+    if (!l.error.empty()) return c->fail(l.error);
+    MeshLayout& m = l.meshes;
+
     RT_HIP(c, hipSetDevice(c->device));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     measured_new_scene(c);
-    c->hostObjMat.clear(); c->hostObjRoot.clear(); c->hostObjSampler.clear(); c->hostSphereMat.clear(); c->hostMats.clear();
+    c->host = SceneSources{};
     c->sc.emitMode = 0; c->sc.emitCount = 0; c->sc.emitSphereMask = 0;
     c->sc.mapFlags = 0;
     c->sc.texCount = 0;  // texture slots belong to the scene's materials: rt_upload_textures follows a new scene
-    const uint32_t nNodes = s->bvhNodeCount, nTris = s->triangleCount;
-
-    // ---- mesh segmentation: every distinct object.bvhIndex starts a mesh
-    std::vector<uint32_t> roots;
-    for (uint32_t i = 0; i < s->objectCount; i++) {
-        if (s->objects[i].bvhIndex >= nNodes) return c->fail("object.bvhIndex out of range");
-        roots.push_back(s->objects[i].bvhIndex);
-    }
-    std::sort(roots.begin(), roots.end());
-    roots.erase(std::unique(roots.begin(), roots.end()), roots.end());
-
-    // ---- device node numbering: shift each mesh so its child pairs (which
-    // follow the root in twos) start on an even index = 64-byte boundary
-    // The child pairs of the top levels of every mesh come first (breadth first over all roots, level by level, at most
-    // RT_HOT_PAIRS of them): k_trace_pw<HOT> keeps exactly those in LDS (DevScene::hotNodes).
-    c->nodeRemap.assign(nNodes, 0xffffffffu);
-    uint32_t devCount = 0;
-    {
-        std::vector<uint32_t> level, next;
-        for (uint32_t root : roots) level.push_back(root);
-        uint32_t hot = 0;
-        for (int depth = 0; depth < 8 && !level.empty() && hot < RT_HOT_PAIRS; depth++) {
-            next.clear();
-            for (uint32_t nidx : level) {
-                const BVHNode& b = s->bvhNodes[nidx];
-                if (b.triCount != 0 || hot >= RT_HOT_PAIRS) continue;
-                if (b.index + 1 >= nNodes) return c->fail("BVH child index out of range");
-                if (c->nodeRemap[b.index] != 0xffffffffu) continue;  // (a malformed BVH that shares children)
-                c->nodeRemap[b.index] = 2 * hot;
-                c->nodeRemap[b.index + 1] = 2 * hot + 1;
-                hot++;
-                next.push_back(b.index);
-                next.push_back(b.index + 1);
-            }
-            level.swap(next);
-        }
-        c->sc.hotNodes = 2 * hot;
-        uint32_t pos = 2 * hot;
-        size_t r = 0;
-        for (uint32_t nidx = 0; nidx < nNodes; nidx++) {
-            const bool isRoot = r < roots.size() && roots[r] == nidx;
-            if (isRoot) r++;
-            if (c->nodeRemap[nidx] != 0xffffffffu) continue;  // a hot pair's node
-            if (isRoot && (pos & 1u) == 0u) pos++;             // root on an odd slot: the pairs that follow it in twos start even
-            c->nodeRemap[nidx] = pos++;
-        }
-        devCount = pos;
-    }
-
-    std::vector<float4> nodes((size_t)std::max(devCount, 2u) * 2, make_float4(0.f, 0.f, 0.f, 0.f));
-    std::vector<uint32_t> leafFirst(std::max(devCount, 1u), 0u);
-    // W0 of a node: child-pair index (interior) or the leaf reference the kernels push and decode
-    auto node_word = [&](uint32_t nidx) -> uint32_t {
-        const BVHNode& b = s->bvhNodes[nidx];
-        if (b.triCount == 0) return c->nodeRemap[b.index];
-        if (b.triCount <= 7u && b.index + b.triCount <= 0x0ffffff0u) return RT_LEAF_BIT | (b.triCount << RT_LEAF_CNT_SHIFT) | b.index;
-        return RT_LEAF_BIT | c->nodeRemap[nidx];
-    };
-    if (devCount > 0x0ffffff0u) return c->fail("BVH too large (node index needs more than 28 bits)");
-    for (uint32_t nidx = 0; nidx < nNodes; nidx++) {
-        const BVHNode& b = s->bvhNodes[nidx];
-        if (b.triCount == 0) {
-            if (b.index + 1 >= nNodes) return c->fail("BVH child index out of range");
-            if (c->nodeRemap[b.index] & 1u) return c->fail("internal: child pair not 64-byte aligned (BVH not built in pairs)");
-        } else if ((uint64_t)b.index + b.triCount > nTris) {
-            return c->fail("BVH leaf triangle range out of bounds");
-        }
-        const uint32_t w0 = node_word(nidx);
-        float4 lo = make_float4(b.boundsX[0], b.boundsY[0], b.boundsZ[0], 0.f);
-        float4 hi = make_float4(b.boundsX[1], b.boundsY[1], b.boundsZ[1], 0.f);
-        memcpy(&lo.w, &w0, 4);
-        memcpy(&hi.w, &b.triCount, 4);
-        nodes[2 * (size_t)c->nodeRemap[nidx]] = lo;
-        nodes[2 * (size_t)c->nodeRemap[nidx] + 1] = hi;
-        leafFirst[c->nodeRemap[nidx]] = b.triCount ? b.index : 0u;
-    }
-
-    // ---- the same child pairs, interleaved for packed fp32 math (k_trace_pw / k_render_fused):
-    // pair at even node index p -> 4 float4 at 2p: {L.minx L.miny L.maxx L.maxy} {R.minx R.miny R.maxx R.maxy}
-    // {L.minz L.maxz R.minz R.maxz} {L.W0 R.W0 - -}
-    std::vector<float4> nodesPk(nodes.size(), make_float4(0.f, 0.f, 0.f, 0.f));
-    for (size_t p = 0; p + 1 < (size_t)devCount; p += 2) {
-        const float4 lo1 = nodes[2 * p], hi1 = nodes[2 * p + 1], lo2 = nodes[2 * p + 2], hi2 = nodes[2 * p + 3];
-        nodesPk[2 * p] = make_float4(lo1.x, lo1.y, hi1.x, hi1.y);
-        nodesPk[2 * p + 1] = make_float4(lo2.x, lo2.y, hi2.x, hi2.y);
-        nodesPk[2 * p + 2] = make_float4(lo1.z, hi1.z, lo2.z, hi2.z);
-        nodesPk[2 * p + 3] = make_float4(lo1.w, lo2.w, 0.f, 0.f);
-    }
-
-    // ---- deepest leaf per mesh decides the LDS stack size
-    std::vector<RootInfo>& rootOf = c->rootOf;
-    rootOf.assign(nNodes, RootInfo{0xffffffffu, 0, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, 0u, 0u});
-    uint32_t maxDepth = 0;
-    {
-        std::vector<std::pair<uint32_t, uint32_t>> st;
-        for (uint32_t root : roots) {
-            const BVHNode& rb = s->bvhNodes[root];
-            rootOf[root] = RootInfo{node_word(root), rb.triCount, {rb.boundsX[0], rb.boundsY[0], rb.boundsZ[0]}, {rb.boundsX[1], rb.boundsY[1], rb.boundsZ[1]}, 0u, 0u};
-            st.clear();
-            st.emplace_back(root, 0u);
-            size_t visited = 0;
-            uint64_t triLo = ~0ull, triHi = 0, triSum = 0;  // the mesh's triangles: the leaves' ranges, one contiguous run as the builder leaves them
-            while (!st.empty()) {
-                auto [nidx, d] = st.back();
-                st.pop_back();
-                if (++visited > (size_t)nNodes + 1) return c->fail("BVH has a cycle");
-                const BVHNode& b = s->bvhNodes[nidx];
-                if (b.triCount) {
-                    maxDepth = std::max(maxDepth, d);
-                    triLo = std::min<uint64_t>(triLo, b.index); triHi = std::max<uint64_t>(triHi, (uint64_t)b.index + b.triCount); triSum += b.triCount;
-                    continue;
-                }
-                st.emplace_back(b.index, d + 1);
-                st.emplace_back(b.index + 1, d + 1);
-            }
-            rootOf[root].triFirst = (uint32_t)triLo;
-            rootOf[root].triTotal = (triSum == triHi - triLo) ? (uint32_t)triSum : 0xffffffffu;
-        }
-    }
-    if (maxDepth > 64) return c->fail("BVH deeper than 64 levels (the reference's builder caps at 64)");
-    c->maxLeafDepth = maxDepth;
-
-    // ---- triangles: positions hot, normals cold, both in the reference's order
-    std::vector<float4> tpos((size_t)std::max(nTris, 1u) * 3), tnrm((size_t)std::max(nTris, 1u) * 3);
-    for (uint32_t t = 0; t < nTris; t++) {
-        const Triangle& tr = s->triangles[t];
-        const uint32_t vi[3] = {tr.v0, tr.v1, tr.v2};
-        for (int k = 0; k < 3; k++) {
-            if (vi[k] >= s->triPointCount) return c->fail("triangle point index out of range");
-            const TrianglePoint& p = s->triPoints[vi[k]];
-            float w = 0.f;
-            if (k == 0) { uint32_t fo = tr.frontOnly ? 1u : 0u; memcpy(&w, &fo, 4); }
-            tpos[3 * (size_t)t + k] = make_float4(p.position[0], p.position[1], p.position[2], w);
-            tnrm[3 * (size_t)t + k] = make_float4(p.normal[0], p.normal[1], p.normal[2], 0.f);
-        }
-    }
-
-    {   // vertex uvs (TrianglePoint: u in position.w, v in normal.w, src/vk_engine.h:64-67), 2 x float4 per triangle
-        std::vector<float4> tuv((size_t)std::max(nTris, 1u) * 2, make_float4(0.f, 0.f, 0.f, 0.f));
-        for (uint32_t t = 0; t < nTris; t++) {
-            const Triangle& tr = s->triangles[t];
-            const TrianglePoint &p0 = s->triPoints[tr.v0], &p1 = s->triPoints[tr.v1], &p2 = s->triPoints[tr.v2];
-            tuv[2 * (size_t)t] = make_float4(p0.position[3], p0.normal[3], p1.position[3], p1.normal[3]);
-            tuv[2 * (size_t)t + 1] = make_float4(p2.position[3], p2.normal[3], 0.f, 0.f);
-        }
-        int rcu = upload(c, c->triUVBuf, tuv.data(), tuv.size() * sizeof(float4));
-        if (rcu) return rcu;
-        c->sc.triUV = (const float4*)c->triUVBuf.p;
-    }
     c->sceneBufs.clear();
     c->sceneBufs.resize(5);
     int rc;
-    if ((rc = upload(c, c->sceneBufs[0], nodes.data(), nodes.size() * sizeof(float4)))) return rc;
-    if ((rc = upload(c, c->sceneBufs[1], tpos.data(), tpos.size() * sizeof(float4)))) return rc;
-    if ((rc = upload(c, c->sceneBufs[2], tnrm.data(), tnrm.size() * sizeof(float4)))) return rc;
-    c->sc.nodes = (const float4*)c->sceneBufs[0].p;
-    c->sc.triPos = (const float4*)c->sceneBufs[1].p;
-    c->sc.triNrm = (const float4*)c->sceneBufs[2].p;
-    if ((rc = upload(c, c->sceneBufs[3], leafFirst.data(), leafFirst.size() * 4))) return rc;
-    c->sc.leafFirst = (const uint32_t*)c->sceneBufs[3].p;
-    if ((rc = upload(c, c->sceneBufs[4], nodesPk.data(), nodesPk.size() * sizeof(float4)))) return rc;
-    c->sc.nodesPk = (const float4*)c->sceneBufs[4].p;
-    c->sc.nodeCount = devCount;
-    c->sc.triCount = nTris;
+    if ((rc = upload_table(c, c->triUVBuf, m.triUV, c->sc.triUV))) return rc;
+    if ((rc = upload_table(c, c->sceneBufs[0], m.nodes, c->sc.nodes))) return rc;
+    if ((rc = upload_table(c, c->sceneBufs[1], m.triPos, c->sc.triPos))) return rc;
+    if ((rc = upload_table(c, c->sceneBufs[2], m.triNrm, c->sc.triNrm))) return rc;
+    if ((rc = upload_table(c, c->sceneBufs[3], m.leafFirst, c->sc.leafFirst))) return rc;
+    if ((rc = upload_table(c, c->sceneBufs[4], m.nodesPk, c->sc.nodesPk))) return rc;
+    c->sc.nodeCount = m.nodeCount;
+    c->sc.triCount = s->triangleCount;
+    c->sc.hotNodes = m.hotNodes;
+    c->maxLeafDepth = m.maxLeafDepth;
+    c->rootOf = std::move(m.rootOf);
 
-    if (s->materialCount == 0) return c->fail("scene needs at least one material");
-    if ((rc = rt_update_materials(c, s->materials, s->materialCount))) return rc;
-    for (uint32_t i = 0; i < s->sphereCount; i++)
-        if (s->spheres[i].materialIndex >= s->materialCount) return c->fail("sphere.materialIndex out of range");
-    if ((rc = rt_update_spheres(c, s->spheres, s->sphereCount))) return rc;
-    return rt_update_objects(c, s->objects, s->objectCount);
+    if ((rc = set_materials(c, s->materials, s->materialCount))) return rc;
+    if ((rc = set_spheres(c, s->spheres, s->sphereCount))) return rc;
+    return set_objects(c, l.objects, s->objects, s->objectCount);
 }
 
 int rt_sync(rt_ctx* c) {

@@ -26,15 +26,13 @@
 #include "rt_amd.h"
 #include "rt_det_math.h"
 #include "rt_probe.h"
+#include "scene_layout.h"   // the formats of the scene tables: node words, object flags, RT_MAP_*, RT_HOT_PAIRS, RT_OBJTREE_LEVELS
 
 #define RT_WAVE 64
-#ifndef RT_TE_REG
-#define RT_MAP_METALNESS 1u
-#define RT_MAP_ALPHA 2u
-#define RT_MAP_BUMP 4u
 #ifndef RT_QUEUE_ORDER
 #define RT_QUEUE_ORDER 0   // k_shade: the ray queue's pieces are {main, NEE, cosine probes} (1: {main, cosine probes, NEE})
 #endif
+#ifndef RT_TE_REG
 #define RT_TE_REG 1        // trace_wave<ROOMY>: a light query's tE rides in a register instead of being re-read from the hit record when a leaf step finds a hit
 #endif
 #ifndef RT_OBJTREE
@@ -47,41 +45,26 @@
 #define RT_FUSED_MAPS_BLOCKS 4   // k_render_fused_maps: work-groups per CU it is built for (__launch_bounds__)
 #endif
 #define RT_BLOCK 256
-#define RT_LEAF_BIT 0x80000000u
 #define RT_HIT_NONE 0xffffffffu
 #define RT_HIT_SPHERE 0x80000000u
-#define RT_OBJTREE_LEVELS 8   // blocks of up to 256 objects in the object hierarchy (DevScene::objTree)
 
 // ---------------------------------------------------------------- scene in HBM
-// All arrays are read-only during a render.
-//   nodes   : 2 x float4 per BVH node  {min.xyz, W0} {max.xyz, triCount}
-//             W0 = index of the child pair (interior), or a ready-made leaf
-//             reference LEAF|count<<28|firstTriangle (count <= 7), or
-//             LEAF|nodeIndex for bigger leaves (first triangle in leafFirst[])
-//             children of an interior node are adjacent and 64-B aligned, so
-//             one interior visit is one 64-B fetch (the reference re-reads the
-//             popped node and both children: 96 B, raytrace.comp:306,326-327)
-//   triPos  : 3 x float4 per triangle   {v0.xyz, frontOnly} {v1.xyz,-} {v2.xyz,-}
-//             in the reference's (builder-permuted) triangle order; hot
-//   triNrm  : 3 x float4 per triangle   vertex normals; cold, read per hit only
-//   objInv  : 3 x float4 per object     rows of inverse(transformMatrix)[0..2]
-//   objFwd  : 3 x float4 per object     rows of transformMatrix[0..2]
-//   objMeta : uint4 per object          {rootIndex|pairIndex, rootTriCount, materialIndex, flags (bit 0: identity transform, bit 1: objBox valid)}
-//   objBox  : 2 x float4 per object     padded world-space box of a general-transform object
-//   mats    : 3 x float4 per material   {albedo, reflectance} {emission, strength} {ior,-,-,-}
-//   spheres : float4 {center, radius} + uint material
+// All arrays are read-only during a render. Their formats are defined in scene_layout.h, next to the host code that builds
+// them (MeshLayout: nodes, nodesPk, leafFirst, triPos, triNrm, triUV; ObjectLayout: objInv, objFwd, objMeta, objBox, maskBox,
+// objSkipCost, objTree, objCost; layout_materials: mats; SphereLayout: spheres, sphereMat). What matters to the kernels:
+//   nodes   : the children of an interior node are adjacent and 64-B aligned, so one interior visit is one 64-B fetch (the
+//             reference re-reads the popped node and both children: 96 B, raytrace.comp:306,326-327)
+//   triPos  : hot; triNrm, triUV: cold, read per hit only
 struct DevScene {
     const float4* nodes;
-    const float4* nodesPk;   // child pairs interleaved for packed math, see rt_upload_scene
+    const float4* nodesPk;   // child pairs interleaved for packed math
     const uint32_t* leafFirst;  // first triangle of a leaf, per node (read only for leaves with > 7 triangles)
     const float4* triPos;
     const float4* triNrm;
     const float4* objInv;
     const float4* objFwd;
     const uint4* objMeta;
-    const float4* objBox;    // 2 x float4 per object: {lo.xyz, flags} {hi.xyz, root triangle count}; flags bit 0 identity transform,
-                             // bit 1 padded world-space box of a general-transform object, bit 2 the box may clear the object's bit in a ray's object mask
-                             // (identity object: its exact root box; general object: the padded world box)
+    const float4* objBox;    // 2 x float4 per object: {lo.xyz, RT_OBJ_* flags} {hi.xyz, root triangle count}
     const float4* mats;
     const float4* spheres;
     const uint32_t* sphereMat;
@@ -127,7 +110,7 @@ struct DevScene {
     const float4* triUV;
     uint32_t texCount;
     // The other three map slots (declared semantics: include/rt_det_math.h). mats[3 m + 2].z / .w carry metalnessIndex / bumpIndex,
-    // objAlpha[object] the alpha map of the object's material and its sampler (slot | clamp << 8; 0xffffffff = none); mapFlags says
+    // objAlpha[object] the alpha map of the object's material and its sampler (RT_OBJALPHA_*, scene_layout.h); mapFlags says
     // which kinds the scene binds at all (RT_MAP_*): the kernels that read them are separate ones (k_shade_maps, k_trace_pw_alpha, k_render_fused_maps)
     const uint32_t* objAlpha;
     uint32_t mapFlags;
@@ -502,9 +485,9 @@ __device__ __forceinline__ uint32_t map_red8(const DevScene& sc, uint32_t slot, 
 // alpha map: is this triangle hit cut out? (trace_wave<ALPHA>, leaf step; objAlpha: DevScene)
 __device__ __forceinline__ bool alpha_cut(const DevScene& sc, uint32_t obj, uint32_t tri, const TriHit& h) {
     const uint32_t oa = rt_global(sc.objAlpha)[obj];
-    if ((oa & 0xffu) >= sc.texCount) return false;   // (0xffffffff: no map)
+    if ((oa & RT_OBJALPHA_SLOT_MASK) >= sc.texCount) return false;   // (RT_OBJALPHA_NONE: no map)
     const HitUV q = hit_uv(sc, tri, h.u, h.v, h.w);
-    return map_red8(sc, oa & 0xffu, (oa & 0x100u) != 0u, q.u, q.v, false, false) < RT_ALPHA_CUT_BYTE;
+    return map_red8(sc, oa & RT_OBJALPHA_SLOT_MASK, (oa & RT_OBJALPHA_CLAMP) != 0u, q.u, q.v, false, false) < RT_ALPHA_CUT_BYTE;
 }
 
 // DevScene::emitPre from the listed triangles' positions: tri_intersect's first lines (raytrace.comp:228-231), same operations
@@ -521,8 +504,6 @@ __global__ void k_emit_precompute(const float4* __restrict__ triPos, const uint2
 }
 
 // ---------------------------------------------------------------- leaf references
-#define RT_LEAF_CNT_SHIFT 28
-#define RT_LEAF_IDX_MASK 0x0fffffffu
 __device__ __forceinline__ void leaf_from_ref(const DevScene& sc, uint32_t ref, uint32_t& first, uint32_t& cnt) {
     cnt = (ref >> RT_LEAF_CNT_SHIFT) & 7u;
     first = ref & RT_LEAF_IDX_MASK;
@@ -690,7 +671,6 @@ __global__ __launch_bounds__(RT_BLOCK) void k_trace(DevScene sc, PathState ps, T
 //     zero, negative-zero or non-finite; other rays take the general path).
 //     The next object's metadata is fetched one object ahead.
 #define RT_META_LDS 128u           // objects whose {root word, flags} a work-group keeps in LDS (1 KB)
-#define RT_HOT_PAIRS 192u          // child pairs of the meshes' top levels that come first in the device numbering; k_trace_pw<HOT> keeps the first HOT of them in LDS
 #define RT_CUR_IDLE 0xffffffffu   // no ray
 #define RT_CUR_NEED 0xfffffffeu   // wants its next node (tail)
 #define RT_CUR_SETUP 0xfffffffdu  // entering object `obj`, which has a general transform
@@ -963,7 +943,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                         fetch_next_meta();
                     }
                     // a new ray whose first object has a general transform goes into it in this very step
-                    bool general = cur == RT_CUR_SETUP || (cur == RT_CUR_INIT && sc.objectCount > 0u && !((nxFlags & 1u) && plain));
+                    bool general = cur == RT_CUR_SETUP || (cur == RT_CUR_INIT && sc.objectCount > 0u && !((nxFlags & RT_OBJ_IDENTITY) && plain));
                     if (CULL && general && plain && origin_within(wo, sc.cullOriginLimit)) {
                         // General-transform objects the ray cannot reach before its closest hit so far are not entered: in
                         // the reference such an object costs the two box tests on its root's children (its root leaf's triangle
@@ -990,7 +970,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                             }
                             const uint32_t i1 = min(obj + 1u, sc.objectCount - 1u);
                             const float4 a0 = sc.objBox[2 * obj], b0 = sc.objBox[2 * obj + 1], a1 = sc.objBox[2 * i1], b1 = sc.objBox[2 * i1 + 1];
-                            if ((__float_as_uint(a0.w) & 3u) != 2u) break;  // identity, or no usable box
+                            if ((__float_as_uint(a0.w) & (RT_OBJ_IDENTITY | RT_OBJ_BOX)) != RT_OBJ_BOX) break;  // identity, or no usable box
                             if (box_intersect(a0, b0, wo, iw) < best) break;
                             const uint32_t c0 = __float_as_uint(b0.w);
                             if (c0 == 0u) { if (PIX) rayBox += 2; else wt.totBox += 2; wt.totSkipBox += 2; }
@@ -998,7 +978,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                             obj++;
                             if (obj >= sc.objectCount) break;
                             if (RT_OBJTREE && sc.objTreeLevels && !(obj & 1u)) continue;  // an even index again: the blocks that start here come first
-                            if ((__float_as_uint(a1.w) & 3u) != 2u) break;
+                            if ((__float_as_uint(a1.w) & (RT_OBJ_IDENTITY | RT_OBJ_BOX)) != RT_OBJ_BOX) break;
                             if (box_intersect(a1, b1, wo, iw) < best) break;
                             const uint32_t c1 = __float_as_uint(b1.w);
                             if (c1 == 0u) { if (PIX) rayBox += 2; else wt.totBox += 2; wt.totSkipBox += 2; }
@@ -1006,7 +986,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                             obj++;
                         }
                         fetch_next_meta();
-                        general = obj < sc.objectCount && !(nxFlags & 1u);
+                        general = obj < sc.objectCount && !(nxFlags & RT_OBJ_IDENTITY);
                     }
                     if (general) {
                         const float4 r0 = sc.objInv[3 * obj], r1 = sc.objInv[3 * obj + 1], r2 = sc.objInv[3 * obj + 2];
@@ -1087,7 +1067,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                 top = stack[((has ? sp : 1u) - 1u) * RT_WAVE];
             }
             const bool objLeft = obj < sc.objectCount;
-            const bool ident = (nxFlags & 1u) && plain;  // identity transform: register moves only
+            const bool ident = (nxFlags & RT_OBJ_IDENTITY) && plain;  // identity transform: register moves only
             const uint32_t whenEmpty = objLeft ? (ident ? (atWorld ? nxW : RT_CUR_WORLD) : RT_CUR_SETUP) : RT_CUR_DONE;
             const bool enter = need && !has && objLeft && ident && atWorld;
             cur = need ? (has ? top : whenEmpty) : cur;
@@ -1207,7 +1187,7 @@ __device__ __forceinline__ rt_vec3 albedo_texel(const DevScene& sc, uint32_t slo
     const bool e01 = a.x == a.z && a.y == a.w, e12 = a.z == b.x && a.w == b.y, e20 = b.x == a.x && b.y == a.y;
     if (e01 || e12 || e20) { u = 0.5f; v = 0.5f; }
     const uint4 ti = rt_global(sc.texInfo)[slot];
-    const bool clampEdge = ((rt_global(sc.objMeta)[obj].w >> 16) & 0xffffu) == 1u;
+    const bool clampEdge = ((rt_global(sc.objMeta)[obj].w >> RT_OBJ_SAMPLER_SHIFT) & RT_OBJ_SAMPLER_MASK) == 1u;
     const uint32_t x = rt_tex_index(u, ti.y, clampEdge), y = rt_tex_index(1.f - v, ti.z, clampEdge);
     const uint32_t t = rt_global(sc.texels)[(size_t)ti.x + (size_t)y * ti.y + x];
     return rt_v3(rt_srgb8_to_linear(t & 0xffu), rt_srgb8_to_linear((t >> 8) & 0xffu), rt_srgb8_to_linear((t >> 16) & 0xffu));
@@ -1234,7 +1214,7 @@ __device__ __forceinline__ FullHit reconstruct_hit(const DevScene& sc, rt_vec3 r
     // the ray (ray_is_plain, trace_wave) and that is tested here on the interpolated normal and the object-space hit point as
     // well. Then neither matrix is fetched nor applied (Sponza: all 25 material groups; raytrace.comp:316-321).
     const uint4 meta = rt_global(sc.objMeta)[obj];
-    const bool ident = RT_SHADE_IDENT && (meta.w & 8u) && ray_is_plain(ro, rd);
+    const bool ident = RT_SHADE_IDENT && (meta.w & RT_OBJ_FWD_IDENTITY) && ray_is_plain(ro, rd);
     rt_vec3 trd = rd, tro = ro;
     if (!ident) {
         const float4* inv = rt_global(sc.objInv) + 3 * obj;
@@ -1253,7 +1233,7 @@ __device__ __forceinline__ FullHit reconstruct_hit(const DevScene& sc, rt_vec3 r
         f.u = q.u; f.v = q.v;
         const uint32_t bumpSlot = __float_as_uint(rt_global(sc.mats)[3 * meta.z + 2].w);   // bumpIndex; 0xffffffff (-1) = none
         if (bumpSlot < sc.texCount) {
-            const bool clampEdge = ((meta.w >> 16) & 0xffffu) == 1u;
+            const bool clampEdge = ((meta.w >> RT_OBJ_SAMPLER_SHIFT) & RT_OBJ_SAMPLER_MASK) == 1u;
             const float h0 = rt_srgb8_to_linear(map_red8(sc, bumpSlot, clampEdge, q.u, q.v, false, false));
             const float hx = rt_srgb8_to_linear(map_red8(sc, bumpSlot, clampEdge, q.u, q.v, true, false)) - h0;
             const float hy = rt_srgb8_to_linear(map_red8(sc, bumpSlot, clampEdge, q.u, q.v, false, true)) - h0;
@@ -1492,7 +1472,7 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
         if (MAPS) {  // metalness map: the texel's decoded red replaces the material's reflectance (triangle hits)
             const uint32_t metalSlot = __float_as_uint(mI.z);   // metalnessIndex; 0xffffffff (-1) = none
             if (metalSlot < sc.texCount && !(obj & RT_HIT_SPHERE))
-                mA.w = rt_srgb8_to_linear(map_red8(sc, metalSlot, ((rt_global(sc.objMeta)[obj].w >> 16) & 0xffffu) == 1u, hit.u, hit.v, false, false));
+                mA.w = rt_srgb8_to_linear(map_red8(sc, metalSlot, ((rt_global(sc.objMeta)[obj].w >> RT_OBJ_SAMPLER_SHIFT) & RT_OBJ_SAMPLER_MASK) == 1u, hit.u, hit.v, false, false));
         }
 
         // 0-1 NEE (:501-505)

@@ -4,4 +4,5 @@
 cd "$(dirname "$0")/.." || exit 1
 name=$1; shift
 flags=$(python3 -c "import __graft_entry__ as g; print(' '.join(g.HIPFLAGS))")
-exec /opt/rocm/bin/hipcc $flags "$@" ray_tracer_amd/csrc/scene.cpp ray_tracer_amd/csrc/rt_device.hip -o ray_tracer_amd/librt_amd_$name.so
+sources=$(python3 -c "import __graft_entry__ as g; print(' '.join(g.SOURCES))")
+exec /opt/rocm/bin/hipcc $flags "$@" $sources -o ray_tracer_amd/librt_amd_$name.so

@@ -10,10 +10,11 @@
 # execution 59 618 of the device compile of rt_device.hip is "si-opt-vgpr-liverange on k_render_fused<24, true, false, false>".
 cd "$(dirname "$0")/.." || exit 1
 flags=$(python3 -c "import __graft_entry__ as g; print(' '.join(g.HIPFLAGS))")
+sources=$(python3 -c "import __graft_entry__ as g; print(' '.join(g.SOURCES))")
 case "$1" in
   build)
-    /opt/rocm/bin/hipcc ${flags/-mllvm -amdgpu-opt-vgpr-liverange=0/} ray_tracer_amd/csrc/scene.cpp ray_tracer_amd/csrc/rt_device.hip -o ray_tracer_amd/librt_amd_lr_on.so &
-    /opt/rocm/bin/hipcc $flags ray_tracer_amd/csrc/scene.cpp ray_tracer_amd/csrc/rt_device.hip -o ray_tracer_amd/librt_amd_lr_off.so &
+    /opt/rocm/bin/hipcc ${flags/-mllvm -amdgpu-opt-vgpr-liverange=0/} $sources -o ray_tracer_amd/librt_amd_lr_on.so &
+    /opt/rocm/bin/hipcc $flags $sources -o ray_tracer_amd/librt_amd_lr_off.so &
     wait ;;
   run)
     for v in lr_on lr_off; do

@@ -12,7 +12,6 @@
 cd "$(dirname "$0")/.." || exit 1
 ROOT=$PWD
 F="-O3 -std=c++17 -fPIC -shared --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -Iinclude -Iray_tracer_amd/csrc"
-S="ray_tracer_amd/csrc/scene.cpp ray_tracer_amd/csrc/rt_device.hip"
 K=ray_tracer_amd/csrc/rt_kernels.hip.h
 case "$1" in
   build)
@@ -24,6 +23,7 @@ case "$1" in
         r2_ldstable) sed -i -e 's/if (!CULL \&\& obj < RT_META_LDS)/if (obj < RT_META_LDS)/' -e '/^    if (CULL) return;$/d' -e 's/s_meta\[CULL ? 1 : RT_META_LDS\]/s_meta[RT_META_LDS]/' "$d/$K" ;;
       esac
       ( cd "$d" || exit 1
+        S=$(python3 -c "import __graft_entry__ as g; print(' '.join(g.SOURCES))")   # the sources of that tree
         /opt/rocm/bin/hipcc $F $S -o ray_tracer_amd/librt_amd_A.so &
         /opt/rocm/bin/hipcc $F -mllvm -amdgpu-opt-exec-mask-pre-ra=0 $S -o ray_tracer_amd/librt_amd_B.so &
         /opt/rocm/bin/hipcc $F -mllvm -amdgpu-opt-vgpr-liverange=0 $S -o ray_tracer_amd/librt_amd_C.so &
