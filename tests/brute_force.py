@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE — the closest-hit query in float64, by brute force.
+"""TEST INFRASTRUCTURE — the closest-hit query in float64, by brute force; with the texture maps on request (TEXTURE MAPS below).
 
 Every triangle of every object and every sphere is tested against every ray in float64 and the nearest accepted hit is kept:
 no BVH, no stack, no box test, no float32, no code shared with oracle/ or the kernels (numpy only; `bvhNodes` is read for
@@ -55,6 +55,63 @@ normal.  Barycentric error, same count: |du|, |dv| <= B = g [ c u ((|r| + t |d'|
 scaled sums); through the forward matrix and the normalisation: (|M3| |d ni| + 3u | |M3| |ni| |) / |M3 ni| + 5u. It scales with
 the triangle: thin smooth-shaded triangles get a wide bound, flat ones a few ulp.
 
+TEXTURE MAPS (closest_hit(..., maps=True); set_textures, set_material, Mesh's uvs, the objects' samplerIndex). The semantics are the
+project's own declaration (include/rt_amd.h: the reference's shader samples nothing), restated here from that prose:
+
+  uv         hit.uv = w uv0 + u uv1 + v uv2 with u towards corner 1 and v towards corner 2; (0.5, 0.5) when any two corners share
+             their uv exactly.
+  texel      column floor(u W), row floor((1 - v) H) (v runs upwards, rows downwards); sampler 0 wraps both by a floor modulus,
+             sampler 1 clamps them to the edge; the next texel along an axis wraps to 0 or stays on the last one, by sampler.
+             A slot below 0 or beyond the texture table binds nothing. Spheres are not textured.
+  decode     the sRGB transfer function of a byte, in float64.
+  alpha      inside the search: a triangle candidate (accepted by the triangle test) whose alpha texel's red byte is < 188 is no
+             hit, and the nearest candidate that is left wins: a later triangle, a later object, a sphere, or nothing.
+  albedo     the material's albedo times the decoded rgb of the albedo texel (triangle hits of a material that binds one).
+  mirror     the metalness texel's red byte != 0 (the decode is 0 at byte 0 alone); without a map, reflectance != 0.
+  bump       heights are decoded red bytes; hx, hy = the steps from the hit's texel to the next texel of its row and of its column;
+             n' = normalize(n_interp) - (hx T^ - hy B^) in object space and BEFORE the front-face sign, T = dP/du and B = dP/dv of
+             the triangle (e1 = du1 T + dv1 B, e2 = du2 T + dv2 B), T^, B^ their unit vectors; then the sign, the forward matrix
+             and normalize as for `normal`. Unchanged where hx = hy = 0 or the uv determinant du1 dv2 - du2 dv1 is 0.
+
+Conditioning, on top of (a)-(d): a ray is ill-conditioned if
+  (e) a triangle candidate that takes part in the decision (the winner; with an alpha map every candidate up to the winner, on a
+      miss every one) has u W or (1 - v) H of a map in play within max(eps, B * (|uv1 - uv0| + |uv2 - uv0|) * size) of an integer,
+      B the barycentric bound below: float32 may land on the texel next door. The fallback's (0.5, 0.5) is the same number on
+      both sides and never in doubt.
+  (f) the winner binds a bump map and its uv determinant is nonzero but below eps (|du1 dv2| + |du2 dv1|): its sign, and with it
+      the tangent frame's, hangs on a rounding. A determinant of exactly 0 is exactly 0 in float32 too (equal corner uvs give
+      equal products): well-conditioned.
+  (d) covers the bumped normal's bound too.
+
+Bumped normal, the bound (first order, every float32 operation one relative error <= u, absolute errors in object space):
+  normalize(n_interp)      |d ni| / |ni| (the bound on the interpolated normal above) + 5u for the normalisation
+  hx, hy                   two decodes at 8 ulp = 16u each (tests/test_glsl_builtins.py, + 1e-9) and the difference:
+                           |dhx| <= 16u (h0 + h1) + 2e-9 + u |hx|
+  T^                       normalisation leaves of T = (e1 dv2 - e2 dv1) / det only the direction of the bracket and det's sign:
+                           e1, dv2 and their product 3u, the difference u: 4u (|e1||dv2| + |e2||dv1|) / |e1 dv2 - e2 dv1| = 4u kT;
+                           the scaling by 1 / det u, the normalisation 5u: |dT^| <= (4 kT + 6) u; likewise B^ with kB
+  hx T^, hy B^             |dhx| + |hx| (4 kT + 6) u + u |hx| each; their difference u (|hx| + |hy|); the final difference u |n'|
+  |dn'| <= |d ni| / |ni| + 5u + |dhx| + |dhy| + u |hx| (4 kT + 7) + u |hy| (4 kB + 7) + u (|hx| + |hy|) + u |n'|
+and through the forward matrix and the last normalisation, as for `normal` but with the denominator's own error kept:
+(|M3| |dn'| + 3u | |M3| |n'| |) / (|M3 n'| - |M3| |dn'|) + 5u, infinite where the denominator is not positive (n' near 0: the
+height step cancels the normal; rule (d)).
+
+OBSERVED with maps, on the CPU oracle (tests/test_texture_maps_float64.py prints these; the GPU cases print their own). "map hits" are
+well-conditioned rays that end on a triangle with a bound map; the last column is the largest |dn| / bound over the bumped normals.
+
+    ray set              rays   map hits   excluded   largest |dt| / bound(c = 1)   bumped |dn| / bound
+    albedo_bump/aimed    3000   2818       0.70 %     1.16                          0.040
+    albedo_bump/camera   6144   1708       0.16 %     1.23                          0.011
+    alpha/aimed          3000   2257       1.60 %     1.24                          -
+    alpha/camera         6144   1294       0.24 %     0.97                          -
+    all/aimed            3000   2251       1.80 %     1.24                          0.027
+    all/camera           6144   1294       0.24 %     0.97                          0.011
+
+The bumped normal's ratio is far below 1 because the count charges both decodes their full 16u while the heights' errors largely
+cancel in the step, and B is a worst case over the triangle; a wrong sign, frame or texel moves the normal by the size of the
+step itself, 10^4 bounds and more. The furnace render of the same test file (its tolerance is derived in its docstring, 26u + 1e-9): the
+oracle's worst pixel is 6.7u off. Only the oracle's figures are recorded here; the GPU cases print theirs when they run.
+
 OBSERVED on the CPU oracle.  Largest |dt| / bound(c = 1) on well-conditioned triangle hits, per ray set of
 tests/test_closest_hit_float64.py (which prints these figures, for the GPU cases too, and asserts c >= twice the oracle's ratio).
 "excluded" is the ill-conditioned share at eps = 1e-4, the rays dropped for starting on the surface they hit included.
@@ -79,6 +136,8 @@ import numpy as np
 U32 = 2.0 ** -24      # unit roundoff of float32
 DST_C = 11.0          # the rounding count derived above
 EPS = 1e-4            # conditioning margin
+ALPHA_CUT_BYTE = 188  # srgb8_to_linear(187) = 0.4969, (188) = 0.5029: "decodes below 0.5", as a test on the byte
+DECODE_ULP = 8        # tests/test_glsl_builtins.py holds the float32 decode to 8 ulp (+ 1e-9) of srgb8_to_linear
 
 
 # ---------------------------------------------------------------- camera rays (moved here from tests/test_aovs.py)
@@ -137,10 +196,37 @@ def _transform_error_unit(M, Minv):
     return inverse_error_unit(M) + np.abs(Minv)
 
 
+def srgb8_to_linear(byte):
+    """The sRGB transfer function (IEC 61966-2-1) of a byte, in float64."""
+    c = np.asarray(byte, np.float64) / 255.0
+    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
+
+
+def texel_index(coord, size, clamp):
+    """Nearest filter along one axis: floor(coord * size), clamped to the edge (sampler 1) or wrapped by a floor modulus
+    (sampler 0). Also returns coord * size, for the conditioning verdict."""
+    f = np.asarray(coord, np.float64) * size
+    i = np.floor(f).astype(np.int64)
+    return (np.clip(i, 0, size - 1) if clamp else np.mod(i, size)), f
+
+
+def texel_next(i, size, clamp):
+    """The next texel along an axis: stays on the last one under the clamp sampler, wraps to 0 under the other."""
+    return np.where(i + 1 < size, i + 1, i if clamp else 0)
+
+
+MAP_SLOTS = ("albedo", "alpha", "metalness", "bump")
+
+
 class Mesh:
-    def __init__(self, positions, normals, front_only):
+    def __init__(self, positions, normals, front_only, uvs=None):
         self.P = np.asarray(positions, np.float64).reshape(-1, 3, 3)
         self.N = np.asarray(normals, np.float64).reshape(-1, 3, 3)
+        # per-corner uv as float32 holds them; none given: all (0, 0), which is the fallback everywhere
+        self.UV = (np.zeros((len(self.P), 3, 2)) if uvs is None
+                   else np.asarray(uvs, np.float32).astype(np.float64).reshape(-1, 3, 2))
+        a, b, c = self.UV[:, 0], self.UV[:, 1], self.UV[:, 2]
+        self.fallback = (a == b).all(axis=1) | (b == c).all(axis=1) | (c == a).all(axis=1)
         fo = np.asarray(front_only, bool)
         self.front_only = np.broadcast_to(fo, (len(self.P),)).copy()
         v0 = self.P[:, 0]
@@ -149,6 +235,37 @@ class Mesh:
         self.c0 = np.einsum("ij,ij->i", v0, self.n)
         self.e1xv0, self.e2xv0 = np.cross(self.e1, v0), np.cross(self.e2, v0)
         self.nlen = np.linalg.norm(self.n, axis=1)
+        self.e1l, self.e2l = np.linalg.norm(self.e1, axis=1), np.linalg.norm(self.e2, axis=1)
+
+    def uv_at(self, k, u, v):
+        """hit.uv = w uv0 + u uv1 + v uv2 of the triangles k, (0.5, 0.5) where two corners share their uv; and per axis the
+        corners' uv spread |uv1 - uv0| + |uv2 - uv0| (what a barycentric error is multiplied by)."""
+        UV = self.UV[k]
+        uv = (1.0 - u - v)[:, None] * UV[:, 0] + u[:, None] * UV[:, 1] + v[:, None] * UV[:, 2]
+        uv[self.fallback[k]] = 0.5
+        return uv, np.abs(UV[:, 1] - UV[:, 0]) + np.abs(UV[:, 2] - UV[:, 0])
+
+
+def _bary_bound(e1l, e2l, nlen, rl, t, dlen, d0, do, ddv):
+    """B of the module docstring (the bound on |du|, |dv|), with g, sin(gamma) and cos(theta)."""
+    cos = np.abs(d0) / (dlen * nlen)
+    sin = nlen / (e1l * e2l)
+    den = 1.0 - DST_C * U32 * (1.0 / (sin * cos) + ddv / (dlen * cos))
+    g = np.where(den > 0, 1.0 / den, np.inf)
+    emin = np.minimum(e1l, e2l)
+    B = g * (DST_C * U32 * ((rl + t * dlen) / emin + 1.0) + DST_C * U32 * ((do + rl * ddv / dlen) / emin + ddv / dlen)) / (sin * cos)
+    return B, g, sin, cos
+
+
+def _lookup(tex, uv, spread, B, fallback, clamp, eps):
+    """Texel column and row of a map at uv, and whether float32 may land on another texel: u W or (1 - v) H within
+    max(eps, B * spread * size) of an integer. The fallback's (0.5, 0.5) is exact on both sides: never in doubt."""
+    h, w = tex.shape[:2]
+    x, fx = texel_index(uv[:, 0], w, clamp)
+    y, fy = texel_index(1.0 - uv[:, 1], h, clamp)
+    mx, my = np.maximum(eps, B * spread[:, 0] * w), np.maximum(eps, B * spread[:, 1] * h)
+    near = ~fallback & ~((np.abs(fx - np.rint(fx)) >= mx) & (np.abs(fy - np.rint(fy)) >= my))
+    return x, y, near
 
 
 class BruteScene:
@@ -156,21 +273,37 @@ class BruteScene:
 
     def __init__(self):
         self.sph_c = np.zeros((0, 3)); self.sph_r = np.zeros(0); self.sph_mat = np.zeros(0, np.int64)
-        self.meshes, self.objects = [], []          # objects: [mesh index, M, material]
+        self.meshes, self.objects = [], []          # objects: [mesh index, M, material, samplerIndex]
+        self.materials = {}                         # material index -> dict(albedo, reflectance, <slot>Index ...); absent: no maps
+        self.textures = []                          # uint8 [h, w, 4], in slot order
+
+    def set_textures(self, images):
+        self.textures = [np.asarray(im, np.uint8) for im in images]
+
+    def set_material(self, index, albedo=(1.0, 1.0, 1.0), reflectance=0.0, albedoIndex=-1, alphaIndex=-1, metalnessIndex=-1, bumpIndex=-1):
+        self.materials[int(index)] = dict(albedo=np.asarray(albedo, np.float32).astype(np.float64), reflectance=float(reflectance),
+                                          albedoIndex=int(albedoIndex), alphaIndex=int(alphaIndex),
+                                          metalnessIndex=int(metalnessIndex), bumpIndex=int(bumpIndex))
+
+    def bound_map(self, material, slot):
+        """The texture a material's slot binds; a slot below 0 or beyond the table binds nothing."""
+        m = self.materials.get(int(material))
+        i = -1 if m is None else m[slot + "Index"]
+        return self.textures[i] if 0 <= i < len(self.textures) else None
 
     def set_spheres(self, centres, radii, materials):
         self.sph_c = np.asarray(centres, np.float64).reshape(-1, 3)
         self.sph_r = np.asarray(radii, np.float64).reshape(-1)
         self.sph_mat = np.asarray(materials, np.int64).reshape(-1)
 
-    def add_object(self, positions, normals, matrix, front_only=False, material=0):
-        self.meshes.append(Mesh(positions, normals, front_only))
-        self.objects.append([len(self.meshes) - 1, np.asarray(matrix, np.float64).reshape(4, 4), int(material)])
+    def add_object(self, positions, normals, matrix, front_only=False, material=0, uvs=None, sampler=0):
+        self.meshes.append(Mesh(positions, normals, front_only, uvs))
+        self.objects.append([len(self.meshes) - 1, np.asarray(matrix, np.float64).reshape(4, 4), int(material), int(sampler)])
         return len(self.objects) - 1
 
-    def replace_mesh(self, obj, positions, normals, front_only):
+    def replace_mesh(self, obj, positions, normals, front_only, uvs=None):
         """The test's own arrays instead of what from_numpy read for this object (and for every object sharing its mesh)."""
-        self.meshes[self.objects[obj][0]] = Mesh(positions, normals, front_only)
+        self.meshes[self.objects[obj][0]] = Mesh(positions, normals, front_only, uvs)
 
     @classmethod
     def from_numpy(cls, arrays):
@@ -198,15 +331,22 @@ class BruteScene:
                         stack += [int(index), int(index) + 1]
                 t = tr[np.array(sorted(tris), np.int64)]
                 corners = tp[t[:, 0:3].astype(np.int64)]                  # [T, 3, 8]
-                s.meshes.append(Mesh(corners[:, :, 0:3], corners[:, :, 4:7], t[:, 3] != 0))
+                s.meshes.append(Mesh(corners[:, :, 0:3], corners[:, :, 4:7], t[:, 3] != 0, corners[:, :, [3, 7]]))   # uv = (position.w, normal.w)
                 by_root[root] = len(s.meshes) - 1
             M = of[i, 0:16].astype(np.float64).reshape(4, 4).T            # column-major m[c * 4 + r]
-            s.objects.append([by_root[root], M, int(ou[i, 18])])
+            s.objects.append([by_root[root], M, int(ou[i, 18]), int(ou[i, 19])])
+        mt = arrays.get("materials", ())
+        if len(mt):
+            mf, mi = mt.view(np.float32).reshape(len(mt), -1), mt.view(np.int32).reshape(len(mt), -1)
+            for i in range(len(mt)):
+                s.set_material(i, mf[i, 0:3], mf[i, 8], albedoIndex=mi[i, 10], metalnessIndex=mi[i, 11], alphaIndex=mi[i, 12], bumpIndex=mi[i, 13])
         return s
 
     # ------------------------------------------------------------------------------------------------------------
-    def closest_hit(self, origins, dirs, eps=EPS, max_pairs=3_000_000):
-        """The nearest accepted hit of every ray, its conditioning verdict and its error bounds: a dict of arrays."""
+    def closest_hit(self, origins, dirs, eps=EPS, max_pairs=3_000_000, maps=False):
+        """The nearest accepted hit of every ray, its conditioning verdict and its error bounds: a dict of arrays. With `maps`
+        the texture maps take part (module docstring, TEXTURE MAPS): the alpha cut inside the search, and uv, texels, albedo,
+        mirror and the bumped normal of the hit."""
         o = np.asarray(origins, np.float32).astype(np.float64).reshape(-1, 3)
         d = np.asarray(dirs, np.float32).astype(np.float64).reshape(-1, 3)
         n = len(o)
@@ -216,6 +356,8 @@ class BruteScene:
         bobj = np.zeros(n, np.int64); btri = np.zeros(n, np.int64)
         ill = np.zeros(n, bool)
         sfront = np.zeros(n, bool)
+        near_t = np.full(n, INF)                    # nearest candidate whose alpha texel hangs on a rounding
+        cut_t = np.full(n, INF)                     # nearest candidate the alpha map cut out
 
         def merge(rows, t1, t2, k, obj, tri):
             """t1 <= t2: the two nearest accepted t of one primitive set, for the rays `rows`."""
@@ -248,8 +390,9 @@ class BruteScene:
                 sfront[rows_all[win]] = front[win]
             # ---- triangles
             xf = []
-            for j, (mi, M, _mat) in enumerate(self.objects):
+            for j, (mi, M, mat, sampler) in enumerate(self.objects):
                 mesh = self.meshes[mi]
+                alpha = self.bound_map(mat, "alpha") if maps else None
                 Minv = np.linalg.inv(M)
                 op = o @ Minv[:3, :3].T + Minv[:3, 3]
                 dp = d @ Minv[:3, :3].T
@@ -258,6 +401,10 @@ class BruteScene:
                 if T == 0:
                     continue
                 dlen = np.linalg.norm(dp, axis=1)
+                if alpha is not None:
+                    Wj = _transform_error_unit(M, Minv)
+                    do_all = np.linalg.norm(np.concatenate([np.abs(o), np.ones((n, 1))], axis=1) @ Wj[:3, :].T, axis=1)
+                    ddv_all = np.linalg.norm(np.abs(d) @ Wj[:3, :3].T, axis=1)
                 step = max(1, max_pairs // T)
                 for r0 in range(0, n, step):
                     rows = rows_all[r0:r0 + step]
@@ -271,6 +418,19 @@ class BruteScene:
                     back = ~(d0 >= 1e-8)
                     fo = mesh.front_only[None, :]
                     acc = (t >= 0) & (m >= 0) & ~(fo & back)
+                    if alpha is not None:
+                        # the alpha cut: a candidate whose alpha texel's red byte is below 188 is no hit; the search goes on
+                        ri, ti = np.nonzero(acc)
+                        rr = rows[ri]
+                        tc, uc, vc = t[ri, ti], uu[ri, ti], vv[ri, ti]
+                        rl = np.linalg.norm(oo[ri] - mesh.P[ti, 0], axis=1)
+                        Bc = _bary_bound(mesh.e1l[ti], mesh.e2l[ti], mesh.nlen[ti], rl, tc, dlen[rr], d0[ri, ti], do_all[rr], ddv_all[rr])[0]
+                        uvc, spread = mesh.uv_at(ti, uc, vc)
+                        x, y, near = _lookup(alpha, uvc, spread, Bc, mesh.fallback[ti], sampler == 1, eps)
+                        cut = alpha[y, x, 0] < ALPHA_CUT_BYTE
+                        np.minimum.at(near_t, rr[near], tc[near])
+                        np.minimum.at(cut_t, rr[cut], tc[cut])
+                        acc[ri[cut], ti[cut]] = False
                     cand = (m > -eps) & (t > -eps)
                     bad = cand & ((np.abs(m) < eps) | (np.abs(t) < eps) |
                                   (fo & (np.abs(d0 - 1e-8) < eps * dlen[rows, None] * mesh.nlen[None, :])))
@@ -284,13 +444,28 @@ class BruteScene:
 
             hit = kind >= 0
             ill |= hit & ((second - best) < eps * best)
+            # a candidate that takes part in the decision (the winner, or one cut out in front of it; on a miss every one) and
+            # whose alpha texel a float32 uv may place next door
+            ill |= np.isfinite(near_t) & (near_t <= best)
             res = dict(didHit=hit, isSphere=kind == 0, objectHitIndex=np.where(hit, bobj, 0), triIndex=btri, dst=best,
                        frontFace=np.zeros(n, bool), materialIndex=np.zeros(n, np.int64), hitPoint=np.zeros((n, 3)),
                        normal=np.zeros((n, 3)), corners=np.zeros((n, 3, 3)), ill=ill,
                        dst_bound=np.zeros(n), dst_bound_c1=np.zeros(n), point_bound=np.zeros(n), normal_bound=np.zeros(n))
             res["hitPoint"][hit] = o[hit] + best[hit, None] * d[hit]
+            if maps:
+                res.update(uv=np.zeros((n, 2)), fallback=np.zeros(n, bool), cutNearer=np.isfinite(cut_t) & (cut_t < best), samplerIndex=np.zeros(n, np.int64),
+                           albedo=np.ones((n, 3)), mirror=np.zeros(n, bool), hx=np.zeros(n), hy=np.zeros(n), bumped=np.zeros(n, bool),
+                           texel={k: np.full((n, 2), -1, np.int64) for k in MAP_SLOTS})
             self._finish_spheres(res, o, d, a, sfront)
-            self._finish_triangles(res, o, d, xf, eps)
+            self._finish_triangles(res, o, d, xf, eps, maps)
+            if maps:
+                for mi_ in np.unique(res["materialIndex"][hit]):
+                    mt = self.materials.get(int(mi_))
+                    if mt is not None:
+                        rows = np.flatnonzero(hit & (res["materialIndex"] == mi_))
+                        res["albedo"][rows] *= mt["albedo"]
+                        unmapped = res["isSphere"][rows] | (self.bound_map(mi_, "metalness") is None)
+                        res["mirror"][rows] = np.where(unmapped, mt["reflectance"] != 0.0, res["mirror"][rows])
             # where the first-order count gives no bound (g, or the sphere's root of disc) the ray cannot be held to anything:
             # ill-conditioned, and counted as such, instead of passing under an infinite bound
             for k in ("dst_bound", "point_bound", "normal_bound"):
@@ -318,11 +493,11 @@ class BruteScene:
         # normalize(p - c): the point's error and the difference's rounding over the radius, the normalisation's 5u
         res["normal_bound"][rows] = (pb + U32 * np.linalg.norm(p - c, axis=1)) / np.linalg.norm(p - c, axis=1) + 5 * U32
 
-    def _finish_triangles(self, res, o, d, xf, eps):
+    def _finish_triangles(self, res, o, d, xf, eps, maps=False):
         tri_rows = np.flatnonzero(res["didHit"] & ~res["isSphere"])
         for j in np.unique(res["objectHitIndex"][tri_rows]):
             rows = tri_rows[res["objectHitIndex"][tri_rows] == j]
-            mi, M, mat = self.objects[j]
+            mi, M, mat, sampler = self.objects[j]
             mesh = self.meshes[mi]
             Minv, op, dp = xf[j]
             k = res["triIndex"][rows]
@@ -353,12 +528,9 @@ class BruteScene:
             ddv = np.linalg.norm(np.abs(d[rows]) @ W[:3, :3].T, axis=1)
             rl = np.linalg.norm(r, axis=1)
             e1l, e2l = np.linalg.norm(e1, axis=1), np.linalg.norm(e2, axis=1)
-            cos = np.abs(d0) / (dlen * nlen)
-            sin = nlen / (e1l * e2l)
+            B, g, sin, cos = _bary_bound(e1l, e2l, nlen, rl, t, dlen, d0, do, ddv)
             G = (rl / dlen + t) / (cos * sin)
             T = (do + t * ddv) / (dlen * cos)
-            den = 1.0 - DST_C * U32 * (1.0 / (sin * cos) + ddv / (dlen * cos))
-            g = np.where(den > 0, 1.0 / den, np.inf)
             c1 = U32 * (G + T) * g
             res["dst_bound_c1"][rows] = c1
             res["dst_bound"][rows] = DST_C * c1
@@ -368,11 +540,64 @@ class BruteScene:
             p1 = np.concatenate([pobj, np.ones((len(rows), 1))], axis=1)
             res["point_bound"][rows] = DST_C * c1 * wl + DST_C * U32 * (
                 m2 * (do + t * ddv) + m2 * (np.linalg.norm(oo, axis=1) + t * dlen) + np.linalg.norm(p1 @ np.abs(M[:3, :]).T, axis=1))
-            emin = np.minimum(e1l, e2l)
-            B = g * (DST_C * U32 * ((rl + t * dlen) / emin + 1.0) + DST_C * U32 * ((do + rl * ddv / dlen) / emin + ddv / dlen)) / (sin * cos)
             dni = B * (np.linalg.norm(N1 - N0, axis=1) + np.linalg.norm(N2 - N0, axis=1)) + 8 * U32 * (
                 np.linalg.norm(N0, axis=1) + np.linalg.norm(N1, axis=1) + np.linalg.norm(N2, axis=1))
             res["normal_bound"][rows] = (m2 * dni + 3 * U32 * np.linalg.norm(np.abs(ni) @ np.abs(M3).T, axis=1)) / wnl + 5 * U32
+            if not maps:
+                continue
+            # ---- texture maps (module docstring, TEXTURE MAPS)
+            clamp = sampler == 1
+            fb = mesh.fallback[k]
+            uv, spread = mesh.uv_at(k, uu, vv)
+            res["uv"][rows], res["fallback"][rows], res["samplerIndex"][rows] = uv, fb, sampler
+            near = np.zeros(len(rows), bool)
+            for slot in MAP_SLOTS:
+                tex = self.bound_map(mat, slot)
+                if tex is None:
+                    continue
+                x, y, nr = _lookup(tex, uv, spread, B, fb, clamp, eps)
+                near |= nr
+                res["texel"][slot][rows] = np.stack([x, y], axis=1)
+                if slot == "albedo":
+                    res["albedo"][rows] = srgb8_to_linear(tex[y, x, :3])           # times the material's, in closest_hit
+                elif slot == "metalness":
+                    res["mirror"][rows] = tex[y, x, 0] != 0                       # the decode is 0 at byte 0 alone
+                elif slot == "bump":
+                    h, w = tex.shape[:2]
+                    h0 = srgb8_to_linear(tex[y, x, 0])
+                    hx1, hy1 = srgb8_to_linear(tex[y, texel_next(x, w, clamp), 0]), srgb8_to_linear(tex[texel_next(y, h, clamp), x, 0])
+                    hx, hy = hx1 - h0, hy1 - h0
+                    UV = mesh.UV[k]
+                    du1, dv1 = (UV[:, 1] - UV[:, 0]).T
+                    du2, dv2 = (UV[:, 2] - UV[:, 0]).T
+                    det = du1 * dv2 - du2 * dv1
+                    near |= (det != 0) & (np.abs(det) < eps * (np.abs(du1 * dv2) + np.abs(du2 * dv1)))
+                    on = (det != 0) & ((hx != 0) | (hy != 0))
+                    res["hx"][rows], res["hy"][rows], res["bumped"][rows] = hx, hy, on
+                    a = np.flatnonzero(on)
+                    if not len(a):
+                        continue
+                    Tv = e1[a] * dv2[a, None] - e2[a] * dv1[a, None]              # dP/du and dP/dv, times det: the sign is all
+                    Bv = e2[a] * du1[a, None] - e1[a] * du2[a, None]              # that the normalisation leaves of it
+                    sg = np.sign(det[a])[:, None]
+                    Tl, Bl = np.linalg.norm(Tv, axis=1), np.linalg.norm(Bv, axis=1)
+                    nil = np.linalg.norm(ni[a], axis=1)
+                    nb = ni[a] / nil[:, None] - (hx[a, None] * sg * Tv / Tl[:, None] - hy[a, None] * sg * Bv / Bl[:, None])
+                    wb = (nb * np.where(front[a], 1.0, -1.0)[:, None]) @ M3.T
+                    wbl = np.linalg.norm(wb, axis=1)
+                    res["normal"][rows[a]] = wb / wbl[:, None]
+                    # the bound (module docstring, "bumped normal")
+                    kT = (e1l[a] * np.abs(dv2[a]) + e2l[a] * np.abs(dv1[a])) / Tl
+                    kB = (e2l[a] * np.abs(du1[a]) + e1l[a] * np.abs(du2[a])) / Bl
+                    dec = 2 * DECODE_ULP * U32
+                    dhx = dec * (h0[a] + hx1[a]) + 2e-9 + U32 * np.abs(hx[a])
+                    dhy = dec * (h0[a] + hy1[a]) + 2e-9 + U32 * np.abs(hy[a])
+                    dnb = (dni[a] / nil + 5 * U32 + dhx + dhy + U32 * np.abs(hx[a]) * (4 * kT + 7) + U32 * np.abs(hy[a]) * (4 * kB + 7)
+                           + U32 * (np.abs(hx[a]) + np.abs(hy[a])) + U32 * np.linalg.norm(nb, axis=1))
+                    den = wbl - m2 * dnb
+                    res["normal_bound"][rows[a]] = np.where(
+                        den > 0, (m2 * dnb + 3 * U32 * np.linalg.norm(np.abs(nb) @ np.abs(M3).T, axis=1)) / den + 5 * U32, np.inf)
+            res["ill"][rows] |= near
 
 
 def sphere_dst_bound(o, d, c, r, front):

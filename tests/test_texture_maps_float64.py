@@ -1,0 +1,475 @@
+"""The four texture map slots (albedo, alpha, metalness, bump) against tests/brute_force.py: hit.uv, the texel addressing under both
+samplers, the alpha cut inside the closest-hit search and the bumped normal restated in numpy float64 from DESIGN.md 3a's prose,
+nothing shared with the oracle or the kernels. The CPU half holds oracle/raytrace_oracle.cpp to it, the GPU half rt_trace_rays
+(the ordinary kernels with reconstruct_hit<true>, k_trace_pw_alpha), rt_render_aovs and three rendering pipelines.
+
+Scene: a 12 x 12-quad sheet (vertices jittered out of plane, smooth perturbed normals, warped uvs over [-0.75, 1.9]^2) placed with a
+rotation about all three axes and a non-uniform scale, once under sampler 0 and once more under sampler 1; a second sheet of
+another material 0.12 behind the first and a sphere behind both, for what an alpha-cut hit lets through; a sheet baked in place
+under an exact identity matrix; sixteen triangles whose corners share uvs pairwise (all three pairings). Maps of 24 x 16, 7 x 5 and
+1 x 1 texels generated here: alpha bytes mostly from {0, 187, 188, 255}, random bump heights, metalness bytes 0 / 1 / other, noise in
+the channels that must not matter.
+
+Hit records (aimed rays and the camera rays of a 96 x 64 frame, under three map sets): on the well-conditioned rays (brute_force's
+verdict, which with maps also excludes rays whose texel hangs on a rounding) the discrete fields and the triangle are equal, dst,
+hitPoint and normal are within brute_force's bounds (the bumped normal's derived there), and |dt| / t < 1e-3 on all rays.
+
+Furnace render. A flat sheet y = 0 with the exact normal (0, -1, 0) under an identity matrix, albedo, alpha and metalness maps bound
+(no bump: a tilted mirror normal can reflect back into the sheet; and flat with exact normals, unlike the sheets above, because a
+cosine-sampled direction about a perturbed normal can re-enter a jittered sheet), alone under an environment with horizon = zenith =
+S, ground = G, sun strength 0, seen from the sky side (-y). Every path leaves on the sky side after at most one bounce, the NEE term
+is exactly 0 (no emitter), so in float64 every sample of a pixel is G (camera ray cut, or past the sheet), S (mirror texel) or
+albedo * texel * S (diffuse texel). The float32 pixel is held to that within FURNACE_C = 26 roundings (u = 2^-24), counted along the
+diffuse branch, the longest:
+    texel decode                          16   (8 ulp = 16 u, tests/test_glsl_builtins.py)
+    albedo * texel                         1
+    (albedo * 1/pi) * n.c / (n.c * 1/pi)   4   two products, the pdf's product, the division; the constant and n.c cancel as values
+    S = mix(S, S, t)                       3   1 - t, two products, one sum (t's own error cancels: both ends are S)
+    attenuation * S                        1
+    the sum of two samples                 1   (the division by 2 is exact; 1 / rrProb = 1 and attenuation = 1 * radiance are exact)
+which sum to 26; the decode's absolute term (1e-9 in tests/test_glsl_builtins.py, times albedo * S < 1) is allowed on top:
+|error| <= 26 u value + 1e-9. The oracle's worst (|error| - 1e-9) / (u * value) is printed and 26 is asserted to be at least twice it.
+The floors on the pixel kinds are asserted on the reference alone: at least 500 each of mirror, diffuse and cut pixels (a camera
+ray that the alpha map cut and that goes on to the ground; rays that pass beside the sheet see G too but do not count).
+"""
+import numpy as np
+import pytest
+
+from ray_tracer_amd import engine
+from oracle import pyoracle
+import brute_force as bf
+from util import EditedScene
+from test_closest_hit_float64 import MAX_EXCLUDED, MIN_MESH_HITS, ON_SURFACE, _aimed_rays, _check_placement, _compare, _corners_of
+
+MIN_CUT, MIN_FALLBACK, MIN_STEP = 100, 50, 100
+FURNACE_C = 26.0        # the sum of the table in the module docstring
+FURNACE_ABS = 1e-9      # the decode's absolute term
+W, H = 96, 64
+
+P_SHEET0 = dict(position=(-0.45, -0.2, 0.1), rotation=(80.0, 25.0, -20.0), scale=(0.7, 1.0, 0.5))
+P_SHEET1 = dict(position=(0.55, -0.95, -0.3), rotation=(-30.0, 15.0, 40.0), scale=(0.6, 0.8, 0.65))
+P_BAKED = dict(position=(0.4, 0.15, 0.45), rotation=(60.0, -20.0, 10.0), scale=(0.5, 0.7, 0.45))
+BEHIND = 0.12
+CAMERA = dict(pos=(0.1, -0.5, -2.8), cameraAngles=(3.0, -4.0, 0.0), fov=50.0)
+
+# Material A (the placed sheet under both samplers, the fallback triangles) binds the 7 x 5 maps, B (the sheet behind) and C (the
+# baked sheet) the 24 x 16 ones and the single texel: the texel margin of the conditioning verdict grows with the map's size and
+# with the transform's share of the barycentric error, and 24 x 16 on every placed sheet would exclude more than 2 % of the aimed rays.
+MAP_SETS = {   # slot -> texture, for materials A, B, C
+    "albedo_bump": (dict(albedoIndex=0, bumpIndex=6), dict(albedoIndex=5, bumpIndex=5), dict(albedoIndex=7, bumpIndex=3)),
+    "alpha": (dict(alphaIndex=4), dict(alphaIndex=1), dict(alphaIndex=1)),
+    "all": (dict(albedoIndex=0, alphaIndex=4, metalnessIndex=2, bumpIndex=6), dict(albedoIndex=5, alphaIndex=1, metalnessIndex=2, bumpIndex=3),
+            dict(albedoIndex=7, alphaIndex=1, metalnessIndex=8, bumpIndex=3)),
+}
+ALBEDO_A, ALBEDO_B, ALBEDO_C, ALBEDO_S = (0.8, 0.7, 0.6), (0.35, 0.75, 0.5), (0.6, 0.45, 0.9), (0.9, 0.9, 0.2)
+
+
+def _textures():
+    """Slot 0 albedo 7 x 5, 1 alpha 24 x 16, 2 metalness 7 x 5, 3 bump 24 x 16, 4 alpha 7 x 5, 5 one texel, 6 bump 7 x 5, 7 albedo
+    24 x 16, 8 metalness 24 x 16. Every map's data is its red channel (the albedo's its first three); the rest is noise."""
+    rng = np.random.default_rng(2024)
+
+    def noise(w, h):
+        return rng.integers(0, 256, (h, w, 4)).astype(np.uint8)
+
+    def alpha(w, h):
+        t = noise(w, h)
+        edge = rng.choice(np.array([0, 187, 188, 255]), size=(h, w), p=(0.2, 0.2, 0.3, 0.3))
+        t[..., 0] = np.where(rng.uniform(size=(h, w)) < 0.85, edge, rng.integers(0, 256, (h, w)))
+        t[h // 2, w // 2, 0] = 255       # the fallback's texel, (0.5, 0.5): opaque, or no ray would end on a fallback triangle
+        return t
+
+    def metal(w, h):
+        t = noise(w, h)
+        t[..., 0] = rng.choice(np.array([0, 0, 1, 2, 90, 255]), size=(h, w))
+        return t
+
+    one = noise(1, 1)
+    one[0, 0, 0] = 200
+    return [noise(7, 5), alpha(24, 16), metal(7, 5), noise(24, 16), alpha(7, 5), one, noise(7, 5), noise(24, 16), metal(24, 16)]
+
+
+def _sheet(rng, jitter=0.03, perturb=0.25, nq=12):
+    """[T, 3, 3] positions, normals and [T, 3, 2] uvs of an nq x nq-quad sheet over [-1, 1]^2 of the plane y = 0, front faces
+    towards -y. Inner uvs are warped so that dP/du and dP/dv differ from triangle to triangle."""
+    g = np.linspace(-1.0, 1.0, nq + 1)
+    x, z = np.meshgrid(g, g, indexing="ij")
+    y = rng.uniform(-jitter, jitter, x.shape) if jitter else np.zeros_like(x)
+    P = np.stack([x, y, z], -1)
+    N = np.zeros_like(P)
+    N[..., 1] = -1.0
+    if perturb:
+        N += rng.uniform(-perturb, perturb, N.shape)
+        N /= np.linalg.norm(N, axis=-1, keepdims=True)
+    uv = np.stack([-0.75 + 2.65 * (x + 1) / 2, -0.75 + 2.65 * (z + 1) / 2], -1)
+    uv[1:-1, 1:-1] += rng.uniform(-0.04, 0.04, uv[1:-1, 1:-1].shape)
+    idx = [((i, j), (i + 1, j), (i + 1, j + 1)) for i in range(nq) for j in range(nq)]
+    idx += [((i, j), (i + 1, j + 1), (i, j + 1)) for i in range(nq) for j in range(nq)]
+    ii = np.array(idx)                                                      # [T, 3, 2]
+    take = lambda a: a[ii[..., 0], ii[..., 1]]                              # noqa: E731
+    return take(P).astype(np.float32), take(N).astype(np.float32), take(uv).astype(np.float32)
+
+
+def _fallback_triangles(rng):
+    """Sixteen triangles with two corners sharing their uv exactly: corners (0, 1), (1, 2), (2, 0) in turn, and one with all three."""
+    c = np.array((-0.55, -1.15, -0.45)) + rng.uniform(-0.3, 0.3, (16, 1, 3))
+    P = c + rng.uniform(-0.16, 0.16, (16, 3, 3))
+    N = rng.normal(size=(16, 3, 3))
+    N /= np.linalg.norm(N, axis=-1, keepdims=True)
+    uv = rng.uniform(-0.75, 1.9, (16, 3, 2))
+    for t in range(16):
+        a = t % 3
+        uv[t, (a + 1) % 3] = uv[t, a]
+    uv[15] = uv[15, 0]
+    return P.astype(np.float32), N.astype(np.float32), uv.astype(np.float32)
+
+
+def _material(albedo, **slots):
+    m = engine.default_material(albedo=albedo)
+    for k, v in slots.items():
+        setattr(m, k, v)
+    return m
+
+
+def _scene(map_set):
+    """Objects 0 sheet (sampler 0), 1 the same mesh (sampler 1), 2 the sheet behind object 0, 3 the baked sheet (identity matrix,
+    sampler 1), 4 the fallback triangles; sphere 0 behind objects 0 and 2. Materials 0 = A, 1 = B, 2 = C, 3 = the sphere's."""
+    rng = np.random.default_rng(7)
+    slots_a, slots_b, slots_c = MAP_SETS[map_set]
+    s = engine.Scene()
+    s.add_material(_material(ALBEDO_A, **slots_a))
+    s.add_material(_material(ALBEDO_B, **slots_b))
+    s.add_material(_material(ALBEDO_C, **slots_c))
+    s.add_material(_material(ALBEDO_S, reflectance=1.0))
+    sheet, second, baked = _sheet(rng), _sheet(rng), _sheet(rng)
+    M0 = bf.placement_matrix(**P_SHEET0)
+    back = M0[:3, 1] / np.linalg.norm(M0[:3, 1])           # the sheet's +y, away from its front faces
+    p_second = dict(P_SHEET0, position=tuple(np.asarray(P_SHEET0["position"]) + BEHIND * back))
+    s.add_mesh("sheet", *sheet[:2], engine.placement(**P_SHEET0), 0, uvs=sheet[2])
+    s.add_mesh("sheet", *sheet[:2], engine.placement(**P_SHEET1), 0, uvs=sheet[2])
+    s.add_mesh("second", *second[:2], engine.placement(**p_second), 1, uvs=second[2])
+    Mb = bf.placement_matrix(**P_BAKED)
+    bp = (baked[0].astype(np.float64) @ Mb[:3, :3].T + Mb[:3, 3]).astype(np.float32)
+    bn = baked[1].astype(np.float64) @ Mb[:3, :3].T
+    bn = (bn / np.linalg.norm(bn, axis=-1, keepdims=True)).astype(np.float32)
+    s.add_mesh("baked", bp, bn, engine.placement(), 2, uvs=baked[2])
+    fb = _fallback_triangles(rng)
+    s.add_mesh("fallback", *fb[:2], engine.placement(), 0, uvs=fb[2])
+    s.set_sphere(0, tuple(np.asarray(P_SHEET0["position"]) + 0.5 * back), 0.3, 3)
+    bs = bf.BruteScene.from_numpy(s.numpy())
+    bs.replace_mesh(0, *sheet[:2], False, sheet[2])         # the test's own arrays, not what the scene builder stored
+    bs.replace_mesh(2, *second[:2], False, second[2])
+    bs.replace_mesh(3, bp, bn, False, baked[2])
+    bs.replace_mesh(4, *fb[:2], False, fb[2])
+    bs.set_material(0, ALBEDO_A, **slots_a)
+    bs.set_material(1, ALBEDO_B, **slots_b)
+    bs.set_material(2, ALBEDO_C, **slots_c)
+    bs.set_material(3, ALBEDO_S, reflectance=1.0)
+    # a mesh's only group keeps samplerIndex 0 whatever its placement says (as the reference's read_obj leaves it); the object
+    # editor's field selects the clamp sampler, as in tests/test_textures.py
+    ed = EditedScene(s)
+    for j in (1, 3):
+        ed.objects[j].samplerIndex = 1
+        bs.objects[j][3] = 1
+    _check_placement(s, 0, **P_SHEET0)
+    _check_placement(s, 1, **P_SHEET1)
+    _check_placement(s, 2, **p_second)
+    _check_placement(s, 3)
+    bs.set_textures(_textures())
+    return s, ed, bs
+
+
+_cases = {}
+
+
+def _case(map_set, rays):
+    """The scene, the rays and their float64 answers, once per session. Rays that start on the surface they hit are dropped and
+    counted as excluded, as tests/test_closest_hit_float64.py does."""
+    key = (map_set, rays)
+    if key not in _cases:
+        s, ed, bs = _scene(map_set)
+        if rays == "aimed":
+            o, d = _aimed_rays(bs, [0, 1, 2, 3, 4], 3000, np.random.default_rng(21))
+        else:
+            pc = engine.push_constants(W, H, **CAMERA)
+            d = bf.camera_dirs(pc, W, H).astype(np.float32).reshape(-1, 3)
+            o = np.repeat(np.asarray(list(pc.camInfo.pos), np.float32)[None], len(d), 0)
+        ref = bs.closest_hit(o, d, maps=True)
+        keep = ~(ref["didHit"] & (ref["dst"] * np.linalg.norm(d.astype(np.float64), axis=1) < ON_SURFACE))
+        o, d, ref = o[keep], d[keep], _rows(ref, keep)
+        _cases[key] = (s, ed, bs, o, d, ref, int((~keep).sum()))
+    return _cases[key]
+
+
+def _rows(ref, keep):
+    return {k: ({s: a[keep] for s, a in v.items()} if isinstance(v, dict) else v[keep]) for k, v in ref.items()}
+
+
+def _conditions(map_set, rays, ref, dropped=0):
+    """Conditions on the ray set, checked on the reference alone: the cap on exclusions and the floors on what the set exercises."""
+    n = len(ref["ill"]) + dropped
+    good = ~ref["ill"]
+    excluded = (int(ref["ill"].sum()) + dropped) / n
+    tri = good & ref["didHit"] & ~ref["isSphere"]
+    mapped = tri & (np.stack([ref["texel"][k][:, 0] for k in bf.MAP_SLOTS]) >= 0).any(axis=0)
+    cut, fallback = good & ref["didHit"] & ref["cutNearer"], tri & ref["fallback"]
+    hx, hy = tri & ref["bumped"] & (ref["hx"] != 0), tri & ref["bumped"] & (ref["hy"] != 0)
+    outside = tri & ((ref["uv"] < 0) | (ref["uv"] >= 1)).any(axis=1)
+    print(f"[{map_set}/{rays}] rays {n}  well-conditioned map hits {int(mapped.sum())}  excluded {excluded:.4%}  cut in front {int(cut.sum())}  "
+          f"fallback {int(fallback.sum())}  hx != 0 {int(hx.sum())}  hy != 0 {int(hy.sum())}  "
+          f"uv outside [0, 1): sampler 0 {int((outside & (ref['samplerIndex'] == 0)).sum())}, sampler 1 {int((outside & (ref['samplerIndex'] == 1)).sum())}")
+    assert excluded <= MAX_EXCLUDED, (map_set, rays, excluded)
+    assert mapped.sum() >= MIN_MESH_HITS, (map_set, rays, int(mapped.sum()))
+    for sampler in (0, 1):
+        assert (outside & (ref["samplerIndex"] == sampler)).any(), (map_set, rays, sampler)
+    assert fallback.sum() >= MIN_FALLBACK, (map_set, rays, int(fallback.sum()))
+    if "alphaIndex" in MAP_SETS[map_set][0]:
+        assert cut.sum() >= MIN_CUT, (map_set, rays, int(cut.sum()))
+    if "bumpIndex" in MAP_SETS[map_set][0]:
+        assert hx.sum() >= MIN_STEP and hy.sum() >= MIN_STEP, (map_set, rays, int(hx.sum()), int(hy.sum()))
+        for h in (ref["hx"][hx], ref["hy"][hy]):
+            assert (h > 0).any() and (h < 0).any()
+    return good, int(mapped.sum()), float(excluded)
+
+
+def _bumped_ratio(name, what, ref, got, good):
+    """Largest |dn| / bound on the well-conditioned rays whose normal the bump map tilted (0 if the set binds none)."""
+    m = good & ref["didHit"] & got["didHit"].astype(bool) & ref["bumped"]
+    if not m.any():
+        return 0.0
+    dn = np.linalg.norm(got["normal"][m].astype(np.float64) - ref["normal"][m], axis=1)
+    r = float((dn / ref["normal_bound"][m]).max())
+    print(f"[{name}] {what}: bumped normals {int(m.sum())}  largest |dn| / bound {r:.3f}  largest bound {float(ref['normal_bound'][m].max()):.2e}")
+    return r
+
+
+def test_map_reference_pieces():
+    """The helper against hand-worked values: the barycentric pairing of uv, the row flip, both samplers and their next texel, the
+    fallback, the alpha cut letting the surface behind through (and a sphere behind that), which channel each map reads, the bumped
+    normal on a triangle where dP/du = +x and dP/dv = +z."""
+    b = bf.BruteScene()
+    P = np.array([[(0, 0, 0), (1, 0, 0), (0, 0, 1)]], np.float64)               # e1 x e2 = -y: front faces towards -y
+    N = np.tile(np.array((0.0, -1.0, 0.0)), (1, 3, 1))
+    uv = np.array([[(0.0, 0.0), (2.0, 0.0), (0.0, 2.0)]])                        # u = 2 x, v = 2 z: dP/du = x / 2, dP/dv = z / 2
+    b.add_object(P, N, np.eye(4), material=0, uvs=uv, sampler=0)
+    b.add_object(P + (0, 1, 0), N, np.eye(4), material=1, uvs=uv, sampler=1)
+    b.set_spheres([(0.3, 5.0, 0.3)], [1.0], [2])
+    tex = np.zeros((2, 4, 4), np.uint8)                                          # 4 wide, 2 high
+    tex[..., 0] = [[10, 50, 120, 255], [0, 187, 188, 30]]
+    tex[..., 1] = 77
+    b.set_textures([tex])
+    b.set_material(0, (0.5, 0.25, 1.0), albedoIndex=0, alphaIndex=0, metalnessIndex=0, bumpIndex=0)
+    b.set_material(1, (1.0, 1.0, 1.0), bumpIndex=0, albedoIndex=7)               # slot 7 binds nothing
+    b.set_material(2, reflectance=0.5)
+    # ray 0: x = 0.3, z = 0.1: u = 0.3 (towards corner 1), v = 0.1: uv = (0.6, 0.2): column floor(2.4) = 2, row floor(0.8 * 2) = 1:
+    # byte 188: opaque. Without the flip the row would be 0 (byte 120: cut); with u and v swapped the column would be 0.
+    # ray 1: x = 0.15, z = 0.1: uv = (0.3, 0.2): column 1, row 1: byte 187: cut; the copy behind (y = 1) is hit instead
+    # ray 2: x = 0.6, z = 0.3: uv = (1.2, 0.6): wraps to column floor(4.8) % 4 = 0, row floor(0.4 * 2) = 0: byte 10: cut; behind it
+    #        sampler 1 clamps the column to 3, row 0: byte 255
+    o = np.array([(0.3, -1, 0.1), (0.15, -1, 0.1), (0.6, -1, 0.3)], np.float32)
+    d = np.tile(np.array((0, 1, 0), np.float32), (3, 1))
+    r = b.closest_hit(o, d, maps=True)
+    assert r["objectHitIndex"].tolist() == [0, 1, 1] and r["cutNearer"].tolist() == [False, True, True]
+    assert np.allclose(r["uv"][0], (0.6, 0.2)) and r["texel"]["alpha"][0].tolist() == [2, 1]
+    assert np.allclose(r["albedo"][0], np.array((0.5, 0.25, 1.0)) * bf.srgb8_to_linear(np.array((188, 77, 0))))
+    assert r["mirror"].tolist() == [True, False, False]
+    assert r["texel"]["bump"][1].tolist() == [1, 1] and r["texel"]["bump"][2].tolist() == [3, 0] and (r["texel"]["albedo"][1] == -1).all()
+    plain = b.closest_hit(o, d)
+    assert plain["objectHitIndex"].tolist() == [0, 0, 0] and "uv" not in plain
+    # bump, ray 0 (texel (2, 1), sampler 0): hx = h(3, 1) - h(2, 1), hy wraps to row 0: h(2, 0) - h(2, 1);
+    # n' = (0, -1, 0) - (hx x - hy z); a front face, identity matrix
+    h = bf.srgb8_to_linear
+    hx, hy = h(30) - h(188), h(120) - h(188)
+    n = np.array((-hx, -1.0, hy))
+    assert np.allclose(r["normal"][0], n / np.linalg.norm(n), atol=1e-15) and r["hx"][0] == hx and r["hy"][0] == hy
+    # ray 2 behind (texel (3, 0), sampler 1): the next column stays on 3 (hx = 0), the next row is 1: hy = h(30) - h(255)
+    n = np.array((0.0, -1.0, h(30) - h(255)))
+    assert np.allclose(r["normal"][2], n / np.linalg.norm(n), atol=1e-15) and r["hx"][2] == 0
+    # ray 0's texel cut on both copies (the second under its own sampler): the sphere behind them, a mirror by its reflectance;
+    # then two corners sharing their uv send every ray to (0.5, 0.5): column 2, row 1: opaque, and no tangent frame
+    tex[1, 2, 0] = 0
+    b.set_textures([tex])
+    b.set_material(1, (1.0, 1.0, 1.0), bumpIndex=0, alphaIndex=0)
+    r = b.closest_hit(o[:1], d[:1], maps=True)
+    assert r["didHit"][0] and r["isSphere"][0] and r["mirror"][0] and r["cutNearer"][0]
+    tex[1, 2, 0] = 188
+    b.set_textures([tex])
+    b.replace_mesh(0, P, N, False, np.array([[(0.9, 0.9), (0.1, 0.3), (0.9, 0.9)]]))
+    r = b.closest_hit(o, d, maps=True)
+    assert r["fallback"].all() and np.all(r["uv"] == 0.5) and r["objectHitIndex"].tolist() == [0, 0, 0] and not r["bumped"].any()
+    assert (r["texel"]["alpha"] == (2, 1)).all()
+    assert bf.texel_index(np.array([-0.01, -1.3, 1.0]), 4, False)[0].tolist() == [3, 2, 0]
+    assert bf.texel_index(np.array([-0.01, -1.3, 1.0]), 4, True)[0].tolist() == [0, 0, 3]
+
+
+# ---------------------------------------------------------------------------------------------------------------- hit records
+CASES = [(m, r) for m in MAP_SETS for r in ("aimed", "camera")]
+
+
+@pytest.mark.parametrize("map_set,rays", CASES)
+def test_oracle_hit_records_against_float64(map_set, rays):
+    s, ed, bs, o, d, ref, dropped = _case(map_set, rays)
+    good, _, _ = _conditions(map_set, rays, ref, dropped)
+    name = f"{map_set}/{rays}"
+    try:
+        pyoracle.set_textures(bs.textures)
+        got = engine.hits_to_numpy(pyoracle.trace_rays(ed, o, d))
+    finally:
+        pyoracle.set_textures([])
+    _bumped_ratio(name, "oracle", ref, got, good)
+    ratio = _compare(name, "oracle", ref, got, _corners_of(s), good)
+    assert bf.DST_C >= 2 * ratio, (name, ratio)
+
+
+# ---------------------------------------------------------------------------------------------------------------- furnace
+SKY, GROUND = (0.9, 0.75, 0.6), (0.2, 0.35, 0.5)
+FURNACE_SLOTS = dict(albedoIndex=0, alphaIndex=1, metalnessIndex=2)
+FURNACE_CAMERA = dict(pos=(0.05, -1.7, 0.03), cameraAngles=(90.0, 0.0, 0.0), fov=50.0)
+
+
+def _furnace():
+    """(scene, textures, push constants, expected [H, W, 3] in float64, the well-conditioned pixels, counts per kind)."""
+    if "furnace" not in _cases:
+        s = engine.Scene()
+        s.add_material(_material(ALBEDO_A, **FURNACE_SLOTS))
+        flat = _sheet(np.random.default_rng(9), jitter=0.0, perturb=0.0)
+        s.add_mesh("flat", *flat[:2], engine.placement(samplerIndex=0), 0, uvs=flat[2])
+        bs = bf.BruteScene.from_numpy(s.numpy())
+        bs.replace_mesh(0, *flat[:2], False, flat[2])
+        bs.set_material(0, ALBEDO_A, **FURNACE_SLOTS)
+        bs.set_textures(_textures())
+        _check_placement(s, 0)
+        pc = engine.push_constants(W, H, singleRender=1, sampleLimit=2, bounceLimit=4, environmentOn=True,
+                                   horizonColor=SKY + (50.0,), zenithColor=SKY + (0.0,), groundColor=GROUND, **FURNACE_CAMERA)
+        d = bf.camera_dirs(pc, W, H).astype(np.float32).reshape(-1, 3)
+        o = np.repeat(np.asarray(list(pc.camInfo.pos), np.float32)[None], len(d), 0)
+        assert (d[:, 1] > 0.5).all(), "the camera looks at the sheet from the sky side: a ray that is cut goes on to the ground side"
+        ref = bs.closest_hit(o, d, maps=True)
+        S, G = np.asarray(SKY, np.float32).astype(np.float64), np.asarray(GROUND, np.float32).astype(np.float64)
+        hit = ref["didHit"]
+        want = np.where(hit[:, None], np.where(ref["mirror"][:, None], S, ref["albedo"] * S), G)
+        good = ~ref["ill"]
+        kinds = dict(cut=int((good & ~hit & ref["cutNearer"]).sum()), ground=int((good & ~hit).sum()), mirror=int((good & hit & ref["mirror"]).sum()), diffuse=int((good & hit & ~ref["mirror"]).sum()))
+        _cases["furnace"] = (s, bs.textures, pc, want.reshape(H, W, 3), good.reshape(H, W), kinds, float(ref["ill"].mean()))
+    return _cases["furnace"]
+
+
+def _furnace_ratio(what, img):
+    s, tex, pc, want, good, kinds, excluded = _furnace()
+    err, val = np.abs(img[..., :3].astype(np.float64) - want)[good], want[good]
+    pos = val > 0
+    ratio = float((np.maximum(err[pos] - FURNACE_ABS, 0.0) / (bf.U32 * val[pos])).max())
+    print(f"[furnace] {what}: pixels {W * H}  excluded {excluded:.4%}  ground {kinds['ground']} (cut {kinds['cut']})  mirror {kinds['mirror']}  "
+          f"diffuse {kinds['diffuse']}  largest (|error| - 1e-9) / (u * value) {ratio:.3f}")
+    assert np.all(err[~pos] <= FURNACE_ABS), f"{what}: a channel whose float64 value is 0 is off by more than the decode's absolute term"
+    assert ratio <= FURNACE_C, f"{what}: a well-conditioned pixel is {ratio:.1f} roundings from its float64 value, {FURNACE_C} allowed"
+    assert np.all(img[..., 3] == 1.0)
+    return ratio
+
+
+def test_furnace_conditions():
+    s, tex, pc, want, good, kinds, excluded = _furnace()
+    assert excluded <= MAX_EXCLUDED, excluded
+    assert min(kinds["cut"], kinds["mirror"], kinds["diffuse"]) >= 500, kinds
+
+
+def test_oracle_furnace_against_float64():
+    s, tex, pc, want, good, kinds, excluded = _furnace()
+    try:
+        pyoracle.set_textures(tex)
+        img, _ = pyoracle.render(s, pc, W, H)
+    finally:
+        pyoracle.set_textures([])
+    ratio = _furnace_ratio("oracle", img)
+    assert FURNACE_C >= 2 * ratio, f"{FURNACE_C} roundings are less than twice the worst observed {ratio:.2f}: the count has lost a term"
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU half
+TRACE_DEFAULTS = dict(trace_variant=1, lds_stack=24)
+
+
+@pytest.fixture
+def mapped(renderer):
+    """The session's renderer; afterwards no textures on either side and the knobs these tests turn back at their defaults."""
+    try:
+        yield renderer
+    finally:
+        pyoracle.set_textures([])
+        renderer.upload_textures([])
+        for k, v in dict(TRACE_DEFAULTS, fused_maps=0, pipeline=-1, pixel_refill=0).items():
+            renderer.set_tuning(k, v)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("map_set,rays", CASES)
+def test_trace_rays_with_maps_against_float64(mapped, map_set, rays):
+    """albedo + bump: the ordinary traversal kernels (both variants, LDS stack 8 and 24) with reconstruct_hit<true>; a set with an
+    alpha map: k_trace_pw_alpha, whatever the knobs say; rt_trace_rays counts tests per ray, so here it is the <true> instantiation
+    (launch_trace: pix = pixStats || perRayBox). k_trace_pw_alpha<false> is what render_aovs and the furnace render below launch."""
+    s, ed, bs, o, d, ref, dropped = _case(map_set, rays)
+    good, _, _ = _conditions(map_set, rays, ref, dropped)
+    name, corners = f"{map_set}/{rays}", _corners_of(s)
+    mapped.upload_scene(ed)
+    mapped.upload_textures(bs.textures)
+    alpha = "alphaIndex" in MAP_SETS[map_set][0]
+    for variant, stack in ((1, 24),) if alpha else ((0, 8), (0, 24), (1, 8), (1, 24)):
+        mapped.set_tuning("trace_variant", variant)
+        mapped.set_tuning("lds_stack", stack)
+        got = engine.hits_to_numpy(mapped.trace_rays(o, d))
+        kernel = mapped.last_kernel()
+        what = f"gpu trace_variant={variant} lds_stack={stack} ({kernel})"
+        assert (kernel == "k_trace_pw_alpha<true>") if alpha else ("alpha" not in kernel and kernel.startswith(("k_trace<", "k_trace_pw<")[variant])), what
+        _bumped_ratio(name, what, ref, got, good)
+        _compare(name, what, ref, got, corners, good)
+
+
+@pytest.mark.gpu
+def test_aovs_with_maps_against_float64(mapped):
+    """render_aovs() with all four maps bound: its own ray_dir plane gives the reference's rays; normalDepth, position and ids as the
+    hit records, the albedo plane against albedo * texel: the material's albedo exactly, the decode's 8 ulp and the product's rounding."""
+    s, ed, bs = _scene("all")
+    pc = engine.push_constants(W, H, **CAMERA)
+    mapped.upload_scene(s)
+    ed.push(mapped, "objects")        # the samplers, through rt_update_objects
+    mapped.upload_textures(bs.textures)
+    a = mapped.render_aovs(pc, W, H)
+    assert mapped.last_kernel() == "k_trace_pw_alpha<false>", mapped.last_kernel()
+    d = a["ray_dir"].reshape(-1, 3)
+    o = np.repeat(np.asarray(list(pc.camInfo.pos), np.float32)[None], len(d), 0)
+    ref = bs.closest_hit(o, d, maps=True)
+    good, _, _ = _conditions("all", "aovs", ref)
+    h = a["hit"].reshape(-1)
+    z = lambda x: np.where(h, x.reshape(-1), 0).astype(np.uint32)   # noqa: E731
+    got = dict(dst=a["depth"].reshape(-1), didHit=h.astype(np.uint32), isSphere=a["sphere"].reshape(-1).astype(np.uint32),
+               objectHitIndex=z(a["object"]), triHitIndex=z(a["triangle"]), materialIndex=z(a["material"]),
+               frontFace=a["front_face"].reshape(-1).astype(np.uint32), hitPoint=a["position"].reshape(-1, 3), normal=a["normal"].reshape(-1, 3))
+    _bumped_ratio("all/aovs", "render_aovs", ref, got, good)
+    _compare("all/aovs", "render_aovs", ref, got, _corners_of(s), good)
+    m = good & ref["didHit"] & h
+    alb = a["albedo"].reshape(-1, 3).astype(np.float64)
+    tol = (2 * bf.DECODE_ULP + 1) * bf.U32 * ref["albedo"] + 1e-9
+    err = np.abs(alb - ref["albedo"])
+    print(f"[all/aovs] albedo plane: largest |error| / tolerance {float((err[m] / tol[m]).max()):.3f} on {int(m.sum())} pixels, "
+          f"{int((m & (ref['texel']['albedo'][:, 0] >= 0)).sum())} of them textured")
+    assert np.all(err[m] <= tol[m])
+    assert np.all(alb[good & ~ref["didHit"]] == 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipeline", ["multi_kernel", "fused_block", "fused_refill_8"])
+def test_furnace_against_float64(mapped, pipeline):
+    """The furnace render through k_shade_maps + k_trace_pw_alpha, and through k_render_fused_maps a block at a time and with pixels
+    replaced at 8 free lanes."""
+    s, tex, pc, want, good, kinds, excluded = _furnace()
+    mapped.upload_scene(s)
+    mapped.upload_textures(tex)
+    if pipeline != "multi_kernel":
+        mapped.set_tuning("fused_maps", 1)
+        mapped.set_tuning("pipeline", 1)
+        mapped.set_tuning("pixel_refill", 64 if pipeline == "fused_block" else 8)
+    img = mapped.render(pc, W, H)
+    if pipeline == "multi_kernel":
+        assert mapped.last_pipeline() == 0 and mapped.last_kernel() == "k_trace_pw_alpha<false>", mapped.last_kernel()
+    else:
+        assert mapped.last_pipeline() == 1 and mapped.last_kernel() == "k_render_fused_maps<false>", mapped.last_kernel()
+    _furnace_ratio(f"gpu {pipeline} ({mapped.last_kernel()})", img)
