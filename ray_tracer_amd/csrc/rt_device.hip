@@ -8,6 +8,7 @@
 
 #include "rt_kernels.hip.h"
 #include "bvh_build.hip.h"
+#include "launch_plan.h"   // every decision about how a dispatch is run: this file gathers the facts, asks there, and launches
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -33,8 +34,6 @@ struct DevBuf {  // device memory that belongs to whoever holds this: move-only,
 };
 
 struct EventPair { hipEvent_t a, b; };
-#define RT_MAX_LANES 4
-#define RT_FRAMES_MAX_SLOTS (24ull << 20)   // default for the paths of one multi-frame dispatch (ten 1080p frames or three 4K frames: 5.8 GB of path state)
 // the rows y = row0 + k*rowStride, k in [0,nRows) of a width x height image
 struct RowsOf {
     uint32_t width = 0, height = 0, row0 = 0, rowStride = 0, nRows = 0;
@@ -97,55 +96,11 @@ struct rt_ctx {
     DevBuf dnWorkBuf, dnHostBuf, dnOutBuf;
     size_t dnOutPixels = 0; bool dnValid = false;
 
-    // ---- tuning: what rt_set_tuning writes, each "given explicitly" flag beside the knob it qualifies. Nothing else assigns to it.
-    struct Tuning {
-        int objTreeMin = 48;    // rt_set_tuning("object_tree_min"): general-transform objects from which the object hierarchy is built (0 = never)
-        int framesPerLaunch = 0; // rt_render_frames: most frames of a tile rendered by one launch (0 = as many as fit)
-        uint64_t framesMaxSlots = RT_FRAMES_MAX_SLOTS;  // most paths of one multi-frame dispatch (rt_render_frames)
-        int cameraReuse = 1;    // rt_set_tuning("camera_reuse", 0): trace the camera ray of every sample
-        int lightQueries = 1;   // rt_set_tuning("light_queries", 0): trace every NEE ray and cosine probe in full
-        int lanes = 3;                        // rt_set_tuning("lanes", 1..RT_MAX_LANES)
-        bool lanesSet = false;                // "lanes" given explicitly: no automatic fall-back to one part
-        uint32_t lanesMinSlots = 1u << 20;    // dispatches of fewer paths than this stay in one part
-        int laneGridPct = 0;                  // rt_set_tuning("lane_grid_pct"): share of the resident work-groups a k_trace_pw launch takes while a dispatch runs in several parts (0 = by the parts' size: 50, 40 below 1.2 M paths per part)
-        int traceVariant = 1;   // 0 = one-ray-per-lane k_trace, 1 = persistent waves k_trace_pw
-        int pipeline = -1;      // 0 = multi-kernel wavefront pipeline, 1 = wave-private fused pipeline (k_render_fused), -1 = by tile size
-        uint32_t fusedBelowPixels = 4000000;  // auto: dispatches of fewer paths than this use the fused pipeline — scaled down to 1.5 M as the rays get longer
-                                              // (choose_pipeline: sizeLimit). Sponza, 8 spp, ms per step with 1 / 2 / 4 / 10 frames of 1080p in one dispatch
-                                              // (round 3, multi-kernel in three parts): fused 113.8 / 109.4 / 107.4 / 105, multi-kernel 103.4 / 90.7 / 84.7 / 79.5
-        uint32_t fusedBelowBoxTests = 70;     // auto: ... and so do scenes whose rays are short (EXECUTED box tests per ray, measured), with one exception (choose_pipeline)
-        int refill = 8;         // k_trace_pw: idle lanes that trigger a refill
-        int refillMk = 16;      // the same for k_trace_pw over the global queue when set by hand ("mk_refill"); automatic: 12 for long rays, 16 otherwise (launch_trace)
-        bool refillMkSet = false;  // given explicitly (else by the scene's ray length, launch_trace)
-        int chunk = 256;        // k_trace_pw: most queue entries reserved per atomic
-        int ldsStackCap = 24;   // k_trace_pw: LDS stack entries per lane (8, 16 or 24); deeper BVHs use the overflow buffer
-        int fastLanes = 32;     // k_trace_pw: lanes at interior nodes that skip the full vote (4K Sponza: 24 -> 32 is -2 %, 1080p: equal)
-        bool fastLanesSet = false;  // fast_lanes given explicitly: it then also applies to the fused pipeline
-        int wSetup = 16, wLeaf = 16; // k_trace_pw: vote weights in eighths (interior = 8); the set-up weight when set by hand ("mk_w_setup"), automatic: 32 for long rays, 16 otherwise
-        bool wSetupSet = false, wLeafSet = false;  // given explicitly (the set-up weight else by the scene's ray length, launch_trace)
-        int wSetupFused = 16, wLeafFused = 24;  // vote weights of the fused pipeline (short private lists: leaves and set-ups sooner)
-        int blocksPerCU = 0;    // k_trace_pw: 0 = occupancy query
-        int phaseStats = 0;     // diagnostic: k_trace_pw counts rounds / active lanes per phase
-        int tileSlots = 1;      // slots follow 8x8 pixel blocks instead of rows
-        int fastShare = 10;     // sixteenths of the live lanes that suffice to skip the vote (0 = fixed count only): -1..-2 % everywhere
-        int maskIdentity = 0;   // identity-transform objects in the rays' object masks too (rt_update_objects reads it)
-        int scatter = -1;       // fused pipeline: blocks made of chunks of this many slots from all over the tile; 0 = neighbouring pixels; -1 = auto
-        int hotPairs = 2;       // k_trace_pw: child pairs of the meshes' top levels from LDS. 0 = off, 1 = as many as fit beside the stacks of
-                                // six work-groups per CU, 2 = of five (Sponza, 21-entry stacks, ten frames in flight: 90.4 / 90.6 / 88.7 ms per step)
-        int pixelRefill = 0;    // fused pipeline: free lanes at which a wave reserves new pixels (64 = a block at a time, 0 = by ray length)
-        int batchPixels = 0;    // fused pipeline: pixels per wave-private block (0 = chosen per launch)
-        int batchFixed = 80;    // ... and the fixed part of a block's cost in the chooser, in pixel units
-        int fusedMaps = 0;      // 1: a scene that binds an alpha, metalness or bump map may take the fused pipeline (k_render_fused_maps); 0: multi-kernel only
-        int probe = 1;          // measure an unknown scene with a small dispatch before its first big one
-    } tune;
+    // ---- tuning: what rt_set_tuning writes (launch_plan.h: set_tuning). Nothing else assigns to it.
+    Tuning tune;
 
     // ---- measured on earlier dispatches. Written by poll_ray_cost, request_ray_cost, probe_ray_cost, measured_new_scene and rt_reset_counters only.
-    struct Measured {
-        bool snapPending = false;
-        unsigned long long snapBox = 0, snapRays = 0, snapSeg = 0, snapPaths = 0;  // counters at the previous snapshot
-        double boxPerRay = -1.0;              // < 0: not measured yet
-        double segPerPath = -1.0;             // path segments per pixel sample of this scene, from the same snapshots (< 0: not measured yet)
-    } meas;
+    Measured meas;
 
     // ---- reports: written by the launch functions, harvest_events and rt_bvh_build, zeroed by rt_reset_counters, read by rt_last_* / rt_get_*.
     struct Reports {
@@ -249,71 +204,113 @@ Dispatch one_part(rt_ctx* c, const DevScene& sc, bool pixStats) {
     return Dispatch{sc, pixStats, c->tune.phaseStats, c->tune.pipeline, c->profiling, false, &c->rep.traceLaunchesTotal, c->stream, c->q.counts, 0, 100};
 }
 
-// Paths of a dispatch. Several frames in one dispatch: the paths are {64 tile slots} x {frames} (FrameParams::nFrames; rt_kernels.hip.h:
-// frame_slot), in either pipeline
-uint64_t frame_slots(uint64_t nPixels) { return (nPixels + 63) / 64 * 64; }
-uint64_t dispatch_slots(uint64_t nPixels, uint32_t nFrames) { return nFrames > 1u ? frame_slots(nPixels) * nFrames : nPixels; }
-
-template <int N> using Stack = std::integral_constant<int, N>;
-
-// The traversal kernel's stack for a BVH of depth d and at most `cap` LDS entries per lane: f(Stack<STACK>, bool_constant<OVF>,
-// bool_constant<CULL>), OVF: the deeper entries in the overflow buffer. Only the multi-kernel pipeline has a 20-entry kernel.
-// (tests/test_instantiations.py makes a scene for each depth bucket of these rows)
-template <bool ALLOW20, typename F>
-auto with_stack(uint32_t d, uint32_t cap, bool cull, F&& f) {
-    using Yes = std::true_type; using No = std::false_type;
-    auto go = [&](auto S, auto O) { return cull ? f(S, O, Yes{}) : f(S, O, No{}); };
-    if (d <= 8) return go(Stack<8>{}, No{});
-    if (cap < 16) return go(Stack<8>{}, Yes{});
-    if (d <= 16) return go(Stack<16>{}, No{});
-    if (cap < 24) return go(Stack<16>{}, Yes{});
-    if constexpr (ALLOW20) { if (d <= 20) return go(Stack<20>{}, No{}); }
-    if (d <= 24) return go(Stack<24>{}, No{});
-    return go(Stack<24>{}, Yes{});
+// The facts the launch plan asks for (launch_plan.h), gathered from the context and the dispatch. fp: the dispatch's frame (the
+// traversal launches of rt_trace_rays and of the AOV pass have none); perRay: per-ray counters are wanted (rt_trace_rays)
+SceneFacts scene_facts(const rt_ctx* c, const Dispatch& d) {
+    SceneFacts s;
+    s.maxLeafDepth = c->maxLeafDepth; s.cull = c->cull;
+    s.mapFlags = d.sc.mapFlags; s.hotNodes = d.sc.hotNodes; s.nodeCount = d.sc.nodeCount; s.triCount = d.sc.triCount;
+    return s;
+}
+DispatchFacts dispatch_facts(const Dispatch& d, const FrameParams* fp, bool perRay) {
+    DispatchFacts f;
+    if (fp) { f.nPixels = fp->nPixels; f.nFrames = fp->nFrames; f.samples = fp->samples; f.debug = fp->debug; }
+    f.pixStats = d.pixStats; f.perRay = perRay; f.phaseStats = d.phaseStats; f.pipeline = d.pipeline; f.probe = d.probe; f.gridPct = d.gridPct;
+    f.counted = d.launches != nullptr; f.launches = d.launches ? *d.launches : 0;
+    return f;
 }
 
-// A kernel to launch, the one whose occupancy sizes the grid (no heat maps, no phase statistics), its stack, and its name as a
-// demangler prints it (rt_last_kernel; tests/test_instantiations.py compares it with `nm -C`)
-template <typename K> struct KernelChoice { K kernel, occupancy; int stack; bool ovf; char name[sizeof rt_ctx::Reports::lastKernel]; };
+// A kernel to launch, the one whose occupancy sizes the grid (no heat maps, no phase statistics), and its name as a demangler
+// prints it (rt_last_kernel; tests/test_instantiations.py compares it with `nm -C`). kernel == nullptr: no such instantiation.
+template <typename K> struct KernelChoice { K kernel, occupancy; char name[sizeof rt_ctx::Reports::lastKernel]; };
+using TraceChoice = KernelChoice<void (*)(DevScene, PathState, TraceArgs)>;
 using TracePwChoice = KernelChoice<void (*)(DevScene, PathState, TracePwArgs)>;
 using FusedChoice = KernelChoice<void (*)(FusedKernArgs)>;
 
 template <typename K, typename... A>
-KernelChoice<K> kernel_choice(K kernel, K occupancy, int stack, bool ovf, const char* format, A... a) {
-    KernelChoice<K> k{kernel, occupancy, stack, ovf, ""};
+KernelChoice<K> kernel_choice(K kernel, K occupancy, const char* format, A... a) {
+    KernelChoice<K> k{kernel, occupancy, ""};
     snprintf(k.name, sizeof k.name, format, a...);
     return k;
 }
 const char* tf(bool b) { return b ? "true" : "false"; }
 
+template <int STACK>
+TraceChoice trace_kernel() { return kernel_choice(k_trace<STACK>, k_trace<STACK>, "k_trace<%d>", STACK); }
 template <int STACK, bool OVF, bool PIX, bool STATS, bool CULL, int HOT = 0, int BLOCKS = 6>
 TracePwChoice trace_pw_kernel() {
-    return kernel_choice(k_trace_pw<STACK, OVF, PIX, STATS, CULL, HOT, BLOCKS>, k_trace_pw<STACK, OVF, false, false, CULL, HOT, BLOCKS>, STACK, OVF,
+    return kernel_choice(k_trace_pw<STACK, OVF, PIX, STATS, CULL, HOT, BLOCKS>, k_trace_pw<STACK, OVF, false, false, CULL, HOT, BLOCKS>,
                          "k_trace_pw<%d, %s, %s, %s, %s, %d, %d>", STACK, tf(OVF), tf(PIX), tf(STATS), tf(CULL), HOT, BLOCKS);
 }
 template <int STACK, bool OVF, bool PIX, bool CULL>
 FusedChoice fused_kernel() {
-    return kernel_choice(k_render_fused<STACK, OVF, PIX, CULL>, k_render_fused<STACK, OVF, false, CULL>, STACK, OVF,
+    return kernel_choice(k_render_fused<STACK, OVF, PIX, CULL>, k_render_fused<STACK, OVF, false, CULL>,
                          "k_render_fused<%d, %s, %s, %s>", STACK, tf(OVF), tf(PIX), tf(CULL));
 }
 
+// From a kernel key (launch_plan.h) to the instantiation: the key's arguments become template arguments by a walk over the
+// instantiations there are, and a key that names none of them yields no kernel (the callers fail).
+template <int N> using Stack = std::integral_constant<int, N>;
+
+// f(Stack<STACK>, bool_constant<OVF>, bool_constant<CULL>) for the stacks a family is compiled with. Only the multi-kernel
+// pipeline has a 20-entry kernel. (tests/test_instantiations.py makes a scene for each depth bucket the plan maps to these)
+template <bool ALLOW20, typename F>
+auto with_stack(const KernelKey& k, F&& f) {
+    using Yes = std::true_type; using No = std::false_type;
+    auto go = [&](auto S, auto O) { return k.cull ? f(S, O, Yes{}) : f(S, O, No{}); };
+    if (k.stack == 8) return k.ovf ? go(Stack<8>{}, Yes{}) : go(Stack<8>{}, No{});
+    if (k.stack == 16) return k.ovf ? go(Stack<16>{}, Yes{}) : go(Stack<16>{}, No{});
+    if constexpr (ALLOW20) { if (k.stack == 20 && !k.ovf) return go(Stack<20>{}, No{}); }
+    if (k.stack == 24) return k.ovf ? go(Stack<24>{}, Yes{}) : go(Stack<24>{}, No{});
+    return decltype(go(Stack<8>{}, No{})){};
+}
+
 template <int STACK, bool OVF, bool CULL>
-TracePwChoice choose_trace_pw(const rt_ctx* c, const Dispatch& d, bool pix) {
-    // top-level pairs from LDS (k_trace_pw<HOT>): what 160 KB of LDS per CU leave beside the stacks. hot_pairs 1: six work-groups
-    // per CU, 2: five (more pairs, no spills at 96 registers)
-    // (the overflow-stack kernel with 16 entries in LDS keeps six work-groups AND 120 pairs: deep BVHs, see launch_trace)
-    constexpr int HOT6 = OVF ? (STACK == 16 ? 120 : 0) : STACK == 8 ? 192 : STACK == 16 ? 136 : STACK == 20 ? 72 : 0;
-    constexpr int HOT5 = OVF ? 0 : STACK == 24 ? 80 : STACK == 20 ? 144 : 192;
-    int hotMode = (!pix && !d.phaseStats && d.sc.hotNodes > 0) ? c->tune.hotPairs : 0;
-    if (hotMode == 1 && HOT6 == 0) hotMode = 2;   // (a 24-entry stack leaves no room at six work-groups)
-    if (hotMode == 2 && HOT5 == 0) hotMode = HOT6 ? 1 : 0;   // (overflow-stack instantiations: the table only beside 16-entry stacks)
+TracePwChoice trace_pw_of(const KernelKey& k) {
+    constexpr int HOT6 = hot6(STACK, OVF), HOT5 = hot5(STACK, OVF);
     // (if constexpr: an instantiation the tables can never select is not compiled — every kernel in the library can be
     // launched, and tests/test_instantiations.py launches every one of them against the oracle)
-    if constexpr (HOT6 > 0) { if (hotMode == 1) return trace_pw_kernel<STACK, OVF, false, false, CULL, HOT6, 6>(); }
-    if constexpr (HOT5 > 0) { if (hotMode == 2) return trace_pw_kernel<STACK, OVF, false, false, CULL, HOT5, 5>(); }
-    if (d.phaseStats) return trace_pw_kernel<STACK, OVF, true, true, CULL>();
-    if (pix) return trace_pw_kernel<STACK, OVF, true, false, CULL>();
+    if (k.hot) {
+        if (k.pix || k.stats) return {};
+        if constexpr (HOT6 > 0) { if (k.hot == HOT6 && k.blocks == 6) return trace_pw_kernel<STACK, OVF, false, false, CULL, HOT6, 6>(); }
+        if constexpr (HOT5 > 0) { if (k.hot == HOT5 && k.blocks == 5) return trace_pw_kernel<STACK, OVF, false, false, CULL, HOT5, 5>(); }
+        return {};
+    }
+    if (k.blocks != 6 || (k.stats && !k.pix)) return {};
+    if (k.stats) return trace_pw_kernel<STACK, OVF, true, true, CULL>();
+    if (k.pix) return trace_pw_kernel<STACK, OVF, true, false, CULL>();
     return trace_pw_kernel<STACK, OVF, false, false, CULL>();
+}
+
+TraceChoice trace_choice(const KernelKey& k) {
+    if (k.family != KernelFamily::trace) return {};
+    switch (k.stack) {
+        case 8: return trace_kernel<8>();
+        case 16: return trace_kernel<16>();
+        case 24: return trace_kernel<24>();
+        case 32: return trace_kernel<32>();
+        case 48: return trace_kernel<48>();
+        case 64: return trace_kernel<64>();
+    }
+    return {};
+}
+TracePwChoice trace_pw_choice(const KernelKey& k) {
+    if (k.family == KernelFamily::trace_pw_alpha)
+        return kernel_choice(k.pix ? k_trace_pw_alpha<true> : k_trace_pw_alpha<false>, k_trace_pw_alpha<false>, "k_trace_pw_alpha<%s>", tf(k.pix));
+    if (k.family != KernelFamily::trace_pw) return {};
+    return with_stack<true>(k, [&](auto S, auto O, auto C) { return trace_pw_of<S, O, C>(k); });
+}
+FusedChoice fused_choice(const KernelKey& k) {
+    if (k.family == KernelFamily::render_fused_maps)
+        return kernel_choice(k.pix ? k_render_fused_maps<true> : k_render_fused_maps<false>, k_render_fused_maps<false>, "k_render_fused_maps<%s>", tf(k.pix));
+    if (k.family != KernelFamily::render_fused) return {};
+    return with_stack<false>(k, [&](auto S, auto O, auto C) { return k.pix ? fused_kernel<S, O, true, C>() : fused_kernel<S, O, false, C>(); });
+}
+int no_kernel(rt_ctx* c, const KernelKey& k) {
+    char m[160];
+    snprintf(m, sizeof m, "the launch plan asks for a kernel the library does not hold: family %d <stack %d, ovf %d, pix %d, stats %d, cull %d, hot %d, blocks %d>",
+             (int)k.family, k.stack, (int)k.ovf, (int)k.pix, (int)k.stats, (int)k.cull, k.hot, k.blocks);
+    return c->fail(m);
 }
 
 template <typename K>
@@ -323,13 +320,13 @@ uint32_t resident_blocks(const rt_ctx* c, K kernel) {
     return (uint32_t)perCU * (uint32_t)c->numCUs;
 }
 
-// with_stack picks an OVF kernel only for a BVH deeper than its stack; the map kernels have the buffer at any depth. Each part of
+// The plan picks an OVF kernel only for a BVH deeper than its stack; the map kernels have the buffer at any depth. Each part of
 // a dispatch has its own: their launches run at the same time.
-int overflow_buf(rt_ctx* c, const Dispatch& d, int stack, bool ovf, uint32_t resident, uint32_t** out) {
+int overflow_buf(rt_ctx* c, const Dispatch& d, const KernelKey& k, uint32_t resident, uint32_t** out) {
     *out = nullptr;
-    if (!ovf || c->maxLeafDepth <= (uint32_t)stack) return 0;
+    if (!k.ovf || c->maxLeafDepth <= (uint32_t)k.stack) return 0;
     DevBuf& ob = c->overflowBuf[d.part];
-    int rc = dev_alloc(c, ob, (size_t)(c->maxLeafDepth - stack) * resident * RT_BLOCK * 4);
+    int rc = dev_alloc(c, ob, (size_t)(c->maxLeafDepth - k.stack) * resident * RT_BLOCK * 4);
     if (rc) return rc;
     *out = (uint32_t*)ob.p;
     return 0;
@@ -363,144 +360,71 @@ int prof_end(rt_ctx* c, const Dispatch& d, EventPair* ev) {
     return 0;
 }
 
-// Pixels per wave-private block of k_render_fused. A wave finishes its block's samples one after the
-// other (the reference's RNG runs on from sample to sample of a pixel), so a tile is done when the wave
-// with the most blocks is: nPixels/64 blocks rarely divide evenly over the resident waves (a 1/8-height
-// 1080p tile is 4050 blocks for 5120 waves), and a slightly smaller block that gives every wave the
-// same number of blocks shortens that critical path. Measured block time ~ (80 + pixels) (drain of the
-// longest ray and the shading step do not shrink with the block); beyond two blocks per wave the
-// dynamic hand-out evens the waves out by itself and whole 8x8 blocks are best.
-uint32_t fused_batch_pixels(const rt_ctx* c, uint32_t nPixels, uint32_t waves, uint32_t evenBelow) {
-    if (c->tune.batchPixels > 0) return (uint32_t)std::min(c->tune.batchPixels, (int)RT_WAVE);
-    if (((uint64_t)nPixels + RT_WAVE - 1) / RT_WAVE > (uint64_t)evenBelow * waves) return RT_WAVE;
-    uint32_t best = RT_WAVE;
-    uint64_t bestCost = ~0ull;
-    for (uint32_t b = RT_WAVE; b >= 16; b--) {
-        const uint64_t nb = (nPixels + b - 1) / b;
-        const uint64_t rounds = (nb + waves - 1) / waves;
-        const uint64_t cost = rounds * (uint64_t)((uint32_t)c->tune.batchFixed + b);
-        if (cost < bestCost) { bestCost = cost; best = b; }
-    }
-    return best;
-}
-
 // The whole dispatch in one launch of k_render_fused, or of k_render_fused_maps for a scene that binds a map (fused_maps)
 int launch_fused(rt_ctx* c, const Dispatch& d, const FrameParams& fp, float4* fb) {
+    const DispatchFacts df = dispatch_facts(d, &fp, false);
+    const KernelKey key = fused_kernel_key(c->tune, scene_facts(c, d), df);
+    const FusedChoice k = fused_choice(key);
+    if (!k.kernel) return no_kernel(c, key);
     EventPair* ev;
     int rc = prof_begin(c, d, &ev);
     if (rc) return rc;
-    const FusedChoice k = d.sc.mapFlags  // one kernel, any depth, any objects: <24, true, *, true>
-        ? kernel_choice(d.pixStats ? k_render_fused_maps<true> : k_render_fused_maps<false>, k_render_fused_maps<false>, 24, true, "k_render_fused_maps<%s>", tf(d.pixStats))
-        : with_stack<false>(c->maxLeafDepth, (uint32_t)c->tune.ldsStackCap, c->cull, [&](auto S, auto O, auto C) { return d.pixStats ? fused_kernel<S, O, true, C>() : fused_kernel<S, O, false, C>(); });
     const uint32_t resident = resident_blocks(c, k.occupancy);
-    const uint32_t nSlots = (uint32_t)dispatch_slots(fp.nPixels, fp.nFrames);  // rt_render_frames: frames are more slots of the same tile
-    // Pixels are replaced as they finish when rays are long (Sponza -7 %, its 1/2 and 1/4 tiles -8 % and -11 %: the wave no
-    // longer drains to its slowest pixel once per block) and when a wave gets fewer than five blocks (Cornell + bunny /
-    // + dragon, rank 0's rows of 2 GPUs -3 %, of 4 GPUs -13 %); with short rays and many blocks per wave a block at a
-    // time is 4-7 % faster (the full 1080p frame of Cornell, + bunny, + dragon)
-    // (scenes whose paths end early — open scenes, most samples leave after a bounce or two: fewer than 2.5 segments per sample
-    // against ~4 in a closed box — empty a block's lanes unevenly; there replacing pays up to eight blocks per wave:
-    // tools/heuristics_table.py, 256 bunnies on a floor under the sky, one 1080p frame: 19.1 against 19.7 ms)
-    const uint64_t fewBelow = (c->meas.segPerPath >= 0.0 && c->meas.segPerPath < 2.5) ? 8ull : 5ull;
-    const bool fewBlocks = ((uint64_t)nSlots + RT_WAVE - 1) / RT_WAVE < fewBelow * resident * (RT_BLOCK / RT_WAVE);
-    const uint32_t pixelRefill = c->tune.pixelRefill > 0 ? (uint32_t)c->tune.pixelRefill
-                               : ((c->meas.boxPerRay >= (double)c->tune.fusedBelowBoxTests || fewBlocks) ? 8u : (uint32_t)RT_WAVE);
-    // a wave that replaces its pixels one by one evens out by itself as soon as there is more than one block per wave
-    const uint32_t evenBelow = pixelRefill < RT_WAVE ? 1u : 2u;
-    uint32_t batchPixels = fused_batch_pixels(c, nSlots, resident * (RT_BLOCK / RT_WAVE), evenBelow);
-    // With one or two blocks per wave (one, when pixels are replaced as they finish) the tile is done when the most expensive block is: blocks made of 4-slot chunks from
-    // all over the tile cost about the same (-6 % on a 1/8-height 1080p tile); with more blocks per wave the dynamic
-    // hand-out balances by itself and neighbouring pixels (shared cache lines, coherent rays) are 3-8 % faster.
-    const uint32_t wavesResident = resident * (RT_BLOCK / RT_WAVE);
-    const uint32_t g = fp.nFrames > 1u ? 0u : c->tune.scatter >= 0 ? (uint32_t)c->tune.scatter : ((((uint64_t)nSlots + RT_WAVE - 1) / RT_WAVE <= (uint64_t)evenBelow * wavesResident) ? 4u : 0u);
-    if (g) batchPixels = std::min((uint32_t)RT_WAVE, (batchPixels + g - 1) / g * g);
-    const uint32_t nBatches = g ? ((nSlots + g - 1) / g + batchPixels / g - 1) / (batchPixels / g) : (nSlots + batchPixels - 1) / batchPixels;
-    const uint32_t blocks = std::max(1u, std::min((nBatches + (RT_BLOCK / RT_WAVE) - 1) / (RT_BLOCK / RT_WAVE), resident));
+    const FusedShape s = fused_shape(c->tune, c->meas, df, resident);
     uint32_t* overflow;
-    if ((rc = overflow_buf(c, d, k.stack, k.ovf, resident, &overflow))) return rc;
+    if ((rc = overflow_buf(c, d, key, resident, &overflow))) return rc;
     RT_HIP(c, hipMemsetAsync(d.counts + 5, 0, 4, d.stream));
-    // lanes at interior nodes that make the wave skip the vote: long rays (Sponza: 157 box tests per ray) want the interior step
-    // to wait for more lanes (40: -4 %); 24 for short rays and until the scene is measured
-    const uint32_t fastLanes = c->tune.fastLanesSet ? (uint32_t)c->tune.fastLanes : (c->meas.boxPerRay >= (double)c->tune.fusedBelowBoxTests ? 40u : 24u);
-    const uint32_t wLeaf = (uint32_t)c->tune.wLeafFused;
     unsigned long long* waveTimes = nullptr;
-    if (d.phaseStats && (rc = wave_time_buf(c, blocks, &waveTimes))) return rc;
-    FusedArgs fa{d.counts + 5, fb, (DevCounters*)c->counterBuf.p, overflow, (uint32_t)c->tune.refill, (uint32_t)c->tune.wSetupFused, wLeaf, fastLanes, batchPixels, g, (uint32_t)c->tune.fastShare, waveTimes, pixelRefill};
+    if (s.waveTimes && (rc = wave_time_buf(c, s.blocks, &waveTimes))) return rc;
+    FusedArgs fa{d.counts + 5, fb, (DevCounters*)c->counterBuf.p, overflow, (uint32_t)c->tune.refill, s.wSetup, s.wLeaf, s.fastLanes, s.batchPixels, s.g, (uint32_t)c->tune.fastShare, waveTimes, s.pixelRefill};
     const FusedKernArgs ka{d.sc, c->ps, fp, fa};
     memcpy(c->rep.lastKernel, k.name, sizeof k.name);
-    hipLaunchKernelGGL(k.kernel, dim3(blocks), dim3(RT_BLOCK), 0, d.stream, ka);
+    hipLaunchKernelGGL(k.kernel, dim3(s.blocks), dim3(RT_BLOCK), 0, d.stream, ka);
     RT_HIP(c, hipGetLastError());
     return prof_end(c, d, ev);
-}
-
-template <int STACK>
-void launch_v0_t(rt_ctx* c, const Dispatch& d, uint32_t maxRays, const TraceArgs& ta) {
-    uint32_t blocks = (maxRays + RT_BLOCK - 1) / RT_BLOCK;
-    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_trace<%d>", STACK);
-    hipLaunchKernelGGL((k_trace<STACK>), dim3(blocks), dim3(RT_BLOCK), 0, d.stream, d.sc, c->ps, ta);
 }
 
 // the work counter (counts[4]) must be zero when this is called
 int launch_trace(rt_ctx* c, const Dispatch& d, uint32_t maxRays, const TraceArgs& ta) {
     if (maxRays == 0) return 0;
+    const SceneFacts sf = scene_facts(c, d);
+    const DispatchFacts df = dispatch_facts(d, nullptr, ta.perRayBox != nullptr);
+    const KernelKey key = trace_kernel_key(c->tune, sf, df);
     EventPair* ev;
-    int rc = prof_begin(c, d, &ev);
-    if (rc) return rc;
-    const uint32_t depth = c->maxLeafDepth;
-    const bool pix = d.pixStats || ta.perRayBox;  // per-ray counters are only needed for the pixel heat maps (debug >= 0) and rt_trace_rays
-    const bool alpha = d.sc.mapFlags & RT_MAP_ALPHA;  // a bound alpha map: the one traversal kernel that reads it (any depth, any objects)
-    if (!alpha && c->tune.traceVariant == 0) {  // one ray per lane, whole stack in LDS
-        if (depth <= 8) launch_v0_t<8>(c, d, maxRays, ta);
-        else if (depth <= 16) launch_v0_t<16>(c, d, maxRays, ta);
-        else if (depth <= 24) launch_v0_t<24>(c, d, maxRays, ta);
-        else if (depth <= 32) launch_v0_t<32>(c, d, maxRays, ta);
-        else if (depth <= 48) launch_v0_t<48>(c, d, maxRays, ta);
-        else launch_v0_t<64>(c, d, maxRays, ta);
-    } else {  // persistent waves; at most 24 entries in LDS, deeper ones in the overflow buffer
-        // BVHs deeper than 24: 16 entries in LDS, the rest in the overflow buffer (the stack only holds far siblings and is rarely
-        // that deep), which leaves room for 120 top-level pairs beside six work-groups per CU: C5 at 4K 474 -> 468 ms per step,
-        // flattened 471 -> 462, 1080p 117.5 -> 115.6 (Cornell + dragon: level)
-        const bool tableWanted = c->tune.hotPairs && d.sc.hotNodes > 0 && !d.phaseStats && !pix;  // (choose_trace_pw's condition)
-        const uint32_t cap = (depth > 24u && c->tune.ldsStackCap >= 24 && tableWanted) ? 16u : (uint32_t)c->tune.ldsStackCap;
-        const TracePwChoice k = alpha
-            ? kernel_choice(pix ? k_trace_pw_alpha<true> : k_trace_pw_alpha<false>, k_trace_pw_alpha<false>, 24, true, "k_trace_pw_alpha<%s>", tf(pix))
-            : with_stack<true>(depth, cap, c->cull, [&](auto S, auto O, auto C) { return choose_trace_pw<S, O, C>(c, d, pix); });
+    int rc;
+    if (key.family == KernelFamily::trace) {  // one ray per lane, whole stack in LDS
+        const TraceChoice k = trace_choice(key);
+        if (!k.kernel) return no_kernel(c, key);
+        if ((rc = prof_begin(c, d, &ev))) return rc;
+        memcpy(c->rep.lastKernel, k.name, sizeof k.name);
+        hipLaunchKernelGGL(k.kernel, dim3((maxRays + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, d.stream, d.sc, c->ps, ta);
+    } else {  // persistent waves
+        const TracePwChoice k = trace_pw_choice(key);
+        if (!k.kernel) return no_kernel(c, key);
+        if ((rc = prof_begin(c, d, &ev))) return rc;
         const uint32_t resident = resident_blocks(c, k.occupancy);
-        // a part of a dispatch that runs beside the other parts' launches takes its share of the resident work-groups (Dispatch::gridPct)
-        const uint32_t blocks = std::min((maxRays + RT_BLOCK - 1) / RT_BLOCK, std::max(1u, (uint32_t)((uint64_t)resident * (uint32_t)d.gridPct / 100u)));
+        const TraceShape s = trace_shape(c->tune, c->meas, sf, df, maxRays, resident);
         uint32_t* overflow;
-        if ((rc = overflow_buf(c, d, k.stack, k.ovf, resident, &overflow))) return rc;
+        if ((rc = overflow_buf(c, d, key, resident, &overflow))) return rc;
         unsigned long long* waveTimes = nullptr;
-        const bool times = d.phaseStats == 1 || (d.phaseStats >= 2 && d.launches && *d.launches == (uint64_t)(d.phaseStats - 2));  // 1: the last launch's waves; 2 + k: launch k's (after rt_reset_counters)
-        if (!alpha && times && (rc = wave_time_buf(c, blocks, &waveTimes))) return rc;
-        // Long rays (the measure the pipeline choice uses) want new rays sooner and their set-up served later: idle lanes re-armed at 12
-        // instead of 16, set-up steps voted in at weight 32 instead of 16 (Sponza 81.0 -> 79.4 ms per step, C5 115.4 -> 114.1;
-        // Cornell + bunny / + dragon, short rays: +2.5 / +3.5 % with the same, so they keep 16 / 16). Knobs set by hand win.
-        const bool longRays = c->meas.boxPerRay >= (double)c->tune.fusedBelowBoxTests;
-        const uint32_t refillMk = c->tune.refillMkSet ? (uint32_t)c->tune.refillMk : (longRays ? 12u : 16u);
-        const uint32_t wSetup = c->tune.wSetupSet ? (uint32_t)c->tune.wSetup : (longRays ? 32u : 16u);
-        const TracePwArgs pa{ta.queue, ta.count, d.counts + 4, refillMk, (uint32_t)c->tune.chunk, wSetup, (uint32_t)c->tune.wLeaf, (uint32_t)c->tune.fastLanes, (uint32_t)c->tune.fastShare,
+        if (s.waveTimes && (rc = wave_time_buf(c, s.blocks, &waveTimes))) return rc;
+        const TracePwArgs pa{ta.queue, ta.count, d.counts + 4, s.refillMk, (uint32_t)c->tune.chunk, s.wSetup, (uint32_t)c->tune.wLeaf, (uint32_t)c->tune.fastLanes, (uint32_t)c->tune.fastShare,
                              ta.perRayBox, ta.perRayTri, ta.counters, (unsigned long long*)((char*)c->counterBuf.p + sizeof(DevCounters)), waveTimes, overflow, ta.countAux, ta.countAux2, ta.auxOffset};
         memcpy(c->rep.lastKernel, k.name, sizeof k.name);
-        hipLaunchKernelGGL(k.kernel, dim3(blocks), dim3(RT_BLOCK), 0, d.stream, d.sc, c->ps, pa);
+        hipLaunchKernelGGL(k.kernel, dim3(s.blocks), dim3(RT_BLOCK), 0, d.stream, d.sc, c->ps, pa);
     }
     RT_HIP(c, hipGetLastError());
     return prof_end(c, d, ev);
 }
 
+// the counters the measurements are taken from (launch_plan.h: fold_snapshot, fold_probe)
+RayCounters ray_counters(const DevCounters& dc) { return RayCounters{dc.boxTests, dc.skippedBoxTests, dc.raysTraced, dc.segments, dc.paths}; }
+
 // Fold in the counter snapshot of an earlier dispatch if its copy has arrived (never waits).
 void poll_ray_cost(rt_ctx* c) {
     if (!c->meas.snapPending || hipEventQuery(c->snapEvent) != hipSuccess) return;
     c->meas.snapPending = false;
-    const unsigned long long box = c->snap->boxTests - c->snap->skippedBoxTests, rays = c->snap->raysTraced;  // executed tests: what a ray costs the GPU
-    if (rays > c->meas.snapRays && box >= c->meas.snapBox && rays - c->meas.snapRays > 100000ull)
-        c->meas.boxPerRay = (double)(box - c->meas.snapBox) / (double)(rays - c->meas.snapRays);
-    const unsigned long long seg = c->snap->segments, paths = c->snap->paths;
-    if (paths > c->meas.snapPaths && seg >= c->meas.snapSeg && paths - c->meas.snapPaths > 100000ull) c->meas.segPerPath = (double)(seg - c->meas.snapSeg) / (double)(paths - c->meas.snapPaths);
-    c->meas.snapBox = box;
-    c->meas.snapRays = rays;
-    c->meas.snapSeg = seg;
-    c->meas.snapPaths = paths;
+    fold_snapshot(c->meas, ray_counters(*c->snap));
 }
 // Queue the next snapshot behind the dispatch just enqueued.
 void request_ray_cost(rt_ctx* c) {
@@ -788,52 +712,6 @@ FrameParams frame_camera(const rt_ctx* c, const PushConstants* pc, uint32_t widt
     return fp;
 }
 
-// Both pipelines give the same bits; which one is faster depends on how much a wave has to do per pixel. Small tiles
-// and scenes with short rays (few box tests per ray, measured on this context's earlier dispatches) go to the fused one.
-// 0 = multi-kernel, 1 = fused; `pipeline` is Dispatch::pipeline.
-int choose_pipeline(const rt_ctx::Tuning& t, int pipeline, double boxPerRay, const DevScene& sc, uint32_t nSlots) {
-    const bool shortRays = boxPerRay >= 0.0 && boxPerRay < (double)t.fusedBelowBoxTests;
-    // the longer the rays, the earlier the global queue of the multi-kernel pipeline pays — and with the dispatch in overlapping
-    // parts earlier than it used to (tools/size_sweep.py, one 1080p frame = 2.07 M paths, fused / multi-kernel in parts: Sponza,
-    // 153 executed box tests per ray, 113.8 / 103.4 ms; Sponza + 16 dragons 167.2 / 162.5; the klein bottle x 8, 84 tests,
-    // 70.2 / 76.6; half a frame, 1.04 M paths: 61.5 / 66.3, 91.9 / 106.8, 41.5 / 57.4): 4 M paths up to 90 tests per ray, falling
-    // to 1.5 M at 150
-    double sizeLimit = (double)t.fusedBelowPixels;
-    if (boxPerRay > 90.0) sizeLimit = std::max(0.375 * sizeLimit, sizeLimit - (boxPerRay - 90.0) * (0.625 / 60.0) * sizeLimit);
-    // (the paths of all the frames of the dispatch count: four frames of a quarter of a 4K frame are a 4K frame's worth)
-    // Short rays keep the fused pipeline at any size — unless the traversal misses the caches: a scene whose hot data (child pairs
-    // and triangle positions) exceeds one XCD's 4 MB of L2 is bound by latency even with few tests per ray, and from 10 M paths the
-    // multi-kernel pipeline's extra resident waves and overlapping parts win there too (Cornell + bunny, 33 box tests per ray, ten
-    // 1080p frames: 36.1 against 38.0 ms per frame; + dragon 36.3 against 40.1; level between four and six frames:
-    // tools/frames_sweep.py), while small scenes (bobadog, the 45-object scene)
-    // and scenes of very short rays (fewer than 25 executed tests: 232 k loose triangles on a floor) stay fused (tools/heuristics_table.py)
-    const bool bigScene = (uint64_t)sc.nodeCount * 32u + (uint64_t)sc.triCount * 48u > (4ull << 20);
-    const bool shortButMissing = shortRays && bigScene && boxPerRay >= 25.0 && nSlots >= (10u << 20);
-    const int chosen = pipeline >= 0 ? pipeline : (((double)nSlots < sizeLimit || (shortRays && !shortButMissing)) ? 1 : 0);
-    // a scene that binds a metalness, alpha or bump map: the multi-kernel pipeline's kernels that read them (k_shade_maps,
-    // k_trace_pw_alpha), whatever "pipeline" asks for — unless "fused_maps" lets it choose as usual (k_render_fused_maps)
-    return (sc.mapFlags && !t.fusedMaps) ? 0 : chosen;
-}
-
-// The parts a multi-kernel dispatch is wanted in (ensure_part_streams may grant fewer)
-int choose_parts(const rt_ctx::Tuning& t, const Dispatch& d, bool cull, double boxPerRay, uint32_t samples, uint32_t nSlots) {
-    int nLanes = (samples > 0 && nSlots >= t.lanesMinSlots) ? std::max(1, std::min(t.lanes, (int)RT_MAX_LANES)) : 1;
-    if (d.phaseStats) nLanes = 1;  // the diagnostic kernel's statistics are per launch
-    // One scene shape loses by it (tools/lanes_table.py): long rays that walk into many placed objects (C5: sixteen instanced dragons,
-    // ~190 executed box tests per ray; 116.1 ms per frame in one part against 121.2 in three at 1080p, 472 against 492 at 4K).
-    // Every placed object a ray enters costs a set-up round that reloads the ray from its path state in HBM, so that traversal
-    // competes with the other parts' k_shade for HBM instead of complementing it. Such scenes keep one part unless "lanes" was set.
-    // (from 8 M paths on: a single 1080p frame of the same scene still gains 7 % from its parts, whose launches are short against their tails)
-    if (!t.lanesSet && cull && boxPerRay >= 150.0 && nSlots >= (8u << 20)) nLanes = 1;
-    return nLanes;
-}
-// ... and the share of the resident work-groups each part's k_trace_pw launches take
-// (small parts — one 1080p frame per dispatch is three parts of 0.69 M paths — run better on 40 % grids: 101.7 -> 99.5 ms per
-// frame; the bench's ten frames per dispatch, 6.9 M paths per part, on 50 %: 77.2 against 78.6)
-int part_grid_pct(const rt_ctx::Tuning& t, int nLanes, uint32_t firstPartSlots) {
-    return nLanes > 1 ? (t.laneGridPct > 0 ? t.laneGridPct : (firstPartSlots < 1200000u ? 40 : 50)) : 100;
-}
-
 // The side streams and events of parts 1..nLanes-1, made when first needed; returns the parts there are streams for
 int ensure_part_streams(rt_ctx* c, int nLanes) {
     for (int l = 1; l < nLanes; l++) {
@@ -849,20 +727,13 @@ int ensure_part_streams(rt_ctx* c, int nLanes) {
 
 // One part of a multi-kernel dispatch: what its launches are built with (d), its slots [begin, begin + n) and the state of its rounds
 struct Lane { Dispatch d; hipEvent_t poll; uint32_t begin, n, ubActive; int cur; bool pollPending, done; };
-// The slots of a dispatch in nLanes contiguous ranges of whole blocks
-void slice_parts(rt_ctx* c, const Dispatch& d, uint32_t nSlots, uint32_t nFrames, int nLanes, Lane* lane) {
-    const uint32_t unit = 256u * std::max(1u, nFrames);  // whole blocks of k_shade, whole tile blocks of all their frames
-    const uint32_t units = (nSlots + unit - 1) / unit;
-    uint32_t at = 0;
+// The parts of a dispatch as the plan slices it, each with its stream, counter block and poll event
+void make_parts(rt_ctx* c, const Dispatch& d, const PartSlices& p, int nLanes, Lane* lane) {
     for (int l = 0; l < nLanes; l++) {
-        const uint32_t u = units / (uint32_t)nLanes + ((uint32_t)l < units % (uint32_t)nLanes ? 1u : 0u);
-        const uint32_t end = std::min(nSlots, at + u * unit);
-        lane[l] = Lane{d, l ? c->pollEventSide[l - 1] : c->pollEvent, at, end - at, end - at, 0, false, end == at};
+        lane[l] = Lane{d, l ? c->pollEventSide[l - 1] : c->pollEvent, p.begin[l], p.n[l], p.n[l], 0, false, p.n[l] == 0};
         lane[l].d.stream = l ? c->sideStream[l - 1] : c->stream; lane[l].d.counts = c->q.counts + 16 * l; lane[l].d.part = l;
-        at = end;
+        lane[l].d.gridPct = p.gridPct;
     }
-    const int gridPct = part_grid_pct(c->tune, nLanes, lane[0].n);
-    for (int l = 0; l < nLanes; l++) lane[l].d.gridPct = gridPct;
 }
 
 // The rounds of the multi-kernel pipeline: the parts fork from the ctx stream, each runs traversal, then shading, until none of its
@@ -928,10 +799,10 @@ int render_rounds(rt_ctx* c, const FrameParams& fp, Lane* lane, int nLanes) {
 // state it streams) and the draining tail of its k_trace_pw launch run under the other part's traversal (bound by latency).
 // Part 0 runs on the ctx stream, the others fork from it after the ray generation and join it before the image is written.
 int render_parts(rt_ctx* c, const FrameParams& fp, const Dispatch& d, uint32_t nSlots, float4* fb) {
-    const int nLanes = ensure_part_streams(c, choose_parts(c->tune, d, c->cull, c->meas.boxPerRay, fp.samples, nSlots));
+    const int nLanes = ensure_part_streams(c, choose_parts(c->tune, c->meas, scene_facts(c, d), dispatch_facts(d, &fp, false)));
     c->rep.lastParts = nLanes;
     Lane lane[RT_MAX_LANES];
-    slice_parts(c, d, nSlots, fp.nFrames, nLanes, lane);
+    make_parts(c, d, slice_parts(c->tune, nSlots, fp.nFrames, nLanes), nLanes, lane);
     for (int l = 0; l < nLanes; l++) {
         const Lane& L = lane[l];
         if (!L.n) continue;
@@ -957,10 +828,10 @@ int render_dispatch(rt_ctx* c, const FrameParams& fp, const Dispatch& d, float4*
     const uint32_t nSlots = (uint32_t)dispatch_slots(fp.nPixels, fp.nFrames);
     int rc;
     poll_ray_cost(c);
-    if (c->meas.boxPerRay < 0.0 && c->tune.probe && !d.probe && !d.sc.mapFlags && (uint64_t)fp.nPixels * fp.samples >= 8000000ull && fp.debug < 0 &&
-        (rc = probe_ray_cost(c, fp, d)))
-        return rc;
-    const int pipeline = choose_pipeline(c->tune, d.pipeline, c->meas.boxPerRay, d.sc, nSlots);
+    const SceneFacts sf = scene_facts(c, d);
+    const DispatchFacts df = dispatch_facts(d, &fp, false);
+    if (probe_first(c->tune, c->meas, sf, df) && (rc = probe_ray_cost(c, fp, d))) return rc;
+    const int pipeline = choose_pipeline(c->tune, c->meas, sf, df);
     if (!d.probe) c->rep.lastPipeline = pipeline;
     if (pipeline == 1) {  // wave-private fused pipeline: one launch for the whole dispatch
         rc = launch_fused(c, d, fp, fb);
@@ -975,19 +846,17 @@ int render_dispatch(rt_ctx* c, const FrameParams& fp, const Dispatch& d, float4*
     return rc;
 }
 
-// The launch parameters of both pipelines follow the scene's measured box tests per ray, which the first dispatch of a
-// scene does not have — and a single-render job (the reference's singleRender mode: all samples in one dispatch) is
-// nothing but a first dispatch. Before a big one, eight rows of the same tile are rendered once with one sample per
-// pixel into a scratch image and the counters put back: a few ms, no trace in anything the caller can read.
+// The ray-cost probe (launch_plan.h: probe_first, probe_rows): a few rows of the same tile, rendered once with one sample per
+// pixel into a scratch image, and the counters put back.
 // (fp, d: the big dispatch's. The probe's path state fits in its, and its scene counts are the same.)
 int probe_ray_cost(rt_ctx* c, const FrameParams& fp, const Dispatch& d) {
-    const uint32_t rows = std::min(fp.nRows, 8u), skip = fp.nRows / rows;
+    const TileRows rows = probe_rows(TileRows{fp.row0, fp.rowStride, fp.nRows});
     FrameParams p = fp;
     p.samples = 1; p.progressive = 0; p.debug = -1; p.nFrames = 1;
-    p.row0 = fp.row0 + (skip / 2u) * fp.rowStride; p.rowStride = fp.rowStride * skip; p.nRows = rows; p.nPixels = rows * fp.width;
+    p.row0 = rows.row0; p.rowStride = rows.rowStride; p.nRows = rows.nRows; p.nPixels = rows.nRows * fp.width;
     Dispatch pd = d;  // fused pipeline, no profiling, no phase statistics, launches not counted
     pd.probe = true; pd.pipeline = 1; pd.profiled = false; pd.phaseStats = 0; pd.launches = nullptr;
-    int rc = dev_alloc(c, c->probeBuf, (size_t)rows * fp.width * sizeof(float4));
+    int rc = dev_alloc(c, c->probeBuf, (size_t)p.nPixels * sizeof(float4));
     if (rc) return rc;
     DevCounters before, after;
     RT_HIP(c, hipMemcpyAsync(&before, c->counterBuf.p, sizeof(DevCounters), hipMemcpyDeviceToHost, c->stream));
@@ -998,8 +867,7 @@ int probe_ray_cost(rt_ctx* c, const FrameParams& fp, const Dispatch& d) {
     RT_HIP(c, hipMemcpyAsync(c->counterBuf.p, &before, sizeof(DevCounters), hipMemcpyHostToDevice, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     c->meas.snapPending = false;  // the probe's own snapshot request: its copy has arrived, and it is not wanted
-    if (after.raysTraced > before.raysTraced + 1000ull)
-        c->meas.boxPerRay = (double)((after.boxTests - after.skippedBoxTests) - (before.boxTests - before.skippedBoxTests)) / (double)(after.raysTraced - before.raysTraced);
+    fold_probe(c->meas, ray_counters(before), ray_counters(after));
     return 0;
 }
 
@@ -1059,18 +927,8 @@ int rt_render_frames(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_
                      uint32_t nRows, uint32_t nFrames, float* d_rgba) {
     if (!c || !pc) return -1;
     if (nFrames == 0) return 0;
-    // The frames of one call are one dispatch: their paths share the launch (fused pipeline) or the queues of every round
-    // (multi-kernel pipeline; render_impl picks the pipeline by the paths of all the frames together, so four frames of a
-    // quarter of a 4K frame run like a whole 4K frame). Ordinary frames only (no heat maps: those read per-pixel counters at
-    // resolve time), within the 30-bit slot ids and RT_FRAMES_MAX_SLOTS paths (3.9 GB of path state); more frames than that
-    // go in several dispatches.
-    const uint64_t np = (uint64_t)nRows * width;
-    uint32_t per = 1;  // frames per dispatch
-    if (nFrames > 1u && pc->rayTraceParams.debug < 0 && np > 0) {
-        const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(c->tune.framesMaxSlots, np), (1ull << 30) - 1);
-        per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nFrames, cap / frame_slots(np)));
-        if (c->tune.framesPerLaunch > 0) per = std::min(per, (uint32_t)c->tune.framesPerLaunch);
-    }
+    // The frames of one call are one dispatch, or several when they are too many paths for one (launch_plan.h: frames_per_dispatch)
+    const uint32_t per = frames_per_dispatch(c->tune, (uint64_t)nRows * width, nFrames, pc->rayTraceParams.debug);
     PushConstants p = *pc;
     for (uint32_t f = 0; f < nFrames; f += per) {
         const uint32_t n = std::min(per, nFrames - f);
@@ -1446,42 +1304,9 @@ int rt_last_parts(const rt_ctx* c) { return c ? c->rep.lastParts : 0; }
 
 int rt_set_tuning(rt_ctx* c, const char* key, int value) {
     if (!c || !key) return -1;
-    std::string k(key);
-    if (k == "pipeline") { if (value < -1 || value > 1) return c->fail("pipeline: -1 (auto), 0 or 1"); c->tune.pipeline = value; }
-    else if (k == "probe") { c->tune.probe = value ? 1 : 0; }
-    else if (k == "frames_max_mslots") { if (value < 1 || value > 1000) return c->fail("frames_max_mslots: 1..1000 (millions of paths per multi-frame dispatch)"); c->tune.framesMaxSlots = (uint64_t)value << 20; }
-    else if (k == "frames_per_launch") { if (value < 0) return c->fail("frames_per_launch >= 0"); c->tune.framesPerLaunch = value; }
-    else if (k == "camera_reuse") { c->tune.cameraReuse = value ? 1 : 0; }
-    else if (k == "light_queries") { c->tune.lightQueries = value ? 1 : 0; int rc = rebuild_emitters(c); if (rc) return rc; }
-    else if (k == "fused_below_box_tests") { if (value < 0) return c->fail("fused_below_box_tests >= 0"); c->tune.fusedBelowBoxTests = (uint32_t)value; }
-    else if (k == "fused_below_pixels") { if (value < 0) return c->fail("fused_below_pixels >= 0"); c->tune.fusedBelowPixels = (uint32_t)value; }
-    else if (k == "trace_variant") { if (value < 0 || value > 1) return c->fail("trace_variant: 0 or 1"); c->tune.traceVariant = value; }
-    else if (k == "refill") { if (value < 1 || value > 64) return c->fail("refill: 1..64"); c->tune.refill = value; c->tune.refillMk = value; c->tune.refillMkSet = true; }
-    else if (k == "hot_pairs") { if (value < 0 || value > 2) return c->fail("hot_pairs: 0, 1 (six work-groups per CU) or 2 (five)"); c->tune.hotPairs = value; }
-    else if (k == "mk_refill") { if (value < 1 || value > 64) return c->fail("mk_refill: 1..64"); c->tune.refillMk = value; c->tune.refillMkSet = true; }
-    else if (k == "lds_stack") { if (value != 8 && value != 16 && value != 24) return c->fail("lds_stack: 8, 16 or 24"); c->tune.ldsStackCap = value; }
-    else if (k == "fast_lanes") { if (value < 0 || value > 65) return c->fail("fast_lanes: 1..65 (0: back to the defaults)"); c->tune.fastLanesSet = value != 0; c->tune.fastLanes = value ? value : 32; }
-    else if (k == "chunk") { if (value < 1 || value > 4096) return c->fail("chunk: 1..4096"); c->tune.chunk = value; }
-    else if (k == "w_setup") { if (value < 1 || value > 512) return c->fail("w_setup: 1..512"); c->tune.wSetup = value; c->tune.wSetupFused = value; c->tune.wSetupSet = true; }
-    else if (k == "w_leaf") { if (value < 1 || value > 512) return c->fail("w_leaf: 1..512"); c->tune.wLeaf = value; c->tune.wLeafFused = value; c->tune.wLeafSet = true; }
-    else if (k == "mk_w_setup") { if (value < 1 || value > 512) return c->fail("mk_w_setup: 1..512"); c->tune.wSetup = value; c->tune.wSetupSet = true; }
-    else if (k == "mk_w_leaf") { if (value < 1 || value > 512) return c->fail("mk_w_leaf: 1..512"); c->tune.wLeaf = value; }
-    else if (k == "tile_slots") { c->tune.tileSlots = value != 0; }
-    else if (k == "mask_identity") { c->tune.maskIdentity = value != 0; }
-    else if (k == "fast_share") { if (value < 0 || value > 16) return c->fail("fast_share: 0..16"); c->tune.fastShare = value; }
-    else if (k == "scatter") { if (value != -1 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return c->fail("scatter: -1 (auto), 0, 1, 2, 4, 8 or 16"); c->tune.scatter = value; }
-    else if (k == "fused_maps") { if (value < 0 || value > 1) return c->fail("fused_maps: 0 (map scenes take the multi-kernel pipeline) or 1 (they choose as usual)"); c->tune.fusedMaps = value; }
-    else if (k == "pixel_refill") { if (value < 0 || value > (int)RT_WAVE) return c->fail("pixel_refill must be 0 (by ray length) .. 64"); c->tune.pixelRefill = value; }
-    else if (k == "batch_pixels") { if (value < 0 || value > (int)RT_WAVE) return c->fail("batch_pixels must be 0 (auto) .. 64"); c->tune.batchPixels = value; }
-    else if (k == "batch_fixed") { if (value < 0 || value > 4096) return c->fail("batch_fixed out of range"); c->tune.batchFixed = value; }
-    else if (k == "phase_stats") { if (value < 0) return c->fail("phase_stats >= 0"); c->tune.phaseStats = value; }
-    else if (k == "object_tree_min") { if (value < 0) return c->fail("object_tree_min >= 0"); c->tune.objTreeMin = value; }
-    else if (k == "lanes") { if (value < 0 || value > RT_MAX_LANES) return c->fail("lanes: 1..4 (parts of a multi-kernel dispatch, each on its own stream), 0 = automatic"); c->tune.lanes = value ? value : 3; c->tune.lanesSet = value != 0; }
-    else if (k == "lane_grid_pct") { if (value != 0 && (value < 10 || value > 100)) return c->fail("lane_grid_pct: 0 (by size) or 10..100"); c->tune.laneGridPct = value; }
-    else if (k == "lanes_min_kslots") { if (value < 0) return c->fail("lanes_min_kslots >= 0"); c->tune.lanesMinSlots = (uint32_t)value << 10; }
-    else if (k == "blocks_per_cu") { if (value < 0 || value > 8) return c->fail("blocks_per_cu: 0..8"); c->tune.blocksPerCU = value; }
-    else return c->fail("unknown tuning key " + k);
-    return 0;
+    const TuningChange ch = set_tuning(c->tune, key, value);
+    if (!ch.error.empty()) return c->fail(ch.error);
+    return ch.rebuildEmitters ? rebuild_emitters(c) : 0;
 }
 
 int rt_last_pipeline(const rt_ctx* c) { return c ? c->rep.lastPipeline : -1; }

@@ -27,8 +27,8 @@
 #include "rt_det_math.h"
 #include "rt_probe.h"
 #include "scene_layout.h"   // the formats of the scene tables: node words, object flags, RT_MAP_*, RT_HOT_PAIRS, RT_OBJTREE_LEVELS
+#include "launch_plan.h"    // RT_WAVE, RT_BLOCK: the launch policy sizes grids and blocks with them
 
-#define RT_WAVE 64
 #ifndef RT_QUEUE_ORDER
 #define RT_QUEUE_ORDER 0   // k_shade: the ray queue's pieces are {main, NEE, cosine probes} (1: {main, cosine probes, NEE})
 #endif
@@ -44,7 +44,6 @@
 #ifndef RT_FUSED_MAPS_BLOCKS
 #define RT_FUSED_MAPS_BLOCKS 4   // k_render_fused_maps: work-groups per CU it is built for (__launch_bounds__)
 #endif
-#define RT_BLOCK 256
 #define RT_HIT_NONE 0xffffffffu
 #define RT_HIT_SPHERE 0x80000000u
 
