@@ -399,6 +399,45 @@ int  rt_read_denoised_rgba_f32(rt_ctx* ctx, float* hostOut, size_t nFloats);
 int  rt_denoise_host(rt_ctx* ctx, uint32_t width, uint32_t height, const float* rgba, const RtAovBuffers* aovs,
                      const RtDenoiseParams* params, float* out);
 
+/* Temporal accumulation by reprojection over a whole width x height frame (the temporal half of SVGF; DESIGN.md, "Temporal
+ * accumulation"), to run in front of rt_denoise while the camera moves. The ctx keeps a history: per pixel the accumulated
+ * demodulated colour, two luminance moments, the history length N and the surface it showed (normal, depth, object / sphere /
+ * material), with the camera of the call that wrote it. A call takes the noisy frame, its first-hit planes and the camera it was
+ * rendered with; each filtered pixel (rt_denoise's set: a hit on a material with emissionStrength == 0) takes its world position
+ * back through the previous call's camera, reads the four pixels around where it lands there (bilinear weights; a tap counts
+ * when it is inside the image, has a history, shows the same object / sphere / material, a normal with n.n' >= normalCos and a
+ * depth within depthTolerance, relative, of the pixel's distance to the previous camera), and blends with k = 1 / N,
+ * N = min(N_history + 1, maxHistory); without a valid tap it starts again at N = 1. Kept pixels (misses, emitters) come out bit
+ * for bit, with moments 0, and are never taps. The scene is taken to be static between calls: after an edit that moves or
+ * recolours something, call rt_temporal_reset (rt_upload_scene does; rt_update_* leave that to their caller). */
+typedef struct RtTemporalParams {
+    uint32_t maxHistory;      /* >= 1: the blend factor never falls below 1 / maxHistory; 1 passes the frame through */
+    float    normalCos;       /* in [-1, 1] */
+    float    depthTolerance;  /* > 0, relative */
+} RtTemporalParams;
+void rt_temporal_params_default(RtTemporalParams* p);        /* 32, 0.9, 0.02 (this build's choice: DESIGN.md) */
+/* Asynchronous on the ctx stream. cam: the camera the frame was rendered with (required; kept for the next call). d_rgba,
+ * d_aovs: as rt_denoise has them (NULL: the ctx framebuffer / the ctx planes, each of the whole frame); normalDepth, position,
+ * albedo and ids are read. params NULL: the defaults. d_out: the accumulated RGBA fp32 frame (alpha copied), which may go
+ * straight to rt_denoise as its d_rgba; d_moments: per pixel (m1, m2, max(0, m2 - m1^2), N) of the demodulated luminance; either
+ * may be NULL: a ctx-owned plane (rt_read_temporal_rgba_f32, rt_read_temporal_moments). Outputs overlap neither the inputs nor
+ * each other. A first call, a call after rt_temporal_reset or rt_upload_scene, and a call with another width or height have no
+ * history: N = 1 on every filtered pixel. Needs an uploaded scene (the material table). The pass changes no counter, no ray-cost
+ * figure, none of rt_last_kernel / rt_last_parts / rt_last_pipeline, not the ctx framebuffer or its progressive history, no AOV
+ * plane and not rt_denoise's output plane. A call refused for its arguments leaves the history as it was. */
+int  rt_temporal_accumulate(rt_ctx* ctx, uint32_t width, uint32_t height, const CameraInfo* cam, const float* d_rgba,
+                            const RtAovBuffers* d_aovs, const RtTemporalParams* params, float* d_out, float* d_moments);
+/* forgets the history: the next rt_temporal_accumulate starts at N = 1 */
+int  rt_temporal_reset(rt_ctx* ctx);
+/* copy the ctx-owned output of the last rt_temporal_accumulate(…, d_out = NULL) / (…, d_moments = NULL)
+ * (nFloats = width*height*4 of that call); block */
+int  rt_read_temporal_rgba_f32(rt_ctx* ctx, float* hostOut, size_t nFloats);
+int  rt_read_temporal_moments(rt_ctx* ctx, float* hostOut, size_t nFloats);
+/* rt_temporal_accumulate of host arrays (rgba, out and moments: width*height*4 floats, moments may be NULL; aovs: host planes
+ * as above) on the same history; blocks */
+int  rt_temporal_accumulate_host(rt_ctx* ctx, uint32_t width, uint32_t height, const CameraInfo* cam, const float* rgba,
+                                 const RtAovBuffers* aovs, const RtTemporalParams* params, float* out, float* moments);
+
 int  rt_get_counters(rt_ctx* ctx, RtCounters* out);
 int  rt_reset_counters(rt_ctx* ctx);
 /* When enabled, every traversal-kernel launch is bracketed by HIP events on

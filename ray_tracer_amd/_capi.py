@@ -106,6 +106,10 @@ class RtDenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigmaLuminance", C.c_float), ("sigmaNormal", C.c_float), ("sigmaDepth", C.c_float)]
 
 
+class RtTemporalParams(C.Structure):
+    _fields_ = [("maxHistory", C.c_uint32), ("normalCos", C.c_float), ("depthTolerance", C.c_float)]
+
+
 # every symbol include/rt_amd.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 _vp = C.c_void_p
@@ -157,6 +161,12 @@ SYMBOLS = {
     "rt_denoise": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _P(RtAovBuffers), _P(RtDenoiseParams), _vp]),
     "rt_read_denoised_rgba_f32": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
     "rt_denoise_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _P(RtAovBuffers), _P(RtDenoiseParams), _vp]),
+    "rt_temporal_params_default": (None, [_P(RtTemporalParams)]),
+    "rt_temporal_accumulate": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _P(CameraInfo), _vp, _P(RtAovBuffers), _P(RtTemporalParams), _vp, _vp]),
+    "rt_temporal_reset": (C.c_int, [_vp]),
+    "rt_read_temporal_rgba_f32": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
+    "rt_read_temporal_moments": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
+    "rt_temporal_accumulate_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _P(CameraInfo), _vp, _P(RtAovBuffers), _P(RtTemporalParams), _vp, _vp]),
     "rt_get_counters": (C.c_int, [_vp, _P(RtCounters)]),
     "rt_reset_counters": (C.c_int, [_vp]),
     "rt_set_profiling": (C.c_int, [_vp, C.c_int]),

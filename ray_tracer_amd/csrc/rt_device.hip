@@ -95,6 +95,13 @@ struct rt_ctx {
     // the denoiser (rt_denoise): its work planes, the staging planes of rt_denoise_host and the ctx-owned output
     DevBuf dnWorkBuf, dnHostBuf, dnOutBuf;
     size_t dnOutPixels = 0; bool dnValid = false;
+    // temporal accumulation (rt_temporal_accumulate): the two histories a call reads and writes in turn, the camera and size of the
+    // call that wrote tpHist[tpCur], the staging planes of rt_temporal_accumulate_host and the ctx-owned frame and moments
+    DevBuf tpHist[2], tpHostBuf, tpOutBuf, tpMomBuf;
+    int tpCur = 0; bool tpHistValid = false;
+    uint32_t tpWidth = 0, tpHeight = 0;
+    TemporalCamera tpCam{};
+    size_t tpOutPixels = 0, tpMomPixels = 0; bool tpOutValid = false, tpMomValid = false;
 
     // ---- tuning: what rt_set_tuning writes (launch_plan.h: set_tuning). Nothing else assigns to it.
     Tuning tune;
@@ -642,6 +649,7 @@ int rt_upload_scene(rt_ctx* c, const RtSceneArrays* s) {
     RT_HIP(c, hipSetDevice(c->device));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     measured_new_scene(c);
+    c->tpHistValid = false;  // a new scene: nothing of the old one's frames is its history (rt_temporal_accumulate)
     c->host = SceneSources{};
     c->sc.emitMode = 0; c->sc.emitCount = 0; c->sc.emitSphereMask = 0;
     c->sc.mapFlags = 0;
@@ -1078,9 +1086,9 @@ int check_denoise(rt_ctx* c, uint32_t width, uint32_t height, const RtDenoisePar
     return 0;
 }
 
-std::string not_whole(const char* what, const RowsOf& r, uint32_t width, uint32_t height) {
+std::string not_whole(const char* what, const RowsOf& r, uint32_t width, uint32_t height, const char* fn = "rt_denoise") {
     char m[256];
-    snprintf(m, sizeof(m), "rt_denoise: %s: rows %u + k*%u, k < %u of a %u x %u image, not the whole %u x %u frame", what, r.row0,
+    snprintf(m, sizeof(m), "%s: %s: rows %u + k*%u, k < %u of a %u x %u image, not the whole %u x %u frame", fn, what, r.row0,
              r.rowStride, r.nRows, r.width, r.height, width, height);
     return m;
 }
@@ -1197,6 +1205,175 @@ int rt_denoise_host(rt_ctx* c, uint32_t width, uint32_t height, const float* rgb
     planes.ids = (uint32_t*)(d + 3 * bytes);
     if ((rc = rt_denoise(c, width, height, (const float*)d, &planes, &p, (float*)(d + 4 * bytes)))) return rc;
     RT_HIP(c, hipMemcpyAsync(out, d + 4 * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- temporal accumulation
+namespace {
+// The checks rt_temporal_accumulate and rt_temporal_accumulate_host share
+int check_temporal(rt_ctx* c, uint32_t width, uint32_t height, const CameraInfo* cam, const RtTemporalParams& p, const char* fn) {
+    const std::string f(fn);
+    if (width == 0 || height == 0) return c->fail(f + ": bad image geometry");
+    if ((uint64_t)width * height >= (1ull << 30) || height > 65535u * 16u) return c->fail(f + ": image too large");
+    if (!cam) return c->fail(f + ": the camera the frame was rendered with is required");
+    if (p.maxHistory == 0) return c->fail(f + ": maxHistory must be >= 1");
+    if (!(p.normalCos >= -1.f && p.normalCos <= 1.f)) return c->fail(f + ": normalCos must be in [-1, 1]");
+    if (!(std::isfinite(p.depthTolerance) && p.depthTolerance > 0.f)) return c->fail(f + ": depthTolerance must be finite and > 0");
+    if (!c->sc.nodes) return c->fail(f + " before rt_upload_scene");
+    return 0;
+}
+
+// frame_camera's plane of a camera
+TemporalCamera temporal_camera(const CameraInfo& ci) {
+    TemporalCamera t{};
+    memcpy(t.rot, ci.cameraRotation, 64);
+    memcpy(t.pos, ci.pos, 12);
+    t.planeHeight = ci.nearPlane * rt_tan(rt_radians(ci.fov * 0.5f)) * 2.f;
+    t.planeWidth = t.planeHeight * ci.aspectRatio;
+    t.bottomLeft[0] = -t.planeWidth / 2.f;
+    t.bottomLeft[1] = -t.planeHeight / 2.f;
+    t.bottomLeft[2] = 0.1f;
+    return t;
+}
+}  // namespace
+
+extern "C" {
+
+void rt_temporal_params_default(RtTemporalParams* p) {
+    if (p) *p = RtTemporalParams{32u, 0.9f, 0.02f};
+}
+
+int rt_temporal_reset(rt_ctx* c) {
+    if (!c) return -1;
+    c->tpHistValid = false;   // host state only: the next call reads no history, and the ctx stream orders it after the last one
+    return 0;
+}
+
+int rt_temporal_accumulate(rt_ctx* c, uint32_t width, uint32_t height, const CameraInfo* cam, const float* d_rgba, const RtAovBuffers* d_aovs,
+                           const RtTemporalParams* params, float* d_out, float* d_moments) {
+    if (!c) return -1;
+    RtTemporalParams p;
+    rt_temporal_params_default(&p);
+    if (params) p = *params;
+    int rc = check_temporal(c, width, height, cam, p, "rt_temporal_accumulate");
+    if (rc) return rc;
+    const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
+    const float4* rgba = (const float4*)d_rgba;
+    if (!rgba) {
+        if (!c->fbValid) return c->fail("rt_temporal_accumulate: no ctx-owned framebuffer: rt_render was never called with d_rgba = NULL");
+        if (!c->fbRows.whole(width, height)) return c->fail(not_whole("the ctx framebuffer", c->fbRows, width, height, "rt_temporal_accumulate"));
+        rgba = (const float4*)c->fbBuf.p;
+    }
+    const float4 *nd, *position, *albedo;
+    const uint4* ids;
+    if (!d_aovs) {
+        if (!c->aovValid) return c->fail("rt_temporal_accumulate: no ctx-owned AOV planes: rt_render_aovs was never called with d_out = NULL");
+        if (!c->aovRows.whole(width, height)) return c->fail(not_whole("the ctx AOV planes", c->aovRows, width, height, "rt_temporal_accumulate"));
+        const float4* a = (const float4*)c->aovBuf.p;   // rt_render_aovs's order: normalDepth, position, albedo, rayDir, ids
+        nd = a;
+        position = a + n;
+        albedo = a + 2 * n;
+        ids = (const uint4*)(a + 4 * n);
+    } else {
+        if (!d_aovs->normalDepth || !d_aovs->position || !d_aovs->albedo || !d_aovs->ids)
+            return c->fail("rt_temporal_accumulate: d_aovs needs the normalDepth, position, albedo and ids planes");
+        nd = (const float4*)d_aovs->normalDepth;
+        position = (const float4*)d_aovs->position;
+        albedo = (const float4*)d_aovs->albedo;
+        ids = (const uint4*)d_aovs->ids;
+    }
+    for (const void* o : {(const void*)d_out, (const void*)d_moments}) {
+        if (!o) continue;
+        for (const void* in : {(const void*)rgba, (const void*)nd, (const void*)position, (const void*)albedo, (const void*)ids})
+            if (overlap(o, in, bytes)) return c->fail("rt_temporal_accumulate: an output overlaps an input");
+    }
+    if (d_out && d_moments && overlap(d_out, d_moments, bytes)) return c->fail("rt_temporal_accumulate: d_out overlaps d_moments");
+    RT_HIP(c, hipSetDevice(c->device));
+    // growing a plane frees the old one, which a call still in flight may be using
+    if (c->tpHist[0].bytes < 3 * bytes || c->tpHist[1].bytes < 3 * bytes || (!d_out && c->tpOutBuf.bytes < bytes) || (!d_moments && c->tpMomBuf.bytes < bytes))
+        RT_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->tpWidth != width || c->tpHeight != height) c->tpHistValid = false;   // a history of another size is none
+    for (DevBuf& h : c->tpHist)
+        if (h.bytes < 3 * bytes) {
+            c->tpHistValid = false;
+            if ((rc = dev_alloc(c, h, 3 * bytes))) return rc;
+        }
+    float4 *out = (float4*)d_out, *mom = (float4*)d_moments;
+    if (!out) {
+        if ((rc = dev_alloc(c, c->tpOutBuf, bytes))) return rc;
+        out = (float4*)c->tpOutBuf.p;
+        c->tpOutPixels = n;
+        c->tpOutValid = true;
+    }
+    if (!mom) {
+        if ((rc = dev_alloc(c, c->tpMomBuf, bytes))) return rc;
+        mom = (float4*)c->tpMomBuf.p;
+        c->tpMomPixels = n;
+        c->tpMomValid = true;
+    }
+    const int next = 1 - c->tpCur;
+    const TemporalFrame f{rgba, nd, position, albedo, ids, c->tpHistValid ? (const float4*)c->tpHist[c->tpCur].p : nullptr,
+                          (float4*)c->tpHist[next].p, out, mom, width, height};
+    const dim3 grid((width + 15u) / 16u, (height + 15u) / 16u), block(RT_DN_BLOCK);
+    hipLaunchKernelGGL(k_tp_accumulate, grid, block, 0, c->stream, f, c->tpCam, c->sc.mats, c->sc.materialCount, (float)p.maxHistory, p.normalCos,
+                       p.depthTolerance);
+    RT_HIP(c, hipGetLastError());
+    c->tpCur = next;
+    c->tpHistValid = true;
+    c->tpWidth = width; c->tpHeight = height;
+    c->tpCam = temporal_camera(*cam);
+    return 0;
+}
+
+int rt_read_temporal_rgba_f32(rt_ctx* c, float* out, size_t nFloats) {
+    if (!c || !out) return -1;
+    if (!c->tpOutValid) return c->fail("no ctx-owned accumulated frame: rt_temporal_accumulate was never called with d_out = NULL");
+    if (nFloats != c->tpOutPixels * 4) return c->fail("rt_read_temporal_rgba_f32: size mismatch");
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipMemcpyAsync(out, c->tpOutBuf.p, nFloats * 4, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int rt_read_temporal_moments(rt_ctx* c, float* out, size_t nFloats) {
+    if (!c || !out) return -1;
+    if (!c->tpMomValid) return c->fail("no ctx-owned moments: rt_temporal_accumulate was never called with d_moments = NULL");
+    if (nFloats != c->tpMomPixels * 4) return c->fail("rt_read_temporal_moments: size mismatch");
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipMemcpyAsync(out, c->tpMomBuf.p, nFloats * 4, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int rt_temporal_accumulate_host(rt_ctx* c, uint32_t width, uint32_t height, const CameraInfo* cam, const float* rgba, const RtAovBuffers* aovs,
+                                const RtTemporalParams* params, float* out, float* moments) {
+    if (!c) return -1;
+    RtTemporalParams p;
+    rt_temporal_params_default(&p);
+    if (params) p = *params;
+    int rc = check_temporal(c, width, height, cam, p, "rt_temporal_accumulate_host");
+    if (rc) return rc;
+    if (!rgba || !out) return c->fail("rt_temporal_accumulate_host: rgba and out are required");
+    if (!aovs || !aovs->normalDepth || !aovs->position || !aovs->albedo || !aovs->ids)
+        return c->fail("rt_temporal_accumulate_host: aovs needs the normalDepth, position, albedo and ids planes");
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    RT_HIP(c, hipSetDevice(c->device));
+    if (c->tpHostBuf.bytes < 7 * bytes) RT_HIP(c, hipStreamSynchronize(c->stream));
+    if ((rc = dev_alloc(c, c->tpHostBuf, 7 * bytes))) return rc;
+    char* d = (char*)c->tpHostBuf.p;   // rgba, normalDepth, position, albedo, ids, out, moments
+    const void* src[5] = {rgba, aovs->normalDepth, aovs->position, aovs->albedo, aovs->ids};
+    for (int k = 0; k < 5; k++) RT_HIP(c, hipMemcpyAsync(d + k * bytes, src[k], bytes, hipMemcpyHostToDevice, c->stream));
+    RtAovBuffers planes{};
+    planes.normalDepth = (float*)(d + bytes);
+    planes.position = (float*)(d + 2 * bytes);
+    planes.albedo = (float*)(d + 3 * bytes);
+    planes.ids = (uint32_t*)(d + 4 * bytes);
+    if ((rc = rt_temporal_accumulate(c, width, height, cam, (const float*)d, &planes, &p, (float*)(d + 5 * bytes), (float*)(d + 6 * bytes)))) return rc;
+    RT_HIP(c, hipMemcpyAsync(out, d + 5 * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (moments) RT_HIP(c, hipMemcpyAsync(moments, d + 6 * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit,
-                    RtPlacement, RtSceneArrays, RtTexture, Sphere, Triangle, TrianglePoint)
+                    RtPlacement, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
 
@@ -409,6 +409,40 @@ class Renderer:
         self._check(self._l.rt_denoise_host(self._h, W, H, frame.ctypes.data, C.byref(b), C.byref(p), out.ctypes.data),
                     "rt_denoise_host")
         return out
+
+    def temporal_accumulate(self, pc_or_cam, frame=None, aovs=None, max_history=32, normal_cos=0.9, depth_tolerance=0.02, moments=False):
+        """Temporal accumulation by reprojection (rt_temporal_accumulate; DESIGN.md, "Temporal accumulation") of a whole frame into
+        the context's history: returns the accumulated (H, W, 4) float32 frame, to hand to denoise(), and with `moments` also the
+        (H, W, 4) plane (m1, m2, variance, history length). `pc_or_cam` is the PushConstants (or its CameraInfo) the frame was
+        rendered with. Without `frame` and `aovs` it takes the context's own frame and planes, as denoise() does; otherwise the
+        (H, W, 4) array and the dict render_aovs() returns, through rt_temporal_accumulate_host. The history is the same either way."""
+        cam = pc_or_cam.camInfo if isinstance(pc_or_cam, PushConstants) else pc_or_cam
+        p = RtTemporalParams(int(max_history), float(normal_cos), float(depth_tolerance))
+        fp = C.POINTER(C.c_float)
+        if frame is None and aovs is None:
+            H, W = self._aov_shape or (0, 0)
+            self._check(self._l.rt_temporal_accumulate(self._h, W, H, C.byref(cam), None, None, C.byref(p), None, None), "rt_temporal_accumulate")
+            out, mom = np.empty((H, W, 4), np.float32), np.empty((H, W, 4), np.float32)
+            self._check(self._l.rt_read_temporal_rgba_f32(self._h, out.ctypes.data_as(fp), out.size), "rt_read_temporal_rgba_f32")
+            if moments:
+                self._check(self._l.rt_read_temporal_moments(self._h, mom.ctypes.data_as(fp), mom.size), "rt_read_temporal_moments")
+            return (out, mom) if moments else out
+        if frame is None or aovs is None:
+            raise ValueError("temporal_accumulate() takes both a frame and its AOV planes, or neither (the context's own)")
+        frame = np.ascontiguousarray(frame, np.float32)
+        H, W = frame.shape[:2]
+        if frame.shape != (H, W, 4) or aovs["depth"].shape != (H, W):
+            raise ValueError(f"frame {frame.shape} and planes {aovs['depth'].shape}: not one (H, W, 4) frame and its (H, W) planes")
+        planes = numpy_to_aovs(aovs)
+        b = RtAovBuffers(**{k: v.ctypes.data for k, v in planes.items()})
+        out, mom = np.empty_like(frame), np.empty_like(frame)
+        self._check(self._l.rt_temporal_accumulate_host(self._h, W, H, C.byref(cam), frame.ctypes.data, C.byref(b), C.byref(p), out.ctypes.data,
+                                                        mom.ctypes.data), "rt_temporal_accumulate_host")
+        return (out, mom) if moments else out
+
+    def temporal_reset(self):
+        """Forgets the temporal history (rt_temporal_reset): after a scene edit, or to start a new sequence."""
+        self._check(self._l.rt_temporal_reset(self._h), "rt_temporal_reset")
 
     def pick(self, pc, width, height, x, y):
         """What the camera ray of pixel (x, y) hits: one row of render_aovs(), the record at x (scalars and 3-vectors)."""

@@ -69,6 +69,11 @@ def build_parser():
     ap.add_argument("--denoise", action="store_true",
                     help="write the frame through the edge-aware a-trous denoiser (Renderer.denoise, defaults; DESIGN.md, "
                          "\"Denoising\") to --out; it runs the first-hit AOV pass itself unless --aov-out did")
+    ap.add_argument("--temporal-frames", type=int, default=0, metavar="N",
+                    help="render N non-progressive frames of --rays-per-pixel samples with consecutive frameCounts and one fixed camera, "
+                         "accumulate them through the temporal pass (Renderer.temporal_accumulate, defaults; DESIGN.md, \"Temporal "
+                         "accumulation\") and write the result, through --denoise afterwards if given. One process only: the pass needs "
+                         "the whole frame on one GPU")
     # Ray Tracer Info panel
     ap.add_argument("--progressive", action="store_true")
     ap.add_argument("--frames-in-flight", type=int, default=1,
@@ -164,6 +169,10 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     device = args.device
+    if args.temporal_frames < 0:
+        raise SystemExit("--temporal-frames must be >= 0")
+    if args.temporal_frames and world > 1:   # before any rank waits for another
+        raise SystemExit(f"--temporal-frames needs the whole frame on one GPU: launched on {world} ranks, run it as a single process")
     if world > 1:
         import torch
         import torch.distributed as dist
@@ -191,7 +200,19 @@ def main(argv=None):
     t0 = time.perf_counter()
     frames = 0
     img = None
-    while True:
+    temporal = args.temporal_frames > 0
+    if temporal:   # N independent frames of one camera, blended by the temporal pass instead of the progressive framebuffer
+        pc.rayTraceParams.progressive, pc.rayTraceParams.singleRender = 0, 0
+        aovs = r.render_aovs(pc, W, H)
+        for k in range(args.temporal_frames):
+            pc.frameCount = k
+            r.render(pc, W, H, sync=False)
+            img = r.temporal_accumulate(pc)
+            frames += 1
+        r.totalSamples = args.temporal_frames * args.rays_per_pixel
+        if args.denoise:
+            img = r.denoise(img, aovs)
+    while not temporal:
         out = r.run_compute(pc, W, H, frames=args.frames_in_flight, **tile)
         if out is None:
             break
@@ -199,8 +220,9 @@ def main(argv=None):
         frames += 1
         if not args.progressive and not args.single_render:
             break  # every further dispatch would be this very frame again (frameCount does not advance)
-    denoise = args.denoise and img is not None
-    aovs = r.render_aovs(pc, W, H, **tile) if args.aov_out or denoise else None
+    denoise = args.denoise and img is not None and not temporal
+    if not temporal:
+        aovs = r.render_aovs(pc, W, H, **tile) if args.aov_out or denoise else None
     on = f"cuda:{device}" if args.backend == "nccl" else "cpu"
     if world > 1 and aovs is not None:
         aovs = gather_planes(aovs, H, world, rank, on)
@@ -228,7 +250,7 @@ def main(argv=None):
                 np.save(args.out, img)
             else:
                 from PIL import Image
-                Image.fromarray((srgb8(img) if world > 1 or denoise else r.read_rgba8_srgb())[..., :3]).save(args.out)
+                Image.fromarray((srgb8(img) if world > 1 or denoise or temporal else r.read_rgba8_srgb())[..., :3]).save(args.out)
             print("wrote", args.out)
         if args.aov_out:
             np.savez(args.aov_out, **aovs)

@@ -17,8 +17,17 @@ from . import _capi, engine
 
 
 class InteractiveSession:
-    def __init__(self, renderer, scene, width, height):
+    def __init__(self, renderer, scene, width, height, temporal=False, denoise=False):
+        """temporal: every draw() that dispatched also runs the first-hit AOV pass and, while the camera moves (progressive
+        accumulation off), the temporal pass (Renderer.temporal_accumulate); `filtered` is the result, `history_length` its N
+        plane, and `image` stays the raw frame. While the camera rests the reference's own progressive accumulation converges
+        and nothing is blended: `filtered` is the progressive framebuffer. The pass only records that frame (max_history = 1
+        passes it through and stores it), so the first moving frame blends into the converged image, not into the last
+        moving one. denoise: `filtered` also goes through Renderer.denoise. set_object, set_sphere
+        and set_material reset the temporal history (the pass takes the scene to be static)."""
         self.r, self.scene, self.W, self.H = renderer, scene, int(width), int(height)
+        self.temporal, self.denoise = bool(temporal), bool(denoise)
+        self.filtered, self.history_length = None, None
         self.pc = engine.push_constants(self.W, self.H)            # defaults of src/vk_engine.h:145-171
         self.params = self.pc.rayTraceParams
         self.cameraAngles = [4.0, 0.0, 0.0]                        # src/vk_engine.h:325
@@ -31,6 +40,8 @@ class InteractiveSession:
         self.dispatches = 0
         renderer.upload_scene(scene)
         renderer.clear_framebuffer()
+        if self.temporal:
+            renderer.temporal_reset()
         self._edited = None
         self._rotation()                                           # cameraInfo.cameraRotation as run_compute leaves it
 
@@ -88,12 +99,26 @@ class InteractiveSession:
             img = self.r.render(self.pc, self.W, self.H)            # run_compute: counts filled, one dispatch
             self.image = img
             self.dispatches += 1
+            if self.temporal or self.denoise:
+                self._filter(img)
         self._frameNumber = self._frameNumber + 1 if self.params.progressive else 0
         self.totalSamples += self.params.sampleLimit if self.totalSamples < self.params.sampleLimit else 0
         if not self.params.singleRender:
             self.totalSamples = 0
         self.frameTime = (time.perf_counter() - t0) * 1e3
         return img
+
+    # ---- temporal accumulation and denoising of the frame draw() just dispatched (not in the reference)
+    def _filter(self, img):
+        aovs = self.r.render_aovs(self.pc, self.W, self.H)
+        out = img
+        if self.temporal:
+            still = bool(self.params.progressive)
+            out, mom = self.r.temporal_accumulate(self.pc, max_history=1 if still else 32, moments=True)
+            self.history_length = mom[..., 3]
+            if still:
+                out = img
+        self.filtered = self.r.denoise(out, aovs) if self.denoise else out
 
     # ---- what is under the cursor: the camera ray of pixel (x, y) with the session's current camera (Renderer.pick)
     def pick(self, x, y):
@@ -116,12 +141,16 @@ class InteractiveSession:
         if m is not None:
             C.memmove(C.byref(a.materials[i]), C.byref(m), C.sizeof(_capi.RayMaterial))
         self.r._check(self.r._l.rt_update_materials(self.r._h, a.materials, a.nMaterials), "rt_update_materials")
+        if self.temporal:
+            self.r.temporal_reset()
 
     def set_sphere(self, i, position, radius, materialIndex):
         a = self._arrays()
         a.spheres[i].position[:] = [float(x) for x in position]
         a.spheres[i].radius, a.spheres[i].materialIndex = float(radius), int(materialIndex)
         self.r._check(self.r._l.rt_update_spheres(self.r._h, a.spheres, a.nSpheres), "rt_update_spheres")
+        if self.temporal:
+            self.r.temporal_reset()
 
     def set_object(self, i, placement=None, materialIndex=None, samplerIndex=None):
         a = self._arrays()
@@ -132,6 +161,8 @@ class InteractiveSession:
         if samplerIndex is not None:
             a.objects[i].samplerIndex = int(samplerIndex)
         self.r._check(self.r._l.rt_update_objects(self.r._h, a.objects, a.nObjects), "rt_update_objects")
+        if self.temporal:
+            self.r.temporal_reset()
 
     def arrays(self):
         """The scene as edited so far (RtSceneArrays), e.g. for the oracle."""

@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""rt_temporal_accumulate (defaults) against one 1-spp rt_render, the first-hit AOV pass and rt_denoise (K = 5) of the same frame,
+along a camera path that yaws 0.5 degrees per frame so that every timed call reprojects into a camera that differs from its
+own: the Sponza stand-in at 1920 x 1080 (scenes.sponza_camera) and Cornell with its spheres at 1728 x 1117 (the CLI's default
+size). The method is tools/denoise_timing.py's: all four write into device buffers (no read-back) and are timed with the host
+clock around the enqueue and an rt_sync; one warm-up of each, then `runs` of each, interleaved; median and min. The last call's
+moments plane is read back once, after the timing, for the share of the frame that kept a history. Then the error ratios of
+tests/test_temporal.py's quality test.
+usage: tools/temporal_timing.py [runs] [out.json]   (default: 7, profiles/temporal_timing.json)"""
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import ctypes as C  # noqa: E402
+
+import numpy as np  # noqa: E402
+
+from ray_tracer_amd import _capi, engine, scenes  # noqa: E402
+
+runs = int(sys.argv[1]) if len(sys.argv) > 1 else 7
+out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "temporal_timing.json")
+CASES = [("sponza stand-in", lambda: scenes.sponza(0)[0], scenes.sponza_camera, (2.0, 0.0, 0.0), 1920, 1080),
+         ("cornell + spheres", lambda: scenes.cornell(True)[0], engine.push_constants, (4.0, 0.0, 0.0), 1728, 1117)]
+# per pixel: five input records, four taps of three records, the frame, the moments and three history records, 16 bytes each
+BYTES_PER_PIXEL = (5 + 4 * 3 + 2 + 3) * 16
+
+r = engine.Renderer(0)
+hip = C.CDLL(_capi.LIB_PATH)   # device buffers from the HIP runtime the library is bound to (dlsym through its handle)
+hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+hip.hipFree.argtypes = [C.c_void_p]
+rows = []
+for label, make, camera, angles, W, H in CASES:
+    r.upload_scene(make())
+    bufs = [C.c_void_p() for _ in range(9)]
+    for b in bufs:
+        assert hip.hipMalloc(C.byref(b), W * H * 16) == 0
+    frame, acc, mom, dout = bufs[0].value, bufs[6].value, bufs[7].value, bufs[8].value
+    ptrs = {k: b.value for k, b in zip(engine.AOV_PLANES, bufs[1:6])}
+    planes = _capi.RtAovBuffers(**ptrs)
+    state = dict(k=0, pc=None)
+
+    def timed(fn):
+        t = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t) * 1e3
+
+    def render():
+        k = state["k"]
+        state["pc"] = camera(W, H, cameraAngles=(angles[0], angles[1] + 0.5 * k, angles[2]), progressive=0, raysPerPixel=1, frameCount=k)
+        state["k"] = k + 1
+        r.render(state["pc"], W, H, out_ptr=frame)   # sync=True: rt_sync
+
+    def aovs():
+        r.render_aovs(state["pc"], W, H, out_ptrs=ptrs)
+
+    def temporal():
+        r._check(r._l.rt_temporal_accumulate(r._h, W, H, C.byref(state["pc"].camInfo), frame, C.byref(planes), None, acc, mom), "rt_temporal_accumulate")
+        r.sync()
+
+    def denoise():
+        r._check(r._l.rt_denoise(r._h, W, H, acc, C.byref(planes), None, dout), "rt_denoise")
+        r.sync()
+
+    steps = (render, aovs, temporal, denoise)
+    for fn in steps:   # warm-up: code objects, the ray-cost probe, the path state, the histories and work planes
+        timed(fn)
+    t = [[] for _ in steps]
+    for _ in range(runs):
+        for ts, fn in zip(t, steps):
+            ts.append(timed(fn))
+    med = statistics.median
+    m = np.empty((H, W, 4), np.float32)
+    assert hip.hipMemcpy(m.ctypes.data, mom, W * H * 16, 2) == 0   # hipMemcpyDeviceToHost
+    N = m[..., 3]
+    row = dict(scene=label, width=W, height=H, spp=1, yaw_deg_per_frame=0.5, runs=runs,
+               frame_ms=round(med(t[0]), 3), frame_ms_min=round(min(t[0]), 3), frame_pipeline=r.last_pipeline(),
+               aov_ms=round(med(t[1]), 3), aov_ms_min=round(min(t[1]), 3),
+               temporal_ms=round(med(t[2]), 3), temporal_ms_min=round(min(t[2]), 3),
+               denoise_ms=round(med(t[3]), 3), denoise_ms_min=round(min(t[3]), 3),
+               temporal_share_of_frame=round(med(t[2]) / med(t[0]), 4), temporal_mpixels_per_s=round(W * H / med(t[2]) / 1e3, 1),
+               bytes_per_pixel=BYTES_PER_PIXEL, temporal_gbytes_per_s=round(W * H * BYTES_PER_PIXEL / med(t[2]) / 1e6, 1),
+               filtered_share=round(float((N > 0).mean()), 4), history_share_of_filtered=round(float((N > 1).sum() / max((N > 0).sum(), 1)), 4),
+               longest_history=float(N.max()))
+    rows.append(row)
+    for b in bufs:
+        hip.hipFree(b)
+    print(json.dumps(row), flush=True)
+
+from test_temporal import quality  # noqa: E402
+
+q = quality(r, scenes.cornell(True)[0], 160, 120)
+row = dict(scene="cornell + spheres", width=160, height=120, spp=4, frames=8, reference_spp=1024,
+           **{k: (round(v, 6) if isinstance(v, float) else v) for k, v in q.items()})
+rows.append(row)
+print(json.dumps(row), flush=True)
+r.close()
+with open(out, "w") as f:
+    json.dump(rows, f, indent=1)
+print("wrote", out)
