@@ -22,6 +22,8 @@ where the answer hangs on a rounding. With the margin eps a ray is ill-condition
   (b) some sphere has |disc| / (a r^2) < eps (r = 0: / (a |oc|^2)), or a root with |t| < eps;
   (c) the second-nearest accepted t is within eps (relative) of the nearest;
   (d) the hit has no finite error bound (below): the first-order count breaks down there, nothing can be asked of the ray.
+For the rays of a path, which start 1e-5 off the surface they leave, closest_hit(offset_rays=True) reads "|t| < eps" in (a) and (b)
+as "|t| is within a few of the candidate's own dst bounds of 0" (its docstring); the verdicts without it are unchanged.
 
 ERROR BOUNDS (closest_hit returns them per ray; u = 2^-24 is the unit roundoff of float32, round to nearest)
 
@@ -218,6 +220,14 @@ def texel_next(i, size, clamp):
 MAP_SLOTS = ("albedo", "alpha", "metalness", "bump")
 
 
+def material_records(arrays):
+    """Every material's full record from Scene.numpy(), the float32 values widened to float64: albedo [M, 3], emissionColor [M, 3],
+    emissionStrength, reflectance and ior [M] (src/vk_engine.h:69-79). What tests/paths_float64.py shades with."""
+    mt = arrays.get("materials", ())
+    f = (mt.view(np.float32).reshape(len(mt), -1) if len(mt) else np.zeros((0, 16), np.float32)).astype(np.float64)
+    return dict(albedo=f[:, 0:3], emissionColor=f[:, 4:7], emissionStrength=f[:, 7], reflectance=f[:, 8], ior=f[:, 9])
+
+
 class Mesh:
     def __init__(self, positions, normals, front_only, uvs=None):
         self.P = np.asarray(positions, np.float64).reshape(-1, 3, 3)
@@ -276,6 +286,7 @@ class BruteScene:
         self.meshes, self.objects = [], []          # objects: [mesh index, M, material, samplerIndex]
         self.materials = {}                         # material index -> dict(albedo, reflectance, <slot>Index ...); absent: no maps
         self.textures = []                          # uint8 [h, w, 4], in slot order
+        self.material_table = None                  # material_records() of the scene from_numpy read
 
     def set_textures(self, images):
         self.textures = [np.asarray(im, np.uint8) for im in images]
@@ -314,9 +325,12 @@ class BruteScene:
             f, u = sp.view(np.float32).reshape(len(sp), -1), sp.view(np.uint32).reshape(len(sp), -1)
             s.set_spheres(f[:, 0:3], f[:, 3], u[:, 4])
         tp = arrays["triPoints"].view(np.float32).reshape(-1, 8)
+        ob = arrays["objects"]
+        if not len(ob):                                                       # spheres alone
+            s.material_table = material_records(arrays)
+            return s
         tr = arrays["triangles"].view(np.uint32).reshape(len(arrays["triangles"]), -1)
         nodes = arrays["bvhNodes"].view(np.uint32).reshape(len(arrays["bvhNodes"]), -1)[:, 6:8]
-        ob = arrays["objects"]
         of, ou = ob.view(np.float32).reshape(len(ob), -1), ob.view(np.uint32).reshape(len(ob), -1)
         by_root = {}
         for i in range(len(ob)):
@@ -340,13 +354,23 @@ class BruteScene:
             mf, mi = mt.view(np.float32).reshape(len(mt), -1), mt.view(np.int32).reshape(len(mt), -1)
             for i in range(len(mt)):
                 s.set_material(i, mf[i, 0:3], mf[i, 8], albedoIndex=mi[i, 10], metalnessIndex=mi[i, 11], alphaIndex=mi[i, 12], bumpIndex=mi[i, 13])
+        s.material_table = material_records(arrays)
         return s
 
     # ------------------------------------------------------------------------------------------------------------
-    def closest_hit(self, origins, dirs, eps=EPS, max_pairs=3_000_000, maps=False):
+    def closest_hit(self, origins, dirs, eps=EPS, max_pairs=3_000_000, maps=False, offset_rays=False):
         """The nearest accepted hit of every ray, its conditioning verdict and its error bounds: a dict of arrays. With `maps`
         the texture maps take part (module docstring, TEXTURE MAPS): the alpha cut inside the search, and uv, texels, albedo,
-        mirror and the bumped normal of the hit."""
+        mirror and the bumped normal of the hit.
+
+        `offset_rays` (tests/paths_float64.py): the rays are a path's, which leave a surface from 1e-5 (or 0.01) off it along the
+        normal, so the surface they left is a candidate with |t| = 1e-5 / cos(theta) and rules (a) and (b) would call every such
+        ray ill. The only decision that hangs on a small t is its sign, and float32 gets t wrong by no more than the dst bound of
+        that very candidate, which shrinks with 1 / cos(theta) as t does. With offset_rays, "|t| < eps" in (a) and (b) reads
+        "|t| < max(1e-6, 4 x the candidate's own dst bound)": the first-order bound of the module docstring without the
+        transform's share, times 4 to cover that share and the second order; for a sphere, whose bound is complete to first order
+        (sphere_dst_bound), times 2. A ray that leaves a sphere of radius r from 1e-5 off it has |t| = 12 / r bounds: beyond
+        r = 6 float32 cannot tell which side of the sphere such a ray starts on. Everything else is as without it."""
         o = np.asarray(origins, np.float32).astype(np.float64).reshape(-1, 3)
         d = np.asarray(dirs, np.float32).astype(np.float64).reshape(-1, 3)
         n = len(o)
@@ -382,7 +406,12 @@ class BruteScene:
                 sq = np.sqrt(np.maximum(disc, 0.0))
                 tn, tf = (b - sq) / a, (b + sq) / a
                 ok = disc >= 0
-                ill |= ok & ((np.abs(tn) < eps) | (np.abs(tf) < eps))
+                if offset_rays:
+                    cc = np.repeat(self.sph_c[i][None], n, 0)
+                    bn, bfar = sphere_dst_bound(o, d, cc, r, np.ones(n, bool)), sphere_dst_bound(o, d, cc, r, np.zeros(n, bool))
+                    ill |= ok & ~((np.abs(tn) >= np.maximum(1e-6, 2 * bn)) & (np.abs(tf) >= np.maximum(1e-6, 2 * bfar)))
+                else:
+                    ill |= ok & ((np.abs(tn) < eps) | (np.abs(tf) < eps))
                 front = tn >= 0
                 t = np.where(front, tn, tf)
                 t = np.where(ok & (t >= 0), t, INF)
@@ -432,7 +461,13 @@ class BruteScene:
                         np.minimum.at(cut_t, rr[cut], tc[cut])
                         acc[ri[cut], ti[cut]] = False
                     cand = (m > -eps) & (t > -eps)
-                    bad = cand & ((np.abs(m) < eps) | (np.abs(t) < eps) |
+                    t_small = np.abs(t) < eps
+                    if offset_rays:
+                        v0 = mesh.P[:, 0]
+                        rl = np.sqrt(np.maximum((oo * oo).sum(axis=1)[:, None] - 2.0 * (oo @ v0.T) + (v0 * v0).sum(axis=1)[None, :], 0.0))
+                        sincos = np.abs(d0) / (dlen[rows, None] * (mesh.e1l * mesh.e2l)[None, :])
+                        t_small = ~(np.abs(t) >= np.maximum(1e-6, 4 * DST_C * U32 * (rl / dlen[rows, None] + np.abs(t)) / sincos))
+                    bad = cand & ((np.abs(m) < eps) | t_small |
                                   (fo & (np.abs(d0 - 1e-8) < eps * dlen[rows, None] * mesh.nlen[None, :])))
                     ill[rows] |= bad.any(axis=1)
                     tt = np.where(acc, t, INF)

@@ -1,0 +1,459 @@
+"""TEST INFRASTRUCTURE — the per-pixel estimator (everything between a hit record and a pixel) restated in numpy, float64.
+
+Written from DESIGN.md 2b ("The estimator, stated"), not from oracle/raytrace_oracle.cpp, include/rt_det_math.h or the kernels, and
+sharing no code with them: numpy only. Every closest-hit query (the path's own ray, the ray towards the light and the cosine probe)
+goes to brute_force.BruteScene.closest_hit: no BVH, no oracle. The random numbers are the PCG hash of DESIGN.md 2b in uint32, whose
+arithmetic is fixed (tests/test_glsl_builtins.py and tests/test_oracle_kat.py pin it); a draw is the binary32 number the shader
+holds, in both modes below. Pixels are vectorised: one array row per pixel, bounce by bounce, under masks. The debug heat maps
+(debug >= 0) are not restated: they count boxes.
+
+TWO MODES (as tests/test_temporal.py's Restatement has)
+  exact     every operation in float64. closest_hit reads its rays as float32 holds them (that is its contract), so a query sees the
+            path's ray rounded once; the path itself goes on unrounded.
+  rounded   the path arithmetic in np.float32, numpy's own elementary functions (sin, cos, log2, exp2, sqrt: a different
+            implementation from the project's, good to an ulp or so). The query is given the float32 ray; its dst, hitPoint and
+            normal are moved to the edge of brute_force's own error bounds (dst_bound, point_bound, normal_bound: what a float32
+            closest hit may be off by) under a seeded random sign and then rounded to float32. With maps, a textured albedo is moved
+            by the decode's 8 ulp and the product's rounding (17 u) the same way. Two exceptions, both forced:
+            - hitPoint moves by its full bound, but within the tangent plane. The bound charges the transform's error to every
+              direction and is 1e-4 on a Cornell wall (median), ten times the 1e-5 the next ray starts off the surface: moved
+              that far across the surface the path would go on from behind it (18 % of Cornell's pixels changed signature).
+              Across the surface a float32 hit point is off by a few 1e-7 (the intersection solves for the surface; what is
+              left is the rounding of o + t d and of the forward transform), which is what the snapshot's offsets presuppose.
+            - a normal one of whose components is exactly +-1 as float32 holds it stays where it is: an axis-aligned wall gives
+              exactly +-1 in float32 (the other components are exactly 0 or below 2^-24), which is what "an exact tie" below
+              relies on.
+            This mode measures what float32 rounding, as brute_force bounds it, does to a pixel, without looking at the code
+            under test. The bounds are worst cases, a hundred times what a float32 hit is off by, and dominate: with
+            SCALE = dict(dst_bound=0, point_bound=0, normal_bound=0) the largest distance to the exact run is 4e-5 on Cornell.
+
+BRANCH SIGNATURE  For every sample and segment of a pixel: whether the segment ran, the hit's identity (didHit, isSphere, object,
+triangle (its index in the brute-force mesh and its nine corner coordinates), frontFace), the BxDF taken, reflect or refract and
+whether by total internal reflection, whether each of the two light queries ended on an emitter, whether roulette ended the path,
+whether the guard fired.
+
+FRAGILE PIXELS are left out of every comparison. A pixel is fragile if
+  - one of its queries is ill-conditioned by brute_force's rules (eps = 1e-4, with offset_rays: a path's ray starts 1e-5 off the
+    surface it leaves, and "|t| < eps" would call every one of them ill; see closest_hit). Queries whose answer nothing reads
+    (the two light queries of a bounce the path ends at: the last segment, or a roulette break) are not asked;
+  - a hard decision of its exact run sits within MARGIN = 1e-4 of its threshold: schlick against the draw; ior * sine against 1; the
+    roulette draw against rrProb (after bounce 5 only: before that rrProb is 1 by decree); |n.x| against 1 in the tangent frame
+    (decided on the float32 value of n.x in both modes, and an exact tie |n.x| == 1 there is not fragile: see above); a component
+    of totalColor against 0 in the guard (an exact 0 is not near 0: black stays black in any arithmetic); -ray.dir.y against
+    -0.01, 0 and 0.4 on an environment miss (the two smoothsteps' edges, the sun mask); a light PDF that is not 0 but below 1e-4;
+  - its signature differs between the exact run and any of the rounded runs (four sign seeds).
+"""
+import numpy as np
+
+import brute_force as bf
+
+MARGIN = 1e-4            # hard decisions
+FLOOR = 1e-3             # |got - ref| <= T * max(|ref|, FLOOR), the floor tests/test_denoise.py and tests/test_temporal.py use
+SIGN_SEEDS = (1, 2, 3, 4)
+KINDS = ("nee", "mirror", "refraction", "fresnel", "tir", "emitter_after_diffuse", "sky_after_bounce", "rr_survived", "rr_ended", "guard")
+SCALE = {}               # for experiments: a factor per bound (dst_bound, point_bound, normal_bound) on the rounded mode's displacements
+REASONS = ("ill", "schlick", "tir", "roulette", "frame", "guard", "environment", "pdf")   # why the exact run calls a pixel fragile
+TEXEL_U = 17             # rounded mode, a textured albedo: the decode's 8 ulp (16 u) and the product with the material's albedo
+
+
+# ---------------------------------------------------------------------------------------------------------------- random numbers
+def pcg(state):
+    """state' = state * 747796405 + 2891336453; r = ((state' >> ((state' >> 28) + 4)) ^ state') * 277803737; r = (r >> 22) ^ r,
+    all modulo 2^32; the draw is float(r) / 4294967295.f in binary32 (the divisor rounds to 2^32). Returns (state', draw)."""
+    s = np.asarray(state).astype(np.uint64)
+    ns = (s * 747796405 + 2891336453) & 0xFFFFFFFF
+    r = (((ns >> ((ns >> 28) + 4)) ^ ns) * 277803737) & 0xFFFFFFFF
+    r = ((r >> 22) ^ r) & 0xFFFFFFFF
+    return ns.astype(np.uint32), r.astype(np.float32) / np.float32(4294967295.0)
+
+
+def frame_seed(frame_count):
+    """uint(random(frameCount) * 23892183.f): the draw from the state `frameCount`, the product in binary32, truncated."""
+    _, r = pcg(np.array([frame_count], np.uint32))
+    return int(np.uint32(np.float32(r[0] * np.float32(23892183.0))))
+
+
+def pixel_states(W, H, frame_count):
+    """The state a pixel's first draw starts from: y * W + x + frame_seed, modulo 2^32."""
+    y, x = np.mgrid[0:H, 0:W].astype(np.uint64)
+    return ((y * W + x + frame_seed(frame_count)) & 0xFFFFFFFF).astype(np.uint32).reshape(-1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- small vector helpers
+def _dot(a, b):
+    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+
+def _normalize(a):
+    return a / np.sqrt(_dot(a, a))[:, None]
+
+
+def _cross(a, b):
+    return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1)
+
+
+def _pow(x, y):
+    """GLSL pow: exp2(y * log2(x)), so NaN for x < 0 and 0 for x = 0, y > 0."""
+    return np.exp2(y * np.log2(x))
+
+
+def _smoothstep(e0, e1, x):
+    t = np.clip((x - e0) / (e1 - e0), 0, 1)
+    return t * t * (3 - 2 * t)
+
+
+def _mix(a, b, t):
+    return a * (1 - t) + b * t
+
+
+def _reflect(i, n):
+    return i - (2 * _dot(n, i))[:, None] * n
+
+
+def _refract(i, n, eta):
+    ni = _dot(n, i)
+    k = 1 - eta * eta * (1 - ni * ni)
+    r = eta[:, None] * i - (eta * ni + np.sqrt(np.maximum(k, 0)))[:, None] * n
+    return np.where((k < 0)[:, None], 0, r).astype(i.dtype)
+
+
+class Run:
+    """What one render leaves: the image, and per pixel the signature, the fragile flags of its own decisions and the kinds."""
+
+    def __init__(self, n, F, rounded):
+        self.F = F
+        self.rng = None if rounded is None else np.random.default_rng(rounded)
+        self.reasons = {k: np.zeros(n, bool) for k in REASONS}
+        self.kinds = {k: np.zeros(n, bool) for k in KINDS}
+        self.codes, self.corners = [], []
+        self.image = None
+        self.magenta = None
+        self.all_zeroed = None
+        self.queries = 0
+
+    def flag(self, reason, rows, mask):
+        self.reasons[reason][rows] |= mask
+
+    @property
+    def fragile(self):
+        return np.any(list(self.reasons.values()), axis=0)
+
+
+class Estimator:
+    """The estimator of DESIGN.md 2b over a brute_force.BruteScene (from_numpy: it needs material_table) and one set of push
+    constants. `maps`: the texture maps take part (brute_force's maps=True: albedo texel, metalness texel, alpha cut, bump)."""
+
+    def __init__(self, brute, pc, W, H, maps=False):
+        self.bs, self.W, self.H, self.maps = brute, int(W), int(H), bool(maps)
+        cam, env, td = pc.camInfo, pc.environment, pc.rayTraceParams
+        self.rotation = np.array(list(cam.cameraRotation), np.float64).reshape(4, 4).T          # column-major
+        self.pos = np.array(list(cam.pos), np.float64)
+        self.near, self.aspect, self.fov = float(cam.nearPlane), float(cam.aspectRatio), float(cam.fov)
+        self.env_on = float(env.lightDir[3]) == 1.0
+        self.horizon, self.zenith = np.array(list(env.horizonColor), np.float64), np.array(list(env.zenithColor), np.float64)
+        self.ground, self.light_dir = np.array(list(env.groundColor), np.float64), np.array(list(env.lightDir), np.float64)[:3]
+        assert td.debug < 0, "the heat maps are not restated"
+        self.samples = int(td.sampleLimit if td.singleRender else td.raysPerPixel)
+        self.bounce_limit, self.progressive, self.frame_count = int(td.bounceLimit), bool(td.progressive), int(pc.frameCount)
+        assert brute.material_table is not None and len(brute.material_table["ior"]), "BruteScene.from_numpy of a scene with materials"
+
+    # ------------------------------------------------------------------------------------------------------------ queries
+    def _query(self, o, d, R):
+        """closest_hit of the rays, in the run's arithmetic: a dict of arrays over the rays."""
+        F = R.F
+        res = self.bs.closest_hit(o, d, maps=self.maps, offset_rays=True)
+        R.queries += len(o)
+        hit = res["didHit"]
+        dst, p, n = res["dst"].copy(), res["hitPoint"].copy(), res["normal"].copy()
+        albedo = res["albedo"].copy() if self.maps else None
+        if R.rng is not None:
+            k = len(o)
+            ok = hit & ~res["ill"]
+            bound = lambda name: np.where(ok & np.isfinite(res[name]), res[name], 0.0) * SCALE.get(name, 1.0)   # noqa: E731
+            s3 = lambda: R.rng.choice(np.array([-1.0, 1.0]), size=(k, 3)) / np.sqrt(3.0)  # noqa: E731
+            dst = dst + R.rng.choice(np.array([-1.0, 1.0]), size=k) * bound("dst_bound")
+            s = s3()
+            p = p + (s - (s * n).sum(axis=1, keepdims=True) * n) * bound("point_bound")[:, None]     # within the tangent plane
+            tie = (np.abs(n.astype(np.float32)) == 1).any(axis=1)
+            n = np.where(tie[:, None], n, n + s3() * bound("normal_bound")[:, None])
+            if self.maps:
+                textured = res["texel"]["albedo"][:, 0] >= 0
+                albedo = np.where(textured[:, None], albedo * (1.0 + s3() * np.sqrt(3.0) * TEXEL_U * bf.U32), albedo)
+        with np.errstate(all="ignore"):
+            out = dict(didHit=hit, isSphere=res["isSphere"], object=res["objectHitIndex"], tri=np.where(hit & ~res["isSphere"], res["triIndex"], 0),
+                       front=res["frontFace"], mat=res["materialIndex"], ill=res["ill"], corners=res["corners"].reshape(len(o), 9),
+                       dst=dst.astype(F), p=p.astype(F), n=n.astype(F))
+        if self.maps:
+            out["albedo"], out["mirror"] = albedo.astype(F), res["mirror"]
+        return out
+
+    # ------------------------------------------------------------------------------------------------------------ pieces
+    def camera(self, F):
+        """Origin and direction of every pixel's ray (the same for all its samples): rows of [H * W, 3]."""
+        W, H = self.W, self.H
+        height = F(self.near) * np.tan(np.radians(F(self.fov) * F(0.5))) * F(2)
+        width = height * F(self.aspect)
+        y, x = np.mgrid[0:H, 0:W]
+        u, v = x.reshape(-1).astype(F) / F(W), y.reshape(-1).astype(F) / F(H)
+        point = np.stack([-width / F(2) + width * u, -height / F(2) + height * v, np.full(W * H, 0.1, F)], 1)
+        d = _normalize(point)
+        M = self.rotation.astype(F)
+        d = np.stack([((M[r, 0] * d[:, 0] + M[r, 1] * d[:, 1]) + M[r, 2] * d[:, 2]) + M[r, 3] for r in range(3)], 1)   # w = 1
+        o = np.repeat(self.pos.astype(F)[None], W * H, 0)
+        assert d.dtype == F and o.dtype == F
+        return o, d
+
+    def environment(self, d, F):
+        """The environment's radiance along d, and whether -d.y sits within MARGIN of one of its three thresholds."""
+        if not self.env_on:
+            return np.zeros((len(d), 3), F), np.zeros(len(d), bool)
+        up = -d[:, 1]
+        hor, zen, gnd = self.horizon.astype(F), self.zenith.astype(F), self.ground.astype(F)
+        sky_t = _pow(_smoothstep(F(0), F(0.4), up), F(0.35))
+        sky = _mix(hor[None, :3], zen[None, :3], sky_t[:, None])
+        to_sun = -self.light_dir.astype(F)
+        sun = _pow(np.fmax(F(0), (d[:, 0] * to_sun[0] + d[:, 1] * to_sun[1]) + d[:, 2] * to_sun[2]), hor[3]) * zen[3]
+        g2s = _smoothstep(F(-0.01), F(0), up)
+        mask = (g2s >= 1).astype(F)
+        out = _mix(gnd[None, :], sky, g2s[:, None]) + (sun * mask)[:, None]
+        near = np.zeros(len(d), bool)
+        for edge in (-0.01, 0.0, 0.4):
+            near |= np.abs(up.astype(np.float64) - edge) < MARGIN
+        return out.astype(F), near
+
+    # ------------------------------------------------------------------------------------------------------------ one sample
+    def _trace(self, o0, d0, state, R):
+        """One sample of every pixel: its radiance [N, 3], whether the guard zeroed it, the states after its draws."""
+        F, B = R.F, self.bounce_limit
+        N = len(state)
+        tbl = self.bs.material_table
+        Le = tbl["emissionColor"].astype(F) * tbl["emissionStrength"].astype(F)[:, None]
+        emissive = tbl["emissionStrength"] != 0
+        ior_of, albedo_of, mirror_of = tbl["ior"].astype(F), tbl["albedo"].astype(F), tbl["reflectance"] != 0
+        INV_PI, PI2 = F(1.0 / np.pi), F(2.0 * np.pi)
+        total, att, direct = np.zeros((N, 3), F), np.ones((N, 3), F), np.zeros((N, 3), F)
+        misw = np.ones(N, F)
+        o, d = o0.copy(), d0.copy()
+        alive, zeroed, after_diffuse = np.ones(N, bool), np.zeros(N, bool), np.zeros(N, bool)
+
+        def draw(rows):
+            state[rows], r = pcg(state[rows])
+            return r.astype(F)
+
+        for j in range(B + 1):
+            code, corners = np.zeros(N, np.int64), np.zeros((N, 9))
+            R.codes.append(code); R.corners.append(corners)
+            idx = np.flatnonzero(alive)
+            if not len(idx):
+                continue
+            h = self._query(o[idx], d[idx], R)
+            R.flag("ill", idx, h["ill"])
+            hit = h["didHit"]
+            code[idx] = 1 | hit << 1 | (hit & h["isSphere"]) << 2 | (hit & h["front"]) << 3 | np.where(hit, h["object"], 0) << 12 | h["tri"] << 32
+            corners[idx] = np.where(hit[:, None], h["corners"], 0)
+            # ---- a miss: the environment through the attenuation, and the path ends
+            im = idx[~hit]
+            if len(im):
+                env, near = self.environment(d[im], F)
+                total[im] += att[im] * env
+                R.flag("environment", im, near)
+                alive[im] = False
+                if j > 0 and self.env_on:
+                    R.kinds["sky_after_bounce"][im] = True
+            # ---- a hit: what the previous bounce left pending, or the surface's own emission after a specular bounce
+            k = np.flatnonzero(hit)
+            ih, mat = idx[k], h["mat"][k]
+            if not len(ih):
+                continue
+            emission = Le[mat] / misw[ih][:, None]
+            sentinel = direct[ih, 0] == -1
+            final = np.where(sentinel[:, None], emission, direct[ih])
+            total[ih] += final * att[ih]
+            if j == 0:
+                total[ih] += emission
+            t = total[ih]
+            bad = np.isnan(t).any(axis=1) | (t < 0).any(axis=1)
+            R.flag("guard", ih, ((t != 0) & (np.abs(t) < MARGIN)).any(axis=1))
+            R.kinds["nee"][ih] |= after_diffuse[ih] & ~sentinel & (direct[ih] != 0).any(axis=1) & ~bad
+            R.kinds["emitter_after_diffuse"][ih] |= after_diffuse[ih] & emissive[mat] & ~bad
+            ib = ih[bad]
+            total[ib], alive[ib], zeroed[ib] = 0, False, True
+            R.kinds["guard"][ib] = True
+            code[ib] |= 1 << 11
+            k, ih, mat = k[~bad], ih[~bad], mat[~bad]
+            if not len(ih):
+                continue
+            # ---- the BxDF: mirror, dielectric, diffuse, in that order of precedence
+            n, p, inc = h["n"][k], h["p"][k], d[ih]
+            mirror = h["mirror"][k] if self.maps else mirror_of[mat]
+            glass = ~mirror & (tbl["ior"][mat] != -1)
+            diffuse = ~mirror & ~glass
+            new_d, radiance = np.zeros((len(ih), 3), F), np.ones((len(ih), 3), F)
+            new_direct, sign, new_w = np.full((len(ih), 3), -1, F), np.ones(len(ih), F), np.ones(len(ih), F)
+            reflects, tir = mirror.copy(), np.zeros(len(ih), bool)
+            new_d[mirror] = _reflect(inc[mirror], n[mirror])
+            R.kinds["mirror"][ih[mirror]] = True
+            g = np.flatnonzero(glass)
+            if len(g):
+                eta = np.where(h["front"][k][g], F(1) / ior_of[mat[g]], ior_of[mat[g]]).astype(F)
+                cosine = _dot(-inc[g], n[g])
+                sine = np.sqrt(1 - cosine * cosine)
+                internal = eta * sine > 1
+                R.flag("tir", ih[g], np.abs(eta * sine - 1) < MARGIN)
+                r0 = (1 - eta) / (1 + eta)
+                r0 = r0 * r0
+                schlick = r0 + (1 - r0) * _pow(1 - cosine, F(5))
+                u = np.zeros(len(g), F)
+                u[~internal] = draw(ih[g][~internal])                       # no draw on total internal reflection
+                fresnel = ~internal & (schlick > u)
+                R.flag("schlick", ih[g], ~internal & (np.abs(schlick - u) < MARGIN))
+                refl = internal | fresnel
+                new_d[g] = np.where(refl[:, None], _reflect(inc[g], n[g]), _refract(inc[g], n[g], eta))
+                sign[g] = np.where(refl, F(1), np.sign(_dot(n[g], inc[g])))
+                reflects[g], tir[g] = refl, internal
+                R.kinds["tir"][ih[g][internal]] = True
+                R.kinds["fresnel"][ih[g][fresnel]] = True
+                R.kinds["refraction"][ih[g][~refl]] = True
+            f = np.flatnonzero(diffuse)
+            if len(f):
+                rows = ih[f]
+                albedo = h["albedo"][k][f] if self.maps else albedo_of[mat[f]]
+                origin = p[f] + n[f] * F(0.01)
+                lx, lz = draw(rows), draw(rows)
+                point = np.stack([_mix(F(-0.33333), F(0.33333), lx), np.full(len(f), -1.5, F), _mix(F(-0.33333), F(0.33333), lz)], 1)
+                to_light = _normalize(point - origin)
+                r1, r2 = draw(rows), draw(rows)
+                phi, s2 = PI2 * r1, np.sqrt(r2)
+                nx32 = np.abs(n[f][:, 0].astype(np.float32))                # the decision on the number float32 holds
+                R.flag("frame", rows, (nx32 != 1) & (np.abs(np.abs(n[f][:, 0].astype(np.float64)) - 1) < MARGIN))
+                axis = np.where((nx32 < 1)[:, None], np.array([1, 0, 0], F), np.array([0, 0, 1], F))
+                tangent = _normalize(_cross(n[f], axis))
+                bitangent = _cross(n[f], tangent)
+                cos_dir = (tangent * (np.cos(phi) * s2)[:, None] + bitangent * (np.sin(phi) * s2)[:, None]) + n[f] * np.sqrt(1 - r2)[:, None]
+                pdf_c = np.fmax(F(0), _dot(cos_dir, n[f]) * INV_PI)
+                radiance[f] = (albedo * INV_PI) * _dot(n[f], cos_dir)[:, None] / pdf_c[:, None]
+                new_d[f] = cos_dir
+                new_direct[f] = 0
+            att[ih] = att[ih] * radiance
+            # ---- Russian roulette: one draw at every bounce, a probability below 1 only after bounce 5
+            rr = np.fmin(np.fmax(np.fmax(att[ih, 0], att[ih, 1]), att[ih, 2]), F(0.95))
+            if j <= 5:
+                rr = np.ones(len(ih), F)
+            u = draw(ih)
+            ended = u > rr
+            if j > 5:
+                R.flag("roulette", ih, np.abs(u - rr) < MARGIN)
+                R.kinds["rr_ended"][ih[ended]] = True
+                R.kinds["rr_survived"][ih[~ended]] = True
+            code[ih] |= np.where(mirror, 1, np.where(glass, 2, 3)) << 4 | reflects.astype(np.int64) << 6 | tir.astype(np.int64) << 7 | ended.astype(np.int64) << 10
+            # ---- the two light queries of a diffuse bounce, where a later segment reads them
+            if len(f) and j < B:
+                q = ~ended[f]
+                fq, rows = f[q], ih[f][q]
+                if len(rows):
+                    nn, alb, L, C, org = n[fq], albedo[q], to_light[q], cos_dir[q], origin[q]
+                    hl = self._query(org, L, R)                              # asked twice by the shader: the same ray, the same answer
+                    hp = self._query(org, C, R)
+                    R.flag("ill", rows, hl["ill"] | hp["ill"])
+                    lit, probe_lit = hl["didHit"] & emissive[hl["mat"]], hp["didHit"] & emissive[hp["mat"]]
+                    pdf_l = np.where(lit, hl["dst"] * hl["dst"] / (-L[:, 1] * F(0.4444444)), F(0)).astype(F)
+                    pdf_lc = np.fmax(F(0), _dot(L, nn) * INV_PI)
+                    w1 = pdf_l * pdf_l / (pdf_l * pdf_l + pdf_lc * pdf_lc)
+                    w1 = np.where(np.isnan(w1), F(0), w1)
+                    pdf_p = np.where(probe_lit, hp["dst"] * hp["dst"] / (-C[:, 1] * F(0.4444444)), F(0)).astype(F)
+                    pdf_cc = pdf_c[q]
+                    w2 = pdf_cc * pdf_cc / (pdf_p * pdf_p + pdf_cc * pdf_cc)
+                    w2 = np.where(np.isnan(w2), F(0), w2)
+                    for pdf in (pdf_l, pdf_p):
+                        R.flag("pdf", rows, (pdf != 0) & (np.abs(pdf) < MARGIN))
+                    light_le = Le[np.where(hl["didHit"], hl["mat"], 0)]       # a miss reads material 0 (times 0)
+                    weight = np.where(pdf_l == 0, F(0), w1 / pdf_l)
+                    new_direct[fq] = light_le * (((alb * INV_PI) * np.fmax(F(0), _dot(nn, L))[:, None]) * weight[:, None])
+                    new_w[fq] = w2
+                    code[rows] |= lit.astype(np.int64) << 8 | probe_lit.astype(np.int64) << 9
+            # ---- the path ends, or goes on from just off the surface
+            alive[ih[ended]] = False
+            go = ~ended
+            ig = ih[go]
+            att[ig] = att[ig] * (F(1) / rr[go])[:, None]
+            direct[ig], misw[ig] = new_direct[go], new_w[go]
+            after_diffuse[ig] = diffuse[go]
+            o[ig] = p[go] + (n[go] * sign[go][:, None]) * F(0.00001)
+            d[ig] = new_d[go]
+            assert total.dtype == F and att.dtype == F and o.dtype == F and d.dtype == F and direct.dtype == F and misw.dtype == F
+        return total, zeroed
+
+    # ------------------------------------------------------------------------------------------------------------ the pixel
+    def render(self, rounded=None, prev=None):
+        """The frame [H, W, 4] as float64 numbers (of float32 precision in the rounded mode) in a Run. `rounded`: None or the
+        sign seed. `prev`: the image the progressive blend reads, zeros if None."""
+        F = np.float64 if rounded is None else np.float32
+        N = self.W * self.H
+        R = Run(N, F, rounded)
+        with np.errstate(all="ignore"):
+            o, d = self.camera(F)
+            state = pixel_states(self.W, self.H, self.frame_count)
+            acc, all_zeroed = np.zeros((N, 3), F), np.ones(N, bool)
+            for _ in range(self.samples):
+                c, zeroed = self._trace(o, d, state, R)
+                acc = acc + c
+                all_zeroed &= zeroed
+            colour = acc / F(self.samples)
+            if self.progressive:
+                w = F(1) / (F(self.frame_count) + F(1))
+                old = np.zeros((N, 3), F) if prev is None else np.asarray(prev)[..., :3].reshape(N, 3).astype(F)
+                colour = old * (F(1) - w) + colour * w
+            magenta = np.isnan(colour).any(axis=1) | np.isinf(colour).any(axis=1)
+            colour = np.where(magenta[:, None], np.array([1, 0, 1], F), colour)
+            assert colour.dtype == F
+        R.image = np.concatenate([colour.astype(np.float64), np.ones((N, 1))], 1).reshape(self.H, self.W, 4)
+        R.magenta, R.all_zeroed = magenta, all_zeroed & (self.samples > 0)
+        R.codes, R.corners = np.stack(R.codes, 1), np.stack(R.corners, 1)
+        return R
+
+
+class Frame:
+    """One frame of a case: the exact run, the rounded runs, the fragile pixels and the rounded-to-exact distance."""
+
+    def __init__(self, exact, rounded, inherited=None):
+        self.exact, self.rounded = exact, rounded
+        fragile = exact.fragile.copy()
+        for r in rounded:
+            fragile |= (r.codes != exact.codes).any(axis=1) | (r.corners != exact.corners).any(axis=(1, 2))
+        if inherited is not None:
+            fragile |= inherited                     # a progressive frame carries what its history hangs on
+        self.fragile = fragile
+        self.compared = ~fragile.reshape(exact.image.shape[:2])
+        self.image = exact.image
+        self.magenta = (exact.magenta & ~fragile).reshape(exact.image.shape[:2])         # to be matched exactly: (1, 0, 1)
+        self.zeroed = (exact.all_zeroed & ~fragile).reshape(exact.image.shape[:2])       # the guard zeroed every sample
+        self.kinds = {k: int((v & ~fragile).sum()) for k, v in exact.kinds.items()}
+        self.rounded_distance = max((distance(r.image, exact.image, self.compared) for r in rounded), default=0.0)
+
+    @property
+    def excluded(self):
+        return float(self.fragile.mean())
+
+
+def distance(got, ref, compared):
+    """Largest |got - ref| / max(|ref|, FLOOR) over the colour channels of the compared pixels (inf if one is not a number)."""
+    g, r = np.asarray(got, np.float64)[..., :3][compared], np.asarray(ref, np.float64)[..., :3][compared]
+    if not len(g):
+        return 0.0
+    with np.errstate(all="ignore"):
+        e = np.abs(g - r) / np.maximum(np.abs(r), FLOOR)
+    return float(np.where(np.isnan(e), np.inf, e).max())
+
+
+def study(brute, pcs, W, H, maps=False, chain=False, seeds=SIGN_SEEDS):
+    """A Frame for each of the push constants `pcs`. `chain`: the frames are one progressive history from a cleared image, each
+    run reading its own previous frame, and a pixel fragile in one frame stays fragile in the later ones."""
+    frames, prev, inherited = [], [None] * (1 + len(seeds)), None
+    for pc in pcs:
+        est = Estimator(brute, pc, W, H, maps)
+        runs = [est.render(None, prev[0])] + [est.render(s, prev[1 + i]) for i, s in enumerate(seeds)]
+        fr = Frame(runs[0], runs[1:], inherited)
+        frames.append(fr)
+        if chain:
+            prev, inherited = [r.image for r in runs], fr.fragile
+    return frames

@@ -15,8 +15,9 @@ from ray_tracer_amd import engine, scenes
 from util import cornell_scene, model_scene
 
 
-def _scenes():
-    yield "cornell", cornell_scene(True), {}
+def emitters_scene():
+    """Cornell with an emissive sphere, glass right under the ceiling light and a second light coplanar with the ceiling (also the
+    "emitters" case of tests/test_paths_float64.py)."""
     s = cornell_scene(True)
     glow = s.add_material(engine.default_material(albedo=(0.1, 0.1, 0.1), emissionColor=(0.3, 0.6, 1.0), emissionStrength=1.2))
     s.set_sphere(3, (-0.6, -0.9, 0.4), 0.2, glow)
@@ -24,7 +25,12 @@ def _scenes():
     quad = np.array([[[-0.2, -1.5, 0.5], [0.2, -1.5, 0.5], [0.2, -1.5, 0.8]], [[-0.2, -1.5, 0.5], [0.2, -1.5, 0.8], [-0.2, -1.5, 0.8]]], np.float32)
     nq = np.zeros_like(quad); nq[..., 1] = 1
     s.add_mesh("coplanar_light", quad, nq, engine.placement(), glow)   # in the plane of the ceiling: equal distances
-    yield "emitters", s, dict(bounceLimit=6)
+    return s
+
+
+def _scenes():
+    yield "cornell", cornell_scene(True), {}
+    yield "emitters", emitters_scene(), dict(bounceLimit=6)
     s = model_scene("bunny.obj", material=0, spheres=True)
     yield "bunny", s, {}
     s, _ = scenes.sponza(0, ntris=20000)

@@ -1,0 +1,383 @@
+"""The path estimator (everything between a hit record and a pixel: DESIGN.md 2b) against tests/paths_float64.py, a numpy float64
+restatement that shares nothing with the oracle or the kernels and asks tests/brute_force.py for every closest hit. The CPU half holds
+oracle/raytrace_oracle.cpp to it, the GPU half both pipelines (k_shade / k_resolve / k_blend_frames and k_render_fused) and both
+map kernels (k_shade_maps, k_render_fused_maps).
+
+A pixel is compared where it is not fragile (paths_float64's docstring): |got - ref| <= T * max(|ref|, 1e-3) per channel, alpha
+exactly 1, and a pixel whose exact run ends in magenta or whose every sample the guard zeroed is matched exactly.
+
+T_MEASURED is the largest distance between the rounded and the exact run of the restatement over the compared pixels of the cases
+that share T (the restatement alone: neither the oracle's nor the kernels' distances, which are printed, ever set it); T is four
+times that, rounded up to one significant figure, the margin tests/test_temporal.py gives a kernel for its own, equally valid
+order of operations. emitters_b3 and sphere_cave have a T of their own, by the same rule, rather than loosening the rest (it is
+not the glass that forces them: in emitters_b3 a hit point moved by its bound, 1e-4, shifts a grazing light sample on a sphere,
+n.L about 1e-3, by a tenth of itself; in sphere_cave ten segments compound). The rounded run is far harsher than float32 is: it
+moves every hit to the edge of brute_force's bounds (median 1e-4 on a Cornell hit point, against the 1e-6 a float32 hit point is
+really off by); with the displacements off its worst distance is 4e-5. So the oracle sits some hundred times nearer to the exact
+run than T asks, and T is what the bounds can promise, not what float32 does. DESIGN.md 2a lists which mutations it still catches.
+
+Measured on the restatement (64 x 48; "excluded" is the largest fragile share of a frame, at most 10 % allowed; the counts are
+compared pixels with at least one such event, summed over the frames; "oracle" is the oracle's largest distance, printed only):
+
+    case          frames  excluded  rounded   T      oracle   nee   mirror  refrac-  fresnel  tir  emitter   sky after  guard  roulette
+                                    distance                                tion                   after d.  a bounce          survived / ended
+    cornell_b2    4       4.56 %    7.34e-3   4e-2   1.3e-4   5130  744     834      210      42   190       0          0
+    cornell_4spp  1       2.90 %    2.88e-3   4e-2   5.1e-5   968   260     287      105      0    85        0          0
+    bunny_b2      2       4.23 %    6.97e-3   4e-2   7.9e-5   2697  0       253      71       0    107       0          0
+    emitters_b3   2       6.32 %    1.17e-1   5e-1   1.7e-4   1851  499     739      196      50   173       0          0
+    sphere_cave   2       0.94 %    6.11e-2   3e-1   6.7e-4   5890  1635    2731     336      34   456       0          1423   1396 / 4000
+    maps          1       4.52 %    6.97e-3   4e-2   2.3e-5   1254  146     0        0        0    46        0          0
+    progressive   3       7.29 %    7.34e-3   4e-2   5.6e-5   3700  562     629      141      32   125       0          0
+    open_sky      2       0.23 %    7.72e-3   4e-2   3.5e-4   0     361     490      56       0    0         1451       0
+
+T_MEASURED = 7.7e-3 (open_sky), T = 4e-2. Nearly all of the excluded share is brute_force's verdict on a query (4.4 % of 4.6 % in
+cornell_b2); the progressive frames inherit their history's. In sphere_cave a quarter of the pixels have every sample zeroed by
+the guard (the emissive sphere seen from behind) and are matched exactly.
+
+open_sky is not in the list the work started from: the Cornell box is closed to a path that starts inside it (its walls' front
+faces look inwards), so there only a camera ray can reach the environment, and the sky after a bounce, the sun's lobe and the
+dropped direct term of a bounce whose next segment misses need a scene that is open. The guard fires in sphere_cave, so
+emitters_b3 needed no aimed pixels.
+"""
+import numpy as np
+import pytest
+
+from ray_tracer_amd import engine
+from oracle import pyoracle
+import brute_force as bf
+import paths_float64 as pf
+from util import cornell_scene, model_scene
+from test_denoise import _checker_scene
+from test_light_queries_oracle import emitters_scene
+
+T_MEASURED = 7.7e-3     # largest rounded-to-exact distance of the restatement over the cases that share T (the table above)
+T = 4e-2                # 4 x T_MEASURED, rounded up to one significant figure
+T_MEASURED_OWN = dict(emitters_b3=1.17e-1, sphere_cave=6.1e-2)    # the two cases whose own distance would loosen the rest
+T_OWN = dict(emitters_b3=5e-1, sphere_cave=3e-1)
+MAX_FRAGILE = 0.10
+W, H = 64, 48
+SKY = dict(environmentOn=True)
+
+# compared pixels per kind, summed over a case's frames, that the case is there for
+FLOORS = {
+    "cornell_b2": dict(nee=500, mirror=100, refraction=100, fresnel=30, emitter_after_diffuse=100),
+    "cornell_4spp": dict(nee=500, mirror=100, refraction=100, fresnel=30),
+    "bunny_b2": dict(nee=500, refraction=100, fresnel=30),
+    "emitters_b3": dict(nee=500, mirror=100, refraction=100, fresnel=30, emitter_after_diffuse=100),
+    "sphere_cave": dict(nee=500, mirror=100, refraction=100, fresnel=30, emitter_after_diffuse=100, rr_survived=200, rr_ended=50, tir=10, guard=10),
+    "maps": dict(nee=500, mirror=100),
+    "progressive": dict(nee=500, mirror=100, refraction=100, fresnel=30),
+    "open_sky": dict(mirror=100, refraction=100, fresnel=30, sky_after_bounce=100),
+}
+CASES = list(FLOORS)
+
+
+def _spheres_scene(materials, spheres):
+    s = engine.Scene()
+    for m in materials:
+        s.add_material(engine.default_material(**m))
+    for i, (c, r, m) in enumerate(spheres):
+        s.set_sphere(i, c, r, m)
+    return s
+
+
+def _cave_scene():
+    """A diffuse sphere of radius 3 seen from inside; in it an emissive sphere around the hard-wired light's rectangle (y = -1.5:
+    surfaces below it see it with a positive PDF, the cave's small cap above it with a negative one), a mirror, two glass spheres, and
+    a small diffuse sphere inside the first glass sphere and off its centre: a ray that entered a sphere from outside meets its
+    inside below the critical angle, always; one scattered off the inner sphere does not."""
+    mats = [dict(albedo=(0.8, 0.75, 0.7)), dict(albedo=(0.2, 0.2, 0.2), emissionColor=(1.0, 0.9, 0.7), emissionStrength=3.0),
+            dict(reflectance=1.0), dict(ior=1.5), dict(ior=1.33), dict(albedo=(0.9, 0.5, 0.3))]
+    sph = [((0.0, 0.8, 0.0), 3.0, 0), ((0.0, -1.5, 0.0), 0.5, 1), ((-1.0, 0.9, 0.6), 0.6, 2), ((0.9, 0.8, -0.2), 0.6, 3),
+           ((0.0, 1.1, -1.2), 0.45, 4), ((1.05, 0.9, -0.25), 0.3, 5)]
+    return _spheres_scene(mats, sph)
+
+
+def _sky_scene():
+    """Spheres under an open sky: a large diffuse one as the ground, a mirror, glass and a diffuse one on it."""
+    mats = [dict(albedo=(0.7, 0.7, 0.6)), dict(reflectance=1.0), dict(ior=1.5), dict(albedo=(0.3, 0.6, 0.9))]
+    sph = [((0.0, 3.5, 0.0), 3.0, 0), ((-0.9, 0.0, 0.3), 0.5, 1), ((0.3, 0.05, -0.4), 0.45, 2), ((1.2, 0.1, 0.6), 0.4, 3)]
+    return _spheres_scene(mats, sph)
+
+
+def _maps_scene():
+    """tests/test_denoise.py's checker quad, its material binding a metalness map besides the albedo map: every other row of texels a mirror."""
+    s, m, tex = _checker_scene()
+    mat = s.material(m)
+    mat.metalnessIndex = 1
+    s.set_material(m, mat)
+    metal = np.zeros((4, 4, 4), np.uint8)
+    metal[..., 1:] = 99                                   # noise in the channels that must not matter
+    metal[::2, :, 0] = (255, 3, 1, 90)
+    return s, [tex, metal]
+
+
+def _constants(name):
+    """(scene, textures or None, the frames' push constants, whether they are one progressive history)."""
+    pc = lambda **kw: engine.push_constants(W, H, singleRender=1, **kw)   # noqa: E731
+    if name == "cornell_b2":
+        return cornell_scene(True), None, [pc(sampleLimit=1, bounceLimit=2, frameCount=f, **e) for e in ({}, SKY) for f in (0, 3)], False
+    if name == "cornell_4spp":
+        return cornell_scene(True), None, [pc(sampleLimit=4, bounceLimit=1)], False
+    if name == "bunny_b2":
+        return model_scene("bunny.obj", spheres=True), None, [pc(sampleLimit=1, bounceLimit=2, frameCount=f) for f in (0, 2)], False
+    if name == "emitters_b3":
+        return emitters_scene(), None, [pc(sampleLimit=1, bounceLimit=3, frameCount=f) for f in (0, 1)], False
+    if name == "sphere_cave":
+        return _cave_scene(), None, [pc(sampleLimit=1, bounceLimit=9, frameCount=f, pos=(0.0, 0.3, -2.5)) for f in (0, 5)], False
+    if name == "maps":
+        s, tex = _maps_scene()
+        return s, tex, [pc(sampleLimit=1, bounceLimit=2)], False
+    if name == "progressive":
+        return cornell_scene(True), None, [pc(sampleLimit=1, bounceLimit=2, progressive=1, frameCount=f) for f in (0, 1, 2)], True
+    if name == "open_sky":
+        sun = dict(lightDir=(0.3, 0.8, -0.5, 1.0), horizonColor=(0.9, 0.8, 0.7, 40.0), zenithColor=(0.2, 0.4, 0.9, 5.0), groundColor=(0.3, 0.25, 0.2))
+        return _sky_scene(), None, [pc(sampleLimit=1, bounceLimit=2, frameCount=f, pos=(0.0, -0.6, -3.5), **sun) for f in (0, 2)], False
+    raise KeyError(name)
+
+
+_cache = {}
+
+
+def _case(name):
+    """The scene, its frames' constants and the restatement's answers (exact and rounded), once per session."""
+    if name not in _cache:
+        s, tex, pcs, chain = _constants(name)
+        bs = bf.BruteScene.from_numpy(s.numpy())
+        if tex is not None:
+            bs.set_textures(tex)
+        frames = pf.study(bs, pcs, W, H, maps=tex is not None, chain=chain)
+        _cache[name] = dict(scene=s, textures=tex, pcs=pcs, chain=chain, frames=frames)
+    return _cache[name]
+
+
+def _conditions(name):
+    """The conditions on the restatement alone: the cap on fragile pixels, the floors per kind, rounded against exact."""
+    c = _case(name)
+    kinds = {k: sum(f.kinds[k] for f in c["frames"]) for k in pf.KINDS}
+    excluded = max(f.excluded for f in c["frames"])
+    rounded = max(f.rounded_distance for f in c["frames"])
+    why = {k: max(float(f.exact.reasons[k].mean()) for f in c["frames"]) for k in pf.REASONS}
+    print(f"[{name}] pixels {W * H} x {len(c['frames'])} frames  excluded {excluded:.2%} (own: " + ", ".join(f"{k} {v:.2%}" for k, v in why.items() if v) +
+          f")  rounded distance {rounded:.2e}  " + "  ".join(f"{k} {v}" for k, v in kinds.items()))
+    assert excluded <= MAX_FRAGILE, (name, excluded)
+    for k, floor in FLOORS[name].items():
+        assert kinds[k] >= floor, (name, k, kinds[k], floor)
+    assert rounded <= _T(name) / 4, (name, rounded)
+    return c
+
+
+def _T(name):
+    return T_OWN.get(name, T)
+
+
+def _check(name, what, c, i, img):
+    """One rendered frame of a case against the exact run."""
+    f = c["frames"][i]
+    d = pf.distance(img, f.image, f.compared)
+    everywhere = pf.distance(img, f.image, np.ones_like(f.compared))
+    T = _T(name)
+    print(f"[{name}] {what} frame {i}: compared {int(f.compared.sum())} of {f.compared.size}  largest distance {d:.2e} (T = {T:.0e}; "
+          f"fragile pixels included: {everywhere:.2e})  magenta {int(f.magenta.sum())}  all samples zeroed {int(f.zeroed.sum())}")
+    img = np.asarray(img)
+    assert img.shape == f.image.shape and np.all(img[..., 3] == 1.0), f"{name} {what}: alpha"
+    exactly = f.magenta | f.zeroed if (i == 0 or not c["chain"]) else f.magenta       # a later progressive frame blends its zero
+    assert np.array_equal(img[..., :3][exactly].astype(np.float64), f.image[..., :3][exactly]), f"{name} {what}: a magenta or zeroed pixel"
+    assert d <= T, f"{name} {what} frame {i}: a compared pixel is {d:.3e} from the float64 estimator, {T} allowed"
+    return d
+
+
+# ---------------------------------------------------------------------------------------------------------------- conditions, oracle
+@pytest.mark.parametrize("name", CASES)
+def test_conditions_on_the_restatement(name):
+    _conditions(name)
+
+
+def test_T_is_four_times_the_measured_distance():
+    own = {n: max(f.rounded_distance for f in _case(n)["frames"]) for n in CASES}
+    worst = max(v for n, v in own.items() if n not in T_OWN)
+    print(f"largest rounded distance over the cases that share T {worst:.3e}; T_MEASURED {T_MEASURED}, T {T}; " + "  ".join(f"{n} {v:.2e}" for n, v in own.items()))
+    # the recorded figures are this measurement (to the few per cent another numpy's float32 sin, cos, exp2 and log2 may move it) ...
+    assert 0.9 * T_MEASURED <= worst <= 1.1 * T_MEASURED, "T_MEASURED is out of date: measure again and set T to four times it"
+    # ... and T is four times the record, rounded up to one significant figure: at most twice that
+    assert 4 * T_MEASURED <= T <= 8 * T_MEASURED and 4 * worst <= T
+    for n, t_own in T_OWN.items():
+        assert 0.9 * T_MEASURED_OWN[n] <= own[n] <= 1.1 * T_MEASURED_OWN[n] and 4 * T_MEASURED_OWN[n] <= t_own <= 8 * T_MEASURED_OWN[n] and 4 * own[n] <= t_own
+        assert 4 * own[n] > T, f"{n} no longer needs a T of its own"
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_oracle_against_float64(name):
+    c = _conditions(name)
+    prev = None
+    try:
+        if c["textures"] is not None:
+            pyoracle.set_textures(c["textures"])
+        for i, pc in enumerate(c["pcs"]):
+            img, _ = pyoracle.render(c["scene"], pc, W, H, prev=prev if c["chain"] else None)
+            prev = img
+            _check(name, "oracle", c, i, img)
+    finally:
+        pyoracle.set_textures([])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the restatement's own properties
+def _hand_scene(spheres, materials, quads=()):
+    """A BruteScene built by hand: spheres (centre, radius, material), quads (4 corners, normal, material), material records."""
+    b = bf.BruteScene()
+    b.set_spheres([s[0] for s in spheres], [s[1] for s in spheres], [s[2] for s in spheres])
+    for corners, normal, m in quads:
+        q = np.asarray(corners, np.float64)
+        b.add_object(np.array([[q[0], q[1], q[2]], [q[0], q[2], q[3]]]), np.tile(np.asarray(normal, np.float64), (2, 3, 1)), np.eye(4), material=m)
+    rec = dict(albedo=(1, 1, 1), emissionColor=(0, 0, 0), emissionStrength=0.0, reflectance=0.0, ior=-1.0)
+    rows = [dict(rec, **m) for m in materials]
+    b.material_table = {k: np.array([np.asarray(r[k], np.float32) for r in rows], np.float64) for k in rec}
+    return b
+
+
+def test_specular_furnace():
+    """A black emissive shell (albedo 0, emission E) around a mirror and two glass spheres of albedo 1, bounce limit 3 (no roulette
+    before bounce 6). Mirror and glass carry radiance 1 whichever way Fresnel's draw falls, and the sentinel hands the next hit's
+    emission on, so every sample is E when its path reaches the shell within four segments and 0 when the bounce limit cuts it
+    inside the glass; the shell's own bounce adds nothing (albedo 0). A pixel of S samples is therefore E k / S with k the
+    number of its samples whose signature ends on the shell: an identity, held here to float64 rounding. A diffuse furnace has no
+    such constant under this estimator: after a diffuse bounce it adds the pending light sample and never the surface's own emission."""
+    E = np.array((0.5, 1.25, 2.0))
+    b = _hand_scene([((0, 0, 0), 6.0, 0), ((-0.8, 0.1, 0.5), 0.6, 1), ((0.7, 0.0, 0.0), 0.55, 2), ((0.0, -0.9, 0.8), 0.4, 3)],
+                    [dict(albedo=(0, 0, 0), emissionColor=E / 2.0, emissionStrength=2.0), dict(reflectance=1.0), dict(ior=1.5), dict(ior=1.8)])
+    w, h, S, B = 24, 18, 4, 3
+    pc = engine.push_constants(w, h, singleRender=1, sampleLimit=S, bounceLimit=B, pos=(0.0, -0.2, -3.0))
+    r = pf.Estimator(b, pc, w, h).render()
+    codes = r.codes.reshape(w * h, S, B + 1)
+    on_shell = ((codes & 0b111) == 0b111) & (((codes >> 12) & 0xFFFFF) == 0)          # ran, hit, a sphere, sphere 0
+    k = on_shell.any(axis=2).sum(axis=1)
+    cut = int((S - k).sum())
+    print(f"specular furnace: {w * h} pixels x {S} samples, {cut} samples cut by the bounce limit, mean {r.image[..., :3].mean(axis=(0, 1))}")
+    assert 0 < cut < w * h * S // 4, "some paths, not many, must be cut inside the glass for the count to mean something"
+    assert (r.kinds["fresnel"].sum() > 20) and (r.kinds["refraction"].sum() > 50) and (r.kinds["mirror"].sum() > 20)
+    want = E[None, :] * (k / S)[:, None]
+    assert np.abs(r.image[..., :3].reshape(-1, 3) - want).max() <= 1e-12
+    assert not r.kinds["guard"].any() and not r.magenta.any()
+
+
+def _form_factor(p, x0, x1, z0, z1, height):
+    """Point-to-rectangle form factor of a horizontal element at p facing a parallel rectangle `height` away, by the corner
+    formula F(a, b) = (a / sqrt(a^2 + c^2) atan(b / sqrt(a^2 + c^2)) + b / sqrt(b^2 + c^2) atan(a / sqrt(b^2 + c^2))) / (2 pi)."""
+    def corner(a, b):
+        c = height
+        f = (np.abs(a) / np.hypot(a, c) * np.arctan(np.abs(b) / np.hypot(a, c)) + np.abs(b) / np.hypot(b, c) * np.arctan(np.abs(a) / np.hypot(b, c))) / (2 * np.pi)
+        return np.sign(a) * np.sign(b) * f
+    ax0, ax1, bz0, bz1 = x0 - p[:, 0], x1 - p[:, 0], z0 - p[:, 2], z1 - p[:, 2]
+    return corner(ax1, bz1) - corner(ax0, bz1) - corner(ax1, bz0) + corner(ax0, bz0)
+
+
+def test_lambert_plane_under_the_hard_wired_light():
+    """A floor y = 0.5 of albedo rho under the hard-wired rectangle (an emissive quad facing down at y = -1.5, |x|, |z| <= 0.33333),
+    bounce limit 1, inside a black sphere of radius 5 so that the cosine ray always hits something. A sample is the light sample alone:
+    E rho (rho / pi) cos_x w1 / pdf_l with pdf_l = d^2 / (cos_l 0.4444444), so its mean over the rectangle is
+    E rho^2 A / 0.4444444 times the integral of cos_x cos_l / (pi d^2) w1 over the rectangle, divided by A. With w1 = 1 the
+    integral is the closed-form form factor (checked here against the same quadrature); w1, the power heuristic against the cosine
+    PDF, has no closed form and is integrated by the midpoint rule on 400 x 400 cells. Each pixel's mean of S samples must lie within
+    4.5 standard errors (the sample's own standard deviation by the same quadrature, over sqrt(S)): under a normal law one of
+    192 pixels leaves that range once in 700 seeds; the frame's mean within 4.5 of its own."""
+    rho, E, a = np.array((0.8, 0.6, 0.4)), np.array((2.0, 1.5, 1.0)), 0.33333
+    big = 1.0
+    b = _hand_scene([((0, 0, 0), 5.0, 0)], [dict(albedo=(0, 0, 0)), dict(albedo=rho), dict(albedo=(0, 0, 0), emissionColor=E, emissionStrength=1.0)],
+                    quads=[([(-big, 0.5, -big), (big, 0.5, -big), (big, 0.5, big), (-big, 0.5, big)], (0, -1, 0), 1),
+                           ([(-a, -1.5, -a), (a, -1.5, -a), (a, -1.5, a), (-a, -1.5, a)], (0, 1, 0), 2)])
+    w, h, S = 16, 12, 64
+    pc = engine.push_constants(w, h, singleRender=1, sampleLimit=S, bounceLimit=1, pos=(0.15, -1.0, 0.1), cameraAngles=(90.0, 0.0, 0.0))
+    est = pf.Estimator(b, pc, w, h)
+    r = est.render()
+    o, d = est.camera(np.float64)
+    t = (0.5 - o[:, 1]) / d[:, 1]
+    assert (d[:, 1] > 0.5).all()
+    p = o + t[:, None] * d
+    # quadrature over the rectangle, per pixel
+    g = (np.arange(400) + 0.5) / 400 * 2 * a - a
+    lx, lz = np.meshgrid(g, g, indexing="ij")
+    y = np.stack([lx.ravel(), np.full(lx.size, -1.5), lz.ravel()], 1)
+    v = y[None] - (p + np.array((0, -0.01, 0)))[:, None, :]                   # from the offset origin, as the estimator sends it
+    d2 = (v * v).sum(-1)
+    cos = -v[..., 1] / np.sqrt(d2)                                            # the same at both ends: parallel planes
+    pdf_l = d2 / (cos * 0.4444444)
+    pdf_c = cos / np.pi
+    w1 = pdf_l ** 2 / (pdf_l ** 2 + pdf_c ** 2)
+    term = cos / np.pi / pdf_l                                                # per unit E rho^2, before w1
+    F = _form_factor(p + np.array((0, -0.01, 0)), -a, a, -a, a, 1.99)
+    assert np.abs(term.mean(axis=1) * (4 * a * a) / 0.4444444 - F * (4 * a * a) / 0.4444444).max() <= 1e-4 * F.max(), "the quadrature against the closed form"
+    mean1, mean2 = (term * w1).mean(axis=1), ((term * w1) ** 2).mean(axis=1)
+    scale = E * rho * rho
+    want = mean1[:, None] * scale
+    sigma = np.sqrt(np.maximum(mean2 - mean1 ** 2, 0))[:, None] * scale / np.sqrt(S)
+    got = r.image[..., :3].reshape(-1, 3)
+    z = np.abs(got - want) / sigma
+    zm = np.abs(got.mean(axis=0) - want.mean(axis=0)) / (np.sqrt((sigma ** 2).sum(axis=0)) / len(got))
+    print(f"lambert plane: {w * h} pixels x {S} samples  form factor {F.min():.4f} .. {F.max():.4f}  w1 {w1.min():.3f} .. {w1.max():.3f}  "
+          f"largest |pixel - expectation| / standard error {z.max():.2f}, of the frame's mean {zm.max():.2f}")
+    assert r.kinds["nee"].all()
+    assert z.max() <= 4.5 and zm.max() <= 4.5
+
+
+def test_frame_count_seeds():
+    """uint(random(frameCount) * 23892183.f) for frames 0..3 and pixel (0, 0)'s first four draws of frame 0, from the formula by
+    hand; a pixel's state is y W + x + seed; frames with equal seeds are equal and others are not."""
+    assert [pf.frame_seed(f) for f in range(4)] == [721543, 15748846, 11432345, 11858218]
+    s = pf.pixel_states(W, H, 0)
+    assert s[0] == 721543 and s[5 * W + 7] == 721543 + 5 * W + 7 and pf.pixel_states(W, H, 3)[W] == 11858218 + W
+    draws, st = [], s[:1]
+    for _ in range(4):
+        st, r = pf.pcg(st)
+        draws.append(r[0])
+    assert draws == [np.float32(x) for x in (0.99591756, 0.8160974, 0.95128745, 0.09933613)]
+    f = _case("cornell_b2")["frames"]
+    assert not np.array_equal(f[0].image, f[1].image)
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU half
+@pytest.fixture
+def gpu(renderer):
+    """The session's renderer; afterwards no textures, a cleared progressive history and the knobs these tests turn at their defaults."""
+    try:
+        yield renderer
+    finally:
+        renderer.upload_textures([])
+        renderer.clear_framebuffer()
+        for k, v in dict(fused_maps=0, pipeline=-1).items():
+            renderer.set_tuning(k, v)
+
+
+def _gpu_case(gpu, name, pipeline, fused_maps=0):
+    c = _conditions(name)
+    gpu.upload_scene(c["scene"])
+    if c["textures"] is not None:
+        gpu.upload_textures(c["textures"])
+    gpu.set_tuning("fused_maps", fused_maps)
+    gpu.set_tuning("pipeline", pipeline)
+    expect = pipeline if (c["textures"] is None or fused_maps) else 0           # a map scene takes the multi-kernel pipeline unless fused_maps
+    gpu.clear_framebuffer()
+    for i, pc in enumerate(c["pcs"]):
+        img = gpu.render(pc, W, H)
+        assert gpu.last_pipeline() == expect, (name, gpu.last_pipeline(), gpu.last_kernel())
+        _check(name, f"gpu pipeline {expect} ({gpu.last_kernel()})", c, i, img)
+    if c["chain"]:       # the same history in one rt_render_frames call
+        gpu.clear_framebuffer()
+        img = gpu.render_frames(c["pcs"][0], W, H, len(c["pcs"]))
+        _check(name, f"gpu pipeline {expect} render_frames", c, len(c["pcs"]) - 1, img)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipeline", [0, 1])
+@pytest.mark.parametrize("name", [n for n in CASES if n != "maps"])
+def test_kernels_against_float64(gpu, name, pipeline):
+    _gpu_case(gpu, name, pipeline)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipeline,fused_maps", [(0, 0), (1, 0), (0, 1), (1, 1)])
+def test_map_kernels_against_float64(gpu, pipeline, fused_maps):
+    """k_shade_maps (the multi-kernel pipeline, which a map scene takes whatever `pipeline` says while fused_maps is 0) and
+    k_render_fused_maps (pipeline 1 with fused_maps 1)."""
+    _gpu_case(gpu, "maps", pipeline, fused_maps)
+    kernel = gpu.last_kernel()
+    assert ("fused_maps" in kernel) == (pipeline == 1 and fused_maps == 1), kernel
