@@ -409,7 +409,8 @@ int  rt_denoise_host(rt_ctx* ctx, uint32_t width, uint32_t height, const float* 
  * depth within depthTolerance, relative, of the pixel's distance to the previous camera), and blends with k = 1 / N,
  * N = min(N_history + 1, maxHistory); without a valid tap it starts again at N = 1. Kept pixels (misses, emitters) come out bit
  * for bit, with moments 0, and are never taps. The scene is taken to be static between calls: after an edit that moves or
- * recolours something, call rt_temporal_reset (rt_upload_scene does; rt_update_* leave that to their caller). */
+ * recolours something, call rt_temporal_reset (rt_upload_scene does; rt_update_* leave that to their caller), or, for edits that
+ * only move things, switch rt_temporal_track_motion on (below). */
 typedef struct RtTemporalParams {
     uint32_t maxHistory;      /* >= 1: the blend factor never falls below 1 / maxHistory; 1 passes the frame through */
     float    normalCos;       /* in [-1, 1] */
@@ -429,6 +430,25 @@ int  rt_temporal_accumulate(rt_ctx* ctx, uint32_t width, uint32_t height, const 
                             const RtAovBuffers* d_aovs, const RtTemporalParams* params, float* d_out, float* d_moments);
 /* forgets the history: the next rt_temporal_accumulate starts at N = 1 */
 int  rt_temporal_reset(rt_ctx* ctx);
+/* Following moved objects and spheres ("Temporal accumulation", "Moved objects and spheres"). default 0. Switching it
+ * (to another value) forgets the history, as rt_temporal_reset does. While it is on, the ctx keeps beside the history a snapshot of
+ * the placements every accepted rt_temporal_accumulate saw: per object the rows of transformMatrix and of its inverse as they are
+ * in the device tables, and bvhIndex; per sphere its centre and radius. rt_update_objects and rt_update_spheres between two calls
+ * then need no reset: a pixel on an object whose rows changed takes its position and normal back through that object's previous
+ * placement (P~ = D P with D = Fwd' Inv, n~ = G n / |G n| with G the inverse transpose of D's linear part) before the previous
+ * camera and the tap tests see them; a pixel on a sphere that moved or changed radius takes P~ = c' + (P - c) r' / r and its own
+ * normal; an object whose bvhIndex changed, and an object or sphere index one of the two calls did not have, has no history
+ * (N = 1); everything else is treated exactly as with tracking off, and a call between which and the previous one nothing moved
+ * runs the same kernel with the same arguments as with tracking off. What is stored for the next call is this frame's own normal,
+ * depth and ids. rt_temporal_reset, rt_upload_scene, another width or height and the switch drop the snapshot with the history; a
+ * call refused for its arguments leaves both as they were.
+ * Only the surface follows. Light that changes because something moved (shadows, reflections, the lit side of a turning object)
+ * lags by up to maxHistory frames. Material edits still want rt_temporal_reset. */
+int  rt_temporal_track_motion(rt_ctx* ctx, int enabled);
+/* of the last rt_temporal_accumulate: how many objects / spheres it treated as moved and as replaced (all 0: it ran the static
+ * kernel). replacedObjects counts the indices only one of the two calls had as well; movedSpheres counts the spheres that moved or
+ * changed radius and the sphere indices only one of the two calls had. Any of the three may be NULL. */
+int  rt_temporal_motion_state(const rt_ctx* ctx, uint32_t* movedObjects, uint32_t* replacedObjects, uint32_t* movedSpheres);
 /* copy the ctx-owned output of the last rt_temporal_accumulate(…, d_out = NULL) / (…, d_moments = NULL)
  * (nFloats = width*height*4 of that call); block */
 int  rt_read_temporal_rgba_f32(rt_ctx* ctx, float* hostOut, size_t nFloats);

@@ -164,6 +164,8 @@ SYMBOLS = {
     "rt_temporal_params_default": (None, [_P(RtTemporalParams)]),
     "rt_temporal_accumulate": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _P(CameraInfo), _vp, _P(RtAovBuffers), _P(RtTemporalParams), _vp, _vp]),
     "rt_temporal_reset": (C.c_int, [_vp]),
+    "rt_temporal_track_motion": (C.c_int, [_vp, C.c_int]),
+    "rt_temporal_motion_state": (C.c_int, [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
     "rt_read_temporal_rgba_f32": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
     "rt_read_temporal_moments": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
     "rt_temporal_accumulate_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _P(CameraInfo), _vp, _P(RtAovBuffers), _P(RtTemporalParams), _vp, _vp]),

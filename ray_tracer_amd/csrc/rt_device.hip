@@ -102,6 +102,15 @@ struct rt_ctx {
     uint32_t tpWidth = 0, tpHeight = 0;
     TemporalCamera tpCam{};
     size_t tpOutPixels = 0, tpMomPixels = 0; bool tpOutValid = false, tpMomValid = false;
+    // following moved objects and spheres (rt_temporal_track_motion): the placements behind the tables now on the device (set_objects,
+    // set_spheres), the snapshot of them an accepted call takes with tracking on (valid with the history only), the motion table on
+    // the device with its pinned staging copy and the event that says the copy has been read, and what the last call found
+    bool tpTrack = false, tpSnapValid = false;
+    PlacementSnapshot tpNow, tpSnap;
+    DevBuf tpMotionBuf;
+    float4* tpMotionHost = nullptr; size_t tpMotionHostBytes = 0;
+    hipEvent_t tpMotionEvent = nullptr;
+    uint32_t tpMoved[3] = {0, 0, 0};   // moved objects, replaced objects, moved or new spheres
 
     // ---- tuning: what rt_set_tuning writes (launch_plan.h: set_tuning). Nothing else assigns to it.
     Tuning tune;
@@ -509,6 +518,7 @@ int set_spheres(rt_ctx* c, const Sphere* s, uint32_t n) {
     c->sc.sphereCount = n;
     c->sc.sphereTestMask = l.testMask;
     c->host.sphereMat.assign(l.mat.begin(), l.mat.begin() + n);
+    c->tpNow.spheres.assign(l.spheres.begin(), l.spheres.begin() + n);
     return rebuild_emitters(c);
 }
 
@@ -532,6 +542,9 @@ int set_objects(rt_ctx* c, const ObjectLayout& l, const RenderObject* o, uint32_
     c->sc.objectCount = n;
     c->host.objMat.resize(n); c->host.objRoot.resize(n); c->host.objSampler.resize(n);
     for (uint32_t i = 0; i < n; i++) { c->host.objMat[i] = o[i].materialIndex; c->host.objRoot[i] = o[i].bvhIndex; c->host.objSampler[i] = o[i].samplerIndex; }
+    c->tpNow.fwd.assign(l.fwd.begin(), l.fwd.begin() + 3 * (size_t)n);
+    c->tpNow.inv.assign(l.inv.begin(), l.inv.begin() + 3 * (size_t)n);
+    c->tpNow.bvhIndex = c->host.objRoot;
     return rebuild_emitters(c);
 }
 
@@ -585,6 +598,8 @@ void rt_destroy(rt_ctx* c) {
     for (auto& e : c->evPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (c->hostCounts) (void)hipHostFree(c->hostCounts);
     if (c->snap) (void)hipHostFree(c->snap);
+    if (c->tpMotionHost) (void)hipHostFree(c->tpMotionHost);
+    if (c->tpMotionEvent) (void)hipEventDestroy(c->tpMotionEvent);
     for (hipEvent_t e : {c->snapEvent, c->pollEvent, c->forkEvent, c->profBase})
         if (e) (void)hipEventDestroy(e);
     for (int l = 0; l < RT_MAX_LANES - 1; l++) {
@@ -650,6 +665,7 @@ int rt_upload_scene(rt_ctx* c, const RtSceneArrays* s) {
     RT_HIP(c, hipStreamSynchronize(c->stream));
     measured_new_scene(c);
     c->tpHistValid = false;  // a new scene: nothing of the old one's frames is its history (rt_temporal_accumulate)
+    c->tpSnapValid = false;
     c->host = SceneSources{};
     c->sc.emitMode = 0; c->sc.emitCount = 0; c->sc.emitSphereMask = 0;
     c->sc.mapFlags = 0;
@@ -1238,6 +1254,33 @@ TemporalCamera temporal_camera(const CameraInfo& ci) {
     t.bottomLeft[2] = 0.1f;
     return t;
 }
+
+// The motion table onto the device, on the ctx stream: stream order keeps the copy behind the launch that still reads the table of
+// the call before, and the call stays asynchronous. The pinned staging copy is this call's until the event says the copy engine has
+// read it; only a second upload before that waits.
+int upload_motion(rt_ctx* c, const MotionTable& mt, TemporalMotion& mo) {
+    const size_t ob = mt.objects.size() * sizeof(float4), sb = mt.spheres.size() * sizeof(float4), bytes = ob + sb;
+    if (!c->tpMotionEvent) RT_HIP(c, hipEventCreateWithFlags(&c->tpMotionEvent, hipEventDisableTiming));
+    else RT_HIP(c, hipEventSynchronize(c->tpMotionEvent));
+    if (c->tpMotionHostBytes < bytes) {
+        if (c->tpMotionHost) (void)hipHostFree(c->tpMotionHost);
+        c->tpMotionHost = nullptr; c->tpMotionHostBytes = 0;
+        RT_HIP(c, hipHostMalloc((void**)&c->tpMotionHost, bytes, hipHostMallocDefault));
+        c->tpMotionHostBytes = bytes;
+    }
+    if (c->tpMotionBuf.bytes < bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees a table a launch may still read
+    int rc = dev_alloc(c, c->tpMotionBuf, bytes);
+    if (rc) return rc;
+    memcpy(c->tpMotionHost, mt.objects.data(), ob);
+    memcpy((char*)c->tpMotionHost + ob, mt.spheres.data(), sb);
+    RT_HIP(c, hipMemcpyAsync(c->tpMotionBuf.p, c->tpMotionHost, bytes, hipMemcpyHostToDevice, c->stream));
+    RT_HIP(c, hipEventRecord(c->tpMotionEvent, c->stream));
+    mo.objects = (const float4*)c->tpMotionBuf.p;
+    mo.spheres = (const float4*)((const char*)c->tpMotionBuf.p + ob);
+    mo.objectCount = mt.objectCount;
+    mo.sphereCount = mt.sphereCount;
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -1249,6 +1292,24 @@ void rt_temporal_params_default(RtTemporalParams* p) {
 int rt_temporal_reset(rt_ctx* c) {
     if (!c) return -1;
     c->tpHistValid = false;   // host state only: the next call reads no history, and the ctx stream orders it after the last one
+    c->tpSnapValid = false;
+    return 0;
+}
+
+int rt_temporal_track_motion(rt_ctx* c, int enabled) {
+    if (!c) return -1;
+    if (c->tpTrack == (enabled != 0)) return 0;
+    c->tpTrack = enabled != 0;
+    c->tpHistValid = false;   // the history of the other mode has no snapshot to go with it, or one nobody kept up
+    c->tpSnapValid = false;
+    return 0;
+}
+
+int rt_temporal_motion_state(const rt_ctx* c, uint32_t* movedObjects, uint32_t* replacedObjects, uint32_t* movedSpheres) {
+    if (!c) return -1;
+    if (movedObjects) *movedObjects = c->tpMoved[0];
+    if (replacedObjects) *replacedObjects = c->tpMoved[1];
+    if (movedSpheres) *movedSpheres = c->tpMoved[2];
     return 0;
 }
 
@@ -1295,10 +1356,11 @@ int rt_temporal_accumulate(rt_ctx* c, uint32_t width, uint32_t height, const Cam
     // growing a plane frees the old one, which a call still in flight may be using
     if (c->tpHist[0].bytes < 3 * bytes || c->tpHist[1].bytes < 3 * bytes || (!d_out && c->tpOutBuf.bytes < bytes) || (!d_moments && c->tpMomBuf.bytes < bytes))
         RT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->tpWidth != width || c->tpHeight != height) c->tpHistValid = false;   // a history of another size is none
+    if (c->tpWidth != width || c->tpHeight != height) { c->tpHistValid = false; c->tpSnapValid = false; }   // a history of another size is none
     for (DevBuf& h : c->tpHist)
         if (h.bytes < 3 * bytes) {
             c->tpHistValid = false;
+            c->tpSnapValid = false;
             if ((rc = dev_alloc(c, h, 3 * bytes))) return rc;
         }
     float4 *out = (float4*)d_out, *mom = (float4*)d_moments;
@@ -1318,9 +1380,21 @@ int rt_temporal_accumulate(rt_ctx* c, uint32_t width, uint32_t height, const Cam
     const TemporalFrame f{rgba, nd, position, albedo, ids, c->tpHistValid ? (const float4*)c->tpHist[c->tpCur].p : nullptr,
                           (float4*)c->tpHist[next].p, out, mom, width, height};
     const dim3 grid((width + 15u) / 16u, (height + 15u) / 16u), block(RT_DN_BLOCK);
-    hipLaunchKernelGGL(k_tp_accumulate, grid, block, 0, c->stream, f, c->tpCam, c->sc.mats, c->sc.materialCount, (float)p.maxHistory, p.normalCos,
-                       p.depthTolerance);
+    // what moved since the call that wrote the history: only then the motion kernel, else today's launch with today's arguments
+    MotionTable mt;
+    if (c->tpTrack && c->tpHistValid && c->tpSnapValid) mt = motion_table(c->tpSnap, c->tpNow);
+    c->tpMoved[0] = mt.movedObjects; c->tpMoved[1] = mt.replacedObjects; c->tpMoved[2] = mt.movedSpheres + mt.replacedSpheres;
+    if (mt.any()) {
+        TemporalMotion mo{};
+        if ((rc = upload_motion(c, mt, mo))) return rc;
+        hipLaunchKernelGGL(k_tp_accumulate_motion, grid, block, 0, c->stream, f, c->tpCam, c->sc.mats, c->sc.materialCount, (float)p.maxHistory,
+                           p.normalCos, p.depthTolerance, mo);
+    } else {
+        hipLaunchKernelGGL(k_tp_accumulate, grid, block, 0, c->stream, f, c->tpCam, c->sc.mats, c->sc.materialCount, (float)p.maxHistory, p.normalCos,
+                           p.depthTolerance);
+    }
     RT_HIP(c, hipGetLastError());
+    if (c->tpTrack) { c->tpSnap = c->tpNow; c->tpSnapValid = true; }
     c->tpCur = next;
     c->tpHistValid = true;
     c->tpWidth = width; c->tpHeight = height;

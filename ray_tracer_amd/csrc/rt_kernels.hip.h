@@ -28,6 +28,7 @@
 #include "rt_probe.h"
 #include "scene_layout.h"   // the formats of the scene tables: node words, object flags, RT_MAP_*, RT_HOT_PAIRS, RT_OBJTREE_LEVELS
 #include "launch_plan.h"    // RT_WAVE, RT_BLOCK: the launch policy sizes grids and blocks with them
+#include "temporal_motion.h" // the records of the temporal pass's motion table (RT_MOTION_*)
 
 #ifndef RT_QUEUE_ORDER
 #define RT_QUEUE_ORDER 0   // k_shade: the ray queue's pieces are {main, NEE, cosine probes} (1: {main, cosine probes, NEE})
@@ -2056,81 +2057,57 @@ struct TemporalFrame {
     uint32_t width, height;
 };
 
+// The motion table of a call that follows moved objects and spheres (temporal_motion.h has the records): D takes a point of this
+// frame to where its object or sphere had it in the previous call, G its normal.
+struct TemporalMotion {
+    const float4* objects;      // RT_MOTION_OBJECT_RECORDS per object: {flag, -, -, -}, D rows 0..2, G rows 0..2
+    const float4* spheres;      // RT_MOTION_SPHERE_RECORDS per sphere: {c, r' / r} {c', flag}
+    uint32_t objectCount, sphereCount;   // an index at or above its count is replaced
+};
+
+// What a pixel of the motion kernel sends through the previous camera: its position and normal taken back through the previous
+// placement of its own object or sphere. The flag is loaded first, the rest of the record only when it says moved. False: replaced.
+__device__ __forceinline__ bool tp_previous_surface(const TemporalMotion& mo, uint4 id, float4 pos, rt_vec3 np, rt_vec3& pp, rt_vec3& nn) {
+    if (id.w & 2u) {
+        if (id.x >= mo.sphereCount) return false;
+        const float4 s1 = rt_global(mo.spheres)[(size_t)RT_MOTION_SPHERE_RECORDS * id.x + 1];
+        const uint32_t flag = __float_as_uint(s1.w);
+        if (flag == RT_MOTION_MOVED) {
+            const float4 s0 = rt_global(mo.spheres)[(size_t)RT_MOTION_SPHERE_RECORDS * id.x];
+            pp = rt_v3(s1.x + (pos.x - s0.x) * s0.w, s1.y + (pos.y - s0.y) * s0.w, s1.z + (pos.z - s0.z) * s0.w);
+        }
+        return flag == RT_MOTION_MOVED || flag == RT_MOTION_UNMOVED;
+    }
+    if (id.x >= mo.objectCount) return false;
+    const float4* rec = rt_global(mo.objects) + (size_t)RT_MOTION_OBJECT_RECORDS * id.x;
+    const uint32_t flag = __float_as_uint(rec[0].x);
+    if (flag == RT_MOTION_MOVED) {
+        const float4 d0 = rec[1], d1 = rec[2], d2 = rec[3], g0 = rec[4], g1 = rec[5], g2 = rec[6];
+        pp = rt_v3(((d0.x * pos.x + d0.y * pos.y) + d0.z * pos.z) + d0.w, ((d1.x * pos.x + d1.y * pos.y) + d1.z * pos.z) + d1.w,
+                   ((d2.x * pos.x + d2.y * pos.y) + d2.z * pos.z) + d2.w);
+        const rt_vec3 g = rt_v3((g0.x * np.x + g0.y * np.y) + g0.z * np.z, (g1.x * np.x + g1.y * np.y) + g1.z * np.z,
+                                (g2.x * np.x + g2.y * np.y) + g2.z * np.z);
+        const float len = rt_sqrt(rt_dot(g, g));
+        nn = rt_v3(g.x / len, g.y / len, g.z / len);
+    }
+    return flag == RT_MOTION_MOVED || flag == RT_MOTION_UNMOVED;
+}
+
 __global__ __launch_bounds__(RT_DN_BLOCK) void k_tp_accumulate(TemporalFrame f, TemporalCamera cam, const float4* mats, uint32_t materialCount,
                                                                float maxHistory, float normalCos, float depthTolerance) {
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t x = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u), y = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
-    if (x >= f.width || y >= f.height) return;
-    const size_t n = (size_t)f.width * f.height, p = (size_t)y * f.width + x;
-    const uint4 id = f.ids[p];
-    const float4 c = f.rgba[p];
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!((id.w & 1u) && id.z < materialCount && rt_global(mats)[3 * id.z + 1].w == 0.f)) {   // kept: a miss or an emitter
-        f.out[p] = c;
-        f.moments[p] = zero;
-        f.next[p] = zero; f.next[n + p] = zero; f.next[2 * n + p] = zero;
-        return;
-    }
-    const float4 a = f.albedo[p], ndp = f.normalDepth[p], pos = f.position[p];
-    const rt_vec3 d = rt_v3(rt_max(a.x, 1e-3f), rt_max(a.y, 1e-3f), rt_max(a.z, 1e-3f));
-    const rt_vec3 e = rt_v3(c.x / d.x, c.y / d.y, c.z / d.z), np = f4xyz(ndp);
-    const float l = (0.2126f * e.x + 0.7152f * e.y) + 0.0722f * e.z;
-    const uint32_t keyObject = id.x, keyMaterial = (id.z << 1) | ((id.w >> 1) & 1u);
-    rt_vec3 eh = e;
-    float m1 = l, m2 = l * l, N = 1.f;
-    if (f.prev) {
-        const rt_vec3 v = rt_sub(f4xyz(pos), rt_v3(cam.pos[0], cam.pos[1], cam.pos[2]));
-        const float* m = cam.rot;   // q = M^T v: the inverse of primary_dir's rotation
-        const rt_vec3 q = rt_v3((m[0] * v.x + m[1] * v.y) + m[2] * v.z, (m[4] * v.x + m[5] * v.y) + m[6] * v.z, (m[8] * v.x + m[9] * v.y) + m[10] * v.z);
-        if (q.z > 0.f) {
-            const float s = cam.bottomLeft[2] / q.z;
-            const float fx = ((q.x * s - cam.bottomLeft[0]) / cam.planeWidth) * (float)f.width;
-            const float fy = ((q.y * s - cam.bottomLeft[1]) / cam.planeHeight) * (float)f.height;
-            // a tap can lie inside the image only for floor(fx) in [-1, width - 1]; the comparisons also turn away NaN and infinity
-            if (fx >= -1.f && fx < (float)f.width && fy >= -1.f && fy < (float)f.height) {
-                const float flx = __builtin_floorf(fx), fly = __builtin_floorf(fy), tx = fx - flx, ty = fy - fly;
-                const int x0 = (int)flx, y0 = (int)fly;
-                const float dist = rt_sqrt(rt_dot(v, v)), tol = depthTolerance * dist;
-                float S = 0.f, sN = 0.f, s1 = 0.f, s2 = 0.f;
-                rt_vec3 se = rt_v3(0.f, 0.f, 0.f);
-#pragma unroll
-                for (int j = 0; j < 2; j++) {
-                    const int qy = y0 + j;
-                    if (qy < 0 || qy >= (int)f.height) continue;
-#pragma unroll
-                    for (int i = 0; i < 2; i++) {
-                        const int qx = x0 + i;
-                        if (qx < 0 || qx >= (int)f.width) continue;
-                        const size_t t = (size_t)qy * f.width + (uint32_t)qx;
-                        const float4 h0 = f.prev[t];
-                        if (!(h0.w > 0.f)) continue;
-                        const float4 h1 = f.prev[n + t], h2 = f.prev[2 * n + t];
-                        if (__float_as_uint(h1.w) != keyObject || __float_as_uint(h2.w) != keyMaterial) continue;
-                        if (!(rt_dot(np, f4xyz(h2)) >= normalCos)) continue;
-                        if (!(rt_abs(dist - h1.z) <= tol)) continue;
-                        const float w = (i ? tx : 1.f - tx) * (j ? ty : 1.f - ty);
-                        S += w;
-                        se = rt_add(se, rt_scale(f4xyz(h0), w));
-                        sN += w * h0.w; s1 += w * h1.x; s2 += w * h1.y;
-                    }
-                }
-                if (S >= 1e-3f) {
-                    const rt_vec3 he = rt_v3(se.x / S, se.y / S, se.z / S);
-                    const float h1m = s1 / S, h2m = s2 / S;
-                    N = rt_min(sN / S + 1.f, maxHistory);
-                    const float k = 1.f / N;
-                    eh = rt_add(he, rt_scale(rt_sub(e, he), k));
-                    m1 = h1m + k * (l - h1m);
-                    m2 = h2m + k * (l * l - h2m);
-                }
-            }
-        }
-    }
-    f.out[p] = make_float4(eh.x * d.x, eh.y * d.y, eh.z * d.z, c.w);
-    f.moments[p] = make_float4(m1, m2, rt_max(0.f, m2 - m1 * m1), N);
-    f.next[p] = mk4(eh, N);
-    f.next[n + p] = make_float4(m1, m2, ndp.w, __uint_as_float(keyObject));
-    f.next[2 * n + p] = mk4(np, __uint_as_float(keyMaterial));
+#define RT_TP_MOTION 0
+#include "rt_temporal_body.hip.inc"
+#undef RT_TP_MOTION
+}
+
+// The same pass with each pixel's position and normal taken back through its own object's or sphere's previous placement first
+// (P~, n~ in place of P, n). rt_temporal_accumulate launches it only when the host found a moved or replaced entry
+// (temporal_motion.h); a replaced object or sphere has no history.
+__global__ __launch_bounds__(RT_DN_BLOCK) void k_tp_accumulate_motion(TemporalFrame f, TemporalCamera cam, const float4* mats, uint32_t materialCount,
+                                                                      float maxHistory, float normalCos, float depthTolerance, TemporalMotion mo) {
+#define RT_TP_MOTION 1
+#include "rt_temporal_body.hip.inc"
+#undef RT_TP_MOTION
 }
 
 // ---------------------------------------------------------------- misc kernels

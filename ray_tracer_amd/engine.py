@@ -444,6 +444,18 @@ class Renderer:
         """Forgets the temporal history (rt_temporal_reset): after a scene edit, or to start a new sequence."""
         self._check(self._l.rt_temporal_reset(self._h), "rt_temporal_reset")
 
+    def temporal_track_motion(self, on):
+        """Lets the temporal history follow objects and spheres that update_objects / update_spheres move between calls
+        (rt_temporal_track_motion), so that such edits need no temporal_reset(). Off by default; switching forgets the history."""
+        self._check(self._l.rt_temporal_track_motion(self._h, 1 if on else 0), "rt_temporal_track_motion")
+
+    def temporal_motion_state(self):
+        """What the last temporal_accumulate() treated as moved or replaced (rt_temporal_motion_state): a dict of movedObjects,
+        replacedObjects and movedSpheres; all 0: it ran the static kernel."""
+        v = [C.c_uint32() for _ in range(3)]
+        self._check(self._l.rt_temporal_motion_state(self._h, *[C.byref(x) for x in v]), "rt_temporal_motion_state")
+        return dict(movedObjects=v[0].value, replacedObjects=v[1].value, movedSpheres=v[2].value)
+
     def pick(self, pc, width, height, x, y):
         """What the camera ray of pixel (x, y) hits: one row of render_aovs(), the record at x (scalars and 3-vectors)."""
         if not (0 <= x < width and 0 <= y < height):

@@ -17,16 +17,19 @@ from . import _capi, engine
 
 
 class InteractiveSession:
-    def __init__(self, renderer, scene, width, height, temporal=False, denoise=False):
+    def __init__(self, renderer, scene, width, height, temporal=False, denoise=False, track_motion=False):
         """temporal: every draw() that dispatched also runs the first-hit AOV pass and, while the camera moves (progressive
         accumulation off), the temporal pass (Renderer.temporal_accumulate); `filtered` is the result, `history_length` its N
         plane, and `image` stays the raw frame. While the camera rests the reference's own progressive accumulation converges
         and nothing is blended: `filtered` is the progressive framebuffer. The pass only records that frame (max_history = 1
         passes it through and stores it), so the first moving frame blends into the converged image, not into the last
         moving one. denoise: `filtered` also goes through Renderer.denoise. set_object, set_sphere
-        and set_material reset the temporal history (the pass takes the scene to be static)."""
+        and set_material reset the temporal history (the pass takes the scene to be static). track_motion (with temporal): the
+        history follows moved objects and spheres (Renderer.temporal_track_motion), so set_object and set_sphere no longer reset
+        it; set_material still does."""
         self.r, self.scene, self.W, self.H = renderer, scene, int(width), int(height)
         self.temporal, self.denoise = bool(temporal), bool(denoise)
+        self.track_motion = self.temporal and bool(track_motion)
         self.filtered, self.history_length = None, None
         self.pc = engine.push_constants(self.W, self.H)            # defaults of src/vk_engine.h:145-171
         self.params = self.pc.rayTraceParams
@@ -41,6 +44,7 @@ class InteractiveSession:
         renderer.upload_scene(scene)
         renderer.clear_framebuffer()
         if self.temporal:
+            renderer.temporal_track_motion(self.track_motion)
             renderer.temporal_reset()
         self._edited = None
         self._rotation()                                           # cameraInfo.cameraRotation as run_compute leaves it
@@ -149,7 +153,7 @@ class InteractiveSession:
         a.spheres[i].position[:] = [float(x) for x in position]
         a.spheres[i].radius, a.spheres[i].materialIndex = float(radius), int(materialIndex)
         self.r._check(self.r._l.rt_update_spheres(self.r._h, a.spheres, a.nSpheres), "rt_update_spheres")
-        if self.temporal:
+        if self.temporal and not self.track_motion:
             self.r.temporal_reset()
 
     def set_object(self, i, placement=None, materialIndex=None, samplerIndex=None):
@@ -161,7 +165,7 @@ class InteractiveSession:
         if samplerIndex is not None:
             a.objects[i].samplerIndex = int(samplerIndex)
         self.r._check(self.r._l.rt_update_objects(self.r._h, a.objects, a.nObjects), "rt_update_objects")
-        if self.temporal:
+        if self.temporal and not self.track_motion:
             self.r.temporal_reset()
 
     def arrays(self):

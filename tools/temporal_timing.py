@@ -6,7 +6,13 @@ size). The method is tools/denoise_timing.py's: all four write into device buffe
 clock around the enqueue and an rt_sync; one warm-up of each, then `runs` of each, interleaved; median and min. The last call's
 moments plane is read back once, after the timing, for the share of the frame that kept a history. Then the error ratios of
 tests/test_temporal.py's quality test.
-usage: tools/temporal_timing.py [runs] [out.json]   (default: 7, profiles/temporal_timing.json)"""
+--moving-object: the pass with rt_temporal_track_motion on, same scenes, sizes, camera path and method. Every iteration has a
+frame before which one object of the Sponza stand-in (the one with the most pixels on screen) or one Cornell sphere was moved
+0.002 along x through rt_update_objects / rt_update_spheres (not timed), so that the call builds and uploads the motion table and
+runs k_tp_accumulate_motion, and a frame without an edit, on which the same call runs k_tp_accumulate as with tracking off;
+rt_temporal_motion_state says which one ran. Both are timed the same way in the same run, and the ratio is what is reported.
+usage: tools/temporal_timing.py [--moving-object] [runs] [out.json]
+(default: 7, profiles/temporal_timing.json or, with --moving-object, profiles/temporal_motion_timing.json)"""
 import json
 import os
 import statistics
@@ -22,8 +28,10 @@ import numpy as np  # noqa: E402
 
 from ray_tracer_amd import _capi, engine, scenes  # noqa: E402
 
-runs = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "temporal_timing.json")
+MOVING = "--moving-object" in sys.argv
+argv = [a for a in sys.argv if a != "--moving-object"]
+runs = int(argv[1]) if len(argv) > 1 else 7
+out = argv[2] if len(argv) > 2 else os.path.join(ROOT, "profiles", "temporal_motion_timing.json" if MOVING else "temporal_timing.json")
 CASES = [("sponza stand-in", lambda: scenes.sponza(0)[0], scenes.sponza_camera, (2.0, 0.0, 0.0), 1920, 1080),
          ("cornell + spheres", lambda: scenes.cornell(True)[0], engine.push_constants, (4.0, 0.0, 0.0), 1728, 1117)]
 # per pixel: five input records, four taps of three records, the frame, the moments and three history records, 16 bytes each
@@ -35,6 +43,93 @@ hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
 hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
 hip.hipFree.argtypes = [C.c_void_p]
 rows = []
+
+
+def moving_object_mode():
+    from util import EditedScene
+
+    r.temporal_track_motion(True)
+    for label, make, camera, angles, W, H in CASES:
+        scene = make()
+        e = EditedScene(scene)
+        r.upload_scene(scene)
+        bufs = [C.c_void_p() for _ in range(8)]
+        for b in bufs:
+            assert hip.hipMalloc(C.byref(b), W * H * 16) == 0
+        frame, acc, mom = bufs[0].value, bufs[6].value, bufs[7].value
+        ptrs = {k: b.value for k, b in zip(engine.AOV_PLANES, bufs[1:6])}
+        planes = _capi.RtAovBuffers(**ptrs)
+        state = dict(k=0, edits=0)
+
+        def frame_of(edit):
+            """One frame of the path, after an edit or not: the time of the temporal call alone, and what it says it found."""
+            k = state["k"]
+            state["k"] = k + 1
+            if edit:
+                state["edits"] += 1
+                if target[0] == "object":
+                    e.objects[target[1]].transformMatrix[12] = x0 + 0.002 * state["edits"]
+                    e.push(r, "objects")
+                else:
+                    e.spheres[target[1]].position[0] = x0 + 0.002 * state["edits"]
+                    e.push(r, "spheres")
+            pc = camera(W, H, cameraAngles=(angles[0], angles[1] + 0.5 * k, angles[2]), progressive=0, raysPerPixel=1, frameCount=k)
+            r.render(pc, W, H, out_ptr=frame)
+            r.render_aovs(pc, W, H, out_ptrs=ptrs)
+            r.sync()
+            t = time.perf_counter()
+            r._check(r._l.rt_temporal_accumulate(r._h, W, H, C.byref(pc.camInfo), frame, C.byref(planes), None, acc, mom), "rt_temporal_accumulate")
+            r.sync()
+            return (time.perf_counter() - t) * 1e3, r.temporal_motion_state()
+
+        # what to move: the Cornell sphere 2 (diffuse), or the object with the most pixels in the first frame
+        target, x0 = ("sphere", 2), 0.0
+        frame_of(False)
+        ids = np.empty((H, W, 4), np.uint32)
+        assert hip.hipMemcpy(ids.ctypes.data, ptrs["ids"], W * H * 16, 2) == 0   # hipMemcpyDeviceToHost
+        if label.startswith("sponza"):
+            mesh = ids[..., 0][(ids[..., 3] & 3) == 1]
+            target = ("object", int(np.bincount(mesh).argmax()))
+            x0 = float(e.objects[target[1]].transformMatrix[12])
+        else:
+            x0 = float(e.spheres[2].position[0])
+        for edit in (True, False):   # warm-up of both kernels, the table and its staging copy
+            frame_of(edit)
+        t_motion, t_static = [], []
+        for _ in range(runs):
+            ms, st = frame_of(True)
+            assert st["movedObjects"] + st["movedSpheres"] == 1 and st["replacedObjects"] == 0, st
+            t_motion.append(ms)
+            ms, st = frame_of(False)
+            assert not any(st.values()), st
+            t_static.append(ms)
+        m = np.empty((H, W, 4), np.float32)
+        assert hip.hipMemcpy(m.ctypes.data, mom, W * H * 16, 2) == 0
+        assert hip.hipMemcpy(ids.ctypes.data, ptrs["ids"], W * H * 16, 2) == 0
+        N = m[..., 3]
+        on_target = (ids[..., 0] == target[1]) & ((ids[..., 3] & 3) == (1 if target[0] == "object" else 3))
+        med = statistics.median
+        row = dict(scene=label, width=W, height=H, spp=1, yaw_deg_per_frame=0.5, runs=runs, moved=f"{target[0]} {target[1]}", step=0.002,
+                   temporal_motion_ms=round(med(t_motion), 3), temporal_motion_ms_min=round(min(t_motion), 3),
+                   temporal_static_ms=round(med(t_static), 3), temporal_static_ms_min=round(min(t_static), 3),
+                   motion_over_static=round(med(t_motion) / med(t_static), 3), motion_over_static_min=round(min(t_motion) / min(t_static), 3),
+                   moved_share_of_pixels=round(float(on_target.mean()), 4),
+                   history_share_on_moved=round(float((N[on_target] > 1).sum() / max((N[on_target] > 0).sum(), 1)), 4),
+                   history_share_of_filtered=round(float((N > 1).sum() / max((N > 0).sum(), 1)), 4))
+        rows.append(row)
+        for b in bufs:
+            hip.hipFree(b)
+        print(json.dumps(row), flush=True)
+    r.temporal_track_motion(False)
+    r.close()
+    with open(out, "w") as f:
+        json.dump(rows, f, indent=1)
+    print("wrote", out)
+
+
+if MOVING:
+    moving_object_mode()
+    sys.exit(0)
 for label, make, camera, angles, W, H in CASES:
     r.upload_scene(make())
     bufs = [C.c_void_p() for _ in range(9)]
