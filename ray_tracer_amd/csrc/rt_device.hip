@@ -9,6 +9,7 @@
 #include "rt_kernels.hip.h"
 #include "bvh_build.hip.h"
 #include "launch_plan.h"   // every decision about how a dispatch is run: this file gathers the facts, asks there, and launches
+#include "post_passes.h"   // likewise for the passes over finished frames: their checks, their input planes, the temporal history
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -34,10 +35,14 @@ struct DevBuf {  // device memory that belongs to whoever holds this: move-only,
 };
 
 struct EventPair { hipEvent_t a, b; };
-// the rows y = row0 + k*rowStride, k in [0,nRows) of a width x height image
-struct RowsOf {
-    uint32_t width = 0, height = 0, row0 = 0, rowStride = 0, nRows = 0;
-    bool whole(uint32_t w, uint32_t h) const { return width == w && height == h && row0 == 0 && rowStride == 1 && nRows == h; }
+// A plane (or set of planes) the ctx keeps for a caller who passed NULL: the memory, the pixels of the call that last wrote it, whether
+// there was one, and, where the plane has rows, the rows of the image it holds (the passes read it only as a whole frame)
+struct OwnedPlane {
+    DevBuf buf;
+    size_t pixels = 0;
+    bool valid = false;
+    RowsOf rows;
+    OwnedRows owned() const { return OwnedRows{buf.p, valid, rows}; }
 };
 
 }  // namespace
@@ -63,7 +68,8 @@ struct rt_ctx {
     int commRanks = 0, commRank = 0;
     DevBuf gatherBuf;
     // path state
-    DevBuf stateBuf, queueBuf, fbBuf, counterBuf, scratchBuf;
+    DevBuf stateBuf, queueBuf, counterBuf, scratchBuf;
+    OwnedPlane fb;          // the ctx framebuffer (render_impl writes it, rt_clear_framebuffer forgets it)
     DevBuf overflowBuf[RT_MAX_LANES];     // per part (Dispatch::part): the traversal stack entries beyond LDS
     // Multi-kernel pipeline in `lanes` independent parts (render_parts): the paths of a dispatch are split into contiguous slot
     // ranges, each with its own queues, counters and stream, so that one part's k_shade and the tail of its k_trace_pw launch
@@ -73,7 +79,6 @@ struct rt_ctx {
     uint32_t capacity = 0;  // pixels the state buffers hold
     PathState ps{}; Queues q{};
     uint32_t* hostCounts = nullptr;  // pinned, 4 words
-    uint32_t fbPixels = 0; bool fbValid = false;
     // profiling of the traversal kernel (rt_set_profiling switches it; prof_begin takes events from the pool, harvest_events returns them)
     bool profiling = false;
     std::vector<EventPair> evPool;
@@ -87,30 +92,26 @@ struct rt_ctx {
     DevBuf waveTimeBuf;     // phase_stats: per-wave start/end clocks of the last k_trace_pw launch
     // first-hit AOV passes (rt_render_aovs): the ctx-owned planes of the last pass into them, and a counter block of their own, which
     // rt_get_counters adds to the rendering counters and the ray-cost snapshots never see
-    DevBuf aovBuf, aovCounterBuf;
+    OwnedPlane aov;         // the five planes in AovPlane's order (rt_render_aovs writes them)
+    DevBuf aovCounterBuf;
     DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
-    uint32_t aovPixels = 0; bool aovValid = false;
-    // the rows of the image the ctx framebuffer and the ctx AOV planes hold (rt_denoise reads them only as a whole frame)
-    RowsOf fbRows, aovRows;
     // the denoiser (rt_denoise): its work planes, the staging planes of rt_denoise_host and the ctx-owned output
-    DevBuf dnWorkBuf, dnHostBuf, dnOutBuf;
-    size_t dnOutPixels = 0; bool dnValid = false;
-    // temporal accumulation (rt_temporal_accumulate): the two histories a call reads and writes in turn, the camera and size of the
-    // call that wrote tpHist[tpCur], the staging planes of rt_temporal_accumulate_host and the ctx-owned frame and moments
-    DevBuf tpHist[2], tpHostBuf, tpOutBuf, tpMomBuf;
-    int tpCur = 0; bool tpHistValid = false;
-    uint32_t tpWidth = 0, tpHeight = 0;
-    TemporalCamera tpCam{};
-    size_t tpOutPixels = 0, tpMomPixels = 0; bool tpOutValid = false, tpMomValid = false;
-    // following moved objects and spheres (rt_temporal_track_motion): the placements behind the tables now on the device (set_objects,
-    // set_spheres), the snapshot of them an accepted call takes with tracking on (valid with the history only), the motion table on
-    // the device with its pinned staging copy and the event that says the copy has been read, and what the last call found
-    bool tpTrack = false, tpSnapValid = false;
-    PlacementSnapshot tpNow, tpSnap;
+    DevBuf dnWorkBuf, dnHostBuf;
+    OwnedPlane dnOut;
+    // temporal accumulation (rt_temporal_accumulate): the two histories a call reads and writes in turn, the staging planes of
+    // rt_temporal_accumulate_host and the ctx-owned frame and moments
+    DevBuf tpHist[2], tpHostBuf;
+    OwnedPlane tpOut, tpMom;
+    // following moved objects and spheres: the motion table on the device with its pinned staging copy and the event that says the
+    // copy has been read (upload_motion)
     DevBuf tpMotionBuf;
     float4* tpMotionHost = nullptr; size_t tpMotionHostBytes = 0;
     hipEvent_t tpMotionEvent = nullptr;
-    uint32_t tpMoved[3] = {0, 0, 0};   // moved objects, replaced objects, moved or new spheres
+
+    // ---- the temporal history as the host sees it: which of tpHist the last accepted call wrote, at what size and through which
+    // camera, the placements it saw and the ones now on the device (post_passes.h). Written through its own transitions only, by
+    // rt_upload_scene, set_objects, set_spheres, rt_temporal_reset, rt_temporal_track_motion and rt_temporal_accumulate.
+    TemporalHistory temporal;
 
     // ---- tuning: what rt_set_tuning writes (launch_plan.h: set_tuning). Nothing else assigns to it.
     Tuning tune;
@@ -160,6 +161,17 @@ int upload(rt_ctx* c, DevBuf& b, const void* src, size_t bytes) {
     if (rc) return rc;
     if (bytes) RT_HIP(c, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));  // src is borrowed for the call only
+    return 0;
+}
+
+// A ctx-owned plane of 16-byte records to the host; blocks. fn: the entry point, never: what it says when no call ever wrote the plane
+int read_plane(rt_ctx* c, const OwnedPlane* pl, const char* fn, const char* never, float* out, size_t nFloats) {
+    if (!c || !out) return -1;
+    if (!pl->valid) return c->fail(never);
+    if (nFloats != pl->pixels * 4) return c->fail(std::string(fn) + ": size mismatch");
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipMemcpyAsync(out, pl->buf.p, nFloats * 4, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -518,7 +530,7 @@ int set_spheres(rt_ctx* c, const Sphere* s, uint32_t n) {
     c->sc.sphereCount = n;
     c->sc.sphereTestMask = l.testMask;
     c->host.sphereMat.assign(l.mat.begin(), l.mat.begin() + n);
-    c->tpNow.spheres.assign(l.spheres.begin(), l.spheres.begin() + n);
+    c->temporal.set_sphere_placements(l.spheres.data(), n);
     return rebuild_emitters(c);
 }
 
@@ -542,9 +554,7 @@ int set_objects(rt_ctx* c, const ObjectLayout& l, const RenderObject* o, uint32_
     c->sc.objectCount = n;
     c->host.objMat.resize(n); c->host.objRoot.resize(n); c->host.objSampler.resize(n);
     for (uint32_t i = 0; i < n; i++) { c->host.objMat[i] = o[i].materialIndex; c->host.objRoot[i] = o[i].bvhIndex; c->host.objSampler[i] = o[i].samplerIndex; }
-    c->tpNow.fwd.assign(l.fwd.begin(), l.fwd.begin() + 3 * (size_t)n);
-    c->tpNow.inv.assign(l.inv.begin(), l.inv.begin() + 3 * (size_t)n);
-    c->tpNow.bvhIndex = c->host.objRoot;
+    c->temporal.set_object_placements(l.fwd.data(), l.inv.data(), c->host.objRoot.data(), n);
     return rebuild_emitters(c);
 }
 
@@ -664,8 +674,7 @@ int rt_upload_scene(rt_ctx* c, const RtSceneArrays* s) {
     RT_HIP(c, hipSetDevice(c->device));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     measured_new_scene(c);
-    c->tpHistValid = false;  // a new scene: nothing of the old one's frames is its history (rt_temporal_accumulate)
-    c->tpSnapValid = false;
+    c->temporal.reset();  // a new scene: nothing of the old one's frames is its history (rt_temporal_accumulate)
     c->host = SceneSources{};
     c->sc.emitMode = 0; c->sc.emitCount = 0; c->sc.emitSphereMask = 0;
     c->sc.mapFlags = 0;
@@ -720,17 +729,16 @@ DevScene dispatch_scene(const rt_ctx* c, const RayTracerData& td) {
     return sc;
 }
 
-// The camera and tile of a dispatch (host side of raytrace.comp:547-556; primary_dir is the device side)
+// The camera and tile of a dispatch (post_passes.h: camera_plane)
 FrameParams frame_camera(const rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
                          uint32_t nRows, uint32_t nPixels) {
     FrameParams fp{};
+    const CameraPlane plane = camera_plane(pc->camInfo);
     memcpy(fp.camRot, pc->camInfo.cameraRotation, 64);
     memcpy(fp.camPos, pc->camInfo.pos, 12);
-    fp.planeHeight = pc->camInfo.nearPlane * rt_tan(rt_radians(pc->camInfo.fov * 0.5f)) * 2.f;
-    fp.planeWidth = fp.planeHeight * pc->camInfo.aspectRatio;
-    fp.bottomLeft[0] = -fp.planeWidth / 2.f;
-    fp.bottomLeft[1] = -fp.planeHeight / 2.f;
-    fp.bottomLeft[2] = 0.1f;
+    fp.planeHeight = plane.planeHeight;
+    fp.planeWidth = plane.planeWidth;
+    memcpy(fp.bottomLeft, plane.bottomLeft, 12);
     fp.tiled = (c->tune.tileSlots && (width % 8u) == 0u) ? 1u : 0u;
     fp.width = width; fp.height = height; fp.row0 = row0; fp.rowStride = rowStride; fp.nRows = nRows; fp.nPixels = nPixels;
     return fp;
@@ -913,13 +921,13 @@ int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t hei
     if (rc) return rc;
     float4* fb = (float4*)d_rgba;
     if (!fb) {
-        const bool fresh = !c->fbBuf.p || c->fbPixels != nPixels;
-        if ((rc = dev_alloc(c, c->fbBuf, (size_t)nPixels * sizeof(float4)))) return rc;
-        if (fresh) RT_HIP(c, hipMemsetAsync(c->fbBuf.p, 0, (size_t)nPixels * sizeof(float4), c->stream));
-        c->fbPixels = nPixels;
-        fb = (float4*)c->fbBuf.p;
-        c->fbValid = true;
-        c->fbRows = RowsOf{width, height, row0, rowStride, nRows};
+        const bool fresh = !c->fb.buf.p || c->fb.pixels != nPixels;
+        if ((rc = dev_alloc(c, c->fb.buf, (size_t)nPixels * sizeof(float4)))) return rc;
+        if (fresh) RT_HIP(c, hipMemsetAsync(c->fb.buf.p, 0, (size_t)nPixels * sizeof(float4), c->stream));
+        c->fb.pixels = nPixels;
+        fb = (float4*)c->fb.buf.p;
+        c->fb.valid = true;
+        c->fb.rows = RowsOf{width, height, row0, rowStride, nRows};
     }
 
     // ---- per-frame constants (host side of raytrace.comp:547-564)
@@ -965,25 +973,19 @@ int rt_render_frames(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_
 
 int rt_clear_framebuffer(rt_ctx* c) {
     if (!c) return -1;
-    c->fbPixels = 0;  // the next rt_render(..., NULL) starts from a zeroed image
-    c->fbValid = false;
+    c->fb.pixels = 0;  // the next rt_render(..., NULL) starts from a zeroed image
+    c->fb.valid = false;
     return 0;
 }
 
 int rt_read_rgba_f32(rt_ctx* c, float* out, size_t nFloats) {
-    if (!c || !out) return -1;
-    if (!c->fbValid) return c->fail("no ctx-owned framebuffer: rt_render was never called with d_rgba = NULL");
-    if (nFloats != (size_t)c->fbPixels * 4) return c->fail("rt_read_rgba_f32: size mismatch");
-    RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, hipMemcpyAsync(out, c->fbBuf.p, nFloats * 4, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return read_plane(c, c ? &c->fb : nullptr, "rt_read_rgba_f32", NO_OWNED_FRAMEBUFFER, out, nFloats);
 }
 
 int rt_read_rgba8_srgb(rt_ctx* c, uint8_t* out, size_t nBytes) {
     if (!c || !out) return -1;
-    if (!c->fbValid || nBytes != (size_t)c->fbPixels * 4) return c->fail("rt_read_rgba8_srgb: size mismatch");
-    std::vector<float> tmp((size_t)c->fbPixels * 4);
+    if (!c->fb.valid || nBytes != c->fb.pixels * 4) return c->fail("rt_read_rgba8_srgb: size mismatch");
+    std::vector<float> tmp(c->fb.pixels * 4);
     int rc = rt_read_rgba_f32(c, tmp.data(), tmp.size());
     if (rc) return rc;
     // display encoding only; parity is defined on the fp32 buffer
@@ -1046,17 +1048,14 @@ int rt_render_aovs(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t 
     // so that waits for the device first.
     if (c->capacity < nPixels || !c->stateBuf.p) RT_HIP(c, hipStreamSynchronize(c->stream));
     if ((rc = ensure_state(c, nPixels))) return rc;
-    AovOut out;
-    if (d_out) {
-        out = AovOut{(float4*)d_out->normalDepth, (float4*)d_out->position, (float4*)d_out->albedo, (float4*)d_out->rayDir, (uint4*)d_out->ids};
-    } else {
-        if ((rc = dev_alloc(c, c->aovBuf, (size_t)nPixels * sizeof(float4) * 5))) return rc;
-        float4* p = (float4*)c->aovBuf.p;
-        out = AovOut{p, p + nPixels, p + 2 * (size_t)nPixels, p + 3 * (size_t)nPixels, (uint4*)(p + 4 * (size_t)nPixels)};
-        c->aovPixels = nPixels;
-        c->aovValid = true;
-        c->aovRows = RowsOf{width, height, row0, rowStride, nRows};
+    if (!d_out) {
+        if ((rc = dev_alloc(c, c->aov.buf, (size_t)nPixels * sizeof(float4) * AOV_PLANES))) return rc;
+        c->aov.pixels = nPixels;
+        c->aov.valid = true;
+        c->aov.rows = RowsOf{width, height, row0, rowStride, nRows};
     }
+    const auto plane = [&](AovPlane k) { return d_out ? aov_plane(*d_out, k) : aov_plane(c->aov.buf.p, k, nPixels); };
+    const AovOut out{(float4*)plane(AOV_NORMAL_DEPTH), (float4*)plane(AOV_POSITION), (float4*)plane(AOV_ALBEDO), (float4*)plane(AOV_RAY_DIR), (uint4*)plane(AOV_IDS)};
     FrameParams fp = frame_camera(c, pc, width, height, row0, rowStride, nRows, nPixels);
     fp.nFrames = 1;
     // this pass gets its scene counts, no per-pixel statistics and no phase statistics, and its launch is counted apart
@@ -1075,184 +1074,52 @@ int rt_render_aovs(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t 
 
 int rt_read_aovs(rt_ctx* c, const RtAovBuffers* out, size_t nPixels) {
     if (!c || !out) return -1;
-    if (!c->aovValid) return c->fail("no ctx-owned AOV planes: rt_render_aovs was never called with d_out = NULL");
-    if (nPixels != (size_t)c->aovPixels) return c->fail("rt_read_aovs: size mismatch");
+    if (!c->aov.valid) return c->fail(NO_OWNED_AOVS);
+    if (nPixels != c->aov.pixels) return c->fail("rt_read_aovs: size mismatch");
     RT_HIP(c, hipSetDevice(c->device));
-    const float4* p = (const float4*)c->aovBuf.p;
-    void* const dst[5] = {out->normalDepth, out->position, out->albedo, out->rayDir, out->ids};
-    for (int k = 0; k < 5; k++)
-        if (dst[k]) RT_HIP(c, hipMemcpyAsync(dst[k], p + (size_t)k * nPixels, nPixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    for (int k = 0; k < AOV_PLANES; k++)
+        if (void* dst = aov_plane(*out, (AovPlane)k))
+            RT_HIP(c, hipMemcpyAsync(dst, aov_plane(c->aov.buf.p, (AovPlane)k, nPixels), nPixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 }  // extern "C"
 
+// ---- the passes over finished frames: denoising and temporal accumulation. Each reads as: check, resolve the inputs, check the
+// outputs against them (post_passes.h), allocate, launch.
 namespace {
-// The checks rt_denoise and rt_denoise_host share: geometry, parameters, an uploaded scene (its material table says which hits
-// are emitters)
-int check_denoise(rt_ctx* c, uint32_t width, uint32_t height, const RtDenoiseParams& p, const char* fn) {
-    const std::string f(fn);
-    if (width == 0 || height == 0) return c->fail(f + ": bad image geometry");
-    if ((uint64_t)width * height >= (1ull << 30) || height > 65535u * 16u) return c->fail(f + ": image too large");
-    if (p.iterations > 10) return c->fail(f + ": iterations must be 0..10");
-    if (!(std::isfinite(p.sigmaLuminance) && p.sigmaLuminance > 0.f)) return c->fail(f + ": sigmaLuminance must be finite and > 0");
-    if (!(std::isfinite(p.sigmaNormal) && p.sigmaNormal >= 0.f)) return c->fail(f + ": sigmaNormal must be finite and >= 0");
-    if (!(std::isfinite(p.sigmaDepth) && p.sigmaDepth > 0.f)) return c->fail(f + ": sigmaDepth must be finite and > 0");
-    if (!c->sc.nodes) return c->fail(f + " before rt_upload_scene");
-    return 0;
-}
+// The parameters of a pass: the caller's, or the defaults
+template <typename P>
+P params_or(const P* given, void (*defaults)(P*)) { P p; defaults(&p); return given ? *given : p; }
 
-std::string not_whole(const char* what, const RowsOf& r, uint32_t width, uint32_t height, const char* fn = "rt_denoise") {
-    char m[256];
-    snprintf(m, sizeof(m), "%s: %s: rows %u + k*%u, k < %u of a %u x %u image, not the whole %u x %u frame", fn, what, r.row0,
-             r.rowStride, r.nRows, r.width, r.height, width, height);
-    return m;
-}
-
-bool overlap(const void* a, const void* b, size_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
-}
-}  // namespace
-
-extern "C" {
-
-void rt_denoise_params_default(RtDenoiseParams* p) {
-    if (p) *p = RtDenoiseParams{5u, 4.f, 128.f, 1.f};
-}
-
-int rt_denoise(rt_ctx* c, uint32_t width, uint32_t height, const float* d_rgba, const RtAovBuffers* d_aovs, const RtDenoiseParams* params,
-               float* d_out) {
-    if (!c) return -1;
-    RtDenoiseParams p;
-    rt_denoise_params_default(&p);
-    if (params) p = *params;
-    int rc = check_denoise(c, width, height, p, "rt_denoise");
+// The output of a pass: the caller's plane, or the ctx's own for `n` pixels (the caller has synchronised if that grows it)
+int output_plane(rt_ctx* c, float* d_out, OwnedPlane& own, size_t n, float4** out) {
+    *out = (float4*)d_out;
+    if (d_out) return 0;
+    int rc = dev_alloc(c, own.buf, n * sizeof(float4));
     if (rc) return rc;
-    const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
-    const float4* rgba = (const float4*)d_rgba;
-    if (!rgba) {
-        if (!c->fbValid) return c->fail("rt_denoise: no ctx-owned framebuffer: rt_render was never called with d_rgba = NULL");
-        if (!c->fbRows.whole(width, height)) return c->fail(not_whole("the ctx framebuffer", c->fbRows, width, height));
-        rgba = (const float4*)c->fbBuf.p;
-    }
-    const float4 *nd, *albedo;
-    const uint4* ids;
-    if (!d_aovs) {
-        if (!c->aovValid) return c->fail("rt_denoise: no ctx-owned AOV planes: rt_render_aovs was never called with d_out = NULL");
-        if (!c->aovRows.whole(width, height)) return c->fail(not_whole("the ctx AOV planes", c->aovRows, width, height));
-        const float4* a = (const float4*)c->aovBuf.p;   // rt_render_aovs's order: normalDepth, position, albedo, rayDir, ids
-        nd = a;
-        albedo = a + 2 * n;
-        ids = (const uint4*)(a + 4 * n);
-    } else {
-        if (!d_aovs->normalDepth || !d_aovs->albedo || !d_aovs->ids) return c->fail("rt_denoise: d_aovs needs the normalDepth, albedo and ids planes");
-        nd = (const float4*)d_aovs->normalDepth;
-        albedo = (const float4*)d_aovs->albedo;
-        ids = (const uint4*)d_aovs->ids;
-    }
-    if (d_out)
-        for (const void* in : {(const void*)rgba, (const void*)nd, (const void*)albedo, (const void*)ids})
-            if (overlap(d_out, in, bytes)) return c->fail("rt_denoise: d_out overlaps an input");
-    RT_HIP(c, hipSetDevice(c->device));
-    // growing a plane frees the old one, which a denoise still in flight may be using
-    const size_t workBytes = 2 * bytes + n * sizeof(float2);
-    if ((p.iterations && c->dnWorkBuf.bytes < workBytes) || (!d_out && c->dnOutBuf.bytes < bytes)) RT_HIP(c, hipStreamSynchronize(c->stream));
-    float4* out = (float4*)d_out;
-    if (!out) {
-        if ((rc = dev_alloc(c, c->dnOutBuf, bytes))) return rc;
-        out = (float4*)c->dnOutBuf.p;
-        c->dnOutPixels = n;
-        c->dnValid = true;
-    }
-    if (p.iterations == 0) {
-        RT_HIP(c, hipMemcpyAsync(out, rgba, bytes, hipMemcpyDeviceToDevice, c->stream));
-        return 0;
-    }
-    if ((rc = dev_alloc(c, c->dnWorkBuf, workBytes))) return rc;
-    float4* const work[2] = {(float4*)c->dnWorkBuf.p, (float4*)c->dnWorkBuf.p + n};
-    const DenoiseFrame f{rgba, nd, albedo, ids, (float2*)(work[1] + n), width, height};
-    const dim3 grid((width + 15u) / 16u, (height + 15u) / 16u), block(RT_DN_BLOCK);
-    hipLaunchKernelGGL(k_dn_demod, grid, block, 0, c->stream, f, c->sc.mats, c->sc.materialCount, work[0]);
-    hipLaunchKernelGGL(k_dn_variance, grid, block, 0, c->stream, f, (const float4*)work[0], work[1]);
-    for (uint32_t k = 0; k < p.iterations; k++) {   // pass k reads work[1 - k % 2] and writes work[k % 2], the last one `out`
-        const float4* in = work[1 - (k & 1u)];
-        if (k + 1 < p.iterations)
-            hipLaunchKernelGGL(k_dn_atrous<false>, grid, block, 0, c->stream, f, in, work[k & 1u], (float4*)nullptr, 1 << k, p.sigmaLuminance,
-                               p.sigmaNormal, p.sigmaDepth);
-        else
-            hipLaunchKernelGGL(k_dn_atrous<true>, grid, block, 0, c->stream, f, in, (float4*)nullptr, out, 1 << k, p.sigmaLuminance,
-                               p.sigmaNormal, p.sigmaDepth);
-    }
-    RT_HIP(c, hipGetLastError());
+    *out = (float4*)own.buf.p;
+    own.pixels = n;
+    own.valid = true;
     return 0;
 }
 
-int rt_read_denoised_rgba_f32(rt_ctx* c, float* out, size_t nFloats) {
-    if (!c || !out) return -1;
-    if (!c->dnValid) return c->fail("no ctx-owned denoised frame: rt_denoise was never called with d_out = NULL");
-    if (nFloats != c->dnOutPixels * 4) return c->fail("rt_read_denoised_rgba_f32: size mismatch");
+// The host-memory form of a pass: the nIn input planes of `bytes` bytes go up into one ctx buffer, one behind the other, `pass` runs
+// on the device copies with the nOut planes behind them as its outputs, and those come back (a NULL host output is not wanted).
+template <typename Pass>
+int staged(rt_ctx* c, DevBuf& buf, size_t bytes, std::initializer_list<const void*> in, std::initializer_list<void*> out, Pass pass) {
+    const size_t nIn = in.size(), nOut = out.size();
     RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, hipMemcpyAsync(out, c->dnOutBuf.p, nFloats * 4, hipMemcpyDeviceToHost, c->stream));
+    if (buf.bytes < (nIn + nOut) * bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees planes a pass in flight may be using
+    int rc = dev_alloc(c, buf, (nIn + nOut) * bytes);
+    if (rc) return rc;
+    char* d = (char*)buf.p;
+    for (size_t k = 0; k < nIn; k++) RT_HIP(c, hipMemcpyAsync(d + k * bytes, in.begin()[k], bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = pass(d))) return rc;
+    for (size_t k = 0; k < nOut; k++)
+        if (out.begin()[k]) RT_HIP(c, hipMemcpyAsync(out.begin()[k], d + (nIn + k) * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
-}
-
-int rt_denoise_host(rt_ctx* c, uint32_t width, uint32_t height, const float* rgba, const RtAovBuffers* aovs, const RtDenoiseParams* params,
-                    float* out) {
-    if (!c) return -1;
-    RtDenoiseParams p;
-    rt_denoise_params_default(&p);
-    if (params) p = *params;
-    int rc = check_denoise(c, width, height, p, "rt_denoise_host");
-    if (rc) return rc;
-    if (!rgba || !out) return c->fail("rt_denoise_host: rgba and out are required");
-    if (!aovs || !aovs->normalDepth || !aovs->albedo || !aovs->ids) return c->fail("rt_denoise_host: aovs needs the normalDepth, albedo and ids planes");
-    const size_t bytes = (size_t)width * height * sizeof(float4);
-    RT_HIP(c, hipSetDevice(c->device));
-    if (c->dnHostBuf.bytes < 5 * bytes) RT_HIP(c, hipStreamSynchronize(c->stream));
-    if ((rc = dev_alloc(c, c->dnHostBuf, 5 * bytes))) return rc;
-    char* d = (char*)c->dnHostBuf.p;   // rgba, normalDepth, albedo, ids, out
-    const void* src[4] = {rgba, aovs->normalDepth, aovs->albedo, aovs->ids};
-    for (int k = 0; k < 4; k++) RT_HIP(c, hipMemcpyAsync(d + k * bytes, src[k], bytes, hipMemcpyHostToDevice, c->stream));
-    RtAovBuffers planes{};
-    planes.normalDepth = (float*)(d + bytes);
-    planes.albedo = (float*)(d + 2 * bytes);
-    planes.ids = (uint32_t*)(d + 3 * bytes);
-    if ((rc = rt_denoise(c, width, height, (const float*)d, &planes, &p, (float*)(d + 4 * bytes)))) return rc;
-    RT_HIP(c, hipMemcpyAsync(out, d + 4 * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-}  // extern "C"
-
-// ---- temporal accumulation
-namespace {
-// The checks rt_temporal_accumulate and rt_temporal_accumulate_host share
-int check_temporal(rt_ctx* c, uint32_t width, uint32_t height, const CameraInfo* cam, const RtTemporalParams& p, const char* fn) {
-    const std::string f(fn);
-    if (width == 0 || height == 0) return c->fail(f + ": bad image geometry");
-    if ((uint64_t)width * height >= (1ull << 30) || height > 65535u * 16u) return c->fail(f + ": image too large");
-    if (!cam) return c->fail(f + ": the camera the frame was rendered with is required");
-    if (p.maxHistory == 0) return c->fail(f + ": maxHistory must be >= 1");
-    if (!(p.normalCos >= -1.f && p.normalCos <= 1.f)) return c->fail(f + ": normalCos must be in [-1, 1]");
-    if (!(std::isfinite(p.depthTolerance) && p.depthTolerance > 0.f)) return c->fail(f + ": depthTolerance must be finite and > 0");
-    if (!c->sc.nodes) return c->fail(f + " before rt_upload_scene");
-    return 0;
-}
-
-// frame_camera's plane of a camera
-TemporalCamera temporal_camera(const CameraInfo& ci) {
-    TemporalCamera t{};
-    memcpy(t.rot, ci.cameraRotation, 64);
-    memcpy(t.pos, ci.pos, 12);
-    t.planeHeight = ci.nearPlane * rt_tan(rt_radians(ci.fov * 0.5f)) * 2.f;
-    t.planeWidth = t.planeHeight * ci.aspectRatio;
-    t.bottomLeft[0] = -t.planeWidth / 2.f;
-    t.bottomLeft[1] = -t.planeHeight / 2.f;
-    t.bottomLeft[2] = 0.1f;
-    return t;
 }
 
 // The motion table onto the device, on the ctx stream: stream order keeps the copy behind the launch that still reads the table of
@@ -1285,171 +1152,165 @@ int upload_motion(rt_ctx* c, const MotionTable& mt, TemporalMotion& mo) {
 
 extern "C" {
 
+void rt_denoise_params_default(RtDenoiseParams* p) {
+    if (p) *p = RtDenoiseParams{5u, 4.f, 128.f, 1.f};
+}
+
+int rt_denoise(rt_ctx* c, uint32_t width, uint32_t height, const float* d_rgba, const RtAovBuffers* d_aovs, const RtDenoiseParams* params,
+               float* d_out) {
+    if (!c) return -1;
+    const RtDenoiseParams p = params_or(params, rt_denoise_params_default);
+    std::string m = check_denoise(width, height, p, c->sc.nodes != nullptr, "rt_denoise");
+    if (!m.empty()) return c->fail(m);
+    const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
+    const PassInputs in = resolve_inputs("rt_denoise", width, height, d_rgba, d_aovs, false, c->fb.owned(), c->aov.owned());
+    if (!in.error.empty()) return c->fail(in.error);
+    const NamedPlane outs[1] = {{"d_out", d_out}};
+    if (!(m = check_overlap("rt_denoise", in, "d_out", outs, 1, bytes)).empty()) return c->fail(m);
+    RT_HIP(c, hipSetDevice(c->device));
+    // growing a plane frees the old one, which a denoise still in flight may be using
+    const size_t workBytes = 2 * bytes + n * sizeof(float2);
+    if ((p.iterations && c->dnWorkBuf.bytes < workBytes) || (!d_out && c->dnOut.buf.bytes < bytes)) RT_HIP(c, hipStreamSynchronize(c->stream));
+    float4* out;
+    int rc = output_plane(c, d_out, c->dnOut, n, &out);
+    if (rc) return rc;
+    if (p.iterations == 0) {
+        RT_HIP(c, hipMemcpyAsync(out, in.rgba, bytes, hipMemcpyDeviceToDevice, c->stream));
+        return 0;
+    }
+    if ((rc = dev_alloc(c, c->dnWorkBuf, workBytes))) return rc;
+    float4* const work[2] = {(float4*)c->dnWorkBuf.p, (float4*)c->dnWorkBuf.p + n};
+    const DenoiseFrame f{in.rgba, in.normalDepth, in.albedo, in.ids, (float2*)(work[1] + n), width, height};
+    const dim3 grid((width + 15u) / 16u, (height + 15u) / 16u), block(RT_DN_BLOCK);
+    hipLaunchKernelGGL(k_dn_demod, grid, block, 0, c->stream, f, c->sc.mats, c->sc.materialCount, work[0]);
+    hipLaunchKernelGGL(k_dn_variance, grid, block, 0, c->stream, f, (const float4*)work[0], work[1]);
+    for (uint32_t k = 0; k < p.iterations; k++) {   // pass k reads work[1 - k % 2] and writes work[k % 2], the last one `out`
+        const float4* src = work[1 - (k & 1u)];
+        if (k + 1 < p.iterations)
+            hipLaunchKernelGGL(k_dn_atrous<false>, grid, block, 0, c->stream, f, src, work[k & 1u], (float4*)nullptr, 1 << k, p.sigmaLuminance,
+                               p.sigmaNormal, p.sigmaDepth);
+        else
+            hipLaunchKernelGGL(k_dn_atrous<true>, grid, block, 0, c->stream, f, src, (float4*)nullptr, out, 1 << k, p.sigmaLuminance,
+                               p.sigmaNormal, p.sigmaDepth);
+    }
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rt_read_denoised_rgba_f32(rt_ctx* c, float* out, size_t nFloats) {
+    return read_plane(c, c ? &c->dnOut : nullptr, "rt_read_denoised_rgba_f32", "no ctx-owned denoised frame: rt_denoise was never called with d_out = NULL", out, nFloats);
+}
+
+int rt_denoise_host(rt_ctx* c, uint32_t width, uint32_t height, const float* rgba, const RtAovBuffers* aovs, const RtDenoiseParams* params,
+                    float* out) {
+    if (!c) return -1;
+    const RtDenoiseParams p = params_or(params, rt_denoise_params_default);
+    const std::string m = check_denoise(width, height, p, c->sc.nodes != nullptr, "rt_denoise_host");
+    if (!m.empty()) return c->fail(m);
+    if (!rgba || !out) return c->fail("rt_denoise_host: rgba and out are required");
+    if (!aovs || !aovs->normalDepth || !aovs->albedo || !aovs->ids) return c->fail("rt_denoise_host: aovs needs the normalDepth, albedo and ids planes");
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    return staged(c, c->dnHostBuf, bytes, {rgba, aovs->normalDepth, aovs->albedo, aovs->ids}, {out}, [&](char* d) {
+        RtAovBuffers planes{};
+        planes.normalDepth = (float*)(d + bytes);
+        planes.albedo = (float*)(d + 2 * bytes);
+        planes.ids = (uint32_t*)(d + 3 * bytes);
+        return rt_denoise(c, width, height, (const float*)d, &planes, &p, (float*)(d + 4 * bytes));
+    });
+}
+
 void rt_temporal_params_default(RtTemporalParams* p) {
     if (p) *p = RtTemporalParams{32u, 0.9f, 0.02f};
 }
 
 int rt_temporal_reset(rt_ctx* c) {
     if (!c) return -1;
-    c->tpHistValid = false;   // host state only: the next call reads no history, and the ctx stream orders it after the last one
-    c->tpSnapValid = false;
+    c->temporal.reset();
     return 0;
 }
 
 int rt_temporal_track_motion(rt_ctx* c, int enabled) {
     if (!c) return -1;
-    if (c->tpTrack == (enabled != 0)) return 0;
-    c->tpTrack = enabled != 0;
-    c->tpHistValid = false;   // the history of the other mode has no snapshot to go with it, or one nobody kept up
-    c->tpSnapValid = false;
+    c->temporal.set_tracking(enabled != 0);
     return 0;
 }
 
 int rt_temporal_motion_state(const rt_ctx* c, uint32_t* movedObjects, uint32_t* replacedObjects, uint32_t* movedSpheres) {
     if (!c) return -1;
-    if (movedObjects) *movedObjects = c->tpMoved[0];
-    if (replacedObjects) *replacedObjects = c->tpMoved[1];
-    if (movedSpheres) *movedSpheres = c->tpMoved[2];
+    const uint32_t* moved = c->temporal.moved_counts();
+    if (movedObjects) *movedObjects = moved[0];
+    if (replacedObjects) *replacedObjects = moved[1];
+    if (movedSpheres) *movedSpheres = moved[2];
     return 0;
 }
 
 int rt_temporal_accumulate(rt_ctx* c, uint32_t width, uint32_t height, const CameraInfo* cam, const float* d_rgba, const RtAovBuffers* d_aovs,
                            const RtTemporalParams* params, float* d_out, float* d_moments) {
     if (!c) return -1;
-    RtTemporalParams p;
-    rt_temporal_params_default(&p);
-    if (params) p = *params;
-    int rc = check_temporal(c, width, height, cam, p, "rt_temporal_accumulate");
-    if (rc) return rc;
+    const RtTemporalParams p = params_or(params, rt_temporal_params_default);
+    std::string m = check_temporal(width, height, cam, p, c->sc.nodes != nullptr, "rt_temporal_accumulate");
+    if (!m.empty()) return c->fail(m);
     const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
-    const float4* rgba = (const float4*)d_rgba;
-    if (!rgba) {
-        if (!c->fbValid) return c->fail("rt_temporal_accumulate: no ctx-owned framebuffer: rt_render was never called with d_rgba = NULL");
-        if (!c->fbRows.whole(width, height)) return c->fail(not_whole("the ctx framebuffer", c->fbRows, width, height, "rt_temporal_accumulate"));
-        rgba = (const float4*)c->fbBuf.p;
-    }
-    const float4 *nd, *position, *albedo;
-    const uint4* ids;
-    if (!d_aovs) {
-        if (!c->aovValid) return c->fail("rt_temporal_accumulate: no ctx-owned AOV planes: rt_render_aovs was never called with d_out = NULL");
-        if (!c->aovRows.whole(width, height)) return c->fail(not_whole("the ctx AOV planes", c->aovRows, width, height, "rt_temporal_accumulate"));
-        const float4* a = (const float4*)c->aovBuf.p;   // rt_render_aovs's order: normalDepth, position, albedo, rayDir, ids
-        nd = a;
-        position = a + n;
-        albedo = a + 2 * n;
-        ids = (const uint4*)(a + 4 * n);
-    } else {
-        if (!d_aovs->normalDepth || !d_aovs->position || !d_aovs->albedo || !d_aovs->ids)
-            return c->fail("rt_temporal_accumulate: d_aovs needs the normalDepth, position, albedo and ids planes");
-        nd = (const float4*)d_aovs->normalDepth;
-        position = (const float4*)d_aovs->position;
-        albedo = (const float4*)d_aovs->albedo;
-        ids = (const uint4*)d_aovs->ids;
-    }
-    for (const void* o : {(const void*)d_out, (const void*)d_moments}) {
-        if (!o) continue;
-        for (const void* in : {(const void*)rgba, (const void*)nd, (const void*)position, (const void*)albedo, (const void*)ids})
-            if (overlap(o, in, bytes)) return c->fail("rt_temporal_accumulate: an output overlaps an input");
-    }
-    if (d_out && d_moments && overlap(d_out, d_moments, bytes)) return c->fail("rt_temporal_accumulate: d_out overlaps d_moments");
+    const PassInputs in = resolve_inputs("rt_temporal_accumulate", width, height, d_rgba, d_aovs, true, c->fb.owned(), c->aov.owned());
+    if (!in.error.empty()) return c->fail(in.error);
+    const NamedPlane outs[2] = {{"d_out", d_out}, {"d_moments", d_moments}};
+    if (!(m = check_overlap("rt_temporal_accumulate", in, "an output", outs, 2, bytes)).empty()) return c->fail(m);
     RT_HIP(c, hipSetDevice(c->device));
     // growing a plane frees the old one, which a call still in flight may be using
-    if (c->tpHist[0].bytes < 3 * bytes || c->tpHist[1].bytes < 3 * bytes || (!d_out && c->tpOutBuf.bytes < bytes) || (!d_moments && c->tpMomBuf.bytes < bytes))
-        RT_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->tpWidth != width || c->tpHeight != height) { c->tpHistValid = false; c->tpSnapValid = false; }   // a history of another size is none
-    for (DevBuf& h : c->tpHist)
-        if (h.bytes < 3 * bytes) {
-            c->tpHistValid = false;
-            c->tpSnapValid = false;
-            if ((rc = dev_alloc(c, h, 3 * bytes))) return rc;
-        }
-    float4 *out = (float4*)d_out, *mom = (float4*)d_moments;
-    if (!out) {
-        if ((rc = dev_alloc(c, c->tpOutBuf, bytes))) return rc;
-        out = (float4*)c->tpOutBuf.p;
-        c->tpOutPixels = n;
-        c->tpOutValid = true;
+    const bool historyFits = c->tpHist[0].bytes >= 3 * bytes && c->tpHist[1].bytes >= 3 * bytes;
+    if (!historyFits || (!d_out && c->tpOut.buf.bytes < bytes) || (!d_moments && c->tpMom.buf.bytes < bytes)) RT_HIP(c, hipStreamSynchronize(c->stream));
+    float4 *out, *mom;
+    int rc;
+    if ((rc = dev_alloc(c, c->tpHist[0], 3 * bytes)) || (rc = dev_alloc(c, c->tpHist[1], 3 * bytes)) ||
+        (rc = output_plane(c, d_out, c->tpOut, n, &out)) || (rc = output_plane(c, d_moments, c->tpMom, n, &mom))) {
+        if (!historyFits) c->temporal.reset();   // a history buffer may be gone
+        return rc;
     }
-    if (!mom) {
-        if ((rc = dev_alloc(c, c->tpMomBuf, bytes))) return rc;
-        mom = (float4*)c->tpMomBuf.p;
-        c->tpMomPixels = n;
-        c->tpMomValid = true;
-    }
-    const int next = 1 - c->tpCur;
-    const TemporalFrame f{rgba, nd, position, albedo, ids, c->tpHistValid ? (const float4*)c->tpHist[c->tpCur].p : nullptr,
-                          (float4*)c->tpHist[next].p, out, mom, width, height};
+    const TemporalHistory::Step step = c->temporal.begin(width, height, historyFits);
+    const TemporalFrame f{in.rgba, in.normalDepth, in.position, in.albedo, in.ids, step.read < 0 ? nullptr : (const float4*)c->tpHist[step.read].p,
+                          (float4*)c->tpHist[step.write].p, out, mom, width, height};
     const dim3 grid((width + 15u) / 16u, (height + 15u) / 16u), block(RT_DN_BLOCK);
-    // what moved since the call that wrote the history: only then the motion kernel, else today's launch with today's arguments
-    MotionTable mt;
-    if (c->tpTrack && c->tpHistValid && c->tpSnapValid) mt = motion_table(c->tpSnap, c->tpNow);
-    c->tpMoved[0] = mt.movedObjects; c->tpMoved[1] = mt.replacedObjects; c->tpMoved[2] = mt.movedSpheres + mt.replacedSpheres;
-    if (mt.any()) {
+    const TemporalCamera& prevCam = c->temporal.camera();   // of the call that wrote step.read
+    if (step.motion.any()) {
         TemporalMotion mo{};
-        if ((rc = upload_motion(c, mt, mo))) return rc;
-        hipLaunchKernelGGL(k_tp_accumulate_motion, grid, block, 0, c->stream, f, c->tpCam, c->sc.mats, c->sc.materialCount, (float)p.maxHistory,
+        if ((rc = upload_motion(c, step.motion, mo))) return rc;
+        hipLaunchKernelGGL(k_tp_accumulate_motion, grid, block, 0, c->stream, f, prevCam, c->sc.mats, c->sc.materialCount, (float)p.maxHistory,
                            p.normalCos, p.depthTolerance, mo);
     } else {
-        hipLaunchKernelGGL(k_tp_accumulate, grid, block, 0, c->stream, f, c->tpCam, c->sc.mats, c->sc.materialCount, (float)p.maxHistory, p.normalCos,
+        hipLaunchKernelGGL(k_tp_accumulate, grid, block, 0, c->stream, f, prevCam, c->sc.mats, c->sc.materialCount, (float)p.maxHistory, p.normalCos,
                            p.depthTolerance);
     }
     RT_HIP(c, hipGetLastError());
-    if (c->tpTrack) { c->tpSnap = c->tpNow; c->tpSnapValid = true; }
-    c->tpCur = next;
-    c->tpHistValid = true;
-    c->tpWidth = width; c->tpHeight = height;
-    c->tpCam = temporal_camera(*cam);
+    c->temporal.commit(*cam);
     return 0;
 }
 
 int rt_read_temporal_rgba_f32(rt_ctx* c, float* out, size_t nFloats) {
-    if (!c || !out) return -1;
-    if (!c->tpOutValid) return c->fail("no ctx-owned accumulated frame: rt_temporal_accumulate was never called with d_out = NULL");
-    if (nFloats != c->tpOutPixels * 4) return c->fail("rt_read_temporal_rgba_f32: size mismatch");
-    RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, hipMemcpyAsync(out, c->tpOutBuf.p, nFloats * 4, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return read_plane(c, c ? &c->tpOut : nullptr, "rt_read_temporal_rgba_f32", "no ctx-owned accumulated frame: rt_temporal_accumulate was never called with d_out = NULL", out, nFloats);
 }
 
 int rt_read_temporal_moments(rt_ctx* c, float* out, size_t nFloats) {
-    if (!c || !out) return -1;
-    if (!c->tpMomValid) return c->fail("no ctx-owned moments: rt_temporal_accumulate was never called with d_moments = NULL");
-    if (nFloats != c->tpMomPixels * 4) return c->fail("rt_read_temporal_moments: size mismatch");
-    RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, hipMemcpyAsync(out, c->tpMomBuf.p, nFloats * 4, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return read_plane(c, c ? &c->tpMom : nullptr, "rt_read_temporal_moments", "no ctx-owned moments: rt_temporal_accumulate was never called with d_moments = NULL", out, nFloats);
 }
 
 int rt_temporal_accumulate_host(rt_ctx* c, uint32_t width, uint32_t height, const CameraInfo* cam, const float* rgba, const RtAovBuffers* aovs,
                                 const RtTemporalParams* params, float* out, float* moments) {
     if (!c) return -1;
-    RtTemporalParams p;
-    rt_temporal_params_default(&p);
-    if (params) p = *params;
-    int rc = check_temporal(c, width, height, cam, p, "rt_temporal_accumulate_host");
-    if (rc) return rc;
+    const RtTemporalParams p = params_or(params, rt_temporal_params_default);
+    const std::string m = check_temporal(width, height, cam, p, c->sc.nodes != nullptr, "rt_temporal_accumulate_host");
+    if (!m.empty()) return c->fail(m);
     if (!rgba || !out) return c->fail("rt_temporal_accumulate_host: rgba and out are required");
     if (!aovs || !aovs->normalDepth || !aovs->position || !aovs->albedo || !aovs->ids)
         return c->fail("rt_temporal_accumulate_host: aovs needs the normalDepth, position, albedo and ids planes");
     const size_t bytes = (size_t)width * height * sizeof(float4);
-    RT_HIP(c, hipSetDevice(c->device));
-    if (c->tpHostBuf.bytes < 7 * bytes) RT_HIP(c, hipStreamSynchronize(c->stream));
-    if ((rc = dev_alloc(c, c->tpHostBuf, 7 * bytes))) return rc;
-    char* d = (char*)c->tpHostBuf.p;   // rgba, normalDepth, position, albedo, ids, out, moments
-    const void* src[5] = {rgba, aovs->normalDepth, aovs->position, aovs->albedo, aovs->ids};
-    for (int k = 0; k < 5; k++) RT_HIP(c, hipMemcpyAsync(d + k * bytes, src[k], bytes, hipMemcpyHostToDevice, c->stream));
-    RtAovBuffers planes{};
-    planes.normalDepth = (float*)(d + bytes);
-    planes.position = (float*)(d + 2 * bytes);
-    planes.albedo = (float*)(d + 3 * bytes);
-    planes.ids = (uint32_t*)(d + 4 * bytes);
-    if ((rc = rt_temporal_accumulate(c, width, height, cam, (const float*)d, &planes, &p, (float*)(d + 5 * bytes), (float*)(d + 6 * bytes)))) return rc;
-    RT_HIP(c, hipMemcpyAsync(out, d + 5 * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (moments) RT_HIP(c, hipMemcpyAsync(moments, d + 6 * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return staged(c, c->tpHostBuf, bytes, {rgba, aovs->normalDepth, aovs->position, aovs->albedo, aovs->ids}, {out, moments}, [&](char* d) {
+        RtAovBuffers planes{};
+        planes.normalDepth = (float*)(d + bytes);
+        planes.position = (float*)(d + 2 * bytes);
+        planes.albedo = (float*)(d + 3 * bytes);
+        planes.ids = (uint32_t*)(d + 4 * bytes);
+        return rt_temporal_accumulate(c, width, height, cam, (const float*)d, &planes, &p, (float*)(d + 5 * bytes), (float*)(d + 6 * bytes));
+    });
 }
 
 int rt_get_counters(rt_ctx* c, RtCounters* out) {

@@ -29,6 +29,7 @@
 #include "scene_layout.h"   // the formats of the scene tables: node words, object flags, RT_MAP_*, RT_HOT_PAIRS, RT_OBJTREE_LEVELS
 #include "launch_plan.h"    // RT_WAVE, RT_BLOCK: the launch policy sizes grids and blocks with them
 #include "temporal_motion.h" // the records of the temporal pass's motion table (RT_MOTION_*)
+#include "post_passes.h"     // TemporalCamera: the previous call's camera, a kernel argument of the temporal pass
 
 #ifndef RT_QUEUE_ORDER
 #define RT_QUEUE_ORDER 0   // k_shade: the ray queue's pieces are {main, NEE, cosine probes} (1: {main, cosine probes, NEE})
@@ -2038,12 +2039,6 @@ __global__ __launch_bounds__(RT_DN_BLOCK) void k_dn_atrous(DenoiseFrame f, const
 // frame is blended into what the taps that still show the same surface hold. One lane per pixel in the denoiser's 8x8 / 16x16
 // order. A history is three planes of 16-byte records, (e.rgb, N), (m1, m2, z, object) and (n.xyz, material << 1 | sphere), so a
 // tap is three gathers; N = 0 marks a kept pixel, which is never a tap. The launch reads one history and writes the other.
-struct TemporalCamera {   // the previous call's camera, as frame_camera has it
-    float rot[16];
-    float pos[3];
-    float planeWidth, planeHeight;
-    float bottomLeft[3];
-};
 struct TemporalFrame {
     const float4* rgba;         // the noisy frame; pixel (x, y) at y * width + x
     const float4* normalDepth;  // rt_render_aovs's planes of the same frame

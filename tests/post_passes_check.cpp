@@ -1,0 +1,354 @@
+// post_passes_check.cpp — the host logic of the AOV, denoising and temporal passes on the CPU (ray_tracer_amd/csrc/post_passes.h),
+// built with plain g++ by tests/test_post_passes.py: every refusal the GPU tests assert, from the input that provokes it there; where
+// the input planes of a pass are; which outputs overlap them; the temporal history through the call / reset / toggle / upload / resize
+// / refusal scripts of the GPU tests; the image plane of a camera. No plane is ever dereferenced: the addresses are made up.
+// Prints "post passes ok".
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <string>
+
+#include "post_passes.h"
+#include "rt_det_math.h"
+
+namespace {
+
+int failures = 0;
+#define CHECK(x)                                                              \
+    do {                                                                      \
+        if (!(x)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } \
+    } while (0)
+
+bool has(const std::string& m, const char* part) { return m.find(part) != std::string::npos; }
+template <typename T> T* at(uintptr_t a) { return (T*)a; }
+
+const float NaN = std::numeric_limits<float>::quiet_NaN(), Inf = std::numeric_limits<float>::infinity();
+
+// ---------------------------------------------------------------- parameter checks
+void denoise_checks() {
+    const RtDenoiseParams ok{5u, 4.f, 128.f, 1.f};
+    const auto with = [&](uint32_t it, float sl, float sn, float sz) { return check_denoise(8, 8, RtDenoiseParams{it, sl, sn, sz}, true, "rt_denoise"); };
+    CHECK(check_denoise(8, 8, ok, true, "rt_denoise").empty());
+    CHECK(check_denoise(8, 8, ok, false, "rt_denoise") == "rt_denoise before rt_upload_scene");
+    CHECK(check_denoise(8, 8, ok, false, "rt_denoise_host") == "rt_denoise_host before rt_upload_scene");
+    CHECK(check_denoise(0, 8, ok, true, "rt_denoise") == "rt_denoise: bad image geometry");
+    CHECK(check_denoise(8, 0, ok, true, "rt_denoise_host") == "rt_denoise_host: bad image geometry");
+    CHECK(check_denoise(1u << 15, 1u << 15, ok, true, "rt_denoise") == "rt_denoise: image too large");
+    CHECK(check_denoise(1, 65535u * 16u + 1u, ok, true, "rt_denoise") == "rt_denoise: image too large");   // more rows than a grid has
+    CHECK(check_denoise(1, 65535u * 16u, ok, true, "rt_denoise").empty());
+    CHECK(with(11, 4.f, 128.f, 1.f) == "rt_denoise: iterations must be 0..10");
+    CHECK(with(0, 4.f, 128.f, 1.f).empty() && with(10, 4.f, 128.f, 1.f).empty());
+    for (float bad : {0.f, -1.f, NaN, Inf, -Inf}) {
+        CHECK(with(5, bad, 128.f, 1.f) == "rt_denoise: sigmaLuminance must be finite and > 0");
+        CHECK(with(5, 4.f, 128.f, bad) == "rt_denoise: sigmaDepth must be finite and > 0");
+    }
+    for (float bad : {-1.f, NaN, Inf, -Inf}) CHECK(with(5, 4.f, bad, 1.f) == "rt_denoise: sigmaNormal must be finite and >= 0");
+    CHECK(with(5, 4.f, 0.f, 1.f).empty());   // normals that do not stop the filter
+    // the order: geometry, then the parameters in their order, then the scene
+    CHECK(has(check_denoise(0, 8, RtDenoiseParams{11u, 0.f, -1.f, 0.f}, false, "rt_denoise"), "bad image geometry"));
+    CHECK(has(check_denoise(8, 8, RtDenoiseParams{11u, 0.f, -1.f, 0.f}, false, "rt_denoise"), "iterations"));
+    CHECK(has(check_denoise(8, 8, RtDenoiseParams{5u, 0.f, -1.f, 0.f}, false, "rt_denoise"), "sigmaLuminance"));
+    CHECK(has(check_denoise(8, 8, RtDenoiseParams{5u, 4.f, -1.f, 0.f}, false, "rt_denoise"), "sigmaNormal"));
+    CHECK(has(check_denoise(8, 8, RtDenoiseParams{5u, 4.f, 1.f, 0.f}, false, "rt_denoise"), "sigmaDepth"));
+}
+
+void temporal_checks() {
+    const RtTemporalParams ok{32u, 0.9f, 0.02f};
+    const CameraInfo cam{};
+    const auto with = [&](uint32_t mh, float nc, float dt) { return check_temporal(8, 8, &cam, RtTemporalParams{mh, nc, dt}, true, "rt_temporal_accumulate"); };
+    CHECK(check_temporal(8, 8, &cam, ok, true, "rt_temporal_accumulate").empty());
+    CHECK(check_temporal(8, 8, &cam, ok, false, "rt_temporal_accumulate") == "rt_temporal_accumulate before rt_upload_scene");
+    CHECK(check_temporal(8, 8, &cam, ok, false, "rt_temporal_accumulate_host") == "rt_temporal_accumulate_host before rt_upload_scene");
+    CHECK(check_temporal(0, 8, &cam, ok, true, "rt_temporal_accumulate") == "rt_temporal_accumulate: bad image geometry");
+    CHECK(check_temporal(8, 0, &cam, ok, true, "rt_temporal_accumulate") == "rt_temporal_accumulate: bad image geometry");
+    CHECK(check_temporal(1u << 15, 1u << 15, &cam, ok, true, "rt_temporal_accumulate") == "rt_temporal_accumulate: image too large");
+    CHECK(check_temporal(8, 8, nullptr, ok, true, "rt_temporal_accumulate") == "rt_temporal_accumulate: the camera the frame was rendered with is required");
+    CHECK(with(0, 0.9f, 0.02f) == "rt_temporal_accumulate: maxHistory must be >= 1");
+    CHECK(with(1, 0.9f, 0.02f).empty());   // passes the frame through
+    for (float bad : {1.5f, -1.01f, NaN, Inf, -Inf}) CHECK(with(32, bad, 0.02f) == "rt_temporal_accumulate: normalCos must be in [-1, 1]");
+    CHECK(with(32, 1.f, 0.02f).empty() && with(32, -1.f, 0.02f).empty());
+    for (float bad : {0.f, -1.f, NaN, Inf, -Inf}) CHECK(with(32, 0.9f, bad) == "rt_temporal_accumulate: depthTolerance must be finite and > 0");
+    // the order: geometry, the camera, the parameters in their order, then the scene
+    CHECK(has(check_temporal(0, 8, nullptr, RtTemporalParams{0u, 2.f, 0.f}, false, "rt_temporal_accumulate"), "bad image geometry"));
+    CHECK(has(check_temporal(8, 8, nullptr, RtTemporalParams{0u, 2.f, 0.f}, false, "rt_temporal_accumulate"), "camera"));
+    CHECK(has(check_temporal(8, 8, &cam, RtTemporalParams{0u, 2.f, 0.f}, false, "rt_temporal_accumulate"), "maxHistory"));
+    CHECK(has(check_temporal(8, 8, &cam, RtTemporalParams{1u, 2.f, 0.f}, false, "rt_temporal_accumulate"), "normalCos"));
+    CHECK(has(check_temporal(8, 8, &cam, RtTemporalParams{1u, 1.f, 0.f}, false, "rt_temporal_accumulate"), "depthTolerance"));
+}
+
+// ---------------------------------------------------------------- input resolution
+void resolution() {
+    const uintptr_t FB = 0x10000000u, AOV = 0x20000000u;
+    const RowsOf whole8{8, 8, 0, 1, 8}, strip{8, 8, 0, 2, 4}, partial{8, 8, 1, 1, 7};
+    const OwnedRows noFb{nullptr, false, {}}, noAov{nullptr, false, {}};
+    const OwnedRows fb8{at<void>(FB), true, whole8}, aov8{at<void>(AOV), true, whole8};
+    for (const char* fn : {"rt_denoise", "rt_temporal_accumulate"}) {
+        const bool pos = fn[3] == 't';
+        const std::string f(fn);
+        const auto resolve = [&](uint32_t W, uint32_t H, const OwnedRows& fb, const OwnedRows& aov) { return resolve_inputs(fn, W, H, nullptr, nullptr, pos, fb, aov); };
+        // the refusals, in the order the GPU tests meet them
+        CHECK(resolve(8, 8, noFb, noAov).error == f + ": no ctx-owned framebuffer: rt_render was never called with d_rgba = NULL");
+        CHECK(resolve(8, 8, OwnedRows{at<void>(FB), true, strip}, noAov).error ==
+              f + ": the ctx framebuffer: rows 0 + k*2, k < 4 of a 8 x 8 image, not the whole 8 x 8 frame");
+        CHECK(resolve(8, 8, fb8, noAov).error == f + ": no ctx-owned AOV planes: rt_render_aovs was never called with d_out = NULL");
+        CHECK(resolve(8, 8, fb8, OwnedRows{at<void>(AOV), true, partial}).error ==
+              f + ": the ctx AOV planes: rows 1 + k*1, k < 7 of a 8 x 8 image, not the whole 8 x 8 frame");
+        CHECK(resolve(16, 8, fb8, aov8).error == f + ": the ctx framebuffer: rows 0 + k*1, k < 8 of a 8 x 8 image, not the whole 16 x 8 frame");
+        CHECK(has(resolve(16, 8, fb8, aov8).error, "not the whole 16 x 8 frame"));
+        // a frame of the same pixel count in another shape is another frame
+        CHECK(has(resolve(23, 37, OwnedRows{at<void>(FB), true, RowsOf{37, 23, 0, 1, 23}}, aov8).error, "rows 0 + k*1, k < 23 of a 37 x 23 image, not the whole 23 x 37 frame"));
+        // the caller's frame with the ctx planes, which are then the ones checked
+        CHECK(has(resolve_inputs(fn, 16, 8, at<float>(0x500), nullptr, pos, noFb, aov8).error, "the ctx AOV planes: rows 0 + k*1, k < 8 of a 8 x 8 image, not the whole 16 x 8 frame"));
+        // ctx-owned planes: base + k * n * 16 in rt_render_aovs's order (normalDepth 0, position 1, albedo 2, rayDir 3, ids 4), at two sizes
+        const uint32_t sizes[2][2] = {{8, 8}, {37, 23}};
+        for (const auto& s : sizes) {
+            const RowsOf whole{s[0], s[1], 0, 1, s[1]};
+            const size_t n = (size_t)s[0] * s[1];
+            const PassInputs in = resolve(s[0], s[1], OwnedRows{at<void>(FB), true, whole}, OwnedRows{at<void>(AOV), true, whole});
+            CHECK(in.error.empty());
+            CHECK((uintptr_t)in.rgba == FB && (uintptr_t)in.normalDepth == AOV && (uintptr_t)in.albedo == AOV + 2 * n * 16 && (uintptr_t)in.ids == AOV + 4 * n * 16);
+            CHECK((uintptr_t)in.position == (pos ? AOV + n * 16 : 0));
+        }
+    }
+    CHECK((uintptr_t)aov_plane(at<void>(AOV), AOV_RAY_DIR, 64) == AOV + 3 * 64 * 16 && AOV_PLANES == 5);
+    // the caller's planes pass through untouched, whatever the ctx owns; position is the temporal pass's alone
+    RtAovBuffers b{};
+    b.normalDepth = at<float>(0x1000); b.albedo = at<float>(0x3000); b.ids = at<uint32_t>(0x5000); b.rayDir = at<float>(0x4000);
+    PassInputs in = resolve_inputs("rt_denoise", 8, 8, at<float>(0x500), &b, false, noFb, noAov);
+    CHECK(in.error.empty() && (uintptr_t)in.rgba == 0x500 && (uintptr_t)in.normalDepth == 0x1000 && !in.position && (uintptr_t)in.albedo == 0x3000 && (uintptr_t)in.ids == 0x5000);
+    CHECK(resolve_inputs("rt_temporal_accumulate", 8, 8, at<float>(0x500), &b, true, fb8, aov8).error ==
+          "rt_temporal_accumulate: d_aovs needs the normalDepth, position, albedo and ids planes");
+    b.position = at<float>(0x2000);
+    in = resolve_inputs("rt_temporal_accumulate", 8, 8, at<float>(0x500), &b, true, fb8, aov8);
+    CHECK(in.error.empty() && (uintptr_t)in.rgba == 0x500 && (uintptr_t)in.normalDepth == 0x1000 && (uintptr_t)in.position == 0x2000 && (uintptr_t)in.albedo == 0x3000 &&
+          (uintptr_t)in.ids == 0x5000);
+    CHECK(!resolve_inputs("rt_denoise", 8, 8, at<float>(0x500), &b, false, noFb, noAov).position);   // given, and not read
+    RtAovBuffers one{};
+    one.normalDepth = at<float>(0x1000);
+    CHECK(resolve_inputs("rt_denoise", 8, 8, nullptr, &one, false, fb8, noAov).error == "rt_denoise: d_aovs needs the normalDepth, albedo and ids planes");
+    float* RtAovBuffers::*const needed[2] = {&RtAovBuffers::normalDepth, &RtAovBuffers::albedo};
+    for (int missing = 0; missing < 3; missing++) {   // each plane both passes read, missing in turn
+        RtAovBuffers m = b;
+        if (missing < 2) m.*needed[missing] = nullptr; else m.ids = nullptr;
+        CHECK(has(resolve_inputs("rt_denoise", 8, 8, nullptr, &m, false, fb8, noAov).error, "d_aovs needs the normalDepth, albedo and ids planes"));
+        CHECK(has(resolve_inputs("rt_temporal_accumulate", 8, 8, nullptr, &m, true, fb8, noAov).error, "d_aovs needs the normalDepth, position, albedo and ids planes"));
+    }
+}
+
+// ---------------------------------------------------------------- overlap
+void overlaps() {
+    CHECK(overlap(at<void>(0x1000), at<void>(0x1000), 16) && overlap(at<void>(0x1000), at<void>(0x100f), 16) && !overlap(at<void>(0x1000), at<void>(0x1010), 16));
+    const uintptr_t B = 0x40000000u, FB = 0x10000000u, AOV = 0x20000000u;
+    const size_t plane = 8 * 8 * 16;
+    const RowsOf whole8{8, 8, 0, 1, 8};
+    const OwnedRows fb8{at<void>(FB), true, whole8}, aov8{at<void>(AOV), true, whole8};
+    // rt_denoise, as tests/test_denoise.py provokes it: d_out is the frame; d_out inside three planes 64 bytes apart (ctx framebuffer)
+    {
+        const auto denoise = [&](const PassInputs& in, uintptr_t out) {
+            const NamedPlane o[1] = {{"d_out", at<void>(out)}};
+            return check_overlap("rt_denoise", in, "d_out", o, 1, plane);
+        };
+        const PassInputs own = resolve_inputs("rt_denoise", 8, 8, at<float>(B), nullptr, false, fb8, aov8);
+        CHECK(denoise(own, B) == "rt_denoise: d_out overlaps an input");
+        RtAovBuffers b{};
+        b.normalDepth = at<float>(B); b.albedo = at<float>(B + 64); b.ids = at<uint32_t>(B + 128);
+        const PassInputs theirs = resolve_inputs("rt_denoise", 8, 8, nullptr, &b, false, fb8, aov8);
+        CHECK(denoise(theirs, B + 512) == "rt_denoise: d_out overlaps an input");
+        CHECK(denoise(theirs, B + 128 + plane).empty() && denoise(theirs, B - plane).empty());   // adjacent on either side
+        CHECK(denoise(theirs, B - plane + 16) == "rt_denoise: d_out overlaps an input");
+        CHECK(denoise(own, AOV + 1 * plane).empty());   // the ctx position plane, which the denoiser does not read
+        CHECK(denoise(theirs, 0).empty());              // NULL: the ctx's own plane
+    }
+    // rt_temporal_accumulate, the six cases of tests/test_temporal.py
+    const auto temporal = [&](const PassInputs& in, uintptr_t out, uintptr_t moments) {
+        const NamedPlane o[2] = {{"d_out", at<void>(out)}, {"d_moments", at<void>(moments)}};
+        return check_overlap("rt_temporal_accumulate", in, "an output", o, 2, plane);
+    };
+    const PassInputs own = resolve_inputs("rt_temporal_accumulate", 8, 8, at<float>(B), nullptr, true, fb8, aov8);
+    CHECK(own.error.empty());
+    CHECK(temporal(own, B, 0) == "rt_temporal_accumulate: an output overlaps an input");        // 1. an output equal to an input
+    CHECK(temporal(own, 0, B + 16) == "rt_temporal_accumulate: an output overlaps an input");   // 2. an output 16 bytes into an input
+    RtAovBuffers b{};
+    b.normalDepth = at<float>(B); b.position = at<float>(B + plane); b.albedo = at<float>(B + 2 * plane); b.ids = at<uint32_t>(B + 3 * plane);
+    const PassInputs theirs = resolve_inputs("rt_temporal_accumulate", 8, 8, nullptr, &b, true, fb8, aov8);
+    CHECK(theirs.error.empty());
+    CHECK(temporal(theirs, B + 3 * plane + 512, 0) == "rt_temporal_accumulate: an output overlaps an input");   // 3. inside the last input plane
+    CHECK(temporal(theirs, B + 5 * plane, B + 5 * plane + 64) == "rt_temporal_accumulate: d_out overlaps d_moments");   // 4. 64 bytes apart
+    CHECK(temporal(theirs, B + 4 * plane, B + 5 * plane).empty());   // 5. disjoint and adjacent, to the inputs and to each other
+    CHECK(temporal(theirs, 0, B + 4 * plane).empty() && temporal(theirs, B + 4 * plane, 0).empty() && temporal(theirs, 0, 0).empty());   // 6. a NULL output is skipped
+    CHECK(temporal(own, AOV + 1 * plane + 16, 0) == "rt_temporal_accumulate: an output overlaps an input");   // the ctx position plane, which this pass reads
+    CHECK(temporal(own, AOV + 3 * plane, 0).empty());   // rayDir, which it does not
+    CHECK(temporal(theirs, B + 4 * plane, B + 3 * plane + 16) == "rt_temporal_accumulate: an output overlaps an input");   // the input test comes before the pair's
+}
+
+// ---------------------------------------------------------------- the temporal history
+// An object's rows under a translation along x, and its exact inverse
+void place(float4* fwd, float4* inv, float x) {
+    for (int r = 0; r < 3; r++) {
+        fwd[r] = make_float4(r == 0, r == 1, r == 2, r == 0 ? x : 0.f);
+        inv[r] = make_float4(r == 0, r == 1, r == 2, r == 0 ? -x : 0.f);
+    }
+}
+
+// The device side of a script: what a call was told to read and write, against a replay of the rule "the history is what the last
+// accepted call wrote". A refusal is no call at all.
+struct Replay {
+    TemporalHistory h;
+    int lastWrite = 0;   // (the first call writes history 1)
+    uint32_t k = 0;      // how far object 0 has moved
+    const CameraInfo cam{};
+    void push(uint32_t steps, float sphereX = 0.f) {   // rt_update_objects / rt_update_spheres: two objects, object 0 `steps` along, two spheres
+        float4 fwd[6], inv[6];
+        const uint32_t bvh[2] = {0, 1};
+        place(fwd, inv, 0.01f * steps);
+        place(fwd + 3, inv + 3, 0.f);
+        h.set_object_placements(fwd, inv, bvh, 2);
+        const float4 spheres[2] = {make_float4(sphereX, 0.1f, -0.3f, 0.4f), make_float4(1.f, 1.f, 1.f, 0.25f)};
+        h.set_sphere_placements(spheres, 2);
+    }
+    void upload() { h.reset(); push(0); }   // rt_upload_scene: a new scene, its placements
+    // one accepted call: begin, (the launch,) commit. history: it must read the last call's; then: table or none, and the counts
+    void call(int line, uint32_t W, uint32_t H, bool fit, bool history, bool table, uint32_t mo = 0, uint32_t ro = 0, uint32_t ms = 0) {
+        const TemporalHistory::Step s = h.begin(W, H, fit);
+        const uint32_t* m = h.moved_counts();
+        if (s.read != (history ? lastWrite : -1) || s.write != 1 - lastWrite || s.motion.any() != table || m[0] != mo || m[1] != ro || m[2] != ms) {
+            printf("FAILED %s:%d: read %d write %d table %d moved %u %u %u\n", __FILE__, line, s.read, s.write, (int)s.motion.any(), m[0], m[1], m[2]);
+            failures++;
+        }
+        h.commit(cam);
+        lastWrite = s.write;
+    }
+};
+#define CALL(r, ...) (r).call(__LINE__, __VA_ARGS__)
+
+// tests/test_temporal.py: test_reset_upload_and_resize_start_a_new_history (tracking off)
+void history_without_tracking() {
+    Replay r;
+    r.upload();
+    {   // the first two calls, in numbers
+        TemporalHistory h;
+        TemporalHistory::Step s = h.begin(37, 23, false);
+        CHECK(s.read == -1 && s.write == 1 && !s.motion.any());
+        h.commit(r.cam);
+        s = h.begin(37, 23, true);
+        CHECK(s.read == 1 && s.write == 0);
+        h.commit(r.cam);
+        s = h.begin(37, 23, true);
+        CHECK(s.read == 0 && s.write == 1);
+    }
+    CALL(r, 37, 23, false, false, false);   // no buffers yet
+    CALL(r, 37, 23, true, true, false);
+    r.h.reset();
+    CALL(r, 37, 23, true, false, false);
+    CALL(r, 37, 23, true, true, false);
+    r.upload();
+    CALL(r, 37, 23, true, false, false);
+    CALL(r, 37, 23, true, true, false);
+    CALL(r, 23, 37, true, false, false);    // the same pixel count, another shape: the buffers fit, the history does not
+    CALL(r, 23, 37, true, true, false);
+    CALL(r, 40, 23, false, false, false);   // larger: the buffers were replaced
+    CALL(r, 37, 23, true, false, false);    // and back: the history of the first size is gone
+    CALL(r, 37, 23, true, true, false);
+    CALL(r, 37, 23, false, false, false);   // the same size, but a history buffer had to be allocated again
+    CALL(r, 37, 23, true, true, false);
+    // placements edited while tracking is off yield no table
+    r.push(1, 0.5f);
+    CALL(r, 37, 23, true, true, false);
+    r.h.set_tracking(false);                // the same value: nothing is forgotten
+    CALL(r, 37, 23, true, true, false);
+}
+
+// tests/test_temporal_motion.py: test_resets_drop_the_snapshot_and_refusals_keep_it
+void history_with_tracking() {
+    Replay r;
+    r.upload();
+    const auto moved_call = [&](int line, uint32_t W, uint32_t H, bool history) {   // one more call, object 0 a little further along
+        r.push(++r.k);
+        r.call(line, W, H, true, history, history, history ? 1 : 0, 0, 0);
+    };
+#define MOVED(...) moved_call(__LINE__, __VA_ARGS__)
+    r.h.set_tracking(true);
+    r.push(++r.k);
+    CALL(r, 37, 23, false, false, false);
+    MOVED(37, 23, true);
+    r.h.reset();
+    MOVED(37, 23, false);                   // the snapshot went with the history: nothing to compare with
+    MOVED(37, 23, true);
+    r.h.set_tracking(true);                 // the same value: nothing is forgotten
+    MOVED(37, 23, true);
+    r.h.set_tracking(false);                // the toggle, both ways
+    MOVED(37, 23, false);
+    CALL(r, 37, 23, true, true, false);     // nothing moved, and nobody is looking
+    r.push(++r.k);
+    CALL(r, 37, 23, true, true, false);     // moved, and nobody is looking
+    r.h.set_tracking(true);
+    MOVED(37, 23, false);
+    MOVED(37, 23, true);
+    r.upload();
+    MOVED(37, 23, false);
+    MOVED(37, 23, true);
+    MOVED(23, 37, false);                   // the same pixel count, another shape
+    MOVED(23, 37, true);
+    // a refused call reaches neither begin nor commit: the edit made before it is still seen by the next one, and the counts are
+    // still the last accepted call's
+    r.push(++r.k);                          // an edit, a refusal, another edit: both are measured against the last committed snapshot
+    CHECK(r.h.moved_counts()[0] == 1 && r.h.moved_counts()[1] == 0 && r.h.moved_counts()[2] == 0);
+    r.push(r.k, 0.5f);
+    CHECK(r.h.moved_counts()[0] == 1 && r.h.moved_counts()[1] == 0 && r.h.moved_counts()[2] == 0);
+    CALL(r, 23, 37, true, true, true, 1, 0, 1);
+    r.push(r.k);                            // the sphere goes back
+    CALL(r, 23, 37, true, true, true, 0, 0, 1);
+    CALL(r, 23, 37, true, true, false);     // nothing moved since: the launch of a call without tracking
+    // spheres and replaced objects are counted as rt_temporal_motion_state reports them
+    r.push(r.k, 0.5f);
+    CALL(r, 23, 37, true, true, true, 0, 0, 1);
+    float4 fwd[3], inv[3];
+    const uint32_t bvh[1] = {1};
+    place(fwd, inv, 0.01f * r.k);
+    r.h.set_object_placements(fwd, inv, bvh, 1);   // object 0 re-pointed, object 1 gone
+    CALL(r, 23, 37, true, true, true, 0, 2, 0);
+    CALL(r, 23, 37, false, false, false);   // with tracking on too, a replaced buffer is no history: no table either
+#undef MOVED
+}
+
+// ---------------------------------------------------------------- the image plane
+void camera_planes() {
+    const float cases[3][2] = {{40.f, 16.f / 9.f}, {70.f, 1.f}, {90.f, 16.f / 9.f}};
+    for (const auto& cs : cases) {
+        CameraInfo ci{};
+        for (int k = 0; k < 16; k++) ci.cameraRotation[k] = 0.25f * k - 1.f;
+        ci.pos[0] = 0.f; ci.pos[1] = -0.5f; ci.pos[2] = -3.5f;
+        ci.nearPlane = 0.1f; ci.fov = cs[0]; ci.aspectRatio = cs[1];
+        // the expression, written out (host side of raytrace.comp:547-556)
+        float want[5];
+        const float planeHeight = ci.nearPlane * rt_tan(rt_radians(ci.fov * 0.5f)) * 2.f;
+        const float planeWidth = planeHeight * ci.aspectRatio;
+        want[0] = planeWidth; want[1] = planeHeight;
+        want[2] = -planeWidth / 2.f; want[3] = -planeHeight / 2.f; want[4] = 0.1f;
+        const CameraPlane p = camera_plane(ci);
+        const float got[5] = {p.planeWidth, p.planeHeight, p.bottomLeft[0], p.bottomLeft[1], p.bottomLeft[2]};
+        CHECK(!memcmp(got, want, sizeof want));
+        CHECK(planeHeight > 0.f && std::fabs(planeHeight - 0.2f * std::tan(ci.fov * 0.5 * 3.14159265358979323846 / 180.0)) < 1e-6);
+        const TemporalCamera t = temporal_camera(ci);
+        const float tgot[5] = {t.planeWidth, t.planeHeight, t.bottomLeft[0], t.bottomLeft[1], t.bottomLeft[2]};
+        CHECK(!memcmp(tgot, want, sizeof want));
+        CHECK(!memcmp(t.rot, ci.cameraRotation, 64) && !memcmp(t.pos, ci.pos, 12));
+    }
+    CHECK(sizeof(TemporalCamera) == 24 * 4);   // a kernel argument: 16 + 3 + 2 + 3 floats, no padding
+}
+
+}  // namespace
+
+int main() {
+    denoise_checks();
+    temporal_checks();
+    resolution();
+    overlaps();
+    history_without_tracking();
+    history_with_tracking();
+    camera_planes();
+    if (failures) { printf("%d check(s) failed\n", failures); return 1; }
+    printf("post passes ok\n");
+    return 0;
+}
