@@ -37,6 +37,15 @@
 #ifndef RT_TE_REG
 #define RT_TE_REG 1        // trace_wave<ROOMY>: a light query's tE rides in a register instead of being re-read from the hit record when a leaf step finds a hit
 #endif
+#ifndef RT_TE_REG_ALL
+#define RT_TE_REG_ALL 1    // k_trace_pw: ROOMY in every instantiation without phase statistics, not only in those built for five work-groups per CU (0)
+#endif
+#ifndef RT_SHADE_BLOCKS
+#define RT_SHADE_BLOCKS 5  // k_shade, k_shade_maps: work-groups per CU they are built for (__launch_bounds__): 95 registers, no spills
+#endif
+#ifndef RT_LEAF_PRELOAD
+#define RT_LEAF_PRELOAD 1  // trace_wave, leaf step: the second triangle's three loads kept in front of the first triangle's test, where the registers allow it
+#endif
 #ifndef RT_OBJTREE
 #define RT_OBJTREE 1       // trace_wave, set-up step: the object hierarchy's block jumps compiled in (CULL kernels)
 #endif
@@ -727,9 +736,11 @@ struct WaveTotals {
 // goes straight to the interior step; pushes and pops are unconditional LDS accesses with
 // predicated pointer updates; the full vote, the refill and the leaf / setup steps live on a slow
 // path that is only entered when fewer than `fastLanes` lanes are at interior nodes.
-// ROOMY: the kernel is built for five work-groups per CU (96 registers per lane): a light query's tE rides in a register there
-// (-2 % on the bench frame). With the 80 registers of six work-groups per CU, and in the fused kernel, one more live register
-// means one more spill: measured there, it loses (Cornell + bunny +3 %, C5 at 4K +1 %).
+// ROOMY: a light query's tE rides in a register (-2 % on the bench frame when it came to the kernels built for five work-groups per
+// CU). While the SLP vectorizer packed the fp32 algebra, the 80 registers of six work-groups per CU had no room for it: one more live
+// register meant one more spill, and it lost there (Cornell + bunny +3 %, C5 at 4K +1 %). Without the packing every k_trace_pw
+// instantiation without phase statistics has it and stays at 72 registers or fewer with no spill (tests/test_register_budget.py);
+// the STATS instantiations spill either way and keep it only at five work-groups, and so does the fused kernel (it spills too).
 // ALPHA: triangle hits are looked up in their object's alpha map before they count (alpha_cut; k_trace_pw_alpha, k_render_fused_maps).
 template <int STACK, bool OVF, bool PIX, bool STATS, bool LOCAL, bool CULL, int HOT = 0, bool ROOMY = false, bool ALPHA = false>
 __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& ps, const TracePwArgs& ta, uint32_t* stack, uint32_t* ovf,
@@ -865,7 +876,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                     if (PIX) rayTri += jEnd - j; else wt.totTri += jEnd - j;
                     bool closer = false;  // this step found a nearer hit
                     if (cnt != 0u) {
-                        // one or two triangles: both fetched before either is tested
+                        // one or two triangles: both fetched before either is tested (see below: in the binary only where it is pinned)
                         const uint32_t j1 = jEnd - 1u;
                         // Whole 16-byte vectors from the global address space: three aligned loads per triangle. (Through float4, whose
                         // padding words are never read, the compiler fetched a triangle's 44 bytes as 8 + 16 at offset 4 + 8 + 12: four
@@ -873,11 +884,17 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                         const RT_AS_GLOBAL rt_f4v* tp0 = (const RT_AS_GLOBAL rt_f4v*)sc.triPos + 3 * (size_t)j;
                         const RT_AS_GLOBAL rt_f4v* tp1 = (const RT_AS_GLOBAL rt_f4v*)sc.triPos + 3 * (size_t)j1;
                         const rt_f4v a0 = tp0[0], b0 = tp0[1], c0 = tp0[2];
-                        const rt_f4v a1 = tp1[0], b1 = tp1[1], c1 = tp1[2];
+                        rt_f4v a1 = tp1[0], b1 = tp1[1], c1 = tp1[2];
                         if (STATS) RT_STAMP_AFTER_LOADS(wt.dbgLoad[3], tLeaf);
                         const rt_vec3 o = rt_v3(troXY.x, troXY.y, zOI.x);
                         const TriHit h0 = tri_intersect(o, trd, rt_v3(a0.x, a0.y, a0.z), rt_v3(b0.x, b0.y, b0.z), rt_v3(c0.x, c0.y, c0.z), __float_as_uint(a0.w) != 0u);
                         if (h0.didHit && h0.dst < best && !(ALPHA && alpha_cut(sc, cur_object(), j, h0))) { best = h0.dst; bestObj = cur_object(); bestTri = j; closer = true; }
+                        // Left alone, the compiler sinks the second triangle's loads into the branch below, behind the first test: two trips
+                        // to memory per step. They are unconditional in the source (j1 == j is a valid triangle), and an empty statement
+                        // that takes their values keeps them so: six loads, one wait. It costs the kernel six registers, so it is there
+                        // only where the kernel stays within 72 with it: no overflow stack, no per-pixel counters, no object culling
+                        // (tests/test_register_budget.py). Sponza -1.2 %, Cornell + bunny and + dragon no slower (profiles/README.md, round 5).
+                        if (RT_LEAF_PRELOAD && !OVF && !PIX && !STATS && !LOCAL && !CULL && !ALPHA) asm volatile("" : "+v"(a1), "+v"(b1), "+v"(c1));
                         if (j1 != j) {
                             const TriHit h1 = tri_intersect(o, trd, rt_v3(a1.x, a1.y, a1.z), rt_v3(b1.x, b1.y, b1.z), rt_v3(c1.x, c1.y, c1.z), __float_as_uint(a1.w) != 0u);
                             if (h1.didHit && h1.dst < best && !(ALPHA && alpha_cut(sc, cur_object(), j1, h1))) { best = h1.dst; bestObj = cur_object(); bestTri = j1; closer = true; }
@@ -1151,7 +1168,7 @@ __device__ __forceinline__ void trace_pw_block(const DevScene& sc, const PathSta
 
 template <int STACK, bool OVF, bool PIX, bool STATS, bool CULL, int HOT = 0, int BLOCKS = 6>
 __global__ __launch_bounds__(RT_BLOCK, BLOCKS) void k_trace_pw(DevScene sc, PathState ps, TracePwArgs ta) {
-    trace_pw_block<STACK, OVF, PIX, STATS, CULL, HOT, BLOCKS == 5, false>(sc, ps, ta);
+    trace_pw_block<STACK, OVF, PIX, STATS, CULL, HOT, BLOCKS == 5 || (RT_TE_REG_ALL && !STATS), false>(sc, ps, ta);
 }
 // The traversal of a scene that binds an alpha map (DevScene::mapFlags & RT_MAP_ALPHA): one configuration for every such scene —
 // 24 stack entries in LDS with the overflow buffer behind them, object culling compiled in, no top-level table, four work-groups
@@ -1709,9 +1726,9 @@ __device__ __forceinline__ void shade_block(const DevScene& sc, const PathState&
     }
 }
 
-__global__ __launch_bounds__(RT_BLOCK) void k_shade(DevScene sc, PathState ps, ShadeArgs sa, FrameParams fp) { shade_block<false>(sc, ps, sa, fp); }
+__global__ __launch_bounds__(RT_BLOCK, RT_SHADE_BLOCKS) void k_shade(DevScene sc, PathState ps, ShadeArgs sa, FrameParams fp) { shade_block<false>(sc, ps, sa, fp); }
 // the same for a scene that binds a metalness or a bump map (DevScene::mapFlags)
-__global__ __launch_bounds__(RT_BLOCK) void k_shade_maps(DevScene sc, PathState ps, ShadeArgs sa, FrameParams fp) { shade_block<true>(sc, ps, sa, fp); }
+__global__ __launch_bounds__(RT_BLOCK, RT_SHADE_BLOCKS) void k_shade_maps(DevScene sc, PathState ps, ShadeArgs sa, FrameParams fp) { shade_block<true>(sc, ps, sa, fp); }
 
 // ---------------------------------------------------------------- k_resolve
 // raytrace.comp:574-593. `rgba` holds the previous frame when progressive
