@@ -371,6 +371,39 @@ int  rt_render_aovs(rt_ctx* ctx, const PushConstants* pc, uint32_t width, uint32
  * pass); blocks */
 int  rt_read_aovs(rt_ctx* ctx, const RtAovBuffers* hostOut, size_t nPixels);
 
+/* Mirror-following guide planes ("Mirror-following guide planes"): the planes rt_denoise should be guided by where the
+ * camera ray meets a mirror, which has one normal field, one depth ramp and one albedo and so tells an edge-stopping filter nothing
+ * of the image it shows. A mirror segment of a path is deterministic (a plain reflect, no random number, radiance 1), so every
+ * sample of a pixel runs the same chain of mirror segments from the camera to the first surface that is no mirror, and this pass
+ * traces it once. Per pixel, segment 0 is rt_render_aovs' camera ray; segment j's hit is calculateIntersections' closest hit (the
+ * record rt_trace_rays returns for the ray, alpha cut-outs as in rendering). A segment continues when it hit, j < maxBounces and
+ * the hit is a mirror for shading: reflectance != 0, the reflectance being the metalness texel on a triangle hit whose material
+ * binds an uploaded metalness map. The next ray is the one shading would trace, bit for bit: direction reflect(dir, normal) with
+ * the (bump-tilted) normal of the hit, origin hitPoint + (normal * 1) * 0.00001. The chain ends at the first segment that does
+ * not continue; L, 0 <= L <= maxBounces, is the number of segments before it. Dielectrics branch on a random draw: a chain stops
+ * on them as on any other surface.
+ * The guide planes have RtAovBuffers' layout and may be passed as rt_denoise's d_aovs: normalDepth.xyz, position, albedo and
+ * ids.xyz are the final segment's, exactly as rt_render_aovs would write them for that ray; normalDepth.w is the path length
+ * ((d0 + d1) + d2) + ... in fp32 on a final hit, and a final miss writes the miss record unchanged (RT_MISS_DST, not a sum); rayDir
+ * is the final segment's direction; ids.w keeps bits 0-2 of the final hit, bit 3 says the chain was cut (the final hit is itself a
+ * mirror: j reached maxBounces), bits 8-11 hold L. With maxBounces = 0, or in a scene without mirrors, the guide planes equal
+ * rt_render_aovs' bit for bit, except ids.w bit 3 on mirror hits.
+ * maxBounces 0..8. d_guides: device planes (NULL fields are skipped), or NULL: a ctx-owned set of their own (rt_read_guides), which
+ * is not the set rt_render_aovs keeps: rt_denoise(d_aovs = NULL) still means the first-hit planes. d_firstHit: device planes that
+ * receive what rt_render_aovs would write for the tile, bit for bit, from the same first traversal (NULL fields are skipped), or
+ * NULL: not wanted. No plane of d_guides may overlap one of d_firstHit. rt_temporal_accumulate keeps taking the first-hit planes: a
+ * guide position is a point seen in a mirror, which does not reproject through the camera.
+ * Asynchronous on the ctx stream and checked like rt_render_aovs; the host never learns how many chains are alive: it enqueues
+ * maxBounces + 1 traversal launches, each over the rays still alive, and one without rays costs its launches. Like rt_render_aovs
+ * the pass changes nothing a later rt_render produces (framebuffer, progressive history, pipeline, parts and ray-cost choices,
+ * rt_last_parts, rt_last_pipeline) and nothing rt_render_aovs keeps; its traversal work goes to the same counters from the same
+ * block, traceLaunches counting one per round. */
+int  rt_render_guides(rt_ctx* ctx, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
+                      uint32_t nRows, uint32_t maxBounces, const RtAovBuffers* d_guides, const RtAovBuffers* d_firstHit);
+/* copies the ctx-owned guide planes of the last rt_render_guides(…, d_guides = NULL) to the non-NULL host fields (nPixels =
+ * nRows*width of that pass); blocks */
+int  rt_read_guides(rt_ctx* ctx, const RtAovBuffers* hostOut, size_t nPixels);
+
 /* Edge-avoiding a-trous denoiser over a whole width x height frame (the spatial filter of SVGF, Schied et al. 2017, after
  * Dammertz et al. 2010; DESIGN.md, "Denoising"). Pixel p is filtered when ids.w & 1 (a hit), ids.z < the material count and
  * that material's emissionStrength == 0, all in the ctx's current material table; every other pixel (misses, emitters) is kept:

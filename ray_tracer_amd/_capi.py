@@ -157,6 +157,9 @@ SYMBOLS = {
     "rt_trace_rays": (C.c_int, [_vp, C.c_uint32, _P(C.c_float), _P(C.c_float), _P(RtHit)]),
     "rt_render_aovs": (C.c_int, [_vp, _P(PushConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(RtAovBuffers)]),
     "rt_read_aovs": (C.c_int, [_vp, _P(RtAovBuffers), C.c_size_t]),
+    "rt_render_guides": (C.c_int, [_vp, _P(PushConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                   _P(RtAovBuffers), _P(RtAovBuffers)]),
+    "rt_read_guides": (C.c_int, [_vp, _P(RtAovBuffers), C.c_size_t]),
     "rt_denoise_params_default": (None, [_P(RtDenoiseParams)]),
     "rt_denoise": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _P(RtAovBuffers), _P(RtDenoiseParams), _vp]),
     "rt_read_denoised_rgba_f32": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),

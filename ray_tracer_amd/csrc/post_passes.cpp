@@ -71,6 +71,40 @@ std::string check_temporal(uint32_t width, uint32_t height, const CameraInfo* ca
     return "";
 }
 
+// ---------------------------------------------------------------- the passes over a tile's camera rays
+std::string check_tile(const char* fn, const RayTracerData& td, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride, uint32_t nRows,
+                       const UploadedScene& scene) {
+    const std::string f(fn);
+    if (width == 0 || height == 0 || rowStride == 0) return f + ": bad image geometry";
+    if (nRows && (uint64_t)row0 + (uint64_t)(nRows - 1) * rowStride >= height) return f + ": rows exceed the image";
+    if (!scene.uploaded) return f + " before rt_upload_scene";
+    if (td.sphereCount > scene.sphereCount) return "rayTraceParams.sphereCount exceeds the uploaded spheres";
+    if (td.objectCount > scene.objectCount) return "rayTraceParams.objectCount exceeds the uploaded objects";
+    return "";
+}
+
+std::string check_tile_slots(const char* fn, uint32_t width, uint32_t nRows) {
+    if ((uint64_t)nRows * width >= (1ull << 30)) return std::string(fn) + ": tile too large (slot ids are 30 bits)";
+    return "";
+}
+
+std::string check_guides(const RayTracerData& td, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride, uint32_t nRows,
+                         uint32_t maxBounces, const RtAovBuffers* guides, const RtAovBuffers* firstHit, const UploadedScene& scene) {
+    const char* const fn = "rt_render_guides";
+    if (maxBounces > RT_GUIDE_MAX_BOUNCES) return std::string(fn) + ": maxBounces must be 0..8";
+    std::string e = check_tile(fn, td, width, height, row0, rowStride, nRows, scene);
+    if (e.empty()) e = check_tile_slots(fn, width, nRows);
+    if (!e.empty() || !guides || !firstHit) return e;
+    static const char* const names[AOV_PLANES] = {"normalDepth", "position", "albedo", "rayDir", "ids"};
+    const size_t bytes = (size_t)nRows * width * sizeof(float4);
+    for (int g = 0; g < AOV_PLANES; g++)
+        for (int h = 0; h < AOV_PLANES; h++) {
+            const void *a = aov_plane(*guides, (AovPlane)g), *b = aov_plane(*firstHit, (AovPlane)h);
+            if (a && b && overlap(a, b, bytes)) return std::string(fn) + ": d_guides." + names[g] + " overlaps d_firstHit." + names[h];
+        }
+    return "";
+}
+
 // ---------------------------------------------------------------- the planes a pass reads
 PassInputs resolve_inputs(const char* fn, uint32_t width, uint32_t height, const float* rgba, const RtAovBuffers* aovs, bool needPosition,
                           const OwnedRows& fb, const OwnedRows& aov) {

@@ -1,6 +1,7 @@
 // post_passes.h — the host logic of the passes that run on finished frames (rt_render_aovs' planes, rt_denoise,
 // rt_temporal_accumulate): the image plane of a camera, the parameter checks, which planes a pass reads and whether its outputs
-// keep clear of them, and the state of the temporal history. Nothing in this pair of files needs a device or dereferences a plane:
+// keep clear of them, and the state of the temporal history; and what the passes over a tile's camera rays (rt_render,
+// rt_render_aovs, rt_render_guides) refuse of the tile. Nothing in this pair of files needs a device or dereferences a plane:
 // rt_device.hip gathers the facts, asks here, and allocates, copies and launches; tests/post_passes_check.cpp pins every message
 // and transition on the CPU, with made-up addresses.
 // rt_kernels.hip.h includes this header for TemporalCamera, so device compilations read it too: keep it to declarations, plain
@@ -42,6 +43,22 @@ TemporalCamera temporal_camera(const CameraInfo& ci);
 std::string check_denoise(uint32_t width, uint32_t height, const RtDenoiseParams& p, bool sceneUploaded, const char* fn);
 std::string check_temporal(uint32_t width, uint32_t height, const CameraInfo* cam, const RtTemporalParams& p, bool sceneUploaded, const char* fn);
 
+// ---------------------------------------------------------------- the passes over a tile's camera rays
+// What rt_render, rt_render_aovs and rt_render_guides (fn) refuse of a tile and its scene counts: the rows y = row0 + k*rowStride,
+// k in [0,nRows) must lie in the width x height image, a scene must be uploaded and rayTraceParams must not count more spheres or
+// objects than it holds. Empty: accepted.
+struct UploadedScene { bool uploaded; uint32_t sphereCount, objectCount; };
+std::string check_tile(const char* fn, const RayTracerData& td, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride, uint32_t nRows,
+                       const UploadedScene& scene);
+// a tile's pixels must fit the 30 bits of a slot id (rt_render_aovs, rt_render_guides)
+std::string check_tile_slots(const char* fn, uint32_t width, uint32_t nRows);
+// What rt_render_guides refuses before anything is allocated: maxBounces beyond RT_GUIDE_MAX_BOUNCES, then check_tile and
+// check_tile_slots, then a plane of d_guides that shares a byte with a plane of d_firstHit (either may be NULL, and so may any
+// field: such planes are not written).
+enum { RT_GUIDE_MAX_BOUNCES = 8 };
+std::string check_guides(const RayTracerData& td, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride, uint32_t nRows,
+                         uint32_t maxBounces, const RtAovBuffers* guides, const RtAovBuffers* firstHit, const UploadedScene& scene);
+
 // ---------------------------------------------------------------- the planes a pass reads
 // The ctx-owned AOV planes are one buffer of AOV_PLANES planes of nPixels 16-byte records, in this order (rt_render_aovs writes
 // them, rt_read_aovs and the passes find them by it).
@@ -55,6 +72,7 @@ inline void* aov_plane(const RtAovBuffers& b, AovPlane k) {   // the same plane 
 // what a read or a pass says of a plane the ctx was never asked to keep
 inline const char* const NO_OWNED_FRAMEBUFFER = "no ctx-owned framebuffer: rt_render was never called with d_rgba = NULL";
 inline const char* const NO_OWNED_AOVS = "no ctx-owned AOV planes: rt_render_aovs was never called with d_out = NULL";
+inline const char* const NO_OWNED_GUIDES = "no ctx-owned guide planes: rt_render_guides was never called with d_guides = NULL";
 
 // What the ctx owns of a kind (its framebuffer; its AOV planes): where, whether a pass ever wrote it, and the rows it holds
 struct OwnedRows { const void* base; bool valid; RowsOf rows; };

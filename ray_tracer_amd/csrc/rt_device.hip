@@ -94,6 +94,10 @@ struct rt_ctx {
     // rt_get_counters adds to the rendering counters and the ray-cost snapshots never see
     OwnedPlane aov;         // the five planes in AovPlane's order (rt_render_aovs writes them)
     DevBuf aovCounterBuf;
+    // mirror-following guide planes (rt_render_guides): the ctx-owned set of the last pass into it, in the same order, and the ray
+    // counts of the pass's rounds (GUIDE_COUNTS words)
+    OwnedPlane guide;
+    DevBuf guideCountBuf;
     DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
     // the denoiser (rt_denoise): its work planes, the staging planes of rt_denoise_host and the ctx-owned output
     DevBuf dnWorkBuf, dnHostBuf;
@@ -708,16 +712,12 @@ int rt_sync(rt_ctx* c) {
 }  // extern "C"
 
 namespace {
-// The checks rt_render and rt_render_aovs share: the tile's geometry, an uploaded scene, the counts of rayTraceParams
+// The checks rt_render, rt_render_aovs and rt_render_guides share (post_passes.h: check_tile)
+UploadedScene uploaded_scene(const rt_ctx* c) { return UploadedScene{c->sc.nodes != nullptr, c->sc.sphereCount, c->sc.objectCount}; }
 int check_tile(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride, uint32_t nRows,
                const char* fn) {
-    if (width == 0 || height == 0 || rowStride == 0) return c->fail(std::string(fn) + ": bad image geometry");
-    if (nRows && (uint64_t)row0 + (uint64_t)(nRows - 1) * rowStride >= height) return c->fail(std::string(fn) + ": rows exceed the image");
-    if (!c->sc.nodes) return c->fail(std::string(fn) + " before rt_upload_scene");
-    const RayTracerData& td = pc->rayTraceParams;
-    if (td.sphereCount > c->sc.sphereCount) return c->fail("rayTraceParams.sphereCount exceeds the uploaded spheres");
-    if (td.objectCount > c->sc.objectCount) return c->fail("rayTraceParams.objectCount exceeds the uploaded objects");
-    return 0;
+    const std::string e = check_tile(fn, pc->rayTraceParams, width, height, row0, rowStride, nRows, uploaded_scene(c));
+    return e.empty() ? 0 : c->fail(e);
 }
 
 // The scene of a dispatch: the uploaded one with the counts of rayTraceParams
@@ -1038,9 +1038,9 @@ int rt_render_aovs(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t 
     if (!c || !pc) return -1;
     int rc = check_tile(c, pc, width, height, row0, rowStride, nRows, "rt_render_aovs");
     if (rc) return rc;
-    const uint64_t np64 = (uint64_t)nRows * width;
-    if (np64 >= (1ull << 30)) return c->fail("rt_render_aovs: tile too large (slot ids are 30 bits)");
-    const uint32_t nPixels = (uint32_t)np64;
+    const std::string tooLarge = check_tile_slots("rt_render_aovs", width, nRows);
+    if (!tooLarge.empty()) return c->fail(tooLarge);
+    const uint32_t nPixels = nRows * width;
     RT_HIP(c, hipSetDevice(c->device));
     if (nPixels == 0) return 0;
     // The pass's rays live in path-state slots [0, nPixels) and its ray count in the first part's counters: the ctx stream orders it
@@ -1071,17 +1071,82 @@ int rt_render_aovs(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t 
     RT_HIP(c, hipGetLastError());
     return 0;
 }
+}  // extern "C"
 
-int rt_read_aovs(rt_ctx* c, const RtAovBuffers* out, size_t nPixels) {
+namespace {
+// a ctx-owned set of five planes (OwnedPlane in AovPlane's order) to the non-NULL host fields; blocks
+int read_planes(rt_ctx* c, const OwnedPlane& pl, const char* fn, const char* never, const RtAovBuffers* out, size_t nPixels) {
     if (!c || !out) return -1;
-    if (!c->aov.valid) return c->fail(NO_OWNED_AOVS);
-    if (nPixels != c->aov.pixels) return c->fail("rt_read_aovs: size mismatch");
+    if (!pl.valid) return c->fail(never);
+    if (nPixels != pl.pixels) return c->fail(std::string(fn) + ": size mismatch");
     RT_HIP(c, hipSetDevice(c->device));
     for (int k = 0; k < AOV_PLANES; k++)
         if (void* dst = aov_plane(*out, (AovPlane)k))
-            RT_HIP(c, hipMemcpyAsync(dst, aov_plane(c->aov.buf.p, (AovPlane)k, nPixels), nPixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+            RT_HIP(c, hipMemcpyAsync(dst, aov_plane(pl.buf.p, (AovPlane)k, nPixels), nPixels * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
+}
+AovOut aov_out(const RtAovBuffers* given, const void* owned, size_t nPixels) {   // given NULL: the ctx-owned set; both NULL: no plane
+    const auto plane = [&](AovPlane k) -> void* { return given ? aov_plane(*given, k) : owned ? aov_plane(owned, k, nPixels) : nullptr; };
+    return AovOut{(float4*)plane(AOV_NORMAL_DEPTH), (float4*)plane(AOV_POSITION), (float4*)plane(AOV_ALBEDO), (float4*)plane(AOV_RAY_DIR), (uint4*)plane(AOV_IDS)};
+}
+enum { GUIDE_COUNTS = 16 };   // words of guideCountBuf: [j] the rays of round j, j = 1 .. RT_GUIDE_MAX_BOUNCES + 1 (the last one stays 0)
+static_assert(RT_GUIDE_MAX_BOUNCES + 2 <= GUIDE_COUNTS, "a count per round");
+}  // namespace
+
+extern "C" {
+int rt_read_aovs(rt_ctx* c, const RtAovBuffers* out, size_t nPixels) {
+    return c ? read_planes(c, c->aov, "rt_read_aovs", NO_OWNED_AOVS, out, nPixels) : -1;
+}
+
+// Round 0 is rt_render_aovs' own (k_aov_rays, the traversal over every slot). After each round k_guide_follow writes the records of
+// the chains that end there and queues the reflected rays of the others; round j > 0 traces that queue, whose length only the
+// device knows: every round is enqueued, and one without rays costs its launches.
+int rt_render_guides(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
+                     uint32_t nRows, uint32_t maxBounces, const RtAovBuffers* d_guides, const RtAovBuffers* d_firstHit) {
+    if (!c || !pc) return -1;
+    const std::string refusal = check_guides(pc->rayTraceParams, width, height, row0, rowStride, nRows, maxBounces, d_guides, d_firstHit, uploaded_scene(c));
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t nPixels = nRows * width;
+    RT_HIP(c, hipSetDevice(c->device));
+    if (nPixels == 0) return 0;
+    int rc;
+    if (c->capacity < nPixels || !c->stateBuf.p) RT_HIP(c, hipStreamSynchronize(c->stream));   // as rt_render_aovs
+    if ((rc = ensure_state(c, nPixels))) return rc;
+    if ((rc = dev_alloc(c, c->guideCountBuf, GUIDE_COUNTS * sizeof(uint32_t)))) return rc;
+    if (!d_guides) {
+        if ((rc = dev_alloc(c, c->guide.buf, (size_t)nPixels * sizeof(float4) * AOV_PLANES))) return rc;
+        c->guide.pixels = nPixels;
+        c->guide.valid = true;
+        c->guide.rows = RowsOf{width, height, row0, rowStride, nRows};
+    }
+    FrameParams fp = frame_camera(c, pc, width, height, row0, rowStride, nRows, nPixels);
+    fp.nFrames = 1;
+    Dispatch d = one_part(c, dispatch_scene(c, pc->rayTraceParams), false);
+    d.phaseStats = 0; d.launches = &c->rep.aovLaunches;
+    const uint32_t blocks = (nPixels + RT_BLOCK - 1) / RT_BLOCK;
+    uint32_t* const counts = (uint32_t*)c->guideCountBuf.p;
+    GuideArgs ga{nullptr, nullptr, nullptr, nullptr, d.counts + 4, 0u, maxBounces, aov_out(d_guides, c->guide.buf.p, nPixels), aov_out(d_firstHit, nullptr, 0)};
+    RT_HIP(c, hipMemsetAsync(counts, 0, GUIDE_COUNTS * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_aov_rays, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, d.sc, c->ps, fp);
+    hipLaunchKernelGGL(k_init_counts, dim3(1), dim3(64), 0, c->stream, c->q.counts, nPixels);
+    RT_HIP(c, hipGetLastError());
+    for (uint32_t j = 0; j <= maxBounces; j++) {
+        ga.round = j;
+        ga.queue = j ? c->q.rays[j & 1u] : nullptr;
+        ga.count = j ? counts + j : c->q.counts;
+        ga.outQueue = c->q.rays[(j + 1u) & 1u];
+        ga.outCount = counts + j + 1;
+        const TraceArgs ta{ga.queue, ga.count, nullptr, nullptr, (DevCounters*)c->aovCounterBuf.p};
+        if ((rc = launch_trace(c, d, nPixels, ta))) return rc;
+        hipLaunchKernelGGL(k_guide_follow, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, d.sc, c->ps, fp, ga);
+        RT_HIP(c, hipGetLastError());
+    }
+    return 0;
+}
+
+int rt_read_guides(rt_ctx* c, const RtAovBuffers* out, size_t nPixels) {
+    return c ? read_planes(c, c->guide, "rt_read_guides", NO_OWNED_GUIDES, out, nPixels) : -1;
 }
 }  // extern "C"
 

@@ -1891,7 +1891,17 @@ __global__ __launch_bounds__(RT_BLOCK) void k_aov_rays(DevScene sc, PathState ps
 }
 
 // The traversal's {dst, object, triangle} -> the RtHit fields of k_hit_details (reconstruct_hit<true>: bump-tilted normals) and
-// the albedo the diffuse branch of shade_path would use; one 16-byte store per plane and pixel, in pixel order
+// the albedo the diffuse branch of shade_path would use (rt_aov_record.hip.inc, shared with k_guide_follow); one 16-byte store per
+// plane and pixel, in pixel order
+#define RT_AOV_STORE(out, px)                                        \
+    do {                                                             \
+        if ((out).normalDepth) (out).normalDepth[px] = normalDepth;  \
+        if ((out).position) (out).position[px] = position;           \
+        if ((out).albedo) (out).albedo[px] = albedo;                 \
+        if ((out).rayDir) (out).rayDir[px] = mk4(rd, 0.f);           \
+        if ((out).ids) (out).ids[px] = ids;                          \
+    } while (0)
+
 __global__ __launch_bounds__(RT_BLOCK) void k_aov_resolve(DevScene sc, PathState ps, FrameParams fp, AovOut out) {
     const uint32_t slot = blockIdx.x * RT_BLOCK + threadIdx.x;
     if (slot >= fp.nPixels) return;
@@ -1900,27 +1910,69 @@ __global__ __launch_bounds__(RT_BLOCK) void k_aov_resolve(DevScene sc, PathState
     const size_t px = (size_t)krow * fp.width + gx;
     const rt_vec3 ro = f4xyz(ps.rayO()[slot]), rd = f4xyz(ps.rayD()[slot]);
     const float4 hm = ps.hit(RAY_MAIN)[slot];
-    const uint32_t obj = __float_as_uint(hm.y), tri = __float_as_uint(hm.z);
-    float4 normalDepth = make_float4(0.f, 0.f, 0.f, hm.x), position = make_float4(0.f, 0.f, 0.f, 0.f), albedo = position;
-    uint4 ids = make_uint4(RT_HIT_NONE, RT_HIT_NONE, RT_HIT_NONE, 0u);
-    if (obj != RT_HIT_NONE) {
-        const bool sphere = (obj & RT_HIT_SPHERE) != 0u;
-        const FullHit f = reconstruct_hit<true>(sc, ro, rd, obj, tri);
-        const float4* mp = rt_global(sc.mats) + 3 * f.materialIndex;
-        const float4 mA = mp[0];
-        rt_vec3 a = rt_v3(mA.x, mA.y, mA.z);
-        const uint32_t texSlot = __float_as_uint(mp[2].y);   // albedoIndex; 0xffffffff (-1) = none
-        if (texSlot < sc.texCount && !sphere) a = rt_mul(a, albedo_texel(sc, texSlot, tri, obj, ro, rd));
-        normalDepth = mk4(f.normal, hm.x);
-        position = mk4(f.hitPoint, 1.f);
-        albedo = mk4(a, 1.f);
-        ids = make_uint4(obj & ~RT_HIT_SPHERE, sphere ? 0u : tri, f.materialIndex, 1u | (sphere ? 2u : 0u) | (f.frontFace ? 4u : 0u));
+#define RT_AOV_MIRROR 0
+#include "rt_aov_record.hip.inc"
+#undef RT_AOV_MIRROR
+    RT_AOV_STORE(out, px);
+}
+
+// ---------------------------------------------------------------- mirror-following guide planes (rt_render_guides)
+// After each traversal round of the pass, one lane per ray the round traced: the hit's record, and whether the chain goes on there
+// ("Mirror-following guide planes"). Every ray of round j is segment j of its pixel's chain, so L needs no plane of its
+// own; the path length so far rides in rayO().w, which no traversal reads (k_aov_rays leaves 0 there, and 0 + d0 is d0).
+struct GuideArgs {
+    const uint32_t* queue;   // the round's rays, slot * 4 + RAY_MAIN, as the traversal had them; NULL in round 0: every slot of the tile
+    const uint32_t* count;   // ... and how many, on the device
+    uint32_t* outQueue;      // the next round's rays and their count (zero before the launch)
+    uint32_t* outCount;
+    uint32_t* head;          // the traversal's work counter, which its next launch wants zero
+    uint32_t round, maxBounces;
+    AovOut guides, firstHit; // firstHit: round 0 writes every pixel's own record there as k_aov_resolve would
+};
+
+__global__ __launch_bounds__(RT_BLOCK) void k_guide_follow(DevScene sc, PathState ps, FrameParams fp, GuideArgs ga) {
+    const uint32_t i = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (i == 0) *ga.head = 0u;   // (the round's traversal is over and the next one is behind this kernel on the stream)
+    const uint32_t n = ga.queue ? min(*ga.count, fp.nPixels) : fp.nPixels;
+    bool goesOn = false;
+    uint32_t slot = 0;
+    if (i < n) {   // (no early return: the ballot below wants the whole wave)
+        slot = ga.queue ? ga.queue[i] >> 2 : i;
+        if (slot < fp.nPixels) {
+            uint32_t gx, gy, krow;
+            slot_to_pixel(fp, slot, gx, gy, krow);
+            const size_t px = (size_t)krow * fp.width + gx;
+            const float4 sO = ps.rayO()[slot];
+            const rt_vec3 ro = f4xyz(sO), rd = f4xyz(ps.rayD()[slot]);
+            const float4 hm = ps.hit(RAY_MAIN)[slot];
+#define RT_AOV_MIRROR 1
+#include "rt_aov_record.hip.inc"
+#undef RT_AOV_MIRROR
+            if (ga.round == 0u) RT_AOV_STORE(ga.firstHit, px);
+            const float length = sO.w + hm.x;   // ((d0 + d1) + d2) + ...
+            goesOn = mirror && ga.round < ga.maxBounces;
+            if (goesOn) {
+                // the ray shade_path would trace next (its mirror branch: originSign 1), and the seed its creator owes the traversal
+                const rt_vec3 normal = f4xyz(normalDepth), nd = rt_reflect(rd, normal);
+                const rt_vec3 no = rt_add(f4xyz(position), rt_scale(rt_scale(normal, 1.f), 0.00001f));
+                ps.rayO()[slot] = mk4(no, length);
+                ps.rayD()[slot] = mk4(nd, 0.f);
+                ps.hit(RAY_MAIN)[slot] = sphere_seed(sc, no, nd);
+            } else {
+                if (ids.w & 1u) normalDepth.w = length;
+                ids.w |= (mirror ? 8u : 0u) | (ga.round << 8);
+                RT_AOV_STORE(ga.guides, px);
+            }
+        }
     }
-    if (out.normalDepth) out.normalDepth[px] = normalDepth;
-    if (out.position) out.position[px] = position;
-    if (out.albedo) out.albedo[px] = albedo;
-    if (out.rayDir) out.rayDir[px] = mk4(rd, 0.f);
-    if (out.ids) out.ids[px] = ids;
+    // the next round's queue: one atomic per wave
+    const unsigned long long m = __ballot(goesOn);
+    if (m) {
+        uint32_t base = 0;
+        if (lane_id() == 0) base = atomicAdd(ga.outCount, (uint32_t)__popcll(m));
+        base = __shfl(base, 0, RT_WAVE);
+        if (goesOn) ga.outQueue[base + lanes_below(m)] = (slot << 2) | (uint32_t)RAY_MAIN;
+    }
 }
 
 // ---------------------------------------------------------------- a-trous denoiser (rt_denoise)

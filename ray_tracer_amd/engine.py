@@ -223,9 +223,13 @@ class Renderer:
         self._scene = None
         self._shape = None
         self._aov_shape = None
+        self._first_hit_buf = (None, 0)   # device planes render_guides(first_hit=True) hands to rt_render_guides, and their bytes
 
     def close(self):
         if getattr(self, "_h", None):
+            if self._first_hit_buf[0]:
+                _hip().hipFree(self._first_hit_buf[0])
+                self._first_hit_buf = (None, 0)
             self._l.rt_destroy(self._h)
             self._h = None
 
@@ -383,6 +387,49 @@ class Renderer:
         b = RtAovBuffers(**{k: v.ctypes.data for k, v in planes.items()})
         self._check(self._l.rt_read_aovs(self._h, C.byref(b), n * w), "rt_read_aovs")
         return aovs_to_numpy(planes)
+
+    def render_guides(self, pc, width, height, max_bounces=4, first_hit=False, row0=0, rowStride=1, nRows=None):
+        """Mirror-following guide planes (rt_render_guides; DESIGN.md, "Mirror-following guide planes") for the rows render() would
+        render: the dict of aovs_to_numpy for the first surface that is no mirror along each pixel's chain of reflections (`depth` is
+        the length of the whole path), plus `bounces`, the mirror segments before it, and `cut`, whether the chain was cut at
+        `max_bounces` on a mirror. It goes to denoise() in place of render_aovs()'s. With `first_hit` the call returns
+        (guides, first): `first` is what render_aovs() returns for the same tile, from the same traversal (the planes
+        temporal_accumulate() takes). The context's own first-hit planes (render_aovs) are left as they are."""
+        if nRows is None:
+            nRows = (height - row0 + rowStride - 1) // rowStride
+        n = nRows * width
+        first = None
+        if first_hit:
+            first = RtAovBuffers(**{k: self._first_hit_planes(n) + i * n * 16 for i, k in enumerate(AOV_PLANES)})
+        self.fill_counts(pc)
+        self._check(self._l.rt_render_guides(self._h, C.byref(pc), width, height, row0, rowStride, nRows, int(max_bounces), None,
+                                             C.byref(first) if first is not None else None), "rt_render_guides")
+        planes = {k: np.empty((nRows, width, 4), np.uint32 if k == "ids" else np.float32) for k in AOV_PLANES}
+        b = RtAovBuffers(**{k: v.ctypes.data for k, v in planes.items()})
+        self._check(self._l.rt_read_guides(self._h, C.byref(b), n), "rt_read_guides")   # (blocks: the pass is over)
+        g = aovs_to_numpy(planes)
+        g["bounces"], g["cut"] = (planes["ids"][..., 3] >> 8) & 15, (planes["ids"][..., 3] & 8) != 0
+        if first is None:
+            return g
+        planes = {k: np.empty((nRows, width, 4), np.uint32 if k == "ids" else np.float32) for k in AOV_PLANES}
+        for k in AOV_PLANES:
+            if _hip().hipMemcpy(planes[k].ctypes.data, getattr(first, k), n * 16, 2) != 0:   # hipMemcpyDeviceToHost
+                raise RtError("render_guides: the first-hit planes could not be copied back")
+        return g, aovs_to_numpy(planes)
+
+    def _first_hit_planes(self, n):
+        """Device memory for five planes of n pixels, kept between calls and freed with the renderer."""
+        p, have = self._first_hit_buf
+        need = max(n, 1) * 16 * len(AOV_PLANES)
+        if have < need:
+            if p:
+                _hip().hipFree(p)
+                self._first_hit_buf = (None, 0)
+            q = C.c_void_p()
+            if _hip().hipMalloc(C.byref(q), need) != 0 or not q.value:
+                raise RtError(f"render_guides: no device memory for {need} bytes of first-hit planes")
+            self._first_hit_buf = (q.value, need)
+        return self._first_hit_buf[0]
 
     def denoise(self, frame=None, aovs=None, iterations=5, sigma_luminance=4.0, sigma_normal=128.0, sigma_depth=1.0):
         """The edge-aware a-trous denoiser (rt_denoise; DESIGN.md, "Denoising") of a whole frame: an (H, W, 4) float32 array.
@@ -561,6 +608,23 @@ class Renderer:
 
 
 AOV_PLANES = ("normalDepth", "position", "albedo", "rayDir", "ids")   # the fields of RtAovBuffers
+
+_hip_handle = None
+
+
+def _hip():
+    """The HIP runtime the library is bound to, for the few device buffers this module owns. Looked up through the library's own
+    handle (dlsym searches a library and then its dependencies), so that a second copy of the runtime in the process (a
+    framework's wheel bundles one) is never taken for it."""
+    global _hip_handle
+    if _hip_handle is None:
+        h = C.CDLL(_capi.LIB_PATH)
+        h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        h.hipFree.argtypes = [C.c_void_p]
+        _hip_handle = h
+    return _hip_handle
+
 
 
 def aovs_to_numpy(planes):

@@ -69,6 +69,10 @@ def build_parser():
     ap.add_argument("--denoise", action="store_true",
                     help="write the frame through the edge-aware a-trous denoiser (Renderer.denoise, defaults; DESIGN.md, "
                          "\"Denoising\") to --out; it runs the first-hit AOV pass itself unless --aov-out did")
+    ap.add_argument("--guide-bounces", type=int, default=0, metavar="N",
+                    help="with --denoise: guide the denoiser by the first surface that is no mirror along up to N reflections (0..8) of "
+                         "each camera ray, so that reflections keep their edges (Renderer.render_guides; DESIGN.md, \"Mirror-following "
+                         "guide planes\"); 0: by the first hit")
     ap.add_argument("--temporal-frames", type=int, default=0, metavar="N",
                     help="render N non-progressive frames of --rays-per-pixel samples with consecutive frameCounts and one fixed camera, "
                          "accumulate them through the temporal pass (Renderer.temporal_accumulate, defaults; DESIGN.md, \"Temporal "
@@ -171,6 +175,10 @@ def main(argv=None):
     device = args.device
     if args.temporal_frames < 0:
         raise SystemExit("--temporal-frames must be >= 0")
+    if not 0 <= args.guide_bounces <= 8:
+        raise SystemExit("--guide-bounces must be 0..8")
+    if args.guide_bounces and not args.denoise:
+        raise SystemExit("--guide-bounces guides the denoiser: it needs --denoise")
     if args.temporal_frames and world > 1:   # before any rank waits for another
         raise SystemExit(f"--temporal-frames needs the whole frame on one GPU: launched on {world} ranks, run it as a single process")
     if world > 1:
@@ -211,7 +219,7 @@ def main(argv=None):
             frames += 1
         r.totalSamples = args.temporal_frames * args.rays_per_pixel
         if args.denoise:
-            img = r.denoise(img, aovs)
+            img = r.denoise(img, r.render_guides(pc, W, H, args.guide_bounces) if args.guide_bounces else aovs)
     while not temporal:
         out = r.run_compute(pc, W, H, frames=args.frames_in_flight, **tile)
         if out is None:
@@ -224,17 +232,20 @@ def main(argv=None):
     if not temporal:
         aovs = r.render_aovs(pc, W, H, **tile) if args.aov_out or denoise else None
     on = f"cuda:{device}" if args.backend == "nccl" else "cpu"
+    guides = r.render_guides(pc, W, H, args.guide_bounces, **tile) if denoise and args.guide_bounces else None
     if world > 1 and aovs is not None:
         aovs = gather_planes(aovs, H, world, rank, on)
+    if world > 1 and guides is not None:
+        guides = gather_planes(guides, H, world, rank, on)
     if world > 1 and img is not None:   # strips -> frame on rank 0
         strip = torch.from_numpy(img).to(on)
         frame = torch.zeros((H, W, 4), dtype=torch.float32, device=on) if rank == 0 else None
         tiling.gather_frame(strip, frame, H, world, rank)
         img = frame.cpu().numpy() if rank == 0 else None
-    if denoise and world == 1:
+    if denoise and world == 1 and guides is None:
         img = r.denoise()   # the context's own frame and planes
     elif denoise and rank == 0:
-        img = r.denoise(img, aovs)   # the gathered frame and planes
+        img = r.denoise(img, aovs if guides is None else guides)   # the gathered frame and planes, or the guide planes
     dt = time.perf_counter() - t0
     c = r.counters()
     if world > 1:

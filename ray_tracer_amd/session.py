@@ -17,7 +17,7 @@ from . import _capi, engine
 
 
 class InteractiveSession:
-    def __init__(self, renderer, scene, width, height, temporal=False, denoise=False, track_motion=False):
+    def __init__(self, renderer, scene, width, height, temporal=False, denoise=False, track_motion=False, mirror_guides=0):
         """temporal: every draw() that dispatched also runs the first-hit AOV pass and, while the camera moves (progressive
         accumulation off), the temporal pass (Renderer.temporal_accumulate); `filtered` is the result, `history_length` its N
         plane, and `image` stays the raw frame. While the camera rests the reference's own progressive accumulation converges
@@ -26,7 +26,10 @@ class InteractiveSession:
         moving one. denoise: `filtered` also goes through Renderer.denoise. set_object, set_sphere
         and set_material reset the temporal history (the pass takes the scene to be static). track_motion (with temporal): the
         history follows moved objects and spheres (Renderer.temporal_track_motion), so set_object and set_sphere no longer reset
-        it; set_material still does."""
+        it; set_material still does. mirror_guides: N > 0 guides the denoiser by the first surface that is no mirror along up to N
+        reflections (Renderer.render_guides) instead of by the first hit; one pass then yields both those planes and the first-hit
+        planes, which the temporal pass keeps taking. 0: exactly as without it."""
+        self.mirror_guides = int(mirror_guides)
         self.r, self.scene, self.W, self.H = renderer, scene, int(width), int(height)
         self.temporal, self.denoise = bool(temporal), bool(denoise)
         self.track_motion = self.temporal and bool(track_motion)
@@ -114,11 +117,16 @@ class InteractiveSession:
 
     # ---- temporal accumulation and denoising of the frame draw() just dispatched (not in the reference)
     def _filter(self, img):
-        aovs = self.r.render_aovs(self.pc, self.W, self.H)
+        first = None
+        if self.mirror_guides > 0:
+            aovs, first = self.r.render_guides(self.pc, self.W, self.H, max_bounces=self.mirror_guides, first_hit=True)
+        else:
+            aovs = self.r.render_aovs(self.pc, self.W, self.H)
         out = img
         if self.temporal:
             still = bool(self.params.progressive)
-            out, mom = self.r.temporal_accumulate(self.pc, max_history=1 if still else 32, moments=True)
+            src = {} if first is None else dict(frame=img, aovs=first)   # (the guide pass leaves the context's own planes alone)
+            out, mom = self.r.temporal_accumulate(self.pc, max_history=1 if still else 32, moments=True, **src)
             self.history_length = mom[..., 3]
             if still:
                 out = img
