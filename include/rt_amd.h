@@ -331,6 +331,23 @@ int  rt_render(rt_ctx* ctx, const PushConstants* pc, uint32_t width, uint32_t he
  * one dispatch in millions (default 24: 5.8 GB of path state); more frames than that go in several dispatches. */
 int  rt_render_frames(rt_ctx* ctx, const PushConstants* pc, uint32_t width, uint32_t height,
                       uint32_t row0, uint32_t rowStride, uint32_t nRows, uint32_t nFrames, float* d_rgba);
+/* rt_render_frames with a sample count per pixel. d_sampleMap: device pointer to nRows*width counts in d_rgba's pixel order (row k,
+ * column x at k*width + x), read by the dispatch, so it stays valid and unchanged until the stream has passed it. With S what
+ * rt_render would use (singleRender ? sampleLimit : raysPerPixel) and n_p = min(map[p], S):
+ *  - n_p >= 1: pixel p is written, bit for bit, as rt_render_frames would write it with the same arguments and S replaced by n_p
+ *    (a pixel's samples are serial and its RNG seed depends on its global pixel index and frameCount only): the mean over n_p
+ *    samples, the progressive blend with what d_rgba holds, NaN -> magenta, frameCount + f for frame f;
+ *  - n_p = 0: pixel p of d_rgba is not written, rgb or alpha, in any of the nFrames frames, and no path is made for it (a hole in
+ *    the multi-kernel pipeline's queues; a lane of the fused kernel that takes its next pixel at once);
+ *  - d_sampleMap NULL: rt_render_frames, exactly.
+ * Both pipelines, 1..4 parts, camera_reuse on and off, scenes with maps, the ctx framebuffer (d_rgba NULL) and row tiling work as
+ * in rt_render. A call rt_render_frames would split (frames_per_dispatch) uses the same map for every piece. The launch policy
+ * sees S as the dispatch's sample count, and the multi-kernel pipeline enqueues up to S * (bounceLimit + 1) rounds as before; the
+ * ray-cost probe ignores the map. `paths` grows by the sum of n_p per frame, the other counters by the work done. Refused with a
+ * message: the debug heat maps (rayTraceParams.debug >= 0) with a map. Asynchronous on the ctx stream, checked like rt_render. */
+int  rt_render_sampled(rt_ctx* ctx, const PushConstants* pc, uint32_t width, uint32_t height,
+                       uint32_t row0, uint32_t rowStride, uint32_t nRows, uint32_t nFrames,
+                       const uint32_t* d_sampleMap, float* d_rgba);
 int  rt_sync(rt_ctx* ctx);
 /* forget the ctx's own framebuffer: the next rt_render(…, NULL) starts a new progressive history from a zeroed image */
 int  rt_clear_framebuffer(rt_ctx* ctx);
@@ -490,6 +507,38 @@ int  rt_read_temporal_moments(rt_ctx* ctx, float* hostOut, size_t nFloats);
  * as above) on the same history; blocks */
 int  rt_temporal_accumulate_host(rt_ctx* ctx, uint32_t width, uint32_t height, const CameraInfo* cam, const float* rgba,
                                  const RtAovBuffers* aovs, const RtTemporalParams* params, float* out, float* moments);
+
+/* Sample counts for rt_render_sampled from the moments of rt_temporal_accumulate ("Per-pixel sample counts"): where the
+ * accumulated frame is still noisy the next frame gets more samples, where it has converged fewer. Per pixel, from its record
+ * (m1, m2, var, N), all in fp32, in this order, without contraction:
+ *   N = 0 (a kept pixel: a miss or an emitter, noise-free because the camera ray does not jitter)   -> minSamples
+ *   0 < N < 2 (no variance known yet)                                                               -> baseSamples (counted in `unknown`)
+ *   otherwise   d = max(m1, luminanceFloor); den = (N * (tau * tau)) * (d * d); q = (baseSamples * var) / den;
+ *               n = max(minSamples, q < (float)maxSamples ? (q > 0 ? (uint)ceil(q) : 0) : maxSamples)
+ *               (a NaN q gives maxSamples; a q <= 0, which only a negative N or variance gives, counts as 0 before the max)
+ * q is the estimated relative variance of the accumulated mean over tau^2: a pixel at the target gets baseSamples, one r times
+ * noisier r times as many. The map is in the pixel grid of the frame whose moments it read. */
+typedef struct RtSampleMapParams {
+    uint32_t baseSamples, minSamples, maxSamples;   /* minSamples <= baseSamples <= maxSamples */
+    float    targetRelError;                        /* tau > 0 */
+    float    luminanceFloor;                        /* > 0 */
+} RtSampleMapParams;
+void rt_sample_map_params_default(RtSampleMapParams* p);     /* 4, 1, 16, 0.05, 0.01 (this build's choice: DESIGN.md) */
+/* Asynchronous on the ctx stream: one kernel over the width x height frame. d_moments: device plane of width*height records as
+ * rt_temporal_accumulate writes them, or NULL: the ctx-owned plane of the last rt_temporal_accumulate(…, d_moments = NULL), which
+ * must have this width and height. params NULL: the defaults. d_map: width*height counts, required. Changes no counter, no
+ * history and no other plane. */
+int  rt_build_sample_map(rt_ctx* ctx, uint32_t width, uint32_t height, const float* d_moments, const RtSampleMapParams* params,
+                         uint32_t* d_map);
+typedef struct RtSampleMapStats {
+    uint64_t samples;                            /* the sum of the counts */
+    uint32_t pixels, unknown, aboveMin, atMax;   /* width*height; pixels with 0 < N < 2; with a count > minSamples; == maxSamples */
+} RtSampleMapStats;
+/* of the last rt_build_sample_map; blocks */
+int  rt_sample_map_stats(rt_ctx* ctx, RtSampleMapStats* out);
+/* rt_build_sample_map of host arrays (moments: width*height*4 floats, map: width*height counts); blocks */
+int  rt_build_sample_map_host(rt_ctx* ctx, uint32_t width, uint32_t height, const float* moments, const RtSampleMapParams* params,
+                              uint32_t* map);
 
 int  rt_get_counters(rt_ctx* ctx, RtCounters* out);
 int  rt_reset_counters(rt_ctx* ctx);

@@ -110,6 +110,15 @@ class RtTemporalParams(C.Structure):
     _fields_ = [("maxHistory", C.c_uint32), ("normalCos", C.c_float), ("depthTolerance", C.c_float)]
 
 
+class RtSampleMapParams(C.Structure):
+    _fields_ = [("baseSamples", C.c_uint32), ("minSamples", C.c_uint32), ("maxSamples", C.c_uint32), ("targetRelError", C.c_float),
+                ("luminanceFloor", C.c_float)]
+
+
+class RtSampleMapStats(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("pixels", C.c_uint32), ("unknown", C.c_uint32), ("aboveMin", C.c_uint32), ("atMax", C.c_uint32)]
+
+
 # every symbol include/rt_amd.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 _vp = C.c_void_p
@@ -150,6 +159,7 @@ SYMBOLS = {
     "rt_update_objects": (C.c_int, [_vp, _P(RenderObject), C.c_uint32]),
     "rt_render": (C.c_int, [_vp, _P(PushConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
     "rt_render_frames": (C.c_int, [_vp, _P(PushConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    "rt_render_sampled": (C.c_int, [_vp, _P(PushConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "rt_sync": (C.c_int, [_vp]),
     "rt_clear_framebuffer": (C.c_int, [_vp]),
     "rt_read_rgba_f32": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
@@ -172,6 +182,10 @@ SYMBOLS = {
     "rt_read_temporal_rgba_f32": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
     "rt_read_temporal_moments": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
     "rt_temporal_accumulate_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _P(CameraInfo), _vp, _P(RtAovBuffers), _P(RtTemporalParams), _vp, _vp]),
+    "rt_sample_map_params_default": (None, [_P(RtSampleMapParams)]),
+    "rt_build_sample_map": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _P(RtSampleMapParams), _vp]),
+    "rt_sample_map_stats": (C.c_int, [_vp, _P(RtSampleMapStats)]),
+    "rt_build_sample_map_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _P(RtSampleMapParams), _vp]),
     "rt_get_counters": (C.c_int, [_vp, _P(RtCounters)]),
     "rt_reset_counters": (C.c_int, [_vp]),
     "rt_set_profiling": (C.c_int, [_vp, C.c_int]),

@@ -71,6 +71,22 @@ std::string check_temporal(uint32_t width, uint32_t height, const CameraInfo* ca
     return "";
 }
 
+std::string check_sample_map(uint32_t width, uint32_t height, const RtSampleMapParams& p, bool momentsGiven, const OwnedRows& owned, const char* fn) {
+    const std::string f(fn);
+    if (const char* m = bad_frame(width, height)) return f + m;
+    if (p.minSamples > p.baseSamples) return f + ": minSamples must be <= baseSamples";
+    if (p.baseSamples > p.maxSamples) return f + ": baseSamples must be <= maxSamples";
+    if (!(std::isfinite(p.targetRelError) && p.targetRelError > 0.f)) return f + ": targetRelError must be finite and > 0";
+    if (!(std::isfinite(p.luminanceFloor) && p.luminanceFloor > 0.f)) return f + ": luminanceFloor must be finite and > 0";
+    if (!momentsGiven) return check_owned(fn, "the ctx moments", NO_OWNED_MOMENTS, owned, width, height);
+    return "";
+}
+
+std::string check_sampled(const RayTracerData& td, bool mapGiven) {
+    if (mapGiven && td.debug >= 0) return "rt_render_sampled: the debug heat maps take no sample map";
+    return "";
+}
+
 // ---------------------------------------------------------------- the passes over a tile's camera rays
 std::string check_tile(const char* fn, const RayTracerData& td, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride, uint32_t nRows,
                        const UploadedScene& scene) {

@@ -38,10 +38,18 @@ struct TemporalCamera {   // the previous call's camera, as frame_camera has it 
 TemporalCamera temporal_camera(const CameraInfo& ci);
 
 // ---------------------------------------------------------------- parameter checks
+struct OwnedRows;
 // What rt_denoise and rt_denoise_host, rt_temporal_accumulate and rt_temporal_accumulate_host (fn) refuse before anything else:
 // geometry, parameters, then a missing scene (its material table says which hits are emitters). Empty: accepted.
 std::string check_denoise(uint32_t width, uint32_t height, const RtDenoiseParams& p, bool sceneUploaded, const char* fn);
 std::string check_temporal(uint32_t width, uint32_t height, const CameraInfo* cam, const RtTemporalParams& p, bool sceneUploaded, const char* fn);
+
+// What rt_build_sample_map and rt_build_sample_map_host (fn) refuse: geometry, then the parameters. momentsGiven: the caller passed
+// a moments plane; else `owned` is the ctx's own of the last rt_temporal_accumulate(…, d_moments = NULL), which must be there and be
+// this whole frame. Empty: accepted.
+std::string check_sample_map(uint32_t width, uint32_t height, const RtSampleMapParams& p, bool momentsGiven, const OwnedRows& owned, const char* fn);
+// what rt_render_sampled refuses beyond rt_render's checks: a map with the debug heat maps, which count work per pixel
+std::string check_sampled(const RayTracerData& td, bool mapGiven);
 
 // ---------------------------------------------------------------- the passes over a tile's camera rays
 // What rt_render, rt_render_aovs and rt_render_guides (fn) refuse of a tile and its scene counts: the rows y = row0 + k*rowStride,
@@ -73,6 +81,7 @@ inline void* aov_plane(const RtAovBuffers& b, AovPlane k) {   // the same plane 
 inline const char* const NO_OWNED_FRAMEBUFFER = "no ctx-owned framebuffer: rt_render was never called with d_rgba = NULL";
 inline const char* const NO_OWNED_AOVS = "no ctx-owned AOV planes: rt_render_aovs was never called with d_out = NULL";
 inline const char* const NO_OWNED_GUIDES = "no ctx-owned guide planes: rt_render_guides was never called with d_guides = NULL";
+inline const char* const NO_OWNED_MOMENTS = "no ctx-owned moments: rt_temporal_accumulate was never called with d_moments = NULL";
 
 // What the ctx owns of a kind (its framebuffer; its AOV planes): where, whether a pass ever wrote it, and the rows it holds
 struct OwnedRows { const void* base; bool valid; RowsOf rows; };

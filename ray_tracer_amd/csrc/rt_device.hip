@@ -106,6 +106,10 @@ struct rt_ctx {
     // rt_temporal_accumulate_host and the ctx-owned frame and moments
     DevBuf tpHist[2], tpHostBuf;
     OwnedPlane tpOut, tpMom;
+    // sample counts from the moments (rt_build_sample_map): the statistics of the last build, whether there was one, and the staging
+    // planes of rt_build_sample_map_host
+    DevBuf smStatBuf, smHostBuf;
+    bool smBuilt = false;
     // following moved objects and spheres: the motion table on the device with its pinned staging copy and the event that says the
     // copy has been read (upload_motion)
     DevBuf tpMotionBuf;
@@ -885,6 +889,7 @@ int probe_ray_cost(rt_ctx* c, const FrameParams& fp, const Dispatch& d) {
     const TileRows rows = probe_rows(TileRows{fp.row0, fp.rowStride, fp.nRows});
     FrameParams p = fp;
     p.samples = 1; p.progressive = 0; p.debug = -1; p.nFrames = 1;
+    p.sampleMap = nullptr;  // (rt_render_sampled's map covers the big dispatch's rows, not these)
     p.row0 = rows.row0; p.rowStride = rows.rowStride; p.nRows = rows.nRows; p.nPixels = rows.nRows * fp.width;
     Dispatch pd = d;  // fused pipeline, no profiling, no phase statistics, launches not counted
     pd.probe = true; pd.pipeline = 1; pd.profiled = false; pd.phaseStats = 0; pd.launches = nullptr;
@@ -903,13 +908,15 @@ int probe_ray_cost(rt_ctx* c, const FrameParams& fp, const Dispatch& d) {
     return 0;
 }
 
-// rt_render (nFrames = 1) and rt_render_frames: the checks, the path state and the image, then render_dispatch
+// rt_render (nFrames = 1), rt_render_frames and rt_render_sampled (sampleMap): the checks, the path state and the image, then render_dispatch
 int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
-                uint32_t nRows, uint32_t nFrames, float* d_rgba) {
+                uint32_t nRows, uint32_t nFrames, const uint32_t* sampleMap, float* d_rgba) {
     if (!c || !pc) return -1;
     int rc = check_tile(c, pc, width, height, row0, rowStride, nRows, "rt_render");
     if (rc) return rc;
     const RayTracerData& td = pc->rayTraceParams;
+    const std::string refused = check_sampled(td, sampleMap != nullptr);
+    if (!refused.empty()) return c->fail(refused);
     if (td.bounceLimit >= (1u << 28) - 1u) return c->fail("rayTraceParams.bounceLimit needs more than 28 bits");
     const uint64_t np64 = (uint64_t)nRows * width;
     if (frame_slots(np64) * nFrames >= (1ull << 30)) return c->fail("tile too large (slot ids are 30 bits)");
@@ -944,6 +951,7 @@ int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t hei
     fp.boxCap = td.boxCap;
     fp.triCap = td.triangleCap;
     fp.env = pc->environment;
+    fp.sampleMap = sampleMap;
     return render_dispatch(c, fp, one_part(c, dispatch_scene(c, td), td.debug >= 0), fb);
 }
 }  // namespace
@@ -952,11 +960,17 @@ extern "C" {
 
 int rt_render(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
               uint32_t nRows, float* d_rgba) {
-    return render_impl(c, pc, width, height, row0, rowStride, nRows, 1u, d_rgba);
+    return render_impl(c, pc, width, height, row0, rowStride, nRows, 1u, nullptr, d_rgba);
 }
 
 int rt_render_frames(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
                      uint32_t nRows, uint32_t nFrames, float* d_rgba) {
+    return rt_render_sampled(c, pc, width, height, row0, rowStride, nRows, nFrames, nullptr, d_rgba);
+}
+
+// (d_sampleMap NULL is rt_render_frames: the map is one more frame constant, and without it every kernel takes the uniform count)
+int rt_render_sampled(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t height, uint32_t row0, uint32_t rowStride,
+                      uint32_t nRows, uint32_t nFrames, const uint32_t* d_sampleMap, float* d_rgba) {
     if (!c || !pc) return -1;
     if (nFrames == 0) return 0;
     // The frames of one call are one dispatch, or several when they are too many paths for one (launch_plan.h: frames_per_dispatch)
@@ -965,7 +979,7 @@ int rt_render_frames(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_
     for (uint32_t f = 0; f < nFrames; f += per) {
         const uint32_t n = std::min(per, nFrames - f);
         p.frameCount = pc->frameCount + f;
-        int rc = render_impl(c, &p, width, height, row0, rowStride, nRows, n, d_rgba);
+        int rc = render_impl(c, &p, width, height, row0, rowStride, nRows, n, d_sampleMap, d_rgba);
         if (rc) return rc;
     }
     return 0;
@@ -1347,6 +1361,7 @@ int rt_temporal_accumulate(rt_ctx* c, uint32_t width, uint32_t height, const Cam
     }
     RT_HIP(c, hipGetLastError());
     c->temporal.commit(*cam);
+    if (!d_moments) c->tpMom.rows = RowsOf{width, height, 0u, 1u, height};   // (rt_build_sample_map reads the plane as this frame)
     return 0;
 }
 
@@ -1376,6 +1391,62 @@ int rt_temporal_accumulate_host(rt_ctx* c, uint32_t width, uint32_t height, cons
         planes.ids = (uint32_t*)(d + 4 * bytes);
         return rt_temporal_accumulate(c, width, height, cam, (const float*)d, &planes, &p, (float*)(d + 5 * bytes), (float*)(d + 6 * bytes));
     });
+}
+
+void rt_sample_map_params_default(RtSampleMapParams* p) {
+    if (p) *p = RtSampleMapParams{4u, 1u, 16u, 0.05f, 0.01f};
+}
+
+int rt_build_sample_map(rt_ctx* c, uint32_t width, uint32_t height, const float* d_moments, const RtSampleMapParams* params, uint32_t* d_map) {
+    if (!c) return -1;
+    const RtSampleMapParams p = params_or(params, rt_sample_map_params_default);
+    const std::string m = check_sample_map(width, height, p, d_moments != nullptr, c->tpMom.owned(), "rt_build_sample_map");
+    if (!m.empty()) return c->fail(m);
+    if (!d_map) return c->fail("rt_build_sample_map: d_map is required");
+    RT_HIP(c, hipSetDevice(c->device));
+    int rc = dev_alloc(c, c->smStatBuf, RT_SM_STRIPES * sizeof(SampleMapStatsDev));
+    if (rc) return rc;
+    RT_HIP(c, hipMemsetAsync(c->smStatBuf.p, 0, RT_SM_STRIPES * sizeof(SampleMapStatsDev), c->stream));
+    const SampleMapArgs a{d_moments ? (const float4*)d_moments : (const float4*)c->tpMom.buf.p, d_map, (SampleMapStatsDev*)c->smStatBuf.p, width, height,
+                          p.baseSamples, p.minSamples, p.maxSamples, p.targetRelError, p.luminanceFloor};
+    hipLaunchKernelGGL(k_sample_map, dim3((width + 15u) / 16u, (height + 15u) / 16u), dim3(RT_DN_BLOCK), 0, c->stream, a);
+    RT_HIP(c, hipGetLastError());
+    c->smBuilt = true;
+    return 0;
+}
+
+int rt_sample_map_stats(rt_ctx* c, RtSampleMapStats* out) {
+    if (!c || !out) return -1;
+    if (!c->smBuilt) return c->fail("rt_sample_map_stats: rt_build_sample_map was never called");
+    RT_HIP(c, hipSetDevice(c->device));
+    SampleMapStatsDev h[RT_SM_STRIPES];   // the kernel's striped copies (k_sample_map)
+    RT_HIP(c, hipMemcpyAsync(h, c->smStatBuf.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    *out = RtSampleMapStats{};
+    for (const SampleMapStatsDev& s : h) {
+        out->samples += s.samples; out->pixels += s.pixels; out->unknown += s.unknown; out->aboveMin += s.aboveMin; out->atMax += s.atMax;
+    }
+    return 0;
+}
+
+int rt_build_sample_map_host(rt_ctx* c, uint32_t width, uint32_t height, const float* moments, const RtSampleMapParams* params, uint32_t* map) {
+    if (!c) return -1;
+    const RtSampleMapParams p = params_or(params, rt_sample_map_params_default);
+    if (!moments || !map) return c->fail("rt_build_sample_map_host: moments and map are required");
+    const std::string m = check_sample_map(width, height, p, true, OwnedRows{}, "rt_build_sample_map_host");
+    if (!m.empty()) return c->fail(m);
+    const size_t n = (size_t)width * height;
+    RT_HIP(c, hipSetDevice(c->device));
+    if (c->smHostBuf.bytes < n * 20) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees planes a build in flight may be using
+    int rc = dev_alloc(c, c->smHostBuf, n * 20);
+    if (rc) return rc;
+    float* const dMom = (float*)c->smHostBuf.p;
+    uint32_t* const dMap = (uint32_t*)((char*)c->smHostBuf.p + n * 16);
+    RT_HIP(c, hipMemcpyAsync(dMom, moments, n * 16, hipMemcpyHostToDevice, c->stream));
+    if ((rc = rt_build_sample_map(c, width, height, dMom, &p, dMap))) return rc;
+    RT_HIP(c, hipMemcpyAsync(map, dMap, n * 4, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 int rt_get_counters(rt_ctx* c, RtCounters* out) {

@@ -67,10 +67,7 @@
                 valid = a < total && ns < nSlots && (fq->nFrames == 1u || slot_in_tile(*fq, ns) < fq->nPixels);
                 slot = ns;
                 auxMask = 0;
-                if (valid) {
-                    init_path(*sq, ps, *fq, slot);
-                    alive = fp.samples > 0;
-                }
+                if (valid) alive = init_path(*sq, ps, *fq, slot) > 0u;  // (0: rt_render_sampled gives the pixel no sample; resolve_pixel leaves it alone)
             }
         }
         const unsigned long long mA = __ballot(alive);

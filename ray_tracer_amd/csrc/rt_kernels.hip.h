@@ -200,6 +200,8 @@ struct FrameParams {
     int32_t debug;
     uint32_t boxCap, triCap;
     EnvironmentData env;
+    const uint32_t* sampleMap;  // rt_render_sampled: per pixel of the tile (row k, column x at k * width + x) its own sample count, capped at
+                                // `samples`; 0: the pixel has no path and is not written. NULL: every pixel takes `samples` (pixel_samples)
 };
 
 struct DevCounters {
@@ -1349,12 +1351,20 @@ __device__ __forceinline__ void slot_to_pixel(const FrameParams& fp, uint32_t sl
     gy = fp.row0 + k * fp.rowStride;
 }
 
+// The samples pixel `px` of the tile gets in this dispatch: FrameParams::samples, or what the map of rt_render_sampled says, capped at it
+__device__ __forceinline__ uint32_t pixel_samples(const FrameParams& fp, size_t px) {
+    return fp.sampleMap ? min(rt_global(fp.sampleMap)[px], fp.samples) : fp.samples;
+}
+
 // ---------------------------------------------------------------- k_raygen
-// raytrace.comp:547-564 for the pixel of `slot`: camera ray, RNG seed, path reset, sphere seed
-__device__ __forceinline__ void init_path(const DevScene& sc, const PathState& ps, const FrameParams& fp, uint32_t slot) {
+// raytrace.comp:547-564 for the pixel of `slot`: camera ray, RNG seed, path reset, sphere seed. Returns the pixel's sample count
+// (pixel_samples), which shade_path finds in the w of camDir; a pixel the map gives no sample gets no path: nothing is written.
+__device__ __forceinline__ uint32_t init_path(const DevScene& sc, const PathState& ps, const FrameParams& fp, uint32_t slot) {
     uint32_t gx, gy;
     uint32_t krow;
     slot_to_pixel(fp, slot, gx, gy, krow);
+    const uint32_t samples = pixel_samples(fp, (size_t)krow * fp.width + gx);
+    if (fp.sampleMap && samples == 0u) return 0u;
     ps.rayO()[slot] = make_float4(fp.camPos[0], fp.camPos[1], fp.camPos[2], 1.f);                          // misWeight = 1
     const rt_vec3 pd = primary_dir(fp, gx, gy);
     uint32_t startingSeed = fp.startingSeed;
@@ -1363,16 +1373,17 @@ __device__ __forceinline__ void init_path(const DevScene& sc, const PathState& p
         startingSeed = (uint32_t)(rt_random(&lol) * 23892183.f);
     }
     ps.rayD()[slot] = mk4u(pd, gy * fp.width + gx + startingSeed);                                      // RNG seed (:564)
-    ps.camDir()[slot] = mk4(pd, 0.f);
+    ps.camDir()[slot] = mk4u(pd, samples);
     ps.hit(RAY_MAIN)[slot] = sphere_seed(sc, rt_v3(fp.camPos[0], fp.camPos[1], fp.camPos[2]), pd);
     ps.att()[slot] = make_float4(1.f, 1.f, 1.f, __uint_as_float(0u));                                   // j = 0
     ps.total()[slot] = make_float4(0.f, 0.f, 0.f, __uint_as_float(0u));                                 // sample 0
     ps.accum()[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
     ps.statBox()[slot] = 0;
     ps.statTri()[slot] = 0;
+    return samples;
 }
 
-#define RT_QUEUE_HOLE 0xffffffffu   // queue entry without a path (multi-frame dispatch: the padding of a tile that is not a multiple of 64 slots)
+#define RT_QUEUE_HOLE 0xffffffffu   // queue entry without a path (multi-frame dispatch: the padding of a tile that is not a multiple of 64 slots; rt_render_sampled: a pixel without samples)
 // slots [slotBegin, slotEnd) of the dispatch: one part of the multi-kernel pipeline (render_impl); the part's queues start with
 // its slots in order (position = slot - slotBegin)
 __global__ __launch_bounds__(RT_BLOCK) void k_raygen(DevScene sc, PathState ps, uint32_t* activeOut, uint32_t* raysOut, FrameParams fp,
@@ -1386,7 +1397,11 @@ __global__ __launch_bounds__(RT_BLOCK) void k_raygen(DevScene sc, PathState ps, 
         raysOut[pos] = RT_QUEUE_HOLE;
         return;
     }
-    init_path(sc, ps, fp, slot);
+    if (init_path(sc, ps, fp, slot) == 0u && fp.sampleMap) {
+        activeOut[pos] = RT_QUEUE_HOLE;
+        raysOut[pos] = RT_QUEUE_HOLE;
+        return;
+    }
     activeOut[pos] = slot;
     // (always with its seed record, RAY_MAIN: init_path is the fused kernels' too, and a camera ray is one record in the ~47 segments of
     // a pixel's eight samples. k_seed_rays and k_aov_rays feed launches without a queue, which have no entry to mark: they write it as well.)
@@ -1592,11 +1607,13 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
         const rt_vec3 sum = rt_add(f4xyz(acc), total);
         ps.accum()[slot] = mk4(sum, 0.f);
         samplesDone++;
-        if (samplesDone < fp.samples) {
+        // the pixel's own sample count rides in the w of its camera direction (init_path): one load, made only where a sample ends
+        const float4 cD = ps.camDir()[slot];
+        if (samplesDone < __float_as_uint(cD.w)) {
             // next sample of this pixel: same primary ray (kept by init_path rather than derived from the slot again: the
             // whole wave pays for this branch whenever one lane finishes a sample), RNG state runs on (:571-573)
             ro = rt_v3(fp.camPos[0], fp.camPos[1], fp.camPos[2]);
-            rd = f4xyz(ps.camDir()[slot]);
+            rd = f4xyz(cD);
             att = rt_v3(1.f, 1.f, 1.f);
             total = rt_v3(0.f, 0.f, 0.f);
             specular = false;  // directLight = 0 (:487)
@@ -1734,9 +1751,10 @@ __global__ __launch_bounds__(RT_BLOCK, RT_SHADE_BLOCKS) void k_shade_maps(DevSce
 // raytrace.comp:574-593. `rgba` holds the previous frame when progressive
 // (kept in fp32 instead of the reference's 8-bit image).
 // raytrace.comp:574-582 for one frame: sample mean, progressive blend with what the image holds, NaN/Inf -> magenta
-__device__ __forceinline__ rt_vec3 blend_frame(const FrameParams& fp, uint32_t frameCount, float4 oldc, float4 accum) {
+// (samples: the pixel's own count, pixel_samples)
+__device__ __forceinline__ rt_vec3 blend_frame(const FrameParams& fp, uint32_t samples, uint32_t frameCount, float4 oldc, float4 accum) {
     rt_vec3 out = f4xyz(accum);
-    float fs = (float)fp.samples;
+    float fs = (float)samples;
     out = rt_v3(out.x / fs, out.y / fs, out.z / fs);
     float weight = 1.f / ((float)frameCount + 1.f);
     rt_vec3 blended = rt_add(rt_scale(rt_v3(oldc.x, oldc.y, oldc.z), 1.f - weight), rt_scale(out, weight));
@@ -1750,7 +1768,9 @@ __device__ __forceinline__ void resolve_pixel(const PathState& ps, const FramePa
     uint32_t gx, gy, krow;
     slot_to_pixel(fp, slot, gx, gy, krow);
     const size_t px = (size_t)krow * fp.width + gx;
-    rt_vec3 fin = blend_frame(fp, fp.frameCount, rgba[px], ps.accum()[slot]);
+    const uint32_t samples = pixel_samples(fp, px);
+    if (fp.sampleMap && samples == 0u) return;  // rt_render_sampled: no path was made for this pixel, and it keeps what it holds
+    rt_vec3 fin = blend_frame(fp, samples, fp.frameCount, rgba[px], ps.accum()[slot]);
     float s0 = (float)ps.statBox()[slot], s1 = (float)ps.statTri()[slot];
     float boxCap = (float)fp.boxCap, triCap = (float)fp.triCap;
     if (fp.debug == 0) {
@@ -1771,9 +1791,11 @@ __global__ __launch_bounds__(RT_BLOCK) void k_blend_frames(PathState ps, FramePa
     uint32_t gx, gy, krow;
     slot_to_pixel(fp, frame_slot(fp, 0u, slot), gx, gy, krow);
     const size_t px = (size_t)krow * fp.width + gx;
+    const uint32_t samples = pixel_samples(fp, px);
+    if (fp.sampleMap && samples == 0u) return;
     float4 c = rgba[px];
     for (uint32_t f = 0; f < fp.nFrames; f++) {
-        const rt_vec3 fin = blend_frame(fp, fp.frameCount + f, c, ps.accum()[frame_slot(fp, f, slot)]);
+        const rt_vec3 fin = blend_frame(fp, samples, fp.frameCount + f, c, ps.accum()[frame_slot(fp, f, slot)]);
         c = make_float4(fin.x, fin.y, fin.z, 1.f);
     }
     rgba[px] = c;
@@ -2172,6 +2194,67 @@ __global__ __launch_bounds__(RT_DN_BLOCK) void k_tp_accumulate_motion(TemporalFr
 #define RT_TP_MOTION 1
 #include "rt_temporal_body.hip.inc"
 #undef RT_TP_MOTION
+}
+
+// ---------------------------------------------------------------- sample counts from the temporal moments (rt_build_sample_map)
+// One lane per pixel, in k_tp_accumulate's block shape: a 16-byte load of the pixel's moments record (m1, m2, var, N), the rule of
+// rt_amd.h in fp32 in its stated order, a 4-byte store of the count, and per wave one reduction per statistic; the block's four
+// waves meet in LDS and one lane adds the block's sums to one of RT_SM_STRIPES copies of the statistics, each in a cache line of its
+// own (a 1080p frame is 32 400 waves: with an atomic per wave and statistic on one line the kernel took 1.8 ms, all of it waiting
+// for that line; k_shade's statistics are striped for the same reason). rt_sample_map_stats adds the copies up on the host.
+#define RT_SM_STRIPES 64u
+struct SampleMapStatsDev { unsigned long long samples; uint32_t pixels, unknown, aboveMin, atMax; unsigned long long pad[13]; };   // 128 bytes
+struct SampleMapArgs {
+    const float4* moments;
+    uint32_t* map;
+    SampleMapStatsDev* stats;   // [RT_SM_STRIPES], zero before the launch
+    uint32_t width, height;
+    uint32_t baseSamples, minSamples, maxSamples;
+    float targetRelError, luminanceFloor;
+};
+
+__global__ __launch_bounds__(RT_DN_BLOCK) void k_sample_map(SampleMapArgs a) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t x = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u), y = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
+    const bool inside = x < a.width && y < a.height;   // (no early return: the reductions below want the whole wave)
+    uint32_t n = 0u, unknown = 0u;
+    if (inside) {
+        const size_t p = (size_t)y * a.width + x;
+        const float4 m = a.moments[p];
+        const float N = m.w;
+        if (N == 0.f) {
+            n = a.minSamples;    // a kept pixel: a miss or an emitter, which the unjittered camera ray renders without noise
+        } else if (N > 0.f && N < 2.f) {
+            n = a.baseSamples;   // one frame: no variance yet
+            unknown = 1u;
+        } else {
+            const float d = rt_max(m.x, a.luminanceFloor);
+            const float den = (N * (a.targetRelError * a.targetRelError)) * (d * d);
+            const float q = ((float)a.baseSamples * m.z) / den;
+            // (a NaN q fails the first comparison: maxSamples; a q below 0, which no variance gives, counts as 0)
+            const uint32_t c = q < (float)a.maxSamples ? (q > 0.f ? (uint32_t)__builtin_ceilf(q) : 0u) : a.maxSamples;
+            n = max(a.minSamples, c);
+        }
+        a.map[p] = n;
+    }
+    const uint32_t wN = wave_sum_u32(n), wPix = wave_sum_u32(inside ? 1u : 0u), wUnknown = wave_sum_u32(unknown);
+    const uint32_t wAbove = wave_sum_u32(inside && n > a.minSamples ? 1u : 0u), wMax = wave_sum_u32(inside && n == a.maxSamples ? 1u : 0u);
+    __shared__ uint32_t s_sum[RT_DN_BLOCK / RT_WAVE][5];
+    if (lane == 0u) { s_sum[wave][0] = wN; s_sum[wave][1] = wPix; s_sum[wave][2] = wUnknown; s_sum[wave][3] = wAbove; s_sum[wave][4] = wMax; }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t t[5] = {0u, 0u, 0u, 0u, 0u};
+        for (uint32_t w = 0; w < RT_DN_BLOCK / RT_WAVE; w++)
+            for (int k = 0; k < 5; k++) t[k] += s_sum[w][k];
+        SampleMapStatsDev* const st = a.stats + ((blockIdx.y * gridDim.x + blockIdx.x) & (RT_SM_STRIPES - 1u));
+        if (t[1]) {
+            atomicAdd(&st->samples, (unsigned long long)t[0]);
+            atomicAdd(&st->pixels, t[1]);
+            if (t[2]) atomicAdd(&st->unknown, t[2]);
+            if (t[3]) atomicAdd(&st->aboveMin, t[3]);
+            if (t[4]) atomicAdd(&st->atMax, t[4]);
+        }
+    }
 }
 
 // ---------------------------------------------------------------- misc kernels

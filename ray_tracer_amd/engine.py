@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit,
-                    RtPlacement, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
+                    RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
 
@@ -223,13 +223,13 @@ class Renderer:
         self._scene = None
         self._shape = None
         self._aov_shape = None
-        self._first_hit_buf = (None, 0)   # device planes render_guides(first_hit=True) hands to rt_render_guides, and their bytes
+        self._owned = {}                  # device buffers of this module, by name: (pointer, bytes) (_device_buffer)
 
     def close(self):
         if getattr(self, "_h", None):
-            if self._first_hit_buf[0]:
-                _hip().hipFree(self._first_hit_buf[0])
-                self._first_hit_buf = (None, 0)
+            for p, _ in self._owned.values():
+                _hip().hipFree(p)
+            self._owned = {}
             self._l.rt_destroy(self._h)
             self._h = None
 
@@ -308,6 +308,88 @@ class Renderer:
             return None
         self.sync()
         return None if out_ptr else self.read_rgba()
+
+    def render_sampled(self, pc, width, height, sample_map, nFrames=1, row0=0, rowStride=1, nRows=None, out_ptr=None, sync=True):
+        """render_frames() with a sample count per pixel (rt_render_sampled): pixel p gets min(sample_map[p], S) samples, S being the
+        count render() would use, and comes out bit for bit as render_frames() gives it at that count; a pixel with 0 is not written
+        and costs nothing. `sample_map`: an (nRows, width) array of counts in the order of the rows rendered, or a device pointer (int)
+        to such a plane, as build_sample_map(to_host=False) returns it; None: render_frames()."""
+        if nRows is None:
+            nRows = (height - row0 + rowStride - 1) // rowStride
+        d_map = None
+        if sample_map is not None and not isinstance(sample_map, (int, np.integer)):
+            m = np.ascontiguousarray(sample_map, np.uint32)
+            if m.shape != (nRows, width):
+                raise ValueError(f"sample_map {m.shape}: not the ({nRows}, {width}) counts of the rows rendered")
+            self.sync()   # (a dispatch still in flight may be reading the buffer this one reuses)
+            d_map = self._device_buffer("sample_map_in", m.nbytes)
+            if m.nbytes and _hip().hipMemcpy(d_map, m.ctypes.data, m.nbytes, 1) != 0:   # hipMemcpyHostToDevice
+                raise RtError("render_sampled: the sample map could not be copied to the device")
+        elif sample_map is not None:
+            d_map = int(sample_map)
+        self.fill_counts(pc)
+        self._check(self._l.rt_render_sampled(self._h, C.byref(pc), width, height, row0, rowStride, nRows, int(nFrames),
+                                              C.c_void_p(d_map) if d_map else None, C.c_void_p(out_ptr) if out_ptr else None),
+                    "rt_render_sampled")
+        self._shape = (nRows, width, 4)
+        if not sync:
+            return None
+        self.sync()
+        return None if out_ptr else self.read_rgba()
+
+    def build_sample_map(self, moments=None, width=None, height=None, to_host=True, **params):
+        """Sample counts for render_sampled() from the moments of temporal_accumulate() (rt_build_sample_map; DESIGN.md, "Per-pixel
+        sample counts"). `moments`: the (H, W, 4) plane temporal_accumulate(moments=True) returns (through rt_build_sample_map_host),
+        or None: the context's own plane of the last temporal_accumulate() of its own frame. `params`: base_samples, min_samples,
+        max_samples, target_rel_error, luminance_floor (the library's defaults otherwise). Returns the (H, W) uint32 counts, or with
+        to_host=False (context's own moments only) the device pointer of a plane this renderer keeps until the next such call."""
+        p = RtSampleMapParams()
+        self._l.rt_sample_map_params_default(C.byref(p))
+        names = dict(base_samples="baseSamples", min_samples="minSamples", max_samples="maxSamples",
+                     target_rel_error="targetRelError", luminance_floor="luminanceFloor")
+        for k, v in params.items():
+            if k not in names:
+                raise TypeError(f"build_sample_map() got an unexpected parameter {k!r}")
+            setattr(p, names[k], v)
+        if moments is not None:
+            mom = np.ascontiguousarray(moments, np.float32)
+            H, W = mom.shape[:2]
+            if mom.shape != (H, W, 4):
+                raise ValueError(f"moments {mom.shape}: not an (H, W, 4) plane")
+            out = np.empty((H, W), np.uint32)
+            self._check(self._l.rt_build_sample_map_host(self._h, W, H, mom.ctypes.data, C.byref(p), out.ctypes.data), "rt_build_sample_map_host")
+            return out
+        H, W = (height, width) if width and height else (self._aov_shape or (0, 0))
+        self.sync()   # (the plane this call reuses may still be read by a render_sampled() in flight)
+        d_map = self._device_buffer("sample_map_out", max(H * W, 1) * 4)
+        self._check(self._l.rt_build_sample_map(self._h, W, H, None, C.byref(p), C.c_void_p(d_map)), "rt_build_sample_map")
+        if not to_host:
+            return d_map
+        self.sync()
+        out = np.empty((H, W), np.uint32)
+        if out.nbytes and _hip().hipMemcpy(out.ctypes.data, d_map, out.nbytes, 2) != 0:   # hipMemcpyDeviceToHost
+            raise RtError("build_sample_map: the map could not be copied back")
+        return out
+
+    def sample_map_stats(self):
+        """Of the last build_sample_map() (rt_sample_map_stats; blocks): samples, the sum of the counts; pixels; unknown, the pixels
+        without a variance yet; aboveMin and atMax, the pixels above min_samples and at max_samples."""
+        st = RtSampleMapStats()
+        self._check(self._l.rt_sample_map_stats(self._h, C.byref(st)), "rt_sample_map_stats")
+        return {n: getattr(st, n) for n, _ in RtSampleMapStats._fields_}
+
+    def _device_buffer(self, name, need):
+        """Device memory of at least `need` bytes under a name, kept between calls and freed with the renderer."""
+        p, have = self._owned.get(name, (None, 0))
+        if have < need:
+            if p:
+                _hip().hipFree(p)
+                del self._owned[name]
+            q = C.c_void_p()
+            if _hip().hipMalloc(C.byref(q), need) != 0 or not q.value:
+                raise RtError(f"no device memory for {need} bytes ({name})")
+            self._owned[name] = (q.value, need)
+        return self._owned[name][0]
 
     def run_compute(self, pc, width, height, frames=1, **tile):
         """Frame semantics of draw()/run_compute (src/vk_engine.cpp:1782,1812-1814); `tile` = row0 / rowStride / nRows
@@ -400,7 +482,8 @@ class Renderer:
         n = nRows * width
         first = None
         if first_hit:
-            first = RtAovBuffers(**{k: self._first_hit_planes(n) + i * n * 16 for i, k in enumerate(AOV_PLANES)})
+            d_first = self._device_buffer("first_hit", max(n, 1) * 16 * len(AOV_PLANES))   # what rt_render_guides fills beside the guides
+            first = RtAovBuffers(**{k: d_first + i * n * 16 for i, k in enumerate(AOV_PLANES)})
         self.fill_counts(pc)
         self._check(self._l.rt_render_guides(self._h, C.byref(pc), width, height, row0, rowStride, nRows, int(max_bounces), None,
                                              C.byref(first) if first is not None else None), "rt_render_guides")
@@ -416,20 +499,6 @@ class Renderer:
             if _hip().hipMemcpy(planes[k].ctypes.data, getattr(first, k), n * 16, 2) != 0:   # hipMemcpyDeviceToHost
                 raise RtError("render_guides: the first-hit planes could not be copied back")
         return g, aovs_to_numpy(planes)
-
-    def _first_hit_planes(self, n):
-        """Device memory for five planes of n pixels, kept between calls and freed with the renderer."""
-        p, have = self._first_hit_buf
-        need = max(n, 1) * 16 * len(AOV_PLANES)
-        if have < need:
-            if p:
-                _hip().hipFree(p)
-                self._first_hit_buf = (None, 0)
-            q = C.c_void_p()
-            if _hip().hipMalloc(C.byref(q), need) != 0 or not q.value:
-                raise RtError(f"render_guides: no device memory for {need} bytes of first-hit planes")
-            self._first_hit_buf = (q.value, need)
-        return self._first_hit_buf[0]
 
     def denoise(self, frame=None, aovs=None, iterations=5, sigma_luminance=4.0, sigma_normal=128.0, sigma_depth=1.0):
         """The edge-aware a-trous denoiser (rt_denoise; DESIGN.md, "Denoising") of a whole frame: an (H, W, 4) float32 array.

@@ -78,6 +78,10 @@ def build_parser():
                          "accumulate them through the temporal pass (Renderer.temporal_accumulate, defaults; DESIGN.md, \"Temporal "
                          "accumulation\") and write the result, through --denoise afterwards if given. One process only: the pass needs "
                          "the whole frame on one GPU")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="TAU",
+                    help="with --temporal-frames: frame 0 is uniform, every later frame gets a sample count per pixel from the moments "
+                         "so far (Renderer.build_sample_map with target relative error TAU, base --rays-per-pixel, 1 .. 4 x base; "
+                         "Renderer.render_sampled; DESIGN.md, \"Per-pixel sample counts\"); prints the map's statistics per frame")
     # Ray Tracer Info panel
     ap.add_argument("--progressive", action="store_true")
     ap.add_argument("--frames-in-flight", type=int, default=1,
@@ -179,6 +183,10 @@ def main(argv=None):
         raise SystemExit("--guide-bounces must be 0..8")
     if args.guide_bounces and not args.denoise:
         raise SystemExit("--guide-bounces guides the denoiser: it needs --denoise")
+    if args.adaptive is not None and not args.temporal_frames:
+        raise SystemExit("--adaptive takes its sample counts from the temporal pass: it needs --temporal-frames")
+    if args.adaptive is not None and not args.adaptive > 0:
+        raise SystemExit("--adaptive must be > 0")
     if args.temporal_frames and world > 1:   # before any rank waits for another
         raise SystemExit(f"--temporal-frames needs the whole frame on one GPU: launched on {world} ranks, run it as a single process")
     if world > 1:
@@ -212,12 +220,26 @@ def main(argv=None):
     if temporal:   # N independent frames of one camera, blended by the temporal pass instead of the progressive framebuffer
         pc.rayTraceParams.progressive, pc.rayTraceParams.singleRender = 0, 0
         aovs = r.render_aovs(pc, W, H)
+        base, d_map, spent = args.rays_per_pixel, None, 0
         for k in range(args.temporal_frames):
             pc.frameCount = k
-            r.render(pc, W, H, sync=False)
+            if d_map is None:
+                r.render(pc, W, H, sync=False)
+                spent += base * W * H
+            else:   # the frame's own count is the cap of the map's
+                pc.rayTraceParams.raysPerPixel = 4 * base
+                r.render_sampled(pc, W, H, d_map, sync=False)
+                pc.rayTraceParams.raysPerPixel = base
             img = r.temporal_accumulate(pc)
             frames += 1
-        r.totalSamples = args.temporal_frames * args.rays_per_pixel
+            if args.adaptive is not None and k + 1 < args.temporal_frames:
+                d_map = r.build_sample_map(to_host=False, base_samples=base, min_samples=min(1, base), max_samples=4 * base,
+                                           target_rel_error=args.adaptive)
+                st = r.sample_map_stats()
+                spent += st["samples"]
+                print(f"frame {k + 1}: sample map {st['samples']} samples over {st['pixels']} pixels ({st['samples'] / max(st['pixels'], 1):.2f} "
+                      f"per pixel), {st['unknown']} without a variance yet, {st['aboveMin']} above the minimum, {st['atMax']} at the maximum")
+        r.totalSamples = -(-spent // max(W * H, 1)) if args.adaptive is not None else args.temporal_frames * args.rays_per_pixel
         if args.denoise:
             img = r.denoise(img, r.render_guides(pc, W, H, args.guide_bounces) if args.guide_bounces else aovs)
     while not temporal:

@@ -17,7 +17,8 @@ from . import _capi, engine
 
 
 class InteractiveSession:
-    def __init__(self, renderer, scene, width, height, temporal=False, denoise=False, track_motion=False, mirror_guides=0):
+    def __init__(self, renderer, scene, width, height, temporal=False, denoise=False, track_motion=False, mirror_guides=0,
+                 adaptive=False, adaptive_params=None):
         """temporal: every draw() that dispatched also runs the first-hit AOV pass and, while the camera moves (progressive
         accumulation off), the temporal pass (Renderer.temporal_accumulate); `filtered` is the result, `history_length` its N
         plane, and `image` stays the raw frame. While the camera rests the reference's own progressive accumulation converges
@@ -28,7 +29,19 @@ class InteractiveSession:
         history follows moved objects and spheres (Renderer.temporal_track_motion), so set_object and set_sphere no longer reset
         it; set_material still does. mirror_guides: N > 0 guides the denoiser by the first surface that is no mirror along up to N
         reflections (Renderer.render_guides) instead of by the first hit; one pass then yields both those planes and the first-hit
-        planes, which the temporal pass keeps taking. 0: exactly as without it."""
+        planes, which the temporal pass keeps taking. 0: exactly as without it. adaptive (needs temporal): while the camera moves,
+        each draw() renders through Renderer.render_sampled with the counts Renderer.build_sample_map made of the previous draw()'s
+        moments (`sample_map`: the map this frame used, None for a uniform one), so the map is one frame late, in the previous
+        frame's pixel grid. params.raysPerPixel is the cap of every count: with raysPerPixel == base_samples the map can only take
+        samples away, so a caller who wants noisy pixels to get more sets params.raysPerPixel to max_samples (render.py --adaptive
+        renders with 4 x base). adaptive_params (build_sample_map's, min_samples >= 1 so
+        that no pixel keeps stale content) set the rest. False: exactly as without it."""
+        self.adaptive, self.adaptive_params = bool(adaptive), dict(adaptive_params or {})
+        if self.adaptive and not temporal:
+            raise ValueError("adaptive=True takes its sample counts from the temporal pass: it needs temporal=True")
+        if self.adaptive and self.adaptive_params.get("min_samples", 1) < 1:
+            raise ValueError("adaptive: min_samples must be >= 1 (a pixel without samples would keep the previous frame's content)")
+        self.sample_map, self._next_map, self.moments = None, None, None
         self.mirror_guides = int(mirror_guides)
         self.r, self.scene, self.W, self.H = renderer, scene, int(width), int(height)
         self.temporal, self.denoise = bool(temporal), bool(denoise)
@@ -103,7 +116,12 @@ class InteractiveSession:
         if self.totalSamples < self.params.sampleLimit:
             self._rotation()
             self.pc.frameCount = self._frameNumber
-            img = self.r.render(self.pc, self.W, self.H)            # run_compute: counts filled, one dispatch
+            # adaptive, camera moving: the counts the previous draw()'s moments gave
+            self.sample_map = self._next_map if self.adaptive and not self.params.progressive else None
+            if self.sample_map is not None:
+                img = self.r.render_sampled(self.pc, self.W, self.H, self.sample_map)
+            else:
+                img = self.r.render(self.pc, self.W, self.H)        # run_compute: counts filled, one dispatch
             self.image = img
             self.dispatches += 1
             if self.temporal or self.denoise:
@@ -128,6 +146,9 @@ class InteractiveSession:
             src = {} if first is None else dict(frame=img, aovs=first)   # (the guide pass leaves the context's own planes alone)
             out, mom = self.r.temporal_accumulate(self.pc, max_history=1 if still else 32, moments=True, **src)
             self.history_length = mom[..., 3]
+            self.moments = mom
+            if self.adaptive:
+                self._next_map = self.r.build_sample_map(mom, **self.adaptive_params)
             if still:
                 out = img
         self.filtered = self.r.denoise(out, aovs) if self.denoise else out

@@ -32,6 +32,13 @@ def max_rows(height, world):
     return (height + world - 1) // world
 
 
+def sample_map_rows(sample_map, rank, world):
+    """The rows of a whole-frame (H, W) sample map that `rank` renders, in its strip's order: what rank r of N hands to
+    rt_render_sampled with row0 = r, rowStride = N (numpy array or tensor; a contiguous copy)."""
+    rows = sample_map[rank::world]
+    return rows.contiguous() if hasattr(rows, "contiguous") else rows.copy()
+
+
 def gather_frame(strip, frame, height, world, rank, dst=0, force_collective=False):
     """Gather per-rank strips [(rows_r), W, 4] into frame [H, W, 4] on `dst`.
 
