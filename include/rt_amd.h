@@ -202,6 +202,14 @@ uint32_t rt_scene_texture_count(const rt_scene* s);
 const char* rt_scene_texture_path(const rt_scene* s, uint32_t i);
 int  rt_scene_add_texture(rt_scene* s, const char* path);
 int  rt_scene_set_material(rt_scene* s, uint32_t i, const RayMaterial* m);
+/* rt_update_points (below) on the scene's own arrays: replaces triPoints[first, first + count) and refits, by the same rule, the boxes
+ * of bvhNodes of every mesh that uses one of these points; triangles, leaf ranges and node numbering stay. rt_scene_get_arrays then
+ * describes what a context holds after the same rt_update_points: for the oracle, a later plain rt_upload_scene, the other ranks of
+ * a multi-GPU run. Refused with a message, the arrays untouched: a range past the point count; points NULL with count > 0; a
+ * position component that is not finite; and, of the scene itself (the builders make none of these): a mesh that shares BVH nodes
+ * with another mesh, a mesh whose triangles are not one contiguous range, a BVH child, leaf triangle or triangle point index out of
+ * range. count == 0 succeeds and changes nothing. */
+int  rt_scene_update_points(rt_scene* s, const TrianglePoint* points, uint32_t first, uint32_t count);
 /* index of a material loaded from an MTL file, key "<mtlpath>/<name>"; -1 if absent */
 int  rt_scene_find_material(const rt_scene* s, const char* key);
 /* BVH build statistics of the most recent build (printed by the reference, :1187-1193) */
@@ -276,6 +284,32 @@ int  rt_set_stream(rt_ctx* ctx, void* hipStream);
 /* copy_buffer x6 (src/vk_engine.cpp:686,753-757): takes the reference's AoS
  * host arrays, converts to the device layouts, uploads. Borrowed for the call. */
 int  rt_upload_scene(rt_ctx* ctx, const RtSceneArrays* scene);
+/* Deforming meshes in place ("Deforming meshes"). rt_upload_scene_dynamic does what rt_upload_scene does and keeps on the
+ * device what a later refit needs: a copy of triPoints, the triangles' {v0, v1, v2, frontOnly} and the refit plan (per mesh, i.e. per
+ * distinct bvhIndex: its leaves and its interior nodes level by level in the device numbering). Refused with a message, the context
+ * left as it was: a scene rt_upload_scene refuses; a mesh that shares BVH nodes with another mesh; a mesh whose triangles are not one
+ * contiguous range. It resets the temporal history as rt_upload_scene does.
+ * rt_update_points replaces triPoints[first, first + count) of the scene uploaded that way: positions, normals and both uv halves.
+ * Topology is kept (triangles, leaf ranges, node numbering, hot pairs); the boxes of every mesh that uses one of these points are
+ * refit bottom-up on the device. The rule: a leaf's box starts from the builder's sentinels (+1e30, -1e30) and grows by its triangles
+ * in order, corners v0, v1, v2, with the builder's comparisons (lo = p < lo ? p : lo, hi = hi < p ? p : hi); an interior node's box is
+ * its left child's grown by its right child's with the same comparisons. The builder gives every node the exact min / max of its
+ * triangles' vertices, so these are the boxes it would give this topology.
+ * Contract: when the call returns, every device table equals, byte for byte, what rt_upload_scene would upload for the same arrays
+ * with the points replaced and the boxes of bvhNodes refit by the rule (rt_scene_update_points makes exactly those arrays): nodes,
+ * the interleaved pairs, triangle positions / normals / uvs, and through the roots' boxes the padded world boxes, the mask boxes, the
+ * object hierarchy, the origin limit of the skipping code and the emitter list's triangles. Every entry point reads those tables.
+ * The measured ray cost, the textures and the tuning stay. Synchronous, like rt_upload_scene. The temporal history is not reset:
+ * with rt_temporal_track_motion on, every object whose mesh was refit since the last rt_temporal_accumulate has no history in the
+ * next one (RT_MOTION_REPLACED, counted in replacedObjects); with it off the pass takes the scene to be static, as after an
+ * rt_update_objects: call rt_temporal_reset.
+ * What a refit does not do: it keeps the topology the builder chose for the old shape. Under large deformations the boxes overlap
+ * more and rays test more of them (boxTests per ray in rt_get_counters shows it); the cure is a rebuild and rt_upload_scene_dynamic.
+ * Refused with a message before anything is written: a scene not uploaded with rt_upload_scene_dynamic; a range that runs past the
+ * point count; points NULL with count > 0; a position component that is not finite (the builder's comparisons and the kernels'
+ * treat NaN differently). count == 0 succeeds and does nothing. */
+int  rt_upload_scene_dynamic(rt_ctx* ctx, const RtSceneArrays* scene);
+int  rt_update_points(rt_ctx* ctx, const TrianglePoint* points, uint32_t first, uint32_t count);
 /* Textures (bindings raytrace.comp:122,148, upload src/vk_textures.cpp:103-200). Slot i of the scene's texture
  * table, as R8G8B8A8_SRGB texels, rows top to bottom (what stbi_load(..., STBI_rgb_alpha) returns). The snapshot's shader
  * computes hit.uv (raytrace.comp:249-256) and never samples; the semantics here are this build's declared choice

@@ -141,6 +141,7 @@ SYMBOLS = {
     "rt_scene_texture_path": (C.c_char_p, [_vp, C.c_uint32]),
     "rt_scene_add_texture": (C.c_int, [_vp, C.c_char_p]),
     "rt_scene_set_material": (C.c_int, [_vp, C.c_uint32, _P(RayMaterial)]),
+    "rt_scene_update_points": (C.c_int, [_vp, _P(TrianglePoint), C.c_uint32, C.c_uint32]),
     "rt_scene_find_material": (C.c_int, [_vp, C.c_char_p]),
     "rt_scene_last_bvh_stats": (C.c_int, [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
     "rt_scene_set_bvh_hook": (C.c_int, [_vp, _vp, _vp]),
@@ -153,6 +154,8 @@ SYMBOLS = {
     "rt_last_error": (C.c_char_p, [_vp]),
     "rt_set_stream": (C.c_int, [_vp, _vp]),
     "rt_upload_scene": (C.c_int, [_vp, _P(RtSceneArrays)]),
+    "rt_upload_scene_dynamic": (C.c_int, [_vp, _P(RtSceneArrays)]),
+    "rt_update_points": (C.c_int, [_vp, _P(TrianglePoint), C.c_uint32, C.c_uint32]),
     "rt_upload_textures": (C.c_int, [_vp, _P(RtTexture), C.c_uint32]),
     "rt_update_materials": (C.c_int, [_vp, _P(RayMaterial), C.c_uint32]),
     "rt_update_spheres": (C.c_int, [_vp, _P(Sphere), C.c_uint32]),

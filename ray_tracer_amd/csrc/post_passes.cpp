@@ -183,6 +183,12 @@ void TemporalHistory::set_object_placements(const float4* fwd, const float4* inv
 
 void TemporalHistory::set_sphere_placements(const float4* spheres, uint32_t n) { now.spheres.assign(spheres, spheres + n); }
 
+void TemporalHistory::meshes_refit(const uint32_t* bvhIndex, uint32_t n) {
+    for (uint32_t& b : snap.bvhIndex)
+        for (uint32_t k = 0; k < n; k++)
+            if (b == bvhIndex[k]) b = 0xffffffffu;
+}
+
 TemporalHistory::Step TemporalHistory::begin(uint32_t w, uint32_t h, bool historyBuffersFit) {
     if (width != w || height != h || !historyBuffersFit) reset();   // a history of another size is none, nor is one whose buffer was replaced
     width = w; height = h;   // (here and not in commit: after the reset above, the history still valid at this point has this size)

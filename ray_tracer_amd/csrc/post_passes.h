@@ -119,6 +119,9 @@ public:
     // (set_objects); every sphere's {centre, radius} (set_spheres)
     void set_object_placements(const float4* fwd, const float4* inv, const uint32_t* bvhIndex, uint32_t n);
     void set_sphere_placements(const float4* spheres, uint32_t n);
+    // rt_update_points refit these meshes (bvhIndex values): in the snapshot the objects that show them get a bvhIndex no mesh has,
+    // so the next begin finds "another mesh" there (RT_MOTION_REPLACED: no history); the commit after it takes the true ones again
+    void meshes_refit(const uint32_t* bvhIndex, uint32_t n);
     // An accepted call, once its buffers exist. historyBuffersFit: neither history buffer had to be (re)allocated for this size.
     // Drops a history of another size or of a replaced buffer, then records the size: a begin without a commit (a failed upload
     // or launch) leaves the old history valid only where it has this very size, and it was not written to.

@@ -712,6 +712,14 @@ int rt_scene_get_arrays(const rt_scene* s, RtSceneArrays* out) {
     return 0;
 }
 
+}  // extern "C"
+
+// for rt_scene_update_points, which lives with the refit rule (mesh_refit.cpp): the scene's own vectors, and its error string
+RtSceneHost* rt_scene_host(rt_scene* s) { return s; }
+int rt_scene_fail(rt_scene* s, const char* message) { return s->fail(message); }
+
+extern "C" {
+
 uint32_t rt_scene_texture_count(const rt_scene* s) { return s ? (uint32_t)s->texturePaths.size() : 0u; }
 
 const char* rt_scene_texture_path(const rt_scene* s, uint32_t i) {

@@ -29,6 +29,14 @@ struct RtSceneHost {
     float sceneHi[3] = {-1e30f, -1e30f, -1e30f};
     std::unordered_map<std::string, int> loadedObjects;
     std::unordered_map<std::string, int> loadedMaterials;
+    // rt_scene_update_points' list of meshes (mesh_refit.cpp: five words per mesh), valid while the four array sizes it was made
+    // for still hold: geometry is only ever added to a scene
+    std::vector<uint32_t> refitMeshes;
+    size_t refitMeshesFor[4] = {0, 0, 0, 0};   // bvhNodes, triangles, objects, triPoints
     // statistics of the last build_bvh (src/vk_engine.cpp:1187-1193)
     uint32_t statNodeCount = 0, statMaxDepth = 0, statMinDepth = 0xffffffffu, statMaxTri = 0;
 };
+
+// what another unit of the scene half may touch of an rt_scene (scene.cpp): its vectors, and its error string (returns -1)
+RtSceneHost* rt_scene_host(rt_scene* s);
+int rt_scene_fail(rt_scene* s, const char* message);

@@ -81,6 +81,16 @@ def push_constants(width, height, **params):
     return pc
 
 
+def _points_arg(points):
+    """An (n, 8) float32 array (position.xyz, u, normal.xyz, v per point) or a ctypes array of TrianglePoint -> (pointer, n, keep-alive)."""
+    if isinstance(points, C.Array) and points._type_ is TrianglePoint:
+        return C.cast(points, C.POINTER(TrianglePoint)), len(points), points
+    a = np.ascontiguousarray(points, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError(f"points {a.shape}: not an (n, 8) float32 array of TrianglePoint records")
+    return C.cast(a.ctypes.data, C.POINTER(TrianglePoint)), a.shape[0], a
+
+
 class Scene:
     """The reference's CPU-side scene: spheres, rayMaterials, triPoints,
     triangles, objects, bvhNodes (src/vk_engine.h:270-283)."""
@@ -162,6 +172,18 @@ class Scene:
     def set_material(self, i, m):
         self._check(self._l.rt_scene_set_material(self._h, int(i), C.byref(m)), "set_material")
 
+    def update_points(self, points, first=0):
+        """Replaces triPoints[first, first + n) and refits the BVH boxes of the meshes that use them, topology kept
+        (rt_scene_update_points): what Renderer.update_points does to the device tables, on this scene's own arrays. `points`: an
+        (n, 8) float32 array (position.xyz, u, normal.xyz, v per point) or a ctypes array of TrianglePoint."""
+        p, n, _keep = _points_arg(points)
+        self._check(self._l.rt_scene_update_points(self._h, p, int(first), n), "rt_scene_update_points")
+
+    def points(self):
+        """triPoints as an (n, 8) float32 array (copied): position.xyz, u, normal.xyz, v."""
+        a = self.arrays()
+        return self._view(a.triPoints, a.triPointCount, TrianglePoint).copy().view(np.float32).reshape(-1, 8)
+
     def material(self, i):
         a = self.arrays()
         m = RayMaterial()
@@ -242,11 +264,23 @@ class Renderer:
     def set_stream(self, hip_stream_ptr):
         self._check(self._l.rt_set_stream(self._h, C.c_void_p(hip_stream_ptr)), "rt_set_stream")
 
-    def upload_scene(self, scene):
+    def upload_scene(self, scene, dynamic=False):
+        """rt_upload_scene; with `dynamic` rt_upload_scene_dynamic, which also keeps on the device what update_points() needs."""
         a = scene.arrays()
-        self._check(self._l.rt_upload_scene(self._h, C.byref(a)), "rt_upload_scene")
+        if dynamic:
+            self._check(self._l.rt_upload_scene_dynamic(self._h, C.byref(a)), "rt_upload_scene_dynamic")
+        else:
+            self._check(self._l.rt_upload_scene(self._h, C.byref(a)), "rt_upload_scene")
         self._scene = scene
         self._counts = scene.counts()
+
+    def update_points(self, points, first=0):
+        """Deforms the uploaded meshes in place (rt_update_points; DESIGN.md, "Deforming meshes"): replaces triPoints[first, first + n)
+        of a scene uploaded with upload_scene(dynamic=True) and refits the BVH boxes on the device, topology kept. Blocks. `points`:
+        an (n, 8) float32 array (position.xyz, u, normal.xyz, v per point) or a ctypes array of TrianglePoint. The host scene is not
+        touched: Scene.update_points does the same there (InteractiveSession.update_points calls both)."""
+        p, n, _keep = _points_arg(points)
+        self._check(self._l.rt_update_points(self._h, p, int(first), n), "rt_update_points")
 
     def upload_textures(self, images):
         """The scene's texture table: a list of uint8 arrays [h, w, 4] in slot order (rt_upload_textures); [] removes it."""

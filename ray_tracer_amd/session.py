@@ -18,8 +18,9 @@ from . import _capi, engine
 
 class InteractiveSession:
     def __init__(self, renderer, scene, width, height, temporal=False, denoise=False, track_motion=False, mirror_guides=0,
-                 adaptive=False, adaptive_params=None):
-        """temporal: every draw() that dispatched also runs the first-hit AOV pass and, while the camera moves (progressive
+                 adaptive=False, adaptive_params=None, dynamic=False):
+        """dynamic: the scene is uploaded with Renderer.upload_scene(dynamic=True), so that update_points can deform its meshes.
+        temporal: every draw() that dispatched also runs the first-hit AOV pass and, while the camera moves (progressive
         accumulation off), the temporal pass (Renderer.temporal_accumulate); `filtered` is the result, `history_length` its N
         plane, and `image` stays the raw frame. While the camera rests the reference's own progressive accumulation converges
         and nothing is blended: `filtered` is the progressive framebuffer. The pass only records that frame (max_history = 1
@@ -57,7 +58,11 @@ class InteractiveSession:
         self.frameTime = 0.0                                       # renderStats.frameTime, milliseconds (:1900-1902)
         self.image = None
         self.dispatches = 0
-        renderer.upload_scene(scene)
+        self.dynamic = bool(dynamic)
+        if self.dynamic:
+            renderer.upload_scene(scene, dynamic=True)
+        else:
+            renderer.upload_scene(scene)
         renderer.clear_framebuffer()
         if self.temporal:
             renderer.temporal_track_motion(self.track_motion)
@@ -194,6 +199,19 @@ class InteractiveSession:
         if samplerIndex is not None:
             a.objects[i].samplerIndex = int(samplerIndex)
         self.r._check(self.r._l.rt_update_objects(self.r._h, a.objects, a.nObjects), "rt_update_objects")
+        if self.temporal and not self.track_motion:
+            self.r.temporal_reset()
+
+    def update_points(self, points, first=0):
+        """Deforms meshes in place (needs dynamic=True): new triPoints[first, first + n) on the device (Renderer.update_points: the
+        BVH boxes are refit there, topology kept) and in the session's scene (Scene.update_points), so that arrays() keeps describing
+        what the device holds. Both halves refuse the same arguments and the scene goes first, so a refused update changes neither.
+        With track_motion the temporal history drops only the pixels of the objects whose mesh was refit; without it the history
+        is reset, as for set_object."""
+        if not self.dynamic:
+            raise engine.RtError("update_points: the session was not created with dynamic=True")
+        self.scene.update_points(points, first)
+        self.r.update_points(points, first)
         if self.temporal and not self.track_motion:
             self.r.temporal_reset()
 
