@@ -613,6 +613,13 @@ int  rt_get_trace_busy_ms(rt_ctx* ctx, double* msOut);
  *                    The parts only overlap while their streams sit on different hardware queues: ROCm deals a process's
  *                    streams onto GPU_MAX_HW_QUEUES queues (default 4); a host with many streams of its own should start
  *                    with that variable raised (bench.py sets 8)
+ *   "wide_min_kslots"  multi-kernel pipeline: a dispatch of at least this many x 1024 paths whose traversal kernel would be
+ *                    k_trace_pw<20, .., 144, 5> (a BVH 17..20 levels deep, the top-level table of "hot_pairs" 2, no placed
+ *                    objects, no heat map) runs it in work-groups of 768 threads, two per CU: six waves per SIMD instead of
+ *                    five and all 192 top-level pairs in LDS (k_trace_pw_wide). Default 1024 (1 M paths, the size at which
+ *                    a dispatch goes into parts); 0 = always; more than a dispatch can have = never
+ *   "wide_grid_pct"  ... and the share of the resident wide work-groups each part's launch takes while "lane_grid_pct" is 0
+ *                    (10..100, default 40; 0 = the parts' share as it is)
  *   "trace_variant"  0 = one ray per lane (k_trace), 1 = persistent waves (k_trace_pw)
  *   "refill", "mk_refill", "chunk", "w_setup", "w_leaf", "fast_lanes", "lds_stack", "blocks_per_cu",
  *   "tile_slots", "phase_stats": traversal scheduling details, see DESIGN.md
@@ -629,7 +636,7 @@ int  rt_get_trace_busy_ms(rt_ctx* ctx, double* msOut);
  *                    the fixed cost per block, in pixel units, that the chooser assumes) */
 int  rt_set_tuning(rt_ctx* ctx, const char* key, int value);
 /* The traversal kernel instantiation the last launch used, spelled as a demangler prints it ("k_trace_pw<20, false, false,
- * false, false, 144, 5>", "k_render_fused<24, false, false, true>"): tests/test_instantiations.py forces every instantiation in
+ * false, false, 144, 5>", "k_trace_pw_wide<20, 192, 768>", "k_render_fused<24, false, false, true>"): tests/test_instantiations.py forces every instantiation in
  * the library and compares it with the oracle. The string lives in the context. */
 const char* rt_last_kernel(const rt_ctx* ctx);
 /* parts (streams) the last dispatch of the multi-kernel pipeline ran in ("lanes") */

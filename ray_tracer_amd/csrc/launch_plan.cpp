@@ -40,6 +40,8 @@ TuningChange set_tuning(Tuning& t, const std::string& k, int value) {
     else if (k == "lanes") { if (value < 0 || value > RT_MAX_LANES) return refuse("lanes: 1..4 (parts of a multi-kernel dispatch, each on its own stream), 0 = automatic"); t.lanes = value ? value : 3; t.lanesSet = value != 0; }
     else if (k == "lane_grid_pct") { if (value != 0 && (value < 10 || value > 100)) return refuse("lane_grid_pct: 0 (by size) or 10..100"); t.laneGridPct = value; }
     else if (k == "lanes_min_kslots") { if (value < 0) return refuse("lanes_min_kslots >= 0"); t.lanesMinSlots = (uint32_t)value << 10; }
+    else if (k == "wide_min_kslots") { if (value < 0) return refuse("wide_min_kslots >= 0"); t.wideMinSlots = (uint64_t)value << 10; }
+    else if (k == "wide_grid_pct") { if (value != 0 && (value < 10 || value > 100)) return refuse("wide_grid_pct: 0 (the parts' share) or 10..100"); t.wideGridPct = value; }
     else if (k == "blocks_per_cu") { if (value < 0 || value > 8) return refuse("blocks_per_cu: 0..8"); t.blocksPerCU = value; }
     else return refuse("unknown tuning key " + k);
     return TuningChange{};
@@ -193,6 +195,11 @@ KernelKey trace_kernel_key(const Tuning& t, const SceneFacts& sc, const Dispatch
     int hotMode = tableWanted ? t.hotPairs : 0;
     if (hotMode == 1 && h6 == 0) hotMode = 2;   // (a 24-entry stack leaves no room at six work-groups)
     if (hotMode == 2 && h5 == 0) hotMode = h6 ? 1 : 0;   // (overflow-stack instantiations: the table only beside 16-entry stacks)
+    // A big dispatch of a scene whose kernel would be <20, .., 144, 5>: work-groups of RT_WIDE_THREADS threads, RT_WIDE_GROUPS per CU. That
+    // is the sixth wave per SIMD of hot_pairs 1 and, with two copies of the table per CU instead of five, all RT_WIDE_HOT pairs
+    // beside them. Small dispatches keep the 256-thread groups (a grid of few, coarse groups fills the device unevenly).
+    if (hotMode == 2 && b.stack == 20 && !b.ovf && !sc.cull && dispatch_slots(d.nPixels, d.nFrames) >= t.wideMinSlots)
+        return KernelKey{KernelFamily::trace_pw, 20, false, false, false, false, RT_WIDE_HOT, RT_WIDE_GROUPS, RT_WIDE_THREADS};
     if (hotMode == 1) return KernelKey{KernelFamily::trace_pw, b.stack, b.ovf, false, false, sc.cull, h6, 6};
     if (hotMode == 2) return KernelKey{KernelFamily::trace_pw, b.stack, b.ovf, false, false, sc.cull, h5, 5};
     if (d.phaseStats) return KernelKey{KernelFamily::trace_pw, b.stack, b.ovf, true, true, sc.cull, 0, 6};
@@ -209,7 +216,12 @@ KernelKey fused_kernel_key(const Tuning& t, const SceneFacts& sc, const Dispatch
 TraceShape trace_shape(const Tuning& t, const Measured& m, const SceneFacts& sc, const DispatchFacts& d, uint32_t maxRays, uint32_t resident) {
     TraceShape s;
     // a part of a dispatch that runs beside the other parts' launches takes its share of the resident work-groups (DispatchFacts::gridPct)
-    s.blocks = std::min((maxRays + RT_BLOCK - 1) / RT_BLOCK, std::max(1u, (uint32_t)((uint64_t)resident * (uint32_t)d.gridPct / 100u)));
+    // (a work-group per groupThreads rays: 256, or the wide kernel's)
+    const uint32_t threads = std::max(d.groupThreads, (uint32_t)RT_WAVE);
+    // wide work-groups beside the other parts' launches: their own share (Tuning::wideGridPct), unless lane_grid_pct was set by hand
+    const bool wideInParts = threads != RT_BLOCK && d.gridPct < 100 && t.laneGridPct == 0 && t.wideGridPct > 0;
+    const uint32_t pct = wideInParts ? (uint32_t)t.wideGridPct : (uint32_t)d.gridPct;
+    s.blocks = std::min((uint32_t)(((uint64_t)maxRays + threads - 1) / threads), std::max(1u, (uint32_t)((uint64_t)resident * pct / 100u)));
     const bool times = d.phaseStats == 1 || (d.phaseStats >= 2 && d.counted && d.launches == (uint64_t)(d.phaseStats - 2));  // 1: the last launch's waves; 2 + k: launch k's (after rt_reset_counters)
     s.waveTimes = !(sc.mapFlags & RT_MAP_ALPHA) && times;
     // Long rays (the measure the pipeline choice uses) want new rays sooner and their set-up served later: idle lanes re-armed at 12

@@ -11,6 +11,18 @@
 #define RT_WAVE 64
 #define RT_BLOCK 256
 #define RT_MAX_LANES 4
+// the wide work-group of the persistent-wave traversal (k_trace_pw_wide, KernelKey::threads): RT_WIDE_GROUPS groups of RT_WIDE_THREADS
+// threads per CU are six waves per SIMD, and the two of them share the LDS with two copies of the top-level table instead of five
+// or six: all RT_WIDE_HOT = RT_HOT_PAIRS pairs fit beside 21-entry stacks (the static_assert beside hot5 / hot6)
+#ifndef RT_WIDE_THREADS
+#define RT_WIDE_THREADS 768
+#endif
+#ifndef RT_WIDE_GROUPS
+#define RT_WIDE_GROUPS 2
+#endif
+#ifndef RT_WIDE_HOT
+#define RT_WIDE_HOT 192
+#endif
 #define RT_FRAMES_MAX_SLOTS (24ull << 20)   // default for the paths of one multi-frame dispatch (ten 1080p frames or three 4K frames: 5.8 GB of path state)
 
 // ---------------------------------------------------------------- tuning: what rt_set_tuning writes, each "given explicitly" flag beside the knob it qualifies
@@ -23,6 +35,12 @@ struct Tuning {
     int lanes = 3;                        // rt_set_tuning("lanes", 1..RT_MAX_LANES)
     bool lanesSet = false;                // "lanes" given explicitly: no automatic fall-back to one part
     uint32_t lanesMinSlots = 1u << 20;    // dispatches of fewer paths than this stay in one part
+    uint64_t wideMinSlots = 1u << 20;     // rt_set_tuning("wide_min_kslots"): dispatches of at least this many paths run the 20-entry, table-carrying traversal in wide
+                                          // work-groups (k_trace_pw_wide; trace_kernel_key). 0 = always, more than a dispatch can have = never. The default is
+                                          // lanesMinSlots: the dispatches that go into parts
+    int wideGridPct = 40;                 // rt_set_tuning("wide_grid_pct"): the share of the resident WIDE work-groups a launch takes while a dispatch runs in several
+                                          // parts and lane_grid_pct is automatic (0 = the parts' share as it is). Three parts of 6.9 M paths: 67.3 ms per step at 40,
+                                          // 69.5 at 50, 72.5 at 60, 67.7 at 37, 72.4 at 30 (profiles/README.md, Round 6); the 256-thread groups keep their 50
     int laneGridPct = 0;                  // rt_set_tuning("lane_grid_pct"): share of the resident work-groups a k_trace_pw launch takes while a dispatch runs in several parts (0 = by the parts' size: 50, 40 below 1.2 M paths per part)
     int traceVariant = 1;   // 0 = one-ray-per-lane k_trace, 1 = persistent waves k_trace_pw
     int pipeline = -1;      // 0 = multi-kernel wavefront pipeline, 1 = wave-private fused pipeline (k_render_fused), -1 = by tile size
@@ -48,6 +66,7 @@ struct Tuning {
     int scatter = -1;       // fused pipeline: blocks made of chunks of this many slots from all over the tile; 0 = neighbouring pixels; -1 = auto
     int hotPairs = 2;       // k_trace_pw: child pairs of the meshes' top levels from LDS. 0 = off, 1 = as many as fit beside the stacks of
                             // six work-groups per CU, 2 = of five (Sponza, 21-entry stacks, ten frames in flight: 90.4 / 90.6 / 88.7 ms per step)
+                            // — or, for a 20-entry stack in a big dispatch, all of them beside two wide work-groups (wideMinSlots)
     int pixelRefill = 0;    // fused pipeline: free lanes at which a wave reserves new pixels (64 = a block at a time, 0 = by ray length)
     int batchPixels = 0;    // fused pipeline: pixels per wave-private block (0 = chosen per launch)
     int batchFixed = 80;    // ... and the fixed part of a block's cost in the chooser, in pixel units
@@ -88,6 +107,7 @@ struct DispatchFacts {
     int pipeline = -1;       // "pipeline" as it holds for this dispatch
     bool probe = false;      // the ray-cost probe itself
     int gridPct = 100;       // share of the resident work-groups a k_trace_pw launch of this part takes
+    uint32_t groupThreads = RT_BLOCK;  // threads of a work-group of the launch's kernel (KernelKey::threads; trace_shape)
     bool counted = false;    // its traversal launches are counted ...
     uint64_t launches = 0;   // ... and this many have been so far (phase_stats >= 2)
 };
@@ -115,18 +135,26 @@ uint32_t frames_per_dispatch(const Tuning& t, uint64_t framePixels, uint32_t nFr
 // The traversal kernel of a launch, by its template arguments. stack and ovf always say what the kernel's stack is (the overflow
 // buffer is sized by them); the other arguments stay 0 / false where a family does not have them. rt_device.hip turns a key into
 // the instantiation's address and name; a key it has no instantiation for is an error there.
+// blocks: the work-groups per CU the kernel is built for; threads: those of one work-group. RT_BLOCK everywhere but in the wide
+// traversal kernel (family trace_pw with threads == RT_WIDE_THREADS: k_trace_pw_wide<stack, hot, threads>, blocks == RT_WIDE_GROUPS).
 enum class KernelFamily { trace, trace_pw, trace_pw_alpha, render_fused, render_fused_maps };
 struct KernelKey {
     KernelFamily family;
     int stack;
     bool ovf, pix, stats, cull;
     int hot, blocks;
+    int threads = RT_BLOCK;
 };
 // top-level pairs from LDS (k_trace_pw<HOT>): what 160 KB of LDS per CU leave beside the stacks. hot_pairs 1: six work-groups
 // per CU, 2: five (more pairs, no spills at 96 registers)
 // (the overflow-stack kernel with 16 entries in LDS keeps six work-groups AND 120 pairs: deep BVHs, see trace_kernel_key)
 constexpr int hot6(int stack, bool ovf) { return ovf ? (stack == 16 ? 120 : 0) : stack == 8 ? 192 : stack == 16 ? 136 : stack == 20 ? 72 : 0; }
 constexpr int hot5(int stack, bool ovf) { return ovf ? 0 : stack == 24 ? 80 : stack == 20 ? 144 : 192; }
+// the wide kernel's LDS: per work-group the 21-entry stacks of its threads (+1: pushes are unconditional), 1 KB of object metadata
+// (RT_META_LDS) and the table, 64 B a pair; RT_WIDE_GROUPS of them in a CU's 160 KB
+constexpr uint32_t wide_group_lds(int stack, int hot, int threads) { return (uint32_t)threads * (uint32_t)(stack + 1) * 4u + 1024u + (uint32_t)hot * 64u; }
+static_assert(RT_WIDE_GROUPS * wide_group_lds(20, RT_WIDE_HOT, RT_WIDE_THREADS) <= 160u * 1024u, "the wide work-groups of a CU and their tables fit its LDS");
+static_assert(RT_WIDE_THREADS % RT_WAVE == 0 && RT_WIDE_THREADS <= 1024 && RT_WIDE_GROUPS * RT_WIDE_THREADS == 6 * 4 * RT_WAVE, "six waves per SIMD in whole work-groups");
 KernelKey trace_kernel_key(const Tuning& t, const SceneFacts& s, const DispatchFacts& d);   // a traversal launch of the multi-kernel pipeline, rt_trace_rays or an AOV pass
 KernelKey fused_kernel_key(const Tuning& t, const SceneFacts& s, const DispatchFacts& d);   // the fused pipeline's one launch
 

@@ -245,10 +245,11 @@ struct Dispatch {
     uint32_t* counts;    // the part's counter block
     int part;            // which overflow buffer
     int gridPct;         // share of the resident work-groups a k_trace_pw launch of this part takes
+    uint32_t slots;      // the paths of the whole dispatch, all its parts together (0: a pass that is not a dispatch of paths)
 };
 // A dispatch in one part: the ctx stream, the first counter block (which ensure_state makes), the whole grid
 Dispatch one_part(rt_ctx* c, const DevScene& sc, bool pixStats) {
-    return Dispatch{sc, pixStats, c->tune.phaseStats, c->tune.pipeline, c->profiling, false, &c->rep.traceLaunchesTotal, c->stream, c->q.counts, 0, 100};
+    return Dispatch{sc, pixStats, c->tune.phaseStats, c->tune.pipeline, c->profiling, false, &c->rep.traceLaunchesTotal, c->stream, c->q.counts, 0, 100, 0};
 }
 
 // The facts the launch plan asks for (launch_plan.h), gathered from the context and the dispatch. fp: the dispatch's frame (the
@@ -288,6 +289,10 @@ template <int STACK, bool OVF, bool PIX, bool STATS, bool CULL, int HOT = 0, int
 TracePwChoice trace_pw_kernel() {
     return kernel_choice(k_trace_pw<STACK, OVF, PIX, STATS, CULL, HOT, BLOCKS>, k_trace_pw<STACK, OVF, false, false, CULL, HOT, BLOCKS>,
                          "k_trace_pw<%d, %s, %s, %s, %s, %d, %d>", STACK, tf(OVF), tf(PIX), tf(STATS), tf(CULL), HOT, BLOCKS);
+}
+template <int STACK, int HOT, int THREADS>
+TracePwChoice trace_pw_wide_kernel() {
+    return kernel_choice(k_trace_pw_wide<STACK, HOT, THREADS>, k_trace_pw_wide<STACK, HOT, THREADS>, "k_trace_pw_wide<%d, %d, %d>", STACK, HOT, THREADS);
 }
 template <int STACK, bool OVF, bool PIX, bool CULL>
 FusedChoice fused_kernel() {
@@ -345,6 +350,10 @@ TracePwChoice trace_pw_choice(const KernelKey& k) {
     if (k.family == KernelFamily::trace_pw_alpha)
         return kernel_choice(k.pix ? k_trace_pw_alpha<true> : k_trace_pw_alpha<false>, k_trace_pw_alpha<false>, "k_trace_pw_alpha<%s>", tf(k.pix));
     if (k.family != KernelFamily::trace_pw) return {};
+    if (k.threads != RT_BLOCK) {  // wide work-groups: the one instantiation there is
+        if (k.threads != RT_WIDE_THREADS || k.stack != 20 || k.ovf || k.pix || k.stats || k.cull || k.hot != RT_WIDE_HOT || k.blocks != RT_WIDE_GROUPS) return {};
+        return trace_pw_wide_kernel<20, RT_WIDE_HOT, RT_WIDE_THREADS>();
+    }
     return with_stack<true>(k, [&](auto S, auto O, auto C) { return trace_pw_of<S, O, C>(k); });
 }
 FusedChoice fused_choice(const KernelKey& k) {
@@ -355,15 +364,16 @@ FusedChoice fused_choice(const KernelKey& k) {
 }
 int no_kernel(rt_ctx* c, const KernelKey& k) {
     char m[160];
-    snprintf(m, sizeof m, "the launch plan asks for a kernel the library does not hold: family %d <stack %d, ovf %d, pix %d, stats %d, cull %d, hot %d, blocks %d>",
-             (int)k.family, k.stack, (int)k.ovf, (int)k.pix, (int)k.stats, (int)k.cull, k.hot, k.blocks);
+    snprintf(m, sizeof m, "the launch plan asks for a kernel the library does not hold: family %d <stack %d, ovf %d, pix %d, stats %d, cull %d, hot %d, blocks %d, threads %d>",
+             (int)k.family, k.stack, (int)k.ovf, (int)k.pix, (int)k.stats, (int)k.cull, k.hot, k.blocks, k.threads);
     return c->fail(m);
 }
 
+// threads: those of a work-group of the kernel (KernelKey::threads)
 template <typename K>
-uint32_t resident_blocks(const rt_ctx* c, K kernel) {
+uint32_t resident_blocks(const rt_ctx* c, K kernel, int threads = RT_BLOCK) {
     int perCU = c->tune.blocksPerCU;
-    if (perCU <= 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, RT_BLOCK, 0) != hipSuccess || perCU <= 0)) perCU = 4;
+    if (perCU <= 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, threads, 0) != hipSuccess || perCU <= 0)) perCU = std::max(1, 4 * RT_BLOCK / threads);
     return (uint32_t)perCU * (uint32_t)c->numCUs;
 }
 
@@ -373,14 +383,14 @@ int overflow_buf(rt_ctx* c, const Dispatch& d, const KernelKey& k, uint32_t resi
     *out = nullptr;
     if (!k.ovf || c->maxLeafDepth <= (uint32_t)k.stack) return 0;
     DevBuf& ob = c->overflowBuf[d.part];
-    int rc = dev_alloc(c, ob, (size_t)(c->maxLeafDepth - k.stack) * resident * RT_BLOCK * 4);
+    int rc = dev_alloc(c, ob, (size_t)(c->maxLeafDepth - k.stack) * resident * (size_t)k.threads * 4);
     if (rc) return rc;
     *out = (uint32_t*)ob.p;
     return 0;
 }
 
-int wave_time_buf(rt_ctx* c, uint32_t blocks, unsigned long long** out) {
-    c->rep.waveTimesCount = (size_t)blocks * (RT_BLOCK / RT_WAVE);
+int wave_time_buf(rt_ctx* c, uint32_t blocks, unsigned long long** out, int threads = RT_BLOCK) {
+    c->rep.waveTimesCount = (size_t)blocks * (size_t)(threads / RT_WAVE);
     int rc = dev_alloc(c, c->waveTimeBuf, c->rep.waveTimesCount * 16);
     if (rc) return rc;
     *out = (unsigned long long*)c->waveTimeBuf.p;
@@ -435,8 +445,10 @@ int launch_fused(rt_ctx* c, const Dispatch& d, const FrameParams& fp, float4* fb
 int launch_trace(rt_ctx* c, const Dispatch& d, uint32_t maxRays, const TraceArgs& ta) {
     if (maxRays == 0) return 0;
     const SceneFacts sf = scene_facts(c, d);
-    const DispatchFacts df = dispatch_facts(d, nullptr, ta.perRayBox != nullptr);
+    DispatchFacts df = dispatch_facts(d, nullptr, ta.perRayBox != nullptr);
+    df.nPixels = d.slots;   // (no frame here: the dispatch's paths, which decide between the 256-thread and the wide work-groups)
     const KernelKey key = trace_kernel_key(c->tune, sf, df);
+    df.groupThreads = (uint32_t)key.threads;
     EventPair* ev;
     int rc;
     if (key.family == KernelFamily::trace) {  // one ray per lane, whole stack in LDS
@@ -449,16 +461,16 @@ int launch_trace(rt_ctx* c, const Dispatch& d, uint32_t maxRays, const TraceArgs
         const TracePwChoice k = trace_pw_choice(key);
         if (!k.kernel) return no_kernel(c, key);
         if ((rc = prof_begin(c, d, &ev))) return rc;
-        const uint32_t resident = resident_blocks(c, k.occupancy);
+        const uint32_t resident = resident_blocks(c, k.occupancy, key.threads);
         const TraceShape s = trace_shape(c->tune, c->meas, sf, df, maxRays, resident);
         uint32_t* overflow;
         if ((rc = overflow_buf(c, d, key, resident, &overflow))) return rc;
         unsigned long long* waveTimes = nullptr;
-        if (s.waveTimes && (rc = wave_time_buf(c, s.blocks, &waveTimes))) return rc;
+        if (s.waveTimes && (rc = wave_time_buf(c, s.blocks, &waveTimes, key.threads))) return rc;
         const TracePwArgs pa{ta.queue, ta.count, d.counts + 4, s.refillMk, (uint32_t)c->tune.chunk, s.wSetup, (uint32_t)c->tune.wLeaf, (uint32_t)c->tune.fastLanes, (uint32_t)c->tune.fastShare,
                              ta.perRayBox, ta.perRayTri, ta.counters, (unsigned long long*)((char*)c->counterBuf.p + sizeof(DevCounters)), waveTimes, overflow, ta.countAux, ta.countAux2, ta.auxOffset};
         memcpy(c->rep.lastKernel, k.name, sizeof k.name);
-        hipLaunchKernelGGL(k.kernel, dim3(s.blocks), dim3(RT_BLOCK), 0, d.stream, d.sc, c->ps, pa);
+        hipLaunchKernelGGL(k.kernel, dim3(s.blocks), dim3((uint32_t)key.threads), 0, d.stream, d.sc, c->ps, pa);
     }
     RT_HIP(c, hipGetLastError());
     return prof_end(c, d, ev);
@@ -893,11 +905,12 @@ int ensure_part_streams(rt_ctx* c, int nLanes) {
 // One part of a multi-kernel dispatch: what its launches are built with (d), its slots [begin, begin + n) and the state of its rounds
 struct Lane { Dispatch d; hipEvent_t poll; uint32_t begin, n, ubActive; int cur; bool pollPending, done; };
 // The parts of a dispatch as the plan slices it, each with its stream, counter block and poll event
-void make_parts(rt_ctx* c, const Dispatch& d, const PartSlices& p, int nLanes, Lane* lane) {
+void make_parts(rt_ctx* c, const Dispatch& d, const PartSlices& p, uint32_t nSlots, int nLanes, Lane* lane) {
     for (int l = 0; l < nLanes; l++) {
         lane[l] = Lane{d, l ? c->pollEventSide[l - 1] : c->pollEvent, p.begin[l], p.n[l], p.n[l], 0, false, p.n[l] == 0};
         lane[l].d.stream = l ? c->sideStream[l - 1] : c->stream; lane[l].d.counts = c->q.counts + 16 * l; lane[l].d.part = l;
         lane[l].d.gridPct = p.gridPct;
+        lane[l].d.slots = nSlots;
     }
 }
 
@@ -967,7 +980,7 @@ int render_parts(rt_ctx* c, const FrameParams& fp, const Dispatch& d, uint32_t n
     const int nLanes = ensure_part_streams(c, choose_parts(c->tune, c->meas, scene_facts(c, d), dispatch_facts(d, &fp, false)));
     c->rep.lastParts = nLanes;
     Lane lane[RT_MAX_LANES];
-    make_parts(c, d, slice_parts(c->tune, nSlots, fp.nFrames, nLanes), nLanes, lane);
+    make_parts(c, d, slice_parts(c->tune, nSlots, fp.nFrames, nLanes), nSlots, nLanes, lane);
     for (int l = 0; l < nLanes; l++) {
         const Lane& L = lane[l];
         if (!L.n) continue;

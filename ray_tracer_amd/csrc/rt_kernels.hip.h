@@ -744,7 +744,8 @@ struct WaveTotals {
 // instantiation without phase statistics has it and stays at 72 registers or fewer with no spill (tests/test_register_budget.py);
 // the STATS instantiations spill either way and keep it only at five work-groups, and so does the fused kernel (it spills too).
 // ALPHA: triangle hits are looked up in their object's alpha map before they count (alpha_cut; k_trace_pw_alpha, k_render_fused_maps).
-template <int STACK, bool OVF, bool PIX, bool STATS, bool LOCAL, bool CULL, int HOT = 0, bool ROOMY = false, bool ALPHA = false>
+// THREADS: the threads of the work-group the wave belongs to (the waves of the grid size the guided reservations)
+template <int STACK, bool OVF, bool PIX, bool STATS, bool LOCAL, bool CULL, int HOT = 0, bool ROOMY = false, bool ALPHA = false, int THREADS = RT_BLOCK>
 __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& ps, const TracePwArgs& ta, uint32_t* stack, uint32_t* ovf,
                                            size_t ovfStride, const uint32_t* localList, uint32_t n, WaveTotals& wt, const uint2* metaLds,
                                            const float4* hotLds = nullptr) {
@@ -764,7 +765,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
     // wave-uniform refill state. LOCAL: the wave's own ray list is the whole 'queue', already reserved.
     bool exhausted = LOCAL;               // the queue has no entries left to reserve
     uint32_t resBase = 0, resCount = LOCAL ? n : 0u;  // reserved queue entries not yet dealt out
-    uint32_t nextChunk = LOCAL ? 0u : min(ta.chunk, max(16u, n / (2u * gridDim.x * (RT_BLOCK / RT_WAVE))));
+    uint32_t nextChunk = LOCAL ? 0u : min(ta.chunk, max(16u, n / (2u * gridDim.x * (THREADS / RT_WAVE))));
 
     uint32_t thr = ta.fastLanes;
     const uint32_t nMain = LOCAL ? 0u : *ta.count, nAux = (LOCAL || !ta.countAux) ? 0u : *ta.countAux;   // the queue's pieces (TraceArgs::countAux)
@@ -829,7 +830,7 @@ __device__ __forceinline__ void trace_wave(const DevScene& sc, const PathState& 
                     resCount = base < n ? min(nextChunk, n - base) : 0u;
                     if (base + nextChunk >= n) exhausted = true;
                     const uint32_t left = base + nextChunk < n ? n - base - nextChunk : 0u;
-                    nextChunk = min(ta.chunk, max(16u, left / (2u * gridDim.x * (RT_BLOCK / RT_WAVE))));
+                    nextChunk = min(ta.chunk, max(16u, left / (2u * gridDim.x * (THREADS / RT_WAVE))));
                 }
                 const uint32_t take = min(nIdle, resCount);
                 if (STATS) { wt.dbgRounds[0]++; wt.dbgLanes[0] += take; }
@@ -1125,24 +1126,25 @@ __device__ __forceinline__ void fill_meta_lds(const DevScene& sc, uint2* s_meta)
 
 // HOT > 0: the first HOT child pairs of the device numbering (the meshes' top levels, DevScene::hotNodes) are served from a copy
 // in LDS (64 B each); BLOCKS = work-groups per CU the kernel is built for (what the LDS of stack + table leaves room for)
-template <int STACK, bool OVF, bool PIX, bool STATS, bool CULL, int HOT, bool ROOMY, bool ALPHA>
+// THREADS: the work-group's size (RT_BLOCK, or the wide kernel's: k_trace_pw_wide)
+template <int STACK, bool OVF, bool PIX, bool STATS, bool CULL, int HOT, bool ROOMY, bool ALPHA, int THREADS = RT_BLOCK>
 __device__ __forceinline__ void trace_pw_block(const DevScene& sc, const PathState& ps, const TracePwArgs& ta) {
-    __shared__ uint32_t s_stack[(RT_BLOCK / RT_WAVE) * (STACK + 1) * RT_WAVE];  // +1: pushes are unconditional
+    __shared__ uint32_t s_stack[(THREADS / RT_WAVE) * (STACK + 1) * RT_WAVE];  // +1: pushes are unconditional
     __shared__ uint2 s_meta[RT_META_LDS];
     __shared__ float4 s_hot[HOT ? 4 * HOT : 1];
-    if (HOT) for (uint32_t k = threadIdx.x; k < 2u * min(sc.hotNodes, 2u * (uint32_t)HOT); k += RT_BLOCK) s_hot[k] = sc.nodesPk[k];
+    if (HOT) for (uint32_t k = threadIdx.x; k < 2u * min(sc.hotNodes, 2u * (uint32_t)HOT); k += THREADS) s_hot[k] = sc.nodesPk[k];
     fill_meta_lds(sc, s_meta);
     uint32_t* stack = s_stack + (threadIdx.x / RT_WAVE) * (STACK + 1) * RT_WAVE + (threadIdx.x & (RT_WAVE - 1));
     // overflow entries of this lane: index k at ovf[k * ovfStride]
-    uint32_t* ovf = OVF ? ta.overflow + (size_t)blockIdx.x * RT_BLOCK + threadIdx.x : nullptr;
-    const size_t ovfStride = (size_t)gridDim.x * RT_BLOCK;
+    uint32_t* ovf = OVF ? ta.overflow + (size_t)blockIdx.x * THREADS + threadIdx.x : nullptr;
+    const size_t ovfStride = (size_t)gridDim.x * THREADS;
     WaveTotals wt;
     const unsigned long long tStart = STATS ? wall_clock64() : 0ull;
-    trace_wave<STACK, OVF, PIX, STATS, false, CULL, HOT, ROOMY, ALPHA>(sc, ps, ta, stack, ovf, ovfStride, nullptr, *ta.count + (ta.countAux ? *ta.countAux + *ta.countAux2 : 0u), wt, s_meta, s_hot);
+    trace_wave<STACK, OVF, PIX, STATS, false, CULL, HOT, ROOMY, ALPHA, THREADS>(sc, ps, ta, stack, ovf, ovfStride, nullptr, *ta.count + (ta.countAux ? *ta.countAux + *ta.countAux2 : 0u), wt, s_meta, s_hot);
 
     const uint32_t skipTrips = STATS ? wave_sum_u32(wt.dbgWait[3]) : 0u;
     if (STATS && lane_id() == 0) {
-        const size_t w = (size_t)blockIdx.x * (RT_BLOCK / RT_WAVE) + threadIdx.x / RT_WAVE;
+        const size_t w = (size_t)blockIdx.x * (THREADS / RT_WAVE) + threadIdx.x / RT_WAVE;
         if (ta.waveTimes) {
             ta.waveTimes[2 * w] = tStart;
             ta.waveTimes[2 * w + 1] = wall_clock64();
@@ -1171,6 +1173,15 @@ __device__ __forceinline__ void trace_pw_block(const DevScene& sc, const PathSta
 template <int STACK, bool OVF, bool PIX, bool STATS, bool CULL, int HOT = 0, int BLOCKS = 6>
 __global__ __launch_bounds__(RT_BLOCK, BLOCKS) void k_trace_pw(DevScene sc, PathState ps, TracePwArgs ta) {
     trace_pw_block<STACK, OVF, PIX, STATS, CULL, HOT, BLOCKS == 5 || (RT_TE_REG_ALL && !STATS), false>(sc, ps, ta);
+}
+// The same traversal in work-groups of THREADS threads, built for six waves per SIMD (RT_WIDE_GROUPS groups of RT_WIDE_THREADS per
+// CU): fewer, wider groups mean fewer copies of the top-level table in a CU's LDS, so the sixth wave and the whole table of
+// RT_HOT_PAIRS pairs fit together (launch_plan.h: wide_group_lds). One configuration, the one the big dispatches of a scene like
+// the bench frame run (launch_plan.cpp: trace_kernel_key): no overflow stack, no per-ray counters, no phase statistics, no object
+// culling; tE in a register and the leaf preload as in k_trace_pw<STACK, .., 5>.
+template <int STACK, int HOT, int THREADS>
+__global__ __launch_bounds__(THREADS, 6) void k_trace_pw_wide(DevScene sc, PathState ps, TracePwArgs ta) {
+    trace_pw_block<STACK, false, false, false, false, HOT, true, false, THREADS>(sc, ps, ta);
 }
 // The traversal of a scene that binds an alpha map (DevScene::mapFlags & RT_MAP_ALPHA): one configuration for every such scene —
 // 24 stack entries in LDS with the overflow buffer behind them, object culling compiled in, no top-level table, four work-groups

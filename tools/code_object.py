@@ -8,6 +8,7 @@ import os, re, struct, subprocess, sys, tempfile
 LLVM_BIN = os.environ.get("LLVM_BIN", "/opt/rocm/llvm/bin")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".sgpr_spill_count", ".vgpr_spill_count")
+ALSO_READ = (".group_segment_fixed_size", ".max_flat_workgroup_size")   # in kernels()' rows, not in the printed figures
 
 
 def extract(lib, arch="gfx950"):
@@ -51,7 +52,7 @@ def kernels(lib):
         if line.lstrip().startswith("- .agpr_count") and cur:   # the first key of the next kernel's map
             rows[cur[".name"]] = cur
             cur = {}
-        if m.group(1) in FIELDS:
+        if m.group(1) in FIELDS or m.group(1) in ALSO_READ:
             cur[m.group(1)] = int(m.group(2))
         elif m.group(1) == ".name" and line.startswith("    .name"):   # (arguments have a .name of their own, indented deeper)
             cur[".name"] = m.group(2)
