@@ -455,6 +455,69 @@ int  rt_render_guides(rt_ctx* ctx, const PushConstants* pc, uint32_t width, uint
  * nRows*width of that pass); blocks */
 int  rt_read_guides(rt_ctx* ctx, const RtAovBuffers* hostOut, size_t nPixels);
 
+/* Ray queries on batches of the caller's own rays ("Ray queries"): the closest hit, or only whether anything is hit
+ * within a limit. The arrays of a batch are packed: ray i's origin at origins[3 i .. 3 i + 2], likewise dirs (rt_trace_rays'
+ * layout; a contiguous (n, 3) fp32 tensor). */
+typedef struct RtRayBatch {
+    const float* origins;  /* n x 3 floats, packed */
+    const float* dirs;     /* n x 3; not renormalised: distances are in units of |dir|, as in rt_trace_rays */
+    const float* tmax;     /* n floats, or NULL: no limit */
+    uint32_t n;
+} RtRayBatch;
+/* Contract. Ray i with limit T (tmax[i]; RT_MISS_DST when tmax is NULL) runs calculateIntersections (raytrace.comp:276-353) with
+ * its running closest distance started at T instead of at the miss distance: the sphere loop accepts a sphere with dst < T, a box is
+ * entered on d < best and a triangle accepted on dst < best as ever, and alpha maps cut hits out as in rendering.
+ *  - rt_query_closest, tmax NULL: d_hits[i] equals what rt_trace_rays returns for the ray, bit for bit, in every field except
+ *    boxTests and triTests, which are 0 (the pass runs the kernels without per-ray counters, the ones rendering runs). With a
+ *    limit: that same record when its dst < T, otherwise the miss record (dst == RT_MISS_DST, didHit == 0, the rest zero).
+ *  - rt_query_occluded: d_occluded[i] is 1 exactly when that search, started at T, accepts any primitive, else 0. Until the first
+ *    acceptance the bound is the constant T, so the answer does not depend on the order primitives are visited in, and therefore
+ *    not on the kernel, the knobs, the parts or the object hierarchy. Hence occluded => (closest.didHit && closest.dst < T) on
+ *    every ray, exactly; the converse holds except where closest.dst lies within the box tests' rounding below T. The search ends
+ *    at the first acceptance (the early exit of the light queries).
+ *  - A limit that is NaN or <= 0 makes the ray a miss / unoccluded without being traced. n == 0 succeeds and does nothing.
+ * The struct is read on the host; with the plain names its three arrays and the output are device pointers and the call is
+ * asynchronous on the ctx stream (the arrays stay valid and unchanged until the stream has passed it); the _host names take host
+ * arrays and block. Both run in path-state slots [0, n), as rt_render_aovs does, always through the persistent-wave traversal
+ * kernels (k_trace_pw...; rt_last_kernel names the one that ran) whatever "trace_variant" says: k_trace starts every ray at the
+ * miss distance. They count into the AOV passes' counter block (raysTraced: the rays that had to be traversed; raysHit: of a
+ * closest pass the rays that hit, of an occlusion pass the traversed rays that came out unoccluded) and change nothing a later
+ * rt_render, rt_render_aovs, rt_denoise or rt_temporal_accumulate produces or chooses: not the framebuffer or its progressive
+ * history, not rt_last_pipeline, rt_last_parts or the ray cost.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch; origins, dirs or the output NULL with
+ * n > 0; n >= 2^30 (the slot ids). */
+int  rt_query_closest(rt_ctx* ctx, const RtRayBatch* d_rays, RtHit* d_hits);
+int  rt_query_occluded(rt_ctx* ctx, const RtRayBatch* d_rays, uint8_t* d_occluded);
+int  rt_query_closest_host(rt_ctx* ctx, const RtRayBatch* rays, RtHit* hits);
+int  rt_query_occluded_host(rt_ctx* ctx, const RtRayBatch* rays, uint8_t* occluded);
+
+/* Ambient occlusion from first-hit planes ("Ray queries", "Ambient-occlusion plane"). Record i of the planes with
+ * ids.w & 1 shoots `samples` occlusion queries: origin position + (normal * 1) * 0.00001 (the next-ray origin of shading),
+ * direction the shader's cosineHemisphereDir about normalDepth.xyz (raytrace.comp:405-424, the arithmetic of the diffuse branch of
+ * shading), drawn from an rt_random state seeded from (i, sample, seed) (include/rt_ao_rays.h: rt_ao_state), limit `radius`.
+ * ao[i] = (float)(samples - k) / (float)samples with k the occluded ones; a record without the hit bit gets 1 and shoots nothing.
+ * The record index seeds the RNG, so a plane belongs to one tile layout: the planes of one rt_render_aovs pass, in its order. */
+typedef struct RtAoParams {
+    uint32_t samples;   /* 1..64 */
+    float    radius;    /* finite, > 0 */
+    uint32_t seed;      /* any */
+} RtAoParams;
+void rt_ao_params_default(RtAoParams* p);                    /* 4, 0.5, 0 */
+/* Asynchronous on the ctx stream: `samples` rounds of {make the rays, traverse, count}, then one kernel that writes the plane; the
+ * host waits for none of them. d_aovs: device planes of rt_render_aovs' layout (position, normalDepth and ids are read), or NULL:
+ * the ctx planes of the last rt_render_aovs(…, NULL), which must hold nPixels records. params NULL: the defaults. d_ao: nPixels
+ * floats, or NULL: a ctx-owned plane (rt_read_ao). Counters, slots and what it leaves alone: as rt_query_occluded. Refused with a
+ * message, in this order: no uploaded scene; samples outside 1..64 or a radius that is not finite and > 0; nPixels 0 or >= 2^30;
+ * d_aovs without one of the three planes, or NULL without ctx planes of that size. */
+int  rt_render_ao(rt_ctx* ctx, uint32_t nPixels, const RtAovBuffers* d_aovs, const RtAoParams* params, float* d_ao);
+/* copies the ctx-owned plane of the last rt_render_ao(…, d_ao = NULL) (nFloats = nPixels of that call); blocks */
+int  rt_read_ao(rt_ctx* ctx, float* hostOut, size_t nFloats);
+/* Host only, no GPU: the rays of sample `sample` (< samples) as rt_render_ao shoots them, from host planes. origins, dirs:
+ * nPixels x 3 floats (zeros where no ray is shot); valid: nPixels bytes, 1 where record i shoots. Returns 0, or -1 on a NULL
+ * argument, a missing plane or parameters rt_render_ao refuses. */
+int  rt_ao_rays_host(uint32_t nPixels, const RtAovBuffers* aovs, const RtAoParams* params, uint32_t sample,
+                     float* origins, float* dirs, uint8_t* valid);
+
 /* Edge-avoiding a-trous denoiser over a whole width x height frame (the spatial filter of SVGF, Schied et al. 2017, after
  * Dammertz et al. 2010; DESIGN.md, "Denoising"). Pixel p is filtered when ids.w & 1 (a hit), ids.z < the material count and
  * that material's emissionStrength == 0, all in the ctx's current material table; every other pixel (misses, emitters) is kept:

@@ -102,6 +102,14 @@ class RtAovBuffers(C.Structure):
                 ("ids", C.c_void_p)]
 
 
+class RtRayBatch(C.Structure):
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("tmax", C.c_void_p), ("n", C.c_uint32)]
+
+
+class RtAoParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32)]
+
+
 class RtDenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigmaLuminance", C.c_float), ("sigmaNormal", C.c_float), ("sigmaDepth", C.c_float)]
 
@@ -173,6 +181,14 @@ SYMBOLS = {
     "rt_render_guides": (C.c_int, [_vp, _P(PushConstants), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                    _P(RtAovBuffers), _P(RtAovBuffers)]),
     "rt_read_guides": (C.c_int, [_vp, _P(RtAovBuffers), C.c_size_t]),
+    "rt_query_closest": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
+    "rt_query_occluded": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
+    "rt_query_closest_host": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
+    "rt_query_occluded_host": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
+    "rt_ao_params_default": (None, [_P(RtAoParams)]),
+    "rt_render_ao": (C.c_int, [_vp, C.c_uint32, _P(RtAovBuffers), _P(RtAoParams), _vp]),
+    "rt_read_ao": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),
+    "rt_ao_rays_host": (C.c_int, [C.c_uint32, _P(RtAovBuffers), _P(RtAoParams), C.c_uint32, _P(C.c_float), _P(C.c_float), _P(C.c_uint8)]),
     "rt_denoise_params_default": (None, [_P(RtDenoiseParams)]),
     "rt_denoise": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _P(RtAovBuffers), _P(RtDenoiseParams), _vp]),
     "rt_read_denoised_rgba_f32": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),

@@ -11,6 +11,7 @@
 #include "rt_refit.hip.h"  // the kernels of rt_update_points; mesh_refit.h: the plan they run, the checks and the rule
 #include "launch_plan.h"   // every decision about how a dispatch is run: this file gathers the facts, asks there, and launches
 #include "post_passes.h"   // likewise for the passes over finished frames: their checks, their input planes, the temporal history
+#include "ray_queries.h"   // ... and for the ray queries and the ambient-occlusion pass: their checks and the arithmetic of a batch
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -109,6 +110,11 @@ struct rt_ctx {
     // counts of the pass's rounds (GUIDE_COUNTS words)
     OwnedPlane guide;
     DevBuf guideCountBuf;
+    // ray queries and the ambient-occlusion pass (rt_query_*, rt_render_ao): the pass's queue (one entry per ray, holes for the rays
+    // that are answered without a traversal), the staging arrays of the _host forms, the occluded counts of rt_render_ao's rounds and
+    // the ctx-owned plane of the last rt_render_ao(..., d_ao = NULL) with its pixel count (0: never written)
+    DevBuf queryQueueBuf, queryHostBuf, aoCountBuf, aoBuf;
+    size_t aoPixels = 0;
     DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
     // the denoiser (rt_denoise): its work planes, the staging planes of rt_denoise_host and the ctx-owned output
     DevBuf dnWorkBuf, dnHostBuf;
@@ -442,12 +448,17 @@ int launch_fused(rt_ctx* c, const Dispatch& d, const FrameParams& fp, float4* fb
 }
 
 // the work counter (counts[4]) must be zero when this is called
-int launch_trace(rt_ctx* c, const Dispatch& d, uint32_t maxRays, const TraceArgs& ta) {
+// boundFromSeed: the rays' seed records carry a bound the traversal must start from (the ray queries' limits): only the
+// persistent-wave kernels read a seed's distance (k_trace runs the sphere loop itself and starts at the miss distance), so the kernel
+// is chosen as with "trace_variant" 1, whatever the knob says
+int launch_trace(rt_ctx* c, const Dispatch& d, uint32_t maxRays, const TraceArgs& ta, bool boundFromSeed = false) {
     if (maxRays == 0) return 0;
     const SceneFacts sf = scene_facts(c, d);
     DispatchFacts df = dispatch_facts(d, nullptr, ta.perRayBox != nullptr);
     df.nPixels = d.slots;   // (no frame here: the dispatch's paths, which decide between the 256-thread and the wide work-groups)
-    const KernelKey key = trace_kernel_key(c->tune, sf, df);
+    Tuning keyTune = c->tune;
+    if (boundFromSeed) keyTune.traceVariant = 1;
+    const KernelKey key = trace_kernel_key(keyTune, sf, df);
     df.groupThreads = (uint32_t)key.threads;
     EventPair* ev;
     int rc;
@@ -1303,6 +1314,129 @@ int rt_render_guides(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_
 
 int rt_read_guides(rt_ctx* c, const RtAovBuffers* out, size_t nPixels) {
     return c ? read_planes(c, c->guide, "rt_read_guides", NO_OWNED_GUIDES, out, nPixels) : -1;
+}
+}  // extern "C"
+
+// ---- ray queries and the ambient-occlusion plane (ray_queries.h has the checks and the arithmetic; DESIGN.md, "Ray queries")
+namespace {
+// What the query passes share with rt_render_aovs: path-state slots [0, n) on the ctx stream (growing the state frees the old one,
+// so that waits for the device first), a queue of n entries, no phase statistics, launches and traversal work counted with the AOV
+// passes'
+int query_begin(rt_ctx* c, uint32_t n, Dispatch* d) {
+    RT_HIP(c, hipSetDevice(c->device));
+    const QueryShape qs = query_shape(n, RT_BLOCK);
+    if (c->capacity < n || !c->stateBuf.p || c->queryQueueBuf.bytes < qs.queueBytes) RT_HIP(c, hipStreamSynchronize(c->stream));
+    int rc = ensure_state(c, n);
+    if (rc) return rc;
+    if ((rc = dev_alloc(c, c->queryQueueBuf, qs.queueBytes))) return rc;
+    *d = one_part(c, c->sc, false);
+    d->phaseStats = 0; d->launches = &c->rep.aovLaunches;
+    return 0;
+}
+// the traversal of the pass's queue: n entries, holes among them
+int query_trace(rt_ctx* c, const Dispatch& d, uint32_t n) {
+    const TraceArgs ta{(const uint32_t*)c->queryQueueBuf.p, c->q.counts, nullptr, nullptr, (DevCounters*)c->aovCounterBuf.p};
+    return launch_trace(c, d, n, ta, true);
+}
+
+int query_device(rt_ctx* c, const char* fn, const RtRayBatch* rays, void* d_out, bool occlusion) {
+    if (!c) return -1;
+    const std::string refusal = check_ray_query(fn, c->sc.nodes != nullptr, rays, d_out);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = rays->n;
+    if (n == 0) return 0;
+    Dispatch d;
+    int rc = query_begin(c, n, &d);
+    if (rc) return rc;
+    const uint32_t blocks = query_shape(n, RT_BLOCK).blocks;
+    const QueryRays q{rays->origins, rays->dirs, rays->tmax, n, occlusion ? 1u : 0u, (uint32_t*)c->queryQueueBuf.p};
+    hipLaunchKernelGGL(k_query_rays, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, d.sc, c->ps, q);
+    hipLaunchKernelGGL(k_init_counts, dim3(1), dim3(64), 0, c->stream, c->q.counts, n);
+    RT_HIP(c, hipGetLastError());
+    if ((rc = query_trace(c, d, n))) return rc;
+    if (occlusion) hipLaunchKernelGGL(k_query_occluded, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->ps, n, (uint8_t*)d_out);
+    else hipLaunchKernelGGL(k_query_hits, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, d.sc, c->ps, n, (RtHit*)d_out);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The host-memory form: the batch's arrays go up into one ctx buffer (query_staging), the device form runs on the copies, the
+// output comes back; blocks. (The planes of `staged` all have one size; a batch's arrays do not.)
+int query_host(rt_ctx* c, const char* fn, const RtRayBatch* rays, void* out, bool occlusion) {
+    if (!c) return -1;
+    const std::string refusal = check_ray_query(fn, c->sc.nodes != nullptr, rays, out);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = rays->n;
+    if (n == 0) return 0;
+    const size_t rec = occlusion ? sizeof(uint8_t) : sizeof(RtHit);
+    const QueryShape qs = query_shape(n, RT_BLOCK);
+    const QueryStaging g = query_staging(n, rays->tmax != nullptr, rec);
+    RT_HIP(c, hipSetDevice(c->device));
+    if (c->queryHostBuf.bytes < g.bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees arrays a pass in flight may be using
+    int rc = dev_alloc(c, c->queryHostBuf, g.bytes);
+    if (rc) return rc;
+    char* const b = (char*)c->queryHostBuf.p;
+    RT_HIP(c, hipMemcpyAsync(b + g.origins, rays->origins, qs.vecBytes, hipMemcpyHostToDevice, c->stream));
+    RT_HIP(c, hipMemcpyAsync(b + g.dirs, rays->dirs, qs.vecBytes, hipMemcpyHostToDevice, c->stream));
+    if (rays->tmax) RT_HIP(c, hipMemcpyAsync(b + g.tmax, rays->tmax, qs.tmaxBytes, hipMemcpyHostToDevice, c->stream));
+    const RtRayBatch dev{(const float*)(b + g.origins), (const float*)(b + g.dirs), rays->tmax ? (const float*)(b + g.tmax) : nullptr, n};
+    if ((rc = query_device(c, fn, &dev, b + g.out, occlusion))) return rc;
+    RT_HIP(c, hipMemcpyAsync(out, b + g.out, (size_t)n * rec, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+int rt_query_closest(rt_ctx* c, const RtRayBatch* d_rays, RtHit* d_hits) { return query_device(c, "rt_query_closest", d_rays, d_hits, false); }
+int rt_query_occluded(rt_ctx* c, const RtRayBatch* d_rays, uint8_t* d_occluded) { return query_device(c, "rt_query_occluded", d_rays, d_occluded, true); }
+int rt_query_closest_host(rt_ctx* c, const RtRayBatch* rays, RtHit* hits) { return query_host(c, "rt_query_closest_host", rays, hits, false); }
+int rt_query_occluded_host(rt_ctx* c, const RtRayBatch* rays, uint8_t* occluded) { return query_host(c, "rt_query_occluded_host", rays, occluded, true); }
+
+// `samples` rounds of {k_ao_rays, the traversal, k_ao_count}, all enqueued without waiting for the device, then k_ao_resolve
+int rt_render_ao(rt_ctx* c, uint32_t nPixels, const RtAovBuffers* d_aovs, const RtAoParams* params, float* d_ao) {
+    if (!c) return -1;
+    RtAoParams p;
+    rt_ao_params_default(&p);
+    if (params) p = *params;
+    const std::string refusal = check_ao("rt_render_ao", c->sc.nodes != nullptr, nPixels, p, d_aovs, c->aov.valid, c->aov.pixels);
+    if (!refusal.empty()) return c->fail(refusal);
+    Dispatch d;
+    int rc = query_begin(c, nPixels, &d);
+    if (rc) return rc;
+    const size_t countBytes = (size_t)nPixels * sizeof(uint32_t), aoBytes = (size_t)nPixels * sizeof(float);
+    if (c->aoCountBuf.bytes < countBytes || (!d_ao && c->aoBuf.bytes < aoBytes)) RT_HIP(c, hipStreamSynchronize(c->stream));
+    if ((rc = dev_alloc(c, c->aoCountBuf, countBytes))) return rc;
+    if (!d_ao) {
+        if ((rc = dev_alloc(c, c->aoBuf, aoBytes))) return rc;
+        c->aoPixels = nPixels;
+    }
+    const auto plane = [&](AovPlane k) { return d_aovs ? aov_plane(*d_aovs, k) : aov_plane(c->aov.buf.p, k, nPixels); };
+    AoArgs a{(const float4*)plane(AOV_POSITION), (const float4*)plane(AOV_NORMAL_DEPTH), (const uint4*)plane(AOV_IDS), nPixels, 0u, p.samples, p.seed,
+             p.radius, (uint32_t*)c->queryQueueBuf.p, (uint32_t*)c->aoCountBuf.p, d.counts + 4};
+    const uint32_t blocks = query_shape(nPixels, RT_BLOCK).blocks;
+    hipLaunchKernelGGL(k_init_counts, dim3(1), dim3(64), 0, c->stream, c->q.counts, nPixels);
+    for (uint32_t s = 0; s < p.samples; s++) {
+        a.sample = s;
+        hipLaunchKernelGGL(k_ao_rays, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, d.sc, c->ps, a);
+        RT_HIP(c, hipGetLastError());
+        if ((rc = query_trace(c, d, nPixels))) return rc;
+        hipLaunchKernelGGL(k_ao_count, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->ps, a);
+        RT_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ao_resolve, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, a, d_ao ? d_ao : (float*)c->aoBuf.p);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int rt_read_ao(rt_ctx* c, float* out, size_t nFloats) {
+    if (!c || !out) return -1;
+    if (!c->aoPixels) return c->fail("no ctx-owned AO plane: rt_render_ao was never called with d_ao = NULL");
+    if (nFloats != c->aoPixels) return c->fail("rt_read_ao: size mismatch");
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipMemcpyAsync(out, c->aoBuf.p, nFloats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
 }
 }  // extern "C"
 

@@ -26,6 +26,7 @@
 #include "rt_amd.h"
 #include "rt_det_math.h"
 #include "rt_probe.h"
+#include "rt_ao_rays.h"      // the rule that makes the ambient-occlusion pass's rays, shared with the host (rt_ao_rays_host)
 #include "scene_layout.h"   // the formats of the scene tables: node words, object flags, RT_MAP_*, RT_HOT_PAIRS, RT_OBJTREE_LEVELS
 #include "launch_plan.h"    // RT_WAVE, RT_BLOCK: the launch policy sizes grids and blocks with them
 #include "temporal_motion.h" // the records of the temporal pass's motion table (RT_MOTION_*)
@@ -2006,6 +2007,135 @@ __global__ __launch_bounds__(RT_BLOCK) void k_guide_follow(DevScene sc, PathStat
         base = __shfl(base, 0, RT_WAVE);
         if (goesOn) ga.outQueue[base + lanes_below(m)] = (slot << 2) | (uint32_t)RAY_MAIN;
     }
+}
+
+// ---------------------------------------------------------------- ray queries (rt_query_closest, rt_query_occluded, rt_render_ao)
+// The caller's rays through the ordinary persistent-wave traversal; no second traversal: the seed record is the interface. A ray's
+// creator leaves {closest distance so far, its object bits, reach mask, tE} in hit(RAY_MAIN)[slot] (sphere_seed), and the traversal
+// starts from them. A query with limit T starts the running closest distance at min(sphere dst, T) ("Ray queries"):
+//   closest hit : a sphere nearer than T seeds as ever; else {T, RT_HIT_NONE}: a bound nothing beats comes back as it went in, and
+//                 k_query_hits turns every record without an object into the miss record
+//   occlusion   : a sphere nearer than T answers the query at once (a queue hole); else {T, RT_QUERY_BOUND} with tE = +inf in .w, so
+//                 that the first accepted triangle (dst < best <= T < tE) ends the ray through the light queries' exit, which reports
+//                 {RT_MISS_DST, RT_HIT_NONE}: "no hit" is the word for "occluded", and a bound nothing beat comes back as
+//                 RT_QUERY_BOUND: the marker tells the two apart
+// The reach mask does not depend on `best` (reach_mask_from only clears on a box miss). A limit that is NaN or <= 0 is a queue hole
+// with the unoccluded / miss record.
+#define RT_QUERY_BOUND 0xfffffffeu   // object bits no hit has (sphere indices are small): the bound is the caller's limit
+
+struct QuerySeed { float4 seed; bool traced; };
+__device__ __forceinline__ QuerySeed query_seed(const DevScene& sc, rt_vec3 ro, rt_vec3 rd, float T, bool occlusion) {
+    QuerySeed q;
+    q.traced = false;
+    q.seed = make_float4(RT_MISS_DST, __uint_as_float(occlusion ? RT_QUERY_BOUND : RT_HIT_NONE), __uint_as_float(0xffffffffu), 0.f);
+    if (!(T > 0.f)) return q;   // NaN, 0, negative: nothing is nearer
+    const float4 s = sphere_seed(sc, ro, rd);
+    if (__float_as_uint(s.y) != RT_HIT_NONE && s.x < T) {   // the sphere loop, started at T, accepts a sphere (its nearest one: dst < T)
+        if (occlusion) { q.seed = make_float4(RT_MISS_DST, __uint_as_float(RT_HIT_NONE), s.z, 0.f); return q; }
+        q.seed = s;
+    } else {
+        q.seed = make_float4(T, __uint_as_float(occlusion ? RT_QUERY_BOUND : RT_HIT_NONE), s.z, 0.f);
+    }
+    if (occlusion) q.seed.w = __uint_as_float(0x7f800000u);   // tE = +inf
+    q.traced = true;
+    return q;
+}
+
+struct QueryRays {
+    const float* origins;   // n x 3, packed
+    const float* dirs;
+    const float* tmax;      // n, or NULL: RT_MISS_DST
+    uint32_t n, occlusion;
+    uint32_t* queue;        // n entries: slot * 4 + RAY_MAIN, or RT_QUEUE_HOLE
+};
+
+__global__ __launch_bounds__(RT_BLOCK) void k_query_rays(DevScene sc, PathState ps, QueryRays q) {
+    const uint32_t i = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (i >= q.n) return;
+    const size_t r = (size_t)i * 3;
+    const rt_vec3 ro = rt_v3(q.origins[r], q.origins[r + 1], q.origins[r + 2]), rd = rt_v3(q.dirs[r], q.dirs[r + 1], q.dirs[r + 2]);
+    const QuerySeed s = query_seed(sc, ro, rd, q.tmax ? q.tmax[i] : RT_MISS_DST, q.occlusion != 0u);
+    ps.rayO()[i] = mk4(ro, 0.f);
+    ps.rayD()[i] = mk4(rd, 0.f);
+    ps.hit(RAY_MAIN)[i] = s.seed;
+    q.queue[i] = s.traced ? ((i << 2) | (uint32_t)RAY_MAIN) : RT_QUEUE_HOLE;
+}
+
+// k_hit_details without the counter arrays; a record without an object (a miss, or a limit nothing beat) is the miss record
+__global__ __launch_bounds__(RT_BLOCK) void k_query_hits(DevScene sc, PathState ps, uint32_t n, RtHit* out) {
+    const uint32_t i = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    RtHit h;
+    memset(&h, 0, sizeof(h));
+    const float4 hm = ps.hit(RAY_MAIN)[i];
+    const uint32_t obj = __float_as_uint(hm.y), tri = __float_as_uint(hm.z);
+    h.dst = RT_MISS_DST;
+    if (obj != RT_HIT_NONE && obj != RT_QUERY_BOUND) {
+        FullHit f = reconstruct_hit<true>(sc, f4xyz(ps.rayO()[i]), f4xyz(ps.rayD()[i]), obj, tri);
+        h.dst = hm.x;
+        h.didHit = 1;
+        h.isSphere = (obj & RT_HIT_SPHERE) ? 1u : 0u;
+        h.objectHitIndex = obj & ~RT_HIT_SPHERE;
+        h.triHitIndex = h.isSphere ? 0u : tri;
+        h.materialIndex = f.materialIndex;
+        h.frontFace = f.frontFace;
+        h.hitPoint[0] = f.hitPoint.x; h.hitPoint[1] = f.hitPoint.y; h.hitPoint[2] = f.hitPoint.z;
+        h.normal[0] = f.normal.x; h.normal[1] = f.normal.y; h.normal[2] = f.normal.z;
+    }
+    out[i] = h;
+}
+
+// an occlusion query's record: "no hit" is the early exit's (or k_query_rays' own, for a sphere) word for "occluded"
+__device__ __forceinline__ uint32_t query_is_occluded(const PathState& ps, uint32_t slot) {
+    return __float_as_uint(ps.hit(RAY_MAIN)[slot].y) == RT_HIT_NONE ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(RT_BLOCK) void k_query_occluded(PathState ps, uint32_t n, uint8_t* out) {
+    const uint32_t i = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (i < n) out[i] = (uint8_t)query_is_occluded(ps, i);
+}
+
+// ---------------------------------------------------------------- ambient-occlusion plane (rt_render_ao)
+// `samples` rounds of {k_ao_rays, the traversal, k_ao_count} and k_ao_resolve; one lane per record of the first-hit planes.
+struct AoArgs {
+    const float4* position;
+    const float4* normalDepth;
+    const uint4* ids;
+    uint32_t n, sample, samples, seed;
+    float radius;
+    uint32_t* queue;     // as QueryRays::queue
+    uint32_t* occluded;  // n counts: k of the rounds so far
+    uint32_t* head;      // the traversal's work counter, which its next launch wants zero
+};
+
+__global__ __launch_bounds__(RT_BLOCK) void k_ao_rays(DevScene sc, PathState ps, AoArgs a) {
+    const uint32_t i = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    rt_vec3 ro, rd;
+    if (!rt_ao_ray(f4xyz(a.position[i]), f4xyz(a.normalDepth[i]), a.ids[i].w, i, a.sample, a.seed, &ro, &rd)) {
+        ps.hit(RAY_MAIN)[i] = make_float4(RT_MISS_DST, __uint_as_float(RT_QUERY_BOUND), __uint_as_float(0xffffffffu), 0.f);
+        a.queue[i] = RT_QUEUE_HOLE;
+        return;
+    }
+    const QuerySeed s = query_seed(sc, ro, rd, a.radius, true);
+    ps.rayO()[i] = mk4(ro, 0.f);
+    ps.rayD()[i] = mk4(rd, 0.f);
+    ps.hit(RAY_MAIN)[i] = s.seed;
+    a.queue[i] = s.traced ? ((i << 2) | (uint32_t)RAY_MAIN) : RT_QUEUE_HOLE;
+}
+
+__global__ __launch_bounds__(RT_BLOCK) void k_ao_count(PathState ps, AoArgs a) {
+    const uint32_t i = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (i == 0) *a.head = 0u;   // (the round's traversal is over and the next one is behind this kernel on the stream)
+    if (i >= a.n) return;
+    const uint32_t k = query_is_occluded(ps, i);
+    a.occluded[i] = a.sample ? a.occluded[i] + k : k;
+}
+
+__global__ __launch_bounds__(RT_BLOCK) void k_ao_resolve(AoArgs a, float* out) {
+    const uint32_t i = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    out[i] = (a.ids[i].w & 1u) ? (float)(a.samples - a.occluded[i]) / (float)a.samples : 1.f;
 }
 
 // ---------------------------------------------------------------- a-trous denoiser (rt_denoise)

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtRayBatch,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -474,6 +474,81 @@ class Renderer:
                     "rt_trace_rays")
         return hits
 
+    def _query(self, what, origins, dirs, tmax, n, out, sync):
+        """Both ray queries: numpy arrays through the _host entry points, device memory (objects with data_ptr(), or integer device
+        pointers with n=) through the asynchronous ones."""
+        rec = C.sizeof(RtHit) if what == "closest" else 1
+        on_device = [hasattr(x, "data_ptr") or isinstance(x, (int, np.integer)) for x in (origins, dirs)]
+        if not any(on_device):
+            o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+            d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+            if d.shape != o.shape:
+                raise ValueError(f"origins {o.shape} and dirs {d.shape}: not one (n, 3) pair")
+            t = None if tmax is None else np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+            if t is not None and t.shape[0] != o.shape[0]:
+                raise ValueError(f"tmax has {t.shape[0]} limits for {o.shape[0]} rays")
+            if out is not None or not sync:
+                raise ValueError("out= and sync=False go with device-pointer inputs")
+            batch = RtRayBatch(o.ctypes.data, d.ctypes.data, t.ctypes.data if t is not None else None, o.shape[0])
+            res = (RtHit * o.shape[0])() if what == "closest" else np.zeros(o.shape[0], np.uint8)
+            fn = getattr(self._l, f"rt_query_{what}_host")
+            self._check(fn(self._h, C.byref(batch), C.addressof(res) if what == "closest" else res.ctypes.data), f"rt_query_{what}_host")
+            return res if what == "closest" else res.astype(bool)
+        if not all(on_device):
+            raise ValueError("origins and dirs must both be host arrays or both be device memory")
+        if out is None:
+            raise ValueError("device-pointer inputs need out=: device memory for the results")
+        if n is None:
+            if not hasattr(origins, "numel"):
+                raise ValueError("integer device pointers need n=")
+            n = int(origins.numel()) // 3
+        ptrs = [_device_ptr(origins, "origins", 12 * n), _device_ptr(dirs, "dirs", 12 * n),
+                None if tmax is None else _device_ptr(tmax, "tmax", 4 * n)]
+        batch = RtRayBatch(ptrs[0], ptrs[1], ptrs[2], int(n))
+        fn = getattr(self._l, f"rt_query_{what}")
+        self._check(fn(self._h, C.byref(batch), C.c_void_p(_device_ptr(out, "out", rec * n, floats=False))), f"rt_query_{what}")
+        if sync:
+            self.sync()
+        return None
+
+    def query_closest(self, origins, dirs, tmax=None, n=None, out=None, sync=True):
+        """The closest hit of each of the caller's rays within its limit (rt_query_closest; DESIGN.md, "Ray queries"). (n, 3) numpy
+        arrays and an optional (n,) `tmax` go through rt_query_closest_host and come back as an RtHit array (hits_to_numpy); torch
+        tensors on the device (anything with data_ptr(): fp32, contiguous) or integer device pointers with n= go through the
+        asynchronous entry point, the RtHit records are written to `out` (device memory, 60 bytes per ray) and sync=False is allowed."""
+        return self._query("closest", origins, dirs, tmax, n, out, sync)
+
+    def query_occluded(self, origins, dirs, tmax=None, n=None, out=None, sync=True):
+        """Whether each ray hits anything nearer than its limit (rt_query_occluded): a bool array for numpy inputs, one byte per ray
+        in `out` for device memory, as query_closest takes it."""
+        return self._query("occluded", origins, dirs, tmax, n, out, sync)
+
+    def render_ao(self, aovs=None, samples=4, radius=0.5, seed=0):
+        """The ambient-occlusion plane of first-hit planes (rt_render_ao): `samples` cosine-weighted occlusion queries of reach
+        `radius` per hit record. Without `aovs`: the context's own planes of the last render_aovs(); else the dict render_aovs()
+        returns, uploaded for the call. Returns the (nRows, width) float32 plane: 1 = open, 0 = closed in."""
+        p = RtAoParams(int(samples), float(radius), int(seed))
+        if aovs is None:
+            shape = self._aov_shape or (0, 0)
+            n = shape[0] * shape[1]
+            self._check(self._l.rt_render_ao(self._h, n, None, C.byref(p), None), "rt_render_ao")
+        else:
+            planes = numpy_to_aovs(aovs)
+            shape = aovs["depth"].shape
+            n = int(np.prod(shape))
+            self.sync()   # (a pass still in flight may be reading the buffer this one reuses)
+            d = self._device_buffer("ao_planes", max(n, 1) * 16 * 3)
+            b = RtAovBuffers()
+            for i, k in enumerate(("position", "normalDepth", "ids")):
+                a = np.ascontiguousarray(planes[k])
+                if a.nbytes and _hip().hipMemcpy(d + i * n * 16, a.ctypes.data, a.nbytes, 1) != 0:   # hipMemcpyHostToDevice
+                    raise RtError("render_ao: the planes could not be copied to the device")
+                setattr(b, k, d + i * n * 16)
+            self._check(self._l.rt_render_ao(self._h, n, C.byref(b), C.byref(p), None), "rt_render_ao")
+        out = np.empty(shape, np.float32)
+        self._check(self._l.rt_read_ao(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "rt_read_ao")
+        return out
+
     def render_aovs(self, pc, width, height, row0=0, rowStride=1, nRows=None, out_ptrs=None, sync=True):
         """First-hit planes of the tile's camera rays (rt_render_aovs), for the rows render() would render. Returns the dict of
         aovs_to_numpy, arrays shaped (nRows, width[, 3]); with `out_ptrs` (device pointers keyed by the RtAovBuffers field names,
@@ -728,6 +803,36 @@ def _hip():
         _hip_handle = h
     return _hip_handle
 
+
+
+def _device_ptr(x, name, nbytes, floats=True):
+    """The device address behind a tensor-like object (data_ptr(); checked where it says: fp32, contiguous, large enough) or an int."""
+    if isinstance(x, (int, np.integer)):
+        return int(x)
+    if not hasattr(x, "data_ptr"):
+        raise TypeError(f"{name}: neither an integer device pointer nor an object with data_ptr()")
+    if hasattr(x, "is_contiguous") and not x.is_contiguous():
+        raise ValueError(f"{name}: not contiguous")
+    if floats and hasattr(x, "dtype") and not str(x.dtype).endswith("float32"):
+        raise ValueError(f"{name}: {x.dtype}, not float32")
+    if hasattr(x, "numel") and hasattr(x, "element_size") and x.numel() * x.element_size() < nbytes:
+        raise ValueError(f"{name}: {x.numel() * x.element_size()} bytes, {nbytes} needed")
+    return int(x.data_ptr())
+
+
+def ao_rays(aovs, sample, samples=4, radius=0.5, seed=0):
+    """The rays render_ao() shoots for sample `sample` of the planes `aovs` (the dict render_aovs() returns), computed on the host
+    by the rule the device compiles (rt_ao_rays_host; no GPU): (origins (n, 3), dirs (n, 3), valid (n,) bool) in record order."""
+    planes = numpy_to_aovs(aovs)
+    n = int(np.prod(aovs["depth"].shape))
+    b = RtAovBuffers(**{k: np.ascontiguousarray(planes[k]).ctypes.data for k in ("position", "normalDepth", "ids")})
+    p = RtAoParams(int(samples), float(radius), int(seed))
+    o, d, v = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint8)
+    fp = C.POINTER(C.c_float)
+    if _capi.lib().rt_ao_rays_host(n, C.byref(b), C.byref(p), int(sample), o.ctypes.data_as(fp), d.ctypes.data_as(fp),
+                                   v.ctypes.data_as(C.POINTER(C.c_uint8))) != 0:
+        raise RtError("rt_ao_rays_host refused its arguments (samples 1..64, radius finite and > 0, sample < samples, at least one pixel)")
+    return o, d, v.astype(bool)
 
 
 def aovs_to_numpy(planes):
