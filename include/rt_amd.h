@@ -491,6 +491,46 @@ int  rt_query_occluded(rt_ctx* ctx, const RtRayBatch* d_rays, uint8_t* d_occlude
 int  rt_query_closest_host(rt_ctx* ctx, const RtRayBatch* rays, RtHit* hits);
 int  rt_query_occluded_host(rt_ctx* ctx, const RtRayBatch* rays, uint8_t* occluded);
 
+/* Radiance queries: the path-traced radiance along the caller's own rays ("Radiance queries"): what rt_render
+ * estimates for the pinhole camera's rays, for any batch of rays: baking, probes, other camera models, jittered pixels, rays
+ * made on the device. */
+typedef struct RtRadianceParams {
+    uint32_t samples;      /* >= 1: paths per ray; every sample starts with the same ray, its RNG state running on (raytrace.comp:571-573) */
+    uint32_t bounceLimit;  /* as rayTraceParams.bounceLimit; < 2^28 - 1 */
+    uint32_t progressive;  /* 0: out = mean; 1: blended with what d_radiance holds, weight 1 / (frameCount + 1), as rt_render */
+    uint32_t frameCount;   /* seeds the frame (startingSeed) and weighs the blend */
+} RtRadianceParams;
+void rt_radiance_params_default(RtRadianceParams* p);   /* 1, 8, 0, 0 */
+/* Contract. Ray i runs trace() (raytrace.comp:495-534) `samples` times from origin origins[3 i ..] and direction dirs[3 i ..].
+ * The direction is used as given: the estimator assumes unit length and nothing renormalises it. The RNG state of the ray's
+ * first draw is (d_ids ? d_ids[i] : i) + startingSeed, startingSeed = uint(random(frameCount) * 23892183) as rt_render computes
+ * it. d_radiance[4 i .. 4 i + 3] receives what rt_render gives a pixel (raytrace.comp:574-593): rgb the sum over the samples
+ * divided by (float)samples, blended with what d_radiance[4 i ..] holds when `progressive`, (1, 0, 1) where that is NaN or Inf;
+ * alpha 1.
+ *  - Hence a batch of the camera rays of a W x H frame (origin camInfo.pos, directions the rayDir plane of rt_render_aovs) with
+ *    ids gy * W + gx equals rt_render's image for the same constants, bit for bit.
+ *  - A ray's result depends on (origin, dir, id, params, env, scene) only: not on n, its place in the batch, the parts,
+ *    "camera_reuse", "light_queries" or the traversal knobs.
+ *  - tmax of the batch must be NULL: a reach limit on a path has no meaning. env NULL: the environment is off. The sphere and
+ *    object counts are the uploaded scene's, as in the ray queries; texture maps take part as in rendering.
+ * The pass always runs the multi-kernel pipeline (k_radiance_rays, rounds of the persistent-wave traversal and k_shade_rays,
+ * k_radiance_resolve), in parts as a dispatch of n paths would, ray i in path-state slot i. A batch of more than
+ * "radiance_max_kslots" x 1024 rays (rt_set_tuning) runs as consecutive pieces of at most that many rays, each in slots
+ * [0, piece), with the same bits. The struct, the params and env are read on the host. With the plain name the arrays, d_ids and
+ * d_radiance (16-byte aligned, as rt_render's image) are device pointers and the call is asynchronous on the ctx stream: the arrays stay valid and unchanged until the
+ * stream has passed it (the origins are read again wherever a sample ends). The _host name takes host arrays, stages them
+ * through a ctx buffer and blocks.
+ * It changes nothing a later rt_render, rt_render_aovs, rt_denoise or rt_temporal_accumulate produces or chooses: not the ctx
+ * framebuffer or its progressive history, not rt_last_pipeline, rt_last_parts or rt_ray_cost (no snapshot, no probe). Its
+ * counters go to the AOV passes' block, all fields of them: rt_get_counters' paths grows by n x samples. rt_last_kernel names
+ * the traversal kernel that ran.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch or NULL params; (n == 0 succeeds here
+ * and does nothing;) origins, dirs or the output NULL; tmax not NULL; samples 0; bounceLimit >= 2^28 - 1; n >= 2^30. */
+int  rt_query_radiance(rt_ctx* ctx, const RtRayBatch* d_rays, const uint32_t* d_ids, const RtRadianceParams* params,
+                       const EnvironmentData* env, float* d_radiance);
+int  rt_query_radiance_host(rt_ctx* ctx, const RtRayBatch* rays, const uint32_t* ids, const RtRadianceParams* params,
+                            const EnvironmentData* env, float* radiance);
+
 /* Ambient occlusion from first-hit planes ("Ray queries", "Ambient-occlusion plane"). Record i of the planes with
  * ids.w & 1 shoots `samples` occlusion queries: origin position + (normal * 1) * 0.00001 (the next-ray origin of shading),
  * direction the shader's cosineHemisphereDir about normalDepth.xyz (raytrace.comp:405-424, the arithmetic of the diffuse branch of
@@ -683,6 +723,8 @@ int  rt_get_trace_busy_ms(rt_ctx* ctx, double* msOut);
  *                    a dispatch goes into parts); 0 = always; more than a dispatch can have = never
  *   "wide_grid_pct"  ... and the share of the resident wide work-groups each part's launch takes while "lane_grid_pct" is 0
  *                    (10..100, default 40; 0 = the parts' share as it is)
+ *   "radiance_max_kslots"  rt_query_radiance: the most rays x 1024 of one piece of a batch; 0 (default) = the paths
+ *                    "frames_max_mslots" allows one dispatch
  *   "trace_variant"  0 = one ray per lane (k_trace), 1 = persistent waves (k_trace_pw)
  *   "refill", "mk_refill", "chunk", "w_setup", "w_leaf", "fast_lanes", "lds_stack", "blocks_per_cu",
  *   "tile_slots", "phase_stats": traversal scheduling details, see DESIGN.md

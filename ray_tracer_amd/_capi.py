@@ -106,6 +106,10 @@ class RtRayBatch(C.Structure):
     _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("tmax", C.c_void_p), ("n", C.c_uint32)]
 
 
+class RtRadianceParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("bounceLimit", C.c_uint32), ("progressive", C.c_uint32), ("frameCount", C.c_uint32)]
+
+
 class RtAoParams(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32)]
 
@@ -185,6 +189,9 @@ SYMBOLS = {
     "rt_query_occluded": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
     "rt_query_closest_host": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
     "rt_query_occluded_host": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
+    "rt_radiance_params_default": (None, [_P(RtRadianceParams)]),
+    "rt_query_radiance": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),
+    "rt_query_radiance_host": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),
     "rt_ao_params_default": (None, [_P(RtAoParams)]),
     "rt_render_ao": (C.c_int, [_vp, C.c_uint32, _P(RtAovBuffers), _P(RtAoParams), _vp]),
     "rt_read_ao": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),

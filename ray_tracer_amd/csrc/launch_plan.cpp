@@ -11,6 +11,7 @@ TuningChange set_tuning(Tuning& t, const std::string& k, int value) {
     if (k == "pipeline") { if (value < -1 || value > 1) return refuse("pipeline: -1 (auto), 0 or 1"); t.pipeline = value; }
     else if (k == "probe") { t.probe = value ? 1 : 0; }
     else if (k == "frames_max_mslots") { if (value < 1 || value > 1000) return refuse("frames_max_mslots: 1..1000 (millions of paths per multi-frame dispatch)"); t.framesMaxSlots = (uint64_t)value << 20; }
+    else if (k == "radiance_max_kslots") { if (value < 0 || value > (1 << 20)) return refuse("radiance_max_kslots: 1..1048576 (x 1024 rays per piece of a radiance query), 0 = as frames_max_mslots"); t.radianceMaxSlots = (uint64_t)value << 10; }
     else if (k == "frames_per_launch") { if (value < 0) return refuse("frames_per_launch >= 0"); t.framesPerLaunch = value; }
     else if (k == "camera_reuse") { t.cameraReuse = value ? 1 : 0; }
     else if (k == "light_queries") { t.lightQueries = value ? 1 : 0; return TuningChange{"", true}; }

@@ -30,6 +30,7 @@ struct Tuning {
     int objTreeMin = 48;    // rt_set_tuning("object_tree_min"): general-transform objects from which the object hierarchy is built (0 = never)
     int framesPerLaunch = 0; // rt_render_frames: most frames of a tile rendered by one launch (0 = as many as fit)
     uint64_t framesMaxSlots = RT_FRAMES_MAX_SLOTS;  // most paths of one multi-frame dispatch (rt_render_frames)
+    uint64_t radianceMaxSlots = 0;  // rt_set_tuning("radiance_max_kslots"): most rays of one piece of an rt_query_radiance batch (0 = framesMaxSlots)
     int cameraReuse = 1;    // rt_set_tuning("camera_reuse", 0): trace the camera ray of every sample
     int lightQueries = 1;   // rt_set_tuning("light_queries", 0): trace every NEE ray and cosine probe in full
     int lanes = 3;                        // rt_set_tuning("lanes", 1..RT_MAX_LANES)

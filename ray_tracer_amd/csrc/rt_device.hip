@@ -12,6 +12,7 @@
 #include "launch_plan.h"   // every decision about how a dispatch is run: this file gathers the facts, asks there, and launches
 #include "post_passes.h"   // likewise for the passes over finished frames: their checks, their input planes, the temporal history
 #include "ray_queries.h"   // ... and for the ray queries and the ambient-occlusion pass: their checks and the arithmetic of a batch
+#include "radiance_queries.h"   // ... and for the radiance queries: their checks, pieces, staging offsets and seed
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -450,7 +451,8 @@ int launch_fused(rt_ctx* c, const Dispatch& d, const FrameParams& fp, float4* fb
 // the work counter (counts[4]) must be zero when this is called
 // boundFromSeed: the rays' seed records carry a bound the traversal must start from (the ray queries' limits): only the
 // persistent-wave kernels read a seed's distance (k_trace runs the sphere loop itself and starts at the miss distance), so the kernel
-// is chosen as with "trace_variant" 1, whatever the knob says
+// is chosen as with "trace_variant" 1, whatever the knob says (the radiance queries ask for the same, so that every query pass runs one
+// kernel family)
 int launch_trace(rt_ctx* c, const Dispatch& d, uint32_t maxRays, const TraceArgs& ta, bool boundFromSeed = false) {
     if (maxRays == 0) return 0;
     const SceneFacts sf = scene_facts(c, d);
@@ -925,10 +927,26 @@ void make_parts(rt_ctx* c, const Dispatch& d, const PartSlices& p, uint32_t nSlo
     }
 }
 
+// What the rounds shade with and count into. A dispatch of pixels: k_shade / k_shade_maps and the rendering counters. A radiance
+// query (origins != nullptr): k_shade_rays / k_shade_rays_maps, which restart a sample from the caller's origins (`first`: the ray in
+// slot 0), and the AOV passes' counter block, which the ray-cost measurement never reads.
+struct ShadePass { DevCounters* counters; const float* origins; uint32_t first; };
+ShadePass pixel_shading(rt_ctx* c) { return ShadePass{(DevCounters*)c->counterBuf.p, nullptr, 0u}; }
+void launch_shade(const ShadePass& sp, uint32_t blocks, hipStream_t stream, const DevScene& sc, const PathState& ps, const ShadeArgs& sa, const FrameParams& fp) {
+    const bool maps = (sc.mapFlags & (RT_MAP_METALNESS | RT_MAP_BUMP)) != 0;
+    if (sp.origins) {
+        if (maps) hipLaunchKernelGGL(k_shade_rays_maps, dim3(blocks), dim3(RT_BLOCK), 0, stream, sc, ps, sa, fp, sp.origins, sp.first);
+        else hipLaunchKernelGGL(k_shade_rays, dim3(blocks), dim3(RT_BLOCK), 0, stream, sc, ps, sa, fp, sp.origins, sp.first);
+    } else {
+        if (maps) hipLaunchKernelGGL(k_shade_maps, dim3(blocks), dim3(RT_BLOCK), 0, stream, sc, ps, sa, fp);
+        else hipLaunchKernelGGL(k_shade, dim3(blocks), dim3(RT_BLOCK), 0, stream, sc, ps, sa, fp);
+    }
+}
+
 // The rounds of the multi-kernel pipeline: the parts fork from the ctx stream, each runs traversal, then shading, until none of its
 // paths is active, and they join it again
-int render_rounds(rt_ctx* c, const FrameParams& fp, Lane* lane, int nLanes) {
-    DevCounters* dc = (DevCounters*)c->counterBuf.p;
+int render_rounds(rt_ctx* c, const FrameParams& fp, Lane* lane, int nLanes, const ShadePass& sp) {
+    DevCounters* dc = sp.counters;
     int rc = 0;
     if (nLanes > 1) {
         RT_HIP(c, hipEventRecord(c->forkEvent, c->stream));
@@ -953,10 +971,9 @@ int render_rounds(rt_ctx* c, const FrameParams& fp, Lane* lane, int nLanes) {
             hipLaunchKernelGGL(k_zero_counts, dim3(1), dim3(64), 0, stream, counts + nxt, counts + 2 + nxt, counts + 4, counts + 5 + nxt, counts + 7 + nxt);
             TraceArgs ta{rays[cur], counts + 2 + cur, nullptr, nullptr, dc, counts + 5 + cur, counts + 7 + cur, L.n};
             const uint64_t ubRays = std::min<uint64_t>((uint64_t)L.ubActive * 3, (uint64_t)L.n * 3);
-            if ((rc = launch_trace(c, L.d, (uint32_t)ubRays, ta))) break;
+            if ((rc = launch_trace(c, L.d, (uint32_t)ubRays, ta, sp.origins != nullptr))) break;   // (a radiance query: the persistent-wave kernels whatever "trace_variant" says, as the ray queries)
             ShadeArgs sa{active[cur], counts + cur, active[nxt], rays[nxt], counts + nxt, counts + 2 + nxt, (ShadeStatStripe*)c->shadeStatBuf.p, counts + 5 + nxt, counts + 7 + nxt, L.n};
-            if (L.d.sc.mapFlags & (RT_MAP_METALNESS | RT_MAP_BUMP)) hipLaunchKernelGGL(k_shade_maps, dim3((L.ubActive + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, L.d.sc, c->ps, sa, fp);
-            else hipLaunchKernelGGL(k_shade, dim3((L.ubActive + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, L.d.sc, c->ps, sa, fp);
+            launch_shade(sp, (L.ubActive + RT_BLOCK - 1) / RT_BLOCK, stream, L.d.sc, c->ps, sa, fp);
             L.cur = nxt;
             if (L.pollPending && hipEventQuery(L.poll) == hipSuccess) {
                 L.pollPending = false;
@@ -1002,7 +1019,7 @@ int render_parts(rt_ctx* c, const FrameParams& fp, const Dispatch& d, uint32_t n
     }
     RT_HIP(c, hipGetLastError());
     if (fp.samples > 0)
-        if (int rc = render_rounds(c, fp, lane, nLanes)) return rc;
+        if (int rc = render_rounds(c, fp, lane, nLanes, pixel_shading(c))) return rc;
     const uint32_t blocksPix = (fp.nPixels + RT_BLOCK - 1) / RT_BLOCK;
     if (fp.nFrames > 1u) hipLaunchKernelGGL(k_blend_frames, dim3(blocksPix), dim3(RT_BLOCK), 0, c->stream, c->ps, fp, fb);
     else hipLaunchKernelGGL(k_resolve, dim3(blocksPix), dim3(RT_BLOCK), 0, c->stream, c->ps, fp, fb);
@@ -1392,6 +1409,104 @@ int rt_query_closest(rt_ctx* c, const RtRayBatch* d_rays, RtHit* d_hits) { retur
 int rt_query_occluded(rt_ctx* c, const RtRayBatch* d_rays, uint8_t* d_occluded) { return query_device(c, "rt_query_occluded", d_rays, d_occluded, true); }
 int rt_query_closest_host(rt_ctx* c, const RtRayBatch* rays, RtHit* hits) { return query_host(c, "rt_query_closest_host", rays, hits, false); }
 int rt_query_occluded_host(rt_ctx* c, const RtRayBatch* rays, uint8_t* occluded) { return query_host(c, "rt_query_occluded_host", rays, occluded, true); }
+}  // extern "C"
+
+// ---- radiance queries (radiance_queries.h has the checks and the arithmetic; DESIGN.md, "Radiance queries")
+namespace {
+// One piece of a batch through the multi-kernel pipeline, as render_parts runs a dispatch of pixels: ray generation per part,
+// k_init_counts, the rounds, k_radiance_resolve. Nothing of it is reported as a dispatch: rt_last_parts stays.
+int radiance_parts(rt_ctx* c, const FrameParams& fp, const Dispatch& d, const RadianceRays& q, float4* out) {
+    const int nLanes = ensure_part_streams(c, choose_parts(c->tune, c->meas, scene_facts(c, d), dispatch_facts(d, &fp, false)));
+    Lane lane[RT_MAX_LANES];
+    make_parts(c, d, slice_parts(c->tune, q.n, 1u, nLanes), q.n, nLanes, lane);
+    for (int l = 0; l < nLanes; l++) {
+        const Lane& L = lane[l];
+        if (!L.n) continue;
+        hipLaunchKernelGGL(k_radiance_rays, dim3((L.n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, c->stream, d.sc, c->ps,
+                           c->q.active[0] + L.begin, c->q.rays[0] + 3 * (size_t)L.begin, fp, q, L.begin, L.begin + L.n);
+        hipLaunchKernelGGL(k_init_counts, dim3(1), dim3(64), 0, c->stream, L.d.counts, L.n);
+    }
+    RT_HIP(c, hipGetLastError());
+    if (int rc = render_rounds(c, fp, lane, nLanes, ShadePass{(DevCounters*)c->aovCounterBuf.p, q.origins, q.first})) return rc;
+    hipLaunchKernelGGL(k_radiance_resolve, dim3((q.n + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, c->stream, c->ps, fp, q.first, out);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The most rays of one piece (rt_set_tuning("radiance_max_kslots"); by default what "frames_max_mslots" allows a dispatch)
+uint64_t radiance_max_slots(const rt_ctx* c) { return c->tune.radianceMaxSlots ? c->tune.radianceMaxSlots : c->tune.framesMaxSlots; }
+
+int radiance_device(rt_ctx* c, const char* fn, const RtRayBatch* rays, const uint32_t* d_ids, const RtRadianceParams* params,
+                    const EnvironmentData* env, float* d_radiance) {
+    if (!c) return -1;
+    const std::string refusal = check_radiance_query(fn, c->sc.nodes != nullptr, rays, params, d_radiance);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = rays->n;
+    if (n == 0) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    const uint64_t maxSlots = radiance_max_slots(c);
+    const uint32_t cap = std::min(n, radiance_piece_cap(maxSlots));
+    // the pieces' paths live in slots [0, cap) on the ctx stream: growing the path state frees the old one, so that waits for the device first
+    if (c->capacity < cap || !c->stateBuf.p) RT_HIP(c, hipStreamSynchronize(c->stream));
+    int rc = ensure_state(c, cap);
+    if (rc) return rc;
+    // no per-pixel statistics, no phase statistics, launches counted with the AOV passes'; the uploaded scene's counts
+    Dispatch d = one_part(c, c->sc, false);
+    d.phaseStats = 0; d.launches = &c->rep.aovLaunches; d.pipeline = 0;
+    FrameParams fp{};   // (the camera fields are unused: the rays are the caller's)
+    fp.startingSeed = radiance_starting_seed(params->frameCount);
+    fp.samples = params->samples;
+    fp.bounceLimit = params->bounceLimit;
+    fp.progressive = params->progressive;
+    fp.frameCount = params->frameCount;
+    fp.nFrames = 1;
+    fp.camReuse = c->tune.cameraReuse ? 1u : 0u;
+    fp.debug = -1;
+    if (env) fp.env = *env;   // (NULL: environment.enabled == 0)
+    fp.sampleMap = nullptr;
+    const uint32_t pieces = radiance_piece_count(n, maxSlots);
+    for (uint32_t k = 0; k < pieces; k++) {
+        const RadiancePiece pc = radiance_piece(n, maxSlots, k);
+        fp.nPixels = pc.n;
+        const RadianceRays q{rays->origins, rays->dirs, d_ids, pc.first, pc.n};
+        if ((rc = radiance_parts(c, fp, d, q, (float4*)d_radiance))) return rc;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+int rt_query_radiance(rt_ctx* c, const RtRayBatch* d_rays, const uint32_t* d_ids, const RtRadianceParams* params, const EnvironmentData* env,
+                      float* d_radiance) {
+    return radiance_device(c, "rt_query_radiance", d_rays, d_ids, params, env, d_radiance);
+}
+
+// The host-memory form: the arrays go up into the ctx staging buffer (radiance_staging), with what `radiance` holds when the
+// result is blended with it, the device form runs on the copies, the result comes back; blocks.
+int rt_query_radiance_host(rt_ctx* c, const RtRayBatch* rays, const uint32_t* ids, const RtRadianceParams* params, const EnvironmentData* env,
+                           float* radiance) {
+    if (!c) return -1;
+    const char* const fn = "rt_query_radiance_host";
+    const std::string refusal = check_radiance_query(fn, c->sc.nodes != nullptr, rays, params, radiance);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = rays->n;
+    if (n == 0) return 0;
+    const RadianceStaging g = radiance_staging(n, ids != nullptr);
+    RT_HIP(c, hipSetDevice(c->device));
+    if (c->queryHostBuf.bytes < g.bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees arrays a pass in flight may be using
+    int rc = dev_alloc(c, c->queryHostBuf, g.bytes);
+    if (rc) return rc;
+    char* const b = (char*)c->queryHostBuf.p;
+    RT_HIP(c, hipMemcpyAsync(b + g.origins, rays->origins, g.vecBytes, hipMemcpyHostToDevice, c->stream));
+    RT_HIP(c, hipMemcpyAsync(b + g.dirs, rays->dirs, g.vecBytes, hipMemcpyHostToDevice, c->stream));
+    if (ids) RT_HIP(c, hipMemcpyAsync(b + g.ids, ids, g.idBytes, hipMemcpyHostToDevice, c->stream));
+    if (params->progressive) RT_HIP(c, hipMemcpyAsync(b + g.out, radiance, g.outBytes, hipMemcpyHostToDevice, c->stream));
+    const RtRayBatch dev{(const float*)(b + g.origins), (const float*)(b + g.dirs), nullptr, n};
+    if ((rc = radiance_device(c, fn, &dev, ids ? (const uint32_t*)(b + g.ids) : nullptr, params, env, (float*)(b + g.out)))) return rc;
+    RT_HIP(c, hipMemcpyAsync(radiance, b + g.out, g.outBytes, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
 
 // `samples` rounds of {k_ao_rays, the traversal, k_ao_count}, all enqueued without waiting for the device, then k_ao_resolve
 int rt_render_ao(rt_ctx* c, uint32_t nPixels, const RtAovBuffers* d_aovs, const RtAoParams* params, float* d_ao) {
@@ -1732,12 +1847,13 @@ int rt_get_counters(rt_ctx* c, RtCounters* out) {
     RT_HIP(c, hipMemcpyAsync(&h, c->counterBuf.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipMemcpyAsync(&a, c->aovCounterBuf.p, sizeof(a), hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    // the AOV passes' block holds traversal work only (rt_render_aovs)
+    // the AOV passes' block: traversal work only from rt_render_aovs, the guides and the ray queries (their other fields stay 0), and
+    // every field from the radiance queries
     out->boxTests = h.boxTests + a.boxTests; out->triTests = h.triTests + a.triTests;
     out->raysTraced = h.raysTraced + a.raysTraced; out->raysHit = h.raysHit + a.raysHit;
-    out->raysReference = h.raysReference; out->paths = h.paths; out->segments = h.segments;
+    out->raysReference = h.raysReference + a.raysReference; out->paths = h.paths + a.paths; out->segments = h.segments + a.segments;
     out->traceLaunches = c->rep.traceLaunchesTotal + c->rep.aovLaunches;
-    out->emitterTests = h.emitterTests;
+    out->emitterTests = h.emitterTests + a.emitterTests;
     out->skippedBoxTests = h.skippedBoxTests + a.skippedBoxTests;
     if (c->tune.phaseStats) {
         unsigned long long ps[21];

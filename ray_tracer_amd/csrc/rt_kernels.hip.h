@@ -1446,9 +1446,14 @@ struct ShadeArgs {
 // queue entry says so (RAY_MAIN_BLANK); a finished sample's successor reads the kept camera hit where it is (camHit) instead of a
 // copy of it in hit(RAY_MAIN); `total` is stored only when its bits changed. The fused kernels, whose records stay in the
 // wave's own cache lines and whose registers are spilling already, keep the plain form of these three spots.
-template <bool MAPS = false, bool QUEUED = false>
+// RAYS (k_shade_rays, k_shade_rays_maps: rt_query_radiance): the paths start from the caller's rays, not from the camera. The
+// one spot past ray generation that knows where a path starts is the restart of the next sample: it takes its origin from
+// rayOrigins[3 slot ..] (the caller's packed origins, offset to the piece's first ray; alive for the whole dispatch by contract)
+// instead of fp.camPos. A compile-time switch: the other instantiations are what they were.
+template <bool MAPS = false, bool QUEUED = false, bool RAYS = false>
 __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& ps, const FrameParams& fp, uint32_t slot, bool& alive,
-                                           uint32_t& auxMask, uint32_t& refRays, uint32_t& nPaths, uint32_t& emitTests, bool withMask = true) {
+                                           uint32_t& auxMask, uint32_t& refRays, uint32_t& nPaths, uint32_t& emitTests, bool withMask = true,
+                                           const float* rayOrigins = nullptr) {
     bool wantAux = false;  // a diffuse bounce whose MIS the next segment finishes (raytrace.comp:443-460)
     auxMask = 0;
     rt_vec3 auxOrigin = rt_v3(0, 0, 0), auxL = auxOrigin, auxC = auxOrigin;  // probe rays of this bounce (diffuse only)
@@ -1624,7 +1629,12 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
         if (samplesDone < __float_as_uint(cD.w)) {
             // next sample of this pixel: same primary ray (kept by init_path rather than derived from the slot again: the
             // whole wave pays for this branch whenever one lane finishes a sample), RNG state runs on (:571-573)
-            ro = rt_v3(fp.camPos[0], fp.camPos[1], fp.camPos[2]);
+            if (RAYS) {
+                const float* const o = rt_global(rayOrigins) + 3 * (size_t)slot;
+                ro = rt_v3(o[0], o[1], o[2]);
+            } else {
+                ro = rt_v3(fp.camPos[0], fp.camPos[1], fp.camPos[2]);
+            }
             rd = f4xyz(cD);
             att = rt_v3(1.f, 1.f, 1.f);
             total = rt_v3(0.f, 0.f, 0.f);
@@ -1697,8 +1707,9 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
     }
 }
 
-template <bool MAPS>
-__device__ __forceinline__ void shade_block(const DevScene& sc, const PathState& ps, const ShadeArgs& sa, const FrameParams& fp) {
+template <bool MAPS, bool RAYS = false>
+__device__ __forceinline__ void shade_block(const DevScene& sc, const PathState& ps, const ShadeArgs& sa, const FrameParams& fp,
+                                            const float* rayOrigins = nullptr) {
     __shared__ uint32_t s_cnt[RT_BLOCK / RT_WAVE][8];  // per wave: alive, main rays, refRays, paths, segments, emitter tests, NEE rays, cosine probes
     __shared__ uint32_t s_base[4];
     const uint32_t n = *sa.inCount;
@@ -1714,7 +1725,7 @@ __device__ __forceinline__ void shade_block(const DevScene& sc, const PathState&
     if (live) {
         slot = sa.inActive[gid];
         path = slot != 0xffffffffu;  // RT_QUEUE_HOLE
-        if (path) shade_path<MAPS, true>(sc, ps, fp, slot, alive, auxMask, refRays, nPaths, emitTests);
+        if (path) shade_path<MAPS, true, RAYS>(sc, ps, fp, slot, alive, auxMask, refRays, nPaths, emitTests, true, rayOrigins);
     }
 
     // Queue compaction: ranks inside a wave from ballots, wave offsets through LDS, and ONE atomic
@@ -1758,6 +1769,14 @@ __device__ __forceinline__ void shade_block(const DevScene& sc, const PathState&
 __global__ __launch_bounds__(RT_BLOCK, RT_SHADE_BLOCKS) void k_shade(DevScene sc, PathState ps, ShadeArgs sa, FrameParams fp) { shade_block<false>(sc, ps, sa, fp); }
 // the same for a scene that binds a metalness or a bump map (DevScene::mapFlags)
 __global__ __launch_bounds__(RT_BLOCK, RT_SHADE_BLOCKS) void k_shade_maps(DevScene sc, PathState ps, ShadeArgs sa, FrameParams fp) { shade_block<true>(sc, ps, sa, fp); }
+// the same two for paths that start from the caller's rays (rt_query_radiance). origins: the batch's packed origins; first: the
+// ray in slot 0 of the piece
+__global__ __launch_bounds__(RT_BLOCK, RT_SHADE_BLOCKS) void k_shade_rays(DevScene sc, PathState ps, ShadeArgs sa, FrameParams fp, const float* origins, uint32_t first) {
+    shade_block<false, true>(sc, ps, sa, fp, origins + 3 * (size_t)first);
+}
+__global__ __launch_bounds__(RT_BLOCK, RT_SHADE_BLOCKS) void k_shade_rays_maps(DevScene sc, PathState ps, ShadeArgs sa, FrameParams fp, const float* origins, uint32_t first) {
+    shade_block<true, true>(sc, ps, sa, fp, origins + 3 * (size_t)first);
+}
 
 // ---------------------------------------------------------------- k_resolve
 // raytrace.comp:574-593. `rgba` holds the previous frame when progressive
@@ -2136,6 +2155,51 @@ __global__ __launch_bounds__(RT_BLOCK) void k_ao_resolve(AoArgs a, float* out) {
     const uint32_t i = blockIdx.x * RT_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     out[i] = (a.ids[i].w & 1u) ? (float)(a.samples - a.occluded[i]) / (float)a.samples : 1.f;
+}
+
+// ---------------------------------------------------------------- radiance queries (rt_query_radiance)
+// The multi-kernel pipeline on the caller's rays ("Radiance queries"): k_radiance_rays is k_raygen + init_path with the
+// ray and the seed taken from the batch, the rounds are k_trace_pw + k_shade_rays, k_radiance_resolve is k_resolve into the
+// caller's array. Ray first + i of the batch lives in slot i of the piece.
+struct RadianceRays {
+    const float* origins;   // packed, 3 floats per ray of the batch
+    const float* dirs;
+    const uint32_t* ids;    // per ray of the batch, or NULL: the ray's index
+    uint32_t first, n;      // the piece: rays [first, first + n) in slots [0, n)
+};
+
+// slots [slotBegin, slotEnd) of the piece: one part (k_raygen)
+__global__ __launch_bounds__(RT_BLOCK) void k_radiance_rays(DevScene sc, PathState ps, uint32_t* activeOut, uint32_t* raysOut, FrameParams fp,
+                                                            RadianceRays q, uint32_t slotBegin, uint32_t slotEnd) {
+    const uint32_t pos = blockIdx.x * RT_BLOCK + threadIdx.x;
+    const uint32_t slot = slotBegin + pos;
+    if (slot >= slotEnd || slot >= q.n) return;
+    const size_t ray = (size_t)q.first + slot;
+    const float* const o = q.origins + 3 * ray;
+    const float* const d = q.dirs + 3 * ray;
+    const rt_vec3 ro = rt_v3(o[0], o[1], o[2]), rd = rt_v3(d[0], d[1], d[2]);
+    const uint32_t id = q.ids ? q.ids[ray] : (uint32_t)ray;
+    ps.rayO()[slot] = mk4(ro, 1.f);                                                                       // misWeight = 1
+    ps.rayD()[slot] = mk4u(rd, id + fp.startingSeed);                                                     // RNG seed (:564)
+    ps.camDir()[slot] = mk4u(rd, fp.samples);
+    ps.hit(RAY_MAIN)[slot] = sphere_seed(sc, ro, rd);
+    ps.att()[slot] = make_float4(1.f, 1.f, 1.f, __uint_as_float(0u));                                   // j = 0
+    ps.total()[slot] = make_float4(0.f, 0.f, 0.f, __uint_as_float(0u));                                 // sample 0
+    ps.accum()[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
+    ps.statBox()[slot] = 0;
+    ps.statTri()[slot] = 0;
+    activeOut[pos] = slot;
+    raysOut[pos] = slot << 2;   // with its seed record (RAY_MAIN)
+}
+
+// blend_frame and the store of resolve_pixel for the piece's rays; out holds the previous result when progressive
+__global__ __launch_bounds__(RT_BLOCK) void k_radiance_resolve(PathState ps, FrameParams fp, uint32_t first, float4* out) {
+    const uint32_t slot = blockIdx.x * RT_BLOCK + threadIdx.x;
+    if (slot >= fp.nPixels) return;
+    float4* const px = out + (size_t)first + slot;
+    const float4 oldc = fp.progressive ? *px : make_float4(0.f, 0.f, 0.f, 0.f);
+    const rt_vec3 fin = blend_frame(fp, fp.samples, fp.frameCount, oldc, ps.accum()[slot]);
+    *px = make_float4(fin.x, fin.y, fin.z, 1.f);
 }
 
 // ---------------------------------------------------------------- a-trous denoiser (rt_denoise)

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtRayBatch,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtRadianceParams, RtRayBatch,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -522,6 +522,84 @@ class Renderer:
         """Whether each ray hits anything nearer than its limit (rt_query_occluded): a bool array for numpy inputs, one byte per ray
         in `out` for device memory, as query_closest takes it."""
         return self._query("occluded", origins, dirs, tmax, n, out, sync)
+
+    def query_radiance(self, origins, dirs, samples=1, bounces=8, ids=None, progressive=False, frame=0, environment=None, n=None, out=None,
+                       sync=True):
+        """The path-traced radiance along each of the caller's rays (rt_query_radiance; DESIGN.md, "Radiance queries"): `samples`
+        paths of at most `bounces` bounces per ray, the ray's RNG state seeded from ids[i] (or i) and `frame`; `environment`: an
+        EnvironmentData (a PushConstants' .environment), None = off. The directions are used as given (unit length is assumed).
+        (n, 3) float32 numpy arrays (and (n,) uint32 ids) go through rt_query_radiance_host and come back as an (n, 4) float32
+        array; with `progressive`, `out` is the previous result (n, 4) the new one is blended with, and is not modified. Torch
+        tensors on the device (anything with data_ptr(): fp32, contiguous; ids uint32 or int32) or integer device pointers with n=
+        go through the asynchronous entry point into `out` (device memory, 16 bytes per ray, the previous result when
+        `progressive`), and sync=False is allowed. A wrong dtype or shape raises before the library is called."""
+        if environment is not None and not isinstance(environment, _capi.EnvironmentData):
+            raise TypeError("environment: an EnvironmentData (PushConstants.environment) or None")
+        if int(samples) < 0 or int(bounces) < 0 or int(frame) < 0:
+            raise ValueError("samples, bounces and frame are unsigned")
+        p = RtRadianceParams(int(samples), int(bounces), 1 if progressive else 0, int(frame) & 0xFFFFFFFF)
+        env = C.byref(environment) if environment is not None else None
+        on_device = [hasattr(x, "data_ptr") or isinstance(x, (int, np.integer)) for x in (origins, dirs)]
+        if not any(on_device):
+            o, d = np.asarray(origins), np.asarray(dirs)
+            for name, a in (("origins", o), ("dirs", d)):
+                if a.dtype != np.float32:
+                    raise TypeError(f"{name}: {a.dtype}, not float32")
+                if a.ndim != 2 or a.shape[1] != 3:
+                    raise ValueError(f"{name}: shape {a.shape}, not (n, 3)")
+            if d.shape != o.shape:
+                raise ValueError(f"origins {o.shape} and dirs {d.shape}: not one (n, 3) pair")
+            count = o.shape[0]
+            i = None
+            if ids is not None:
+                i = np.asarray(ids)
+                if i.dtype != np.uint32:
+                    raise TypeError(f"ids: {i.dtype}, not uint32")
+                if i.shape != (count,):
+                    raise ValueError(f"ids: shape {i.shape}, not ({count},)")
+                i = np.ascontiguousarray(i)
+            if not sync:
+                raise ValueError("sync=False goes with device-pointer inputs")
+            if out is not None and not progressive:
+                raise ValueError("out= with host arrays is the previous result of a progressive query")
+            if progressive:
+                if out is None:
+                    raise ValueError("progressive needs out=: the previous result")
+                prev = np.asarray(out)
+                if prev.dtype != np.float32:
+                    raise TypeError(f"out: {prev.dtype}, not float32")
+                if prev.shape != (count, 4):
+                    raise ValueError(f"out: shape {prev.shape}, not ({count}, 4)")
+                res = np.array(prev, dtype=np.float32, order="C", copy=True)
+            else:
+                res = np.zeros((count, 4), np.float32)
+            o, d = np.ascontiguousarray(o), np.ascontiguousarray(d)
+            batch = RtRayBatch(o.ctypes.data, d.ctypes.data, None, count)
+            self._check(self._l.rt_query_radiance_host(self._h, C.byref(batch), i.ctypes.data if i is not None else None, C.byref(p), env,
+                                                       res.ctypes.data), "rt_query_radiance_host")
+            return res
+        if not all(on_device):
+            raise ValueError("origins and dirs must both be host arrays or both be device memory")
+        if out is None:
+            raise ValueError("device-pointer inputs need out=: device memory for the results")
+        if n is None:
+            if not hasattr(origins, "numel"):
+                raise ValueError("integer device pointers need n=")
+            if hasattr(origins, "shape") and (len(origins.shape) != 2 or origins.shape[1] != 3):
+                raise ValueError(f"origins: shape {tuple(origins.shape)}, not (n, 3)")
+            n = int(origins.numel()) // 3
+        n = int(n)
+        if hasattr(dirs, "shape") and hasattr(origins, "shape") and tuple(dirs.shape) != tuple(origins.shape):
+            raise ValueError(f"origins {tuple(origins.shape)} and dirs {tuple(dirs.shape)}: not one (n, 3) pair")
+        if ids is not None and hasattr(ids, "dtype") and not str(ids.dtype).endswith(("uint32", "int32")):
+            raise TypeError(f"ids: {ids.dtype}, not uint32 (or int32)")
+        batch = RtRayBatch(_device_ptr(origins, "origins", 12 * n), _device_ptr(dirs, "dirs", 12 * n), None, n)
+        d_ids = None if ids is None else _device_ptr(ids, "ids", 4 * n, floats=False)
+        self._check(self._l.rt_query_radiance(self._h, C.byref(batch), d_ids, C.byref(p), env, C.c_void_p(_device_ptr(out, "out", 16 * n))),
+                    "rt_query_radiance")
+        if sync:
+            self.sync()
+        return None
 
     def render_ao(self, aovs=None, samples=4, radius=0.5, seed=0):
         """The ambient-occlusion plane of first-hit planes (rt_render_ao): `samples` cosine-weighted occlusion queries of reach

@@ -1,0 +1,41 @@
+"""What the radiance queries (rt_query_radiance and its _host form) refuse before anything is allocated, the pieces a batch runs in,
+the staging offsets of the _host form and the frame's seed (ray_tracer_amd/csrc/radiance_queries.h), on the CPU:
+tests/radiance_queries_check.cpp provokes every refusal with made-up addresses, in the stated order, with its message, covers
+[0, n) with the pieces for n = 0, 1, 1023, 1024, 1025 and 3 x 1024 + 5 at "radiance_max_kslots" 1, checks that the staged arrays are
+aligned and do not overlap with and without ids, and prints startingSeed for frameCount 0, 3 and 2^32 - 1, which is compared here
+with the oracle's random() pushed through uint(random(frameCount) * 23892183.f)."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ray_tracer_amd", "csrc")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_radiance_query_checks_on_the_cpu(tmp_path, built):
+    """radiance_queries.cpp + the checker with plain g++ (no hipcc, no HIP runtime, no device), under ASan and UBSan where they
+    are installed."""
+    exe = str(tmp_path / "radiance_queries_check")
+    cc = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
+          os.path.join(CSRC, "radiance_queries.cpp"), os.path.join(ROOT, "tests", "radiance_queries_check.cpp"), "-o", exe]
+    b = subprocess.run(cc + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True, timeout=600)
+    if b.returncode != 0 and ("asan" in b.stderr.lower() or "ubsan" in b.stderr.lower()):
+        b = subprocess.run(cc, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    assert "warning" not in b.stderr, b.stderr[-3000:]
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, (p.stdout + p.stderr)[-4000:]
+    assert "radiance queries ok" in p.stdout
+    seeds = {int(f): int(s) for f, s in re.findall(r"^seed (\d+) (\d+)$", p.stdout, re.M)}
+    assert sorted(seeds) == [0, 3, 2**32 - 1], p.stdout
+    for frame, seed in seeds.items():
+        _, r = pyoracle.random(frame)
+        assert seed == int(np.uint32(np.float32(r) * np.float32(23892183.0))), (frame, seed, r)
+    assert seeds[0] == 721543 and seeds[3] == 11858218   # (tests/test_paths_float64.py: test_frame_count_seeds has them by hand)
