@@ -531,6 +531,53 @@ int  rt_query_radiance(rt_ctx* ctx, const RtRayBatch* d_rays, const uint32_t* d_
 int  rt_query_radiance_host(rt_ctx* ctx, const RtRayBatch* rays, const uint32_t* ids, const RtRadianceParams* params,
                             const EnvironmentData* env, float* radiance);
 
+/* Point queries ("Point queries"): how far each of the caller's points is from the scene, and where the nearest surface
+ * is. The search is not a ray's: a best-first descent pruned by box distance, in a kernel of its own (k_nearest_points) over the
+ * tables the scene already has on the device. */
+typedef struct RtPointBatch {
+    const float* points;   /* n x 3 floats, packed */
+    const float* maxDist;  /* n floats, or NULL: no limit */
+    uint32_t n;
+} RtPointBatch;
+typedef struct RtNearest {
+    float dst;              /* world distance; RT_MISS_DST when found == 0 */
+    uint32_t found, isSphere;
+    uint32_t objectIndex;   /* object, or sphere index when isSphere */
+    uint32_t triIndex;      /* as RtHit.triHitIndex numbers triangles */
+    float uv[2];            /* barycentrics of the point on that triangle; 0 for a sphere */
+    float point[3];         /* the closest point, world space */
+    uint32_t _pad[2];       /* 0: the record is 48 bytes, three 16-byte stores */
+} RtNearest;                /* not found: dst = RT_MISS_DST, everything else 0 */
+/* Contract (include/rt_point_query.h states the rule; both sides compile it). The scene's surfaces are every sphere with
+ * radius > 0 (the sphere table's zeroed slots are none) and every triangle of every object, its corners placed in fp32 by the
+ * object's forward matrix (rt_xform_point; an identity object's corners are used as they are). Distances are Euclidean in world
+ * space whatever the object's scale or shear; frontOnly, materials and alpha maps play no part. Point i with limit T (maxDist[i];
+ * none when maxDist is NULL) keeps a bound best2 started at fl(T * T) (+inf without a limit); a primitive whose squared distance
+ * (rt_point_sphere, rt_point_triangle) is strictly less than best2 replaces the answer; found = 1 when one did and
+ * dst = rt_sqrt(best2). A limit that is NaN or <= 0 gives the not-found record without a search.
+ *  - dst and found do not depend on the order primitives are visited in, nor on the BVH: rt_query_nearest equals
+ *    rt_nearest_exhaustive_host in both, bit for bit (the traversal discards a subtree only where the derivation in DESIGN.md
+ *    shows that it cannot hold a nearer primitive).
+ *  - Which primitive is reported where several are equally near in fp32 (a closest point on a shared edge or vertex) depends on
+ *    the order: it is a minimiser, not a particular one; point and uv belong to the one reported (point = w a + u b + v c of
+ *    its world corners, w = (1 - u) - v).
+ * rt_query_nearest: the struct is read on the host, its arrays and d_out are device pointers, asynchronous on the ctx stream (the
+ * arrays stay valid and unchanged until the stream has passed it). rt_query_nearest_host takes host arrays, stages them through a
+ * ctx buffer and blocks. One lane per point, no path state. rt_last_kernel names the instantiation that ran: k_nearest_points<24,
+ * true> while the scene's deepest BVH leaf is at most 24 levels down, k_nearest_points<64, false> beyond (a scene deeper than
+ * that is refused). The pass adds to the AOV passes' counter block: boxTests (box distances evaluated), triTests
+ * (rt_point_triangle calls), raysTraced (points searched), raysHit (points found), and changes nothing a later rt_render,
+ * rt_render_aovs, rt_denoise, rt_temporal_accumulate or ray query produces or chooses. It reads the tables of the scene as they
+ * are: after rt_update_objects or rt_update_points, the moved and the refit ones.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch; points or the output NULL with n > 0;
+ * n >= 2^30. n == 0 succeeds and does nothing.
+ * rt_nearest_exhaustive_host: the same rule in a plain loop over the host arrays: every sphere in index order, then every triangle
+ * of every object in index order, no pruning; no ctx, no GPU (the BVH only says which triangles an object has). -1: a NULL
+ * argument, n >= 2^30, or arrays that index out of range. */
+int  rt_query_nearest(rt_ctx* ctx, const RtPointBatch* d_points, RtNearest* d_out);
+int  rt_query_nearest_host(rt_ctx* ctx, const RtPointBatch* points, RtNearest* out);
+int  rt_nearest_exhaustive_host(const RtSceneArrays* scene, const RtPointBatch* points, RtNearest* out);
+
 /* Ambient occlusion from first-hit planes ("Ray queries", "Ambient-occlusion plane"). Record i of the planes with
  * ids.w & 1 shoots `samples` occlusion queries: origin position + (normal * 1) * 0.00001 (the next-ray origin of shading),
  * direction the shader's cosineHemisphereDir about normalDepth.xyz (raytrace.comp:405-424, the arithmetic of the diffuse branch of

@@ -106,6 +106,15 @@ class RtRayBatch(C.Structure):
     _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("tmax", C.c_void_p), ("n", C.c_uint32)]
 
 
+class RtPointBatch(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("maxDist", C.c_void_p), ("n", C.c_uint32)]
+
+
+class RtNearest(C.Structure):
+    _fields_ = [("dst", C.c_float), ("found", C.c_uint32), ("isSphere", C.c_uint32), ("objectIndex", C.c_uint32),
+                ("triIndex", C.c_uint32), ("uv", C.c_float * 2), ("point", C.c_float * 3), ("_pad", C.c_uint32 * 2)]
+
+
 class RtRadianceParams(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("bounceLimit", C.c_uint32), ("progressive", C.c_uint32), ("frameCount", C.c_uint32)]
 
@@ -189,6 +198,9 @@ SYMBOLS = {
     "rt_query_occluded": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
     "rt_query_closest_host": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
     "rt_query_occluded_host": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
+    "rt_query_nearest": (C.c_int, [_vp, _P(RtPointBatch), _vp]),
+    "rt_query_nearest_host": (C.c_int, [_vp, _P(RtPointBatch), _vp]),
+    "rt_nearest_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtPointBatch), _vp]),
     "rt_radiance_params_default": (None, [_P(RtRadianceParams)]),
     "rt_query_radiance": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),
     "rt_query_radiance_host": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),

@@ -13,6 +13,8 @@
 #include "post_passes.h"   // likewise for the passes over finished frames: their checks, their input planes, the temporal history
 #include "ray_queries.h"   // ... and for the ray queries and the ambient-occlusion pass: their checks and the arithmetic of a batch
 #include "radiance_queries.h"   // ... and for the radiance queries: their checks, pieces, staging offsets and seed
+#include "rt_nearest.hip.h"     // the kernel of the point queries; point_queries.h: their checks, the arithmetic of a batch, the pruning table
+#include "point_queries.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -115,6 +117,7 @@ struct rt_ctx {
     // that are answered without a traversal), the staging arrays of the _host forms, the occluded counts of rt_render_ao's rounds and
     // the ctx-owned plane of the last rt_render_ao(..., d_ao = NULL) with its pixel count (0: never written)
     DevBuf queryQueueBuf, queryHostBuf, aoCountBuf, aoBuf;
+    DevBuf objNearBuf;      // point queries: the per-object pruning table (layout_nearest), which follows the object tables (set_objects)
     size_t aoPixels = 0;
     DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
     // the denoiser (rt_denoise): its work planes, the staging planes of rt_denoise_host and the ctx-owned output
@@ -589,6 +592,8 @@ int set_objects(rt_ctx* c, const ObjectLayout& l, const RenderObject* o, uint32_
     if ((rc = upload_table(c, c->objSkipBuf, l.skipCost, c->sc.objSkipCost))) return rc;
     if ((rc = upload_table(c, c->objTreeBuf, l.tree, c->sc.objTree))) return rc;
     if ((rc = upload_table(c, c->objCostBuf, l.cost, c->sc.objCost))) return rc;
+    const std::vector<float4> nearTable = layout_nearest(l, o, n, c->rootOf);
+    if ((rc = upload(c, c->objNearBuf, nearTable.data(), nearTable.size() * sizeof(float4)))) return rc;
     for (int k = 0; k <= RT_OBJTREE_LEVELS; k++) c->sc.objTreeOff[k] = l.treeOff[k];
     c->sc.objTreeLevels = l.treeLevels;
     c->sc.reachCount = l.reachCount;
@@ -1409,6 +1414,62 @@ int rt_query_closest(rt_ctx* c, const RtRayBatch* d_rays, RtHit* d_hits) { retur
 int rt_query_occluded(rt_ctx* c, const RtRayBatch* d_rays, uint8_t* d_occluded) { return query_device(c, "rt_query_occluded", d_rays, d_occluded, true); }
 int rt_query_closest_host(rt_ctx* c, const RtRayBatch* rays, RtHit* hits) { return query_host(c, "rt_query_closest_host", rays, hits, false); }
 int rt_query_occluded_host(rt_ctx* c, const RtRayBatch* rays, uint8_t* occluded) { return query_host(c, "rt_query_occluded_host", rays, occluded, true); }
+}  // extern "C"
+
+// ---- point queries (point_queries.h has the checks, the arithmetic and the pruning table; DESIGN.md, "Point queries")
+namespace {
+template <int STACK, bool RETEST>
+void launch_nearest(rt_ctx* c, uint32_t blocks, const NearestArgs& na) {
+    hipLaunchKernelGGL((k_nearest_points<STACK, RETEST>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, na);
+    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_nearest_points<%d, %s>", STACK, tf(RETEST));
+}
+
+int nearest_device(rt_ctx* c, const char* fn, const RtPointBatch* pts, RtNearest* d_out) {
+    if (!c) return -1;
+    const std::string refusal = check_point_query(fn, c->sc.nodes != nullptr, pts, d_out);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = pts->n;
+    if (n == 0) return 0;
+    std::string deep;
+    const uint32_t stack = nearest_stack(fn, c->maxLeafDepth, &deep);
+    if (!stack) return c->fail(deep);
+    RT_HIP(c, hipSetDevice(c->device));
+    const NearestArgs na{pts->points, pts->maxDist, n, (const float4*)c->objNearBuf.p, (float4*)d_out, (DevCounters*)c->aovCounterBuf.p};
+    const uint32_t blocks = point_shape(n, RT_BLOCK).blocks;
+    if (stack == (uint32_t)RT_NEAREST_STACK) launch_nearest<RT_NEAREST_STACK, true>(c, blocks, na);
+    else launch_nearest<RT_NEAREST_STACK_DEEP, false>(c, blocks, na);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The host-memory form: the batch's arrays go up into the staging buffer the ray queries' _host forms use (point_staging), the
+// device form runs on the copies, the records come back; blocks
+int nearest_host(rt_ctx* c, const char* fn, const RtPointBatch* pts, RtNearest* out) {
+    if (!c) return -1;
+    const std::string refusal = check_point_query(fn, c->sc.nodes != nullptr, pts, out);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = pts->n;
+    if (n == 0) return 0;
+    const PointShape ps = point_shape(n, RT_BLOCK);
+    const PointStaging g = point_staging(n, pts->maxDist != nullptr);
+    RT_HIP(c, hipSetDevice(c->device));
+    if (c->queryHostBuf.bytes < g.bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees arrays a pass in flight may be using
+    int rc = dev_alloc(c, c->queryHostBuf, g.bytes);
+    if (rc) return rc;
+    char* const b = (char*)c->queryHostBuf.p;
+    RT_HIP(c, hipMemcpyAsync(b + g.points, pts->points, ps.pointBytes, hipMemcpyHostToDevice, c->stream));
+    if (pts->maxDist) RT_HIP(c, hipMemcpyAsync(b + g.limits, pts->maxDist, ps.limitBytes, hipMemcpyHostToDevice, c->stream));
+    const RtPointBatch dev{(const float*)(b + g.points), pts->maxDist ? (const float*)(b + g.limits) : nullptr, n};
+    if ((rc = nearest_device(c, fn, &dev, (RtNearest*)(b + g.out)))) return rc;
+    RT_HIP(c, hipMemcpyAsync(out, b + g.out, ps.outBytes, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+int rt_query_nearest(rt_ctx* c, const RtPointBatch* d_points, RtNearest* d_out) { return nearest_device(c, "rt_query_nearest", d_points, d_out); }
+int rt_query_nearest_host(rt_ctx* c, const RtPointBatch* points, RtNearest* out) { return nearest_host(c, "rt_query_nearest_host", points, out); }
 }  // extern "C"
 
 // ---- radiance queries (radiance_queries.h has the checks and the arithmetic; DESIGN.md, "Radiance queries")

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtRadianceParams, RtRayBatch,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtNearest, RtPointBatch, RtRadianceParams, RtRayBatch,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -523,6 +523,36 @@ class Renderer:
         in `out` for device memory, as query_closest takes it."""
         return self._query("occluded", origins, dirs, tmax, n, out, sync)
 
+    def query_nearest(self, points, max_dist=None, n=None, out=None, sync=True):
+        """The closest surface point of each of the caller's points within its limit (rt_query_nearest; DESIGN.md, "Point queries").
+        An (n, 3) numpy array and an optional (n,) `max_dist` go through rt_query_nearest_host and come back as an RtNearest array
+        (nearest_to_numpy); a torch tensor on the device (anything with data_ptr(): fp32, contiguous) or an integer device pointer
+        with n= goes through the asynchronous entry point, the RtNearest records are written to `out` (device memory, 16-byte
+        aligned, 48 bytes per point) and sync=False is allowed."""
+        rec = C.sizeof(RtNearest)
+        if not (hasattr(points, "data_ptr") or isinstance(points, (int, np.integer))):
+            p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+            t = None if max_dist is None else np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
+            if t is not None and t.shape[0] != p.shape[0]:
+                raise ValueError(f"max_dist has {t.shape[0]} limits for {p.shape[0]} points")
+            if out is not None or not sync:
+                raise ValueError("out= and sync=False go with device-pointer inputs")
+            batch = RtPointBatch(p.ctypes.data, t.ctypes.data if t is not None else None, p.shape[0])
+            res = (RtNearest * p.shape[0])()
+            self._check(self._l.rt_query_nearest_host(self._h, C.byref(batch), C.addressof(res)), "rt_query_nearest_host")
+            return res
+        if out is None:
+            raise ValueError("device-pointer inputs need out=: device memory for the results")
+        if n is None:
+            if not hasattr(points, "numel"):
+                raise ValueError("integer device pointers need n=")
+            n = int(points.numel()) // 3
+        batch = RtPointBatch(_device_ptr(points, "points", 12 * n), None if max_dist is None else _device_ptr(max_dist, "max_dist", 4 * n), int(n))
+        self._check(self._l.rt_query_nearest(self._h, C.byref(batch), C.c_void_p(_device_ptr(out, "out", rec * n, floats=False))), "rt_query_nearest")
+        if sync:
+            self.sync()
+        return None
+
     def query_radiance(self, origins, dirs, samples=1, bounces=8, ids=None, progressive=False, frame=0, environment=None, n=None, out=None,
                        sync=True):
         """The path-traced radiance along each of the caller's rays (rt_query_radiance; DESIGN.md, "Radiance queries"): `samples`
@@ -946,6 +976,30 @@ def hits_to_numpy(hits):
                 triHitIndex=u[:, 4].copy(), materialIndex=u[:, 5].copy(), frontFace=u[:, 6].copy(),
                 hitPoint=f[:, 7:10].copy(), normal=f[:, 10:13].copy(), boxTests=u[:, 13].copy(),
                 triTests=u[:, 14].copy())
+
+
+def nearest_to_numpy(recs):
+    """RtNearest array -> dict of numpy arrays."""
+    n = len(recs)
+    raw = np.frombuffer(recs, dtype=np.uint8).reshape(n, C.sizeof(RtNearest))
+    f = raw.view(np.float32).reshape(n, -1)
+    u = raw.view(np.uint32).reshape(n, -1)
+    return dict(dst=f[:, 0].copy(), found=u[:, 1].copy(), isSphere=u[:, 2].copy(), objectIndex=u[:, 3].copy(), triIndex=u[:, 4].copy(),
+                uv=f[:, 5:7].copy(), point=f[:, 7:10].copy())
+
+
+def nearest_exhaustive(scene_arrays, points, max_dist=None):
+    """The rule of the point queries in a plain loop over the host arrays (rt_nearest_exhaustive_host; no GPU, no pruning):
+    `scene_arrays` is Scene.arrays(); returns an RtNearest array (nearest_to_numpy)."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    t = None if max_dist is None else np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
+    if t is not None and t.shape[0] != p.shape[0]:
+        raise ValueError(f"max_dist has {t.shape[0]} limits for {p.shape[0]} points")
+    batch = RtPointBatch(p.ctypes.data, t.ctypes.data if t is not None else None, p.shape[0])
+    res = (RtNearest * max(p.shape[0], 1))()
+    if _capi.lib().rt_nearest_exhaustive_host(C.byref(scene_arrays), C.byref(batch), C.addressof(res)) != 0:
+        raise RtError("rt_nearest_exhaustive_host refused its arguments (NULL arrays, n >= 2^30, or indices out of range)")
+    return (RtNearest * p.shape[0]).from_buffer(res) if p.shape[0] else (RtNearest * 0)()
 
 
 def load_textures(scene):
