@@ -10,8 +10,6 @@
 #include "rt_point_query.h"
 
 namespace {
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 const double U32 = 5.9604644775390625e-8;   // 2^-24
 
 // permanents of |M|'s minors: what inverse_error_unit (tests/brute_force.py) counts the cofactors' and the determinant's rounding with
@@ -110,16 +108,6 @@ PointShape point_shape(uint32_t n, uint32_t threads) {
     s.limitBytes = (size_t)n * sizeof(float);
     s.outBytes = (size_t)n * sizeof(RtNearest);
     return s;
-}
-
-PointStaging point_staging(uint32_t n, bool hasLimits) {
-    const PointShape s = point_shape(n, 1);
-    PointStaging g;
-    g.points = 0;
-    g.limits = align256(s.pointBytes);
-    g.out = g.limits + (hasLimits ? align256(s.limitBytes) : 0);
-    g.bytes = g.out + align256(s.outBytes);
-    return g;
 }
 
 uint32_t nearest_stack(const char* fn, uint32_t maxLeafDepth, std::string* error) {

@@ -1,6 +1,6 @@
 // point_queries.h — the host logic of the point queries (rt_query_nearest, rt_query_nearest_host) and the exhaustive host form
 // (rt_nearest_exhaustive_host): what they refuse, in which order and with which words, the block and byte arithmetic of a batch,
-// the staging offsets, the per-object pruning records of the device traversal and the choice of its stack. Nothing in this pair
+// the per-object pruning records of the device traversal and the choice of its stack. Nothing in this pair
 // of files needs a device: the checks do pointer arithmetic only and never dereference an array of a batch. rt_device.hip
 // gathers the facts, asks here, and allocates, copies and launches; tests/point_queries_check.cpp pins every message and figure
 // on the CPU, with made-up addresses. The rule itself (distances, the bound, the pruning test) is include/rt_point_query.h.
@@ -31,10 +31,6 @@ struct PointShape {
     size_t outBytes;       // sizeof(RtNearest) n
 };
 PointShape point_shape(uint32_t n, uint32_t threads);
-
-// The staging buffer of the _host form: the inputs one behind the other, then the output, each at a multiple of 256 bytes
-struct PointStaging { size_t points, limits, out, bytes; };   // offsets (limits == out when the batch has no limits)
-PointStaging point_staging(uint32_t n, bool hasLimits);
 
 // The stack k_nearest_points needs for a scene whose deepest leaf is at maxLeafDepth (MeshLayout::maxLeafDepth: the traversal
 // pushes far siblings only, one per level at most): RT_NEAREST_STACK, RT_NEAREST_STACK_DEEP, or 0 with the refusal in *error

@@ -6,10 +6,6 @@
 
 #include "rt_det_math.h"
 
-namespace {
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-}  // namespace
-
 std::string check_radiance_query(const char* fn, bool sceneUploaded, const RtRayBatch* rays, const RtRadianceParams* params, const void* out) {
     const std::string f(fn);
     if (!sceneUploaded) return f + " before rt_upload_scene";
@@ -38,17 +34,8 @@ RadiancePiece radiance_piece(uint32_t n, uint64_t maxSlots, uint32_t k) {
     return RadiancePiece{(uint32_t)first, (uint32_t)std::min<uint64_t>(cap, (uint64_t)n - first)};
 }
 
-RadianceStaging radiance_staging(uint32_t n, bool hasIds) {
-    RadianceStaging g;
-    g.vecBytes = (size_t)n * 3 * sizeof(float);
-    g.idBytes = hasIds ? (size_t)n * sizeof(uint32_t) : 0;
-    g.outBytes = (size_t)n * 4 * sizeof(float);
-    g.origins = 0;
-    g.dirs = align256(g.vecBytes);
-    g.ids = g.dirs + align256(g.vecBytes);
-    g.out = g.ids + align256(g.idBytes);
-    g.bytes = g.out + align256(g.outBytes);
-    return g;
+RadianceShape radiance_shape(uint32_t n, bool hasIds) {
+    return RadianceShape{(size_t)n * 3 * sizeof(float), hasIds ? (size_t)n * sizeof(uint32_t) : 0, (size_t)n * 4 * sizeof(float)};
 }
 
 uint32_t radiance_starting_seed(uint32_t frameCount) {

@@ -1,5 +1,5 @@
 // radiance_queries.h — the host logic of the radiance queries (rt_query_radiance and its _host form): what they refuse, in which
-// order and with which words, the pieces a batch runs in, the staging offsets of the _host form and the frame's RNG seed. Nothing
+// order and with which words, the pieces a batch runs in, the bytes of its arrays and the frame's RNG seed. Nothing
 // in this pair of files needs a device: it does pointer arithmetic only and never dereferences an array of a batch. rt_device.hip
 // gathers the facts, asks here, and allocates, copies and launches; tests/radiance_queries_check.cpp pins every message and figure
 // on the CPU, with made-up addresses. (ray_queries.h is the same for the hit queries; DESIGN.md, "Radiance queries")
@@ -27,10 +27,10 @@ uint32_t radiance_piece_cap(uint64_t maxSlots);                   // maxSlots cl
 uint32_t radiance_piece_count(uint32_t n, uint64_t maxSlots);     // 0 for n == 0
 RadiancePiece radiance_piece(uint32_t n, uint64_t maxSlots, uint32_t k);
 
-// The staging buffer of the _host form: origins, dirs, the optional ids and the n x 16-byte output one behind the other, each at
-// a multiple of 256 bytes (ids == out when the batch has none)
-struct RadianceStaging { size_t origins, dirs, ids, out, vecBytes, idBytes, outBytes, bytes; };
-RadianceStaging radiance_staging(uint32_t n, bool hasIds);
+// The bytes of a batch's arrays (size_t: 2^30 - 1 results of 16 bytes are past 32 bits): origins and dirs 12 n each, the optional
+// ids 4 n (0 when the batch has none), the result 16 n
+struct RadianceShape { size_t vecBytes, idBytes, outBytes; };
+RadianceShape radiance_shape(uint32_t n, bool hasIds);
 
 // uint(random(frameCount) * 23892183) (raytrace.comp:561), as render_impl computes it for a frame
 uint32_t radiance_starting_seed(uint32_t frameCount);

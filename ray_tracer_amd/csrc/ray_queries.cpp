@@ -3,10 +3,6 @@
 
 #include "rt_ao_rays.h"
 
-namespace {
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-}  // namespace
-
 std::string check_ray_query(const char* fn, bool sceneUploaded, const RtRayBatch* rays, const void* out) {
     const std::string f(fn);
     if (!sceneUploaded) return f + " before rt_upload_scene";
@@ -27,17 +23,6 @@ QueryShape query_shape(uint32_t n, uint32_t threads) {
     s.occludedBytes = (size_t)n;
     s.queueBytes = (size_t)n * sizeof(uint32_t);
     return s;
-}
-
-QueryStaging query_staging(uint32_t n, bool hasTmax, size_t outRecordBytes) {
-    const QueryShape s = query_shape(n, 1);
-    QueryStaging g;
-    g.origins = 0;
-    g.dirs = align256(s.vecBytes);
-    g.tmax = g.dirs + align256(s.vecBytes);
-    g.out = g.tmax + (hasTmax ? align256(s.tmaxBytes) : 0);
-    g.bytes = g.out + align256((size_t)n * outRecordBytes);
-    return g;
 }
 
 std::string check_ao(const char* fn, bool sceneUploaded, uint32_t nPixels, const RtAoParams& p, const RtAovBuffers* aovs, bool ownedValid,

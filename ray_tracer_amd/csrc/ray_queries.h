@@ -32,10 +32,6 @@ struct QueryShape {
 };
 QueryShape query_shape(uint32_t n, uint32_t threads);
 
-// The staging buffer of the _host forms: the inputs one behind the other, then the output, each at a multiple of 256 bytes
-struct QueryStaging { size_t origins, dirs, tmax, out, bytes; };   // offsets (tmax == out when the batch has no limits)
-QueryStaging query_staging(uint32_t n, bool hasTmax, size_t outRecordBytes);
-
 // What rt_render_ao and rt_ao_rays_host (fn) refuse, in this order: no uploaded scene (rt_render_ao only: sceneUploaded is true for
 // the host function); samples outside 1..RT_AO_MAX_SAMPLES or a radius that is not finite and > 0; nPixels 0 or >= 2^30; planes
 // given without position, normalDepth or ids; none given and no ctx-owned planes of nPixels records (ownedValid, ownedPixels).

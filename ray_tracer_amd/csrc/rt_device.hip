@@ -12,7 +12,8 @@
 #include "launch_plan.h"   // every decision about how a dispatch is run: this file gathers the facts, asks there, and launches
 #include "post_passes.h"   // likewise for the passes over finished frames: their checks, their input planes, the temporal history
 #include "ray_queries.h"   // ... and for the ray queries and the ambient-occlusion pass: their checks and the arithmetic of a batch
-#include "radiance_queries.h"   // ... and for the radiance queries: their checks, pieces, staging offsets and seed
+#include "radiance_queries.h"   // ... and for the radiance queries: their checks, pieces, byte counts and seed
+#include "host_staging.h"       // ... and for every _host form: where its arrays lie in the staging buffer
 #include "rt_nearest.hip.h"     // the kernel of the point queries; point_queries.h: their checks, the arithmetic of a batch, the pruning table
 #include "point_queries.h"
 
@@ -84,6 +85,7 @@ struct rt_ctx {
     DevBuf gatherBuf;
     // path state
     DevBuf stateBuf, queueBuf, counterBuf, scratchBuf;
+    DevBuf hostStageBuf;    // the arrays of whichever _host form runs (staged): idle between calls, no pointer into it ever leaves the library
     OwnedPlane fb;          // the ctx framebuffer (render_impl writes it, rt_clear_framebuffer forgets it)
     DevBuf overflowBuf[RT_MAX_LANES];     // per part (Dispatch::part): the traversal stack entries beyond LDS
     // Multi-kernel pipeline in `lanes` independent parts (render_parts): the paths of a dispatch are split into contiguous slot
@@ -114,22 +116,20 @@ struct rt_ctx {
     OwnedPlane guide;
     DevBuf guideCountBuf;
     // ray queries and the ambient-occlusion pass (rt_query_*, rt_render_ao): the pass's queue (one entry per ray, holes for the rays
-    // that are answered without a traversal), the staging arrays of the _host forms, the occluded counts of rt_render_ao's rounds and
-    // the ctx-owned plane of the last rt_render_ao(..., d_ao = NULL) with its pixel count (0: never written)
-    DevBuf queryQueueBuf, queryHostBuf, aoCountBuf, aoBuf;
+    // that are answered without a traversal), the occluded counts of rt_render_ao's rounds and the ctx-owned plane of the last
+    // rt_render_ao(..., d_ao = NULL) with its pixel count (0: never written)
+    DevBuf queryQueueBuf, aoCountBuf, aoBuf;
     DevBuf objNearBuf;      // point queries: the per-object pruning table (layout_nearest), which follows the object tables (set_objects)
     size_t aoPixels = 0;
     DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
-    // the denoiser (rt_denoise): its work planes, the staging planes of rt_denoise_host and the ctx-owned output
-    DevBuf dnWorkBuf, dnHostBuf;
+    // the denoiser (rt_denoise): its work planes and the ctx-owned output
+    DevBuf dnWorkBuf;
     OwnedPlane dnOut;
-    // temporal accumulation (rt_temporal_accumulate): the two histories a call reads and writes in turn, the staging planes of
-    // rt_temporal_accumulate_host and the ctx-owned frame and moments
-    DevBuf tpHist[2], tpHostBuf;
+    // temporal accumulation (rt_temporal_accumulate): the two histories a call reads and writes in turn and the ctx-owned frame and moments
+    DevBuf tpHist[2];
     OwnedPlane tpOut, tpMom;
-    // sample counts from the moments (rt_build_sample_map): the statistics of the last build, whether there was one, and the staging
-    // planes of rt_build_sample_map_host
-    DevBuf smStatBuf, smHostBuf;
+    // sample counts from the moments (rt_build_sample_map): the statistics of the last build and whether there was one
+    DevBuf smStatBuf;
     bool smBuilt = false;
     // following moved objects and spheres: the motion table on the device with its pinned staging copy and the event that says the
     // copy has been read (upload_motion)
@@ -210,6 +210,37 @@ int upload_table(rt_ctx* c, DevBuf& b, const std::vector<T>& v, const T*& field)
     int rc = upload(c, b, v.data(), v.size() * sizeof(T));
     if (rc) return rc;
     field = (const T*)b.p;
+    return 0;
+}
+
+// The host-memory (_host) form of a device entry point. A part is one array of the call: `up` is copied to the device before the
+// pass, `down` is copied back after it (both: in/out), and a part of 0 bytes is absent: the pass sees NULL for it. The parts lie in
+// hostStageBuf by the one rule of host_staging.h; `pass` runs the device form on dev[k], the device address of part k. A pass that
+// returns non-zero ends the call with that code and nothing comes back; otherwise the call blocks until the results are there.
+// One buffer serves every form: a form that succeeds ends with a synchronise of the ctx stream, so the buffer is idle between
+// successful calls; a call that failed after launching may have left work in flight, which is why the buffer still waits before
+// it grows; and no device pointer into it is ever handed to a caller.
+struct StagePart { const void* up; void* down; size_t bytes; };
+
+template <size_t N, typename Pass>
+int staged(rt_ctx* c, const StagePart (&parts)[N], Pass pass) {
+    static_assert(N <= RT_STAGE_MAX_PARTS, "host_staging.h: RT_STAGE_MAX_PARTS");
+    size_t bytes[N];
+    for (size_t k = 0; k < N; k++) bytes[k] = parts[k].bytes;
+    RT_HIP(c, hipSetDevice(c->device));
+    const StageLayout g = stage_layout(bytes, (int)N);
+    if (c->hostStageBuf.bytes < g.bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees arrays a pass in flight may be using
+    int rc = dev_alloc(c, c->hostStageBuf, g.bytes);
+    if (rc) return rc;
+    void* dev[N];
+    for (size_t k = 0; k < N; k++) {
+        dev[k] = bytes[k] ? (char*)c->hostStageBuf.p + g.offset[k] : nullptr;
+        if (dev[k] && parts[k].up) RT_HIP(c, hipMemcpyAsync(dev[k], parts[k].up, bytes[k], hipMemcpyHostToDevice, c->stream));
+    }
+    if ((rc = pass(dev))) return rc;
+    for (size_t k = 0; k < N; k++)
+        if (dev[k] && parts[k].down) RT_HIP(c, hipMemcpyAsync(parts[k].down, dev[k], bytes[k], hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -1129,6 +1160,35 @@ int render_impl(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t hei
     fp.sampleMap = sampleMap;
     return render_dispatch(c, fp, one_part(c, dispatch_scene(c, td), td.debug >= 0), fb);
 }
+
+// How the side passes begin: the first-hit AOVs, the guides, the ray queries with the AO plane, the radiance queries. A pass's rays
+// live in path-state slots [0, nSlots) and its ray count in the first part's counters: the ctx stream orders it after a dispatch
+// still in flight (whose parts join the ctx stream before it ends). Growing the path state frees the old one, so that waits for
+// the device first. The pass runs on `sc` in one part, with no per-pixel statistics and no phase statistics, and its traversal
+// launches are counted apart, in rep.aovLaunches.
+int side_pass_begin(rt_ctx* c, uint32_t nSlots, const DevScene& sc, Dispatch* d) {
+    RT_HIP(c, hipSetDevice(c->device));
+    if (c->capacity < nSlots || !c->stateBuf.p) RT_HIP(c, hipStreamSynchronize(c->stream));
+    int rc = ensure_state(c, nSlots);
+    if (rc) return rc;
+    *d = one_part(c, sc, false);
+    d->phaseStats = 0; d->launches = &c->rep.aovLaunches;
+    return 0;
+}
+
+// The ctx-owned set of five planes (in AovPlane's order) for a pass that was given none: nPixels pixels of these rows
+int claim_planes(rt_ctx* c, OwnedPlane& own, uint32_t nPixels, const RowsOf& rows) {
+    int rc = dev_alloc(c, own.buf, (size_t)nPixels * sizeof(float4) * AOV_PLANES);
+    if (rc) return rc;
+    own.pixels = nPixels;
+    own.valid = true;
+    own.rows = rows;
+    return 0;
+}
+AovOut aov_out(const RtAovBuffers* given, const void* owned, size_t nPixels) {   // given NULL: the ctx-owned set; both NULL: no plane
+    const auto plane = [&](AovPlane k) -> void* { return given ? aov_plane(*given, k) : owned ? aov_plane(owned, k, nPixels) : nullptr; };
+    return AovOut{(float4*)plane(AOV_NORMAL_DEPTH), (float4*)plane(AOV_POSITION), (float4*)plane(AOV_ALBEDO), (float4*)plane(AOV_RAY_DIR), (uint4*)plane(AOV_IDS)};
+}
 }  // namespace
 
 extern "C" {
@@ -1230,26 +1290,14 @@ int rt_render_aovs(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_t 
     const std::string tooLarge = check_tile_slots("rt_render_aovs", width, nRows);
     if (!tooLarge.empty()) return c->fail(tooLarge);
     const uint32_t nPixels = nRows * width;
-    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipSetDevice(c->device));   // (also for a tile without pixels)
     if (nPixels == 0) return 0;
-    // The pass's rays live in path-state slots [0, nPixels) and its ray count in the first part's counters: the ctx stream orders it
-    // after a dispatch still in flight (whose parts join the ctx stream before it ends). Growing the path state frees the old one,
-    // so that waits for the device first.
-    if (c->capacity < nPixels || !c->stateBuf.p) RT_HIP(c, hipStreamSynchronize(c->stream));
-    if ((rc = ensure_state(c, nPixels))) return rc;
-    if (!d_out) {
-        if ((rc = dev_alloc(c, c->aov.buf, (size_t)nPixels * sizeof(float4) * AOV_PLANES))) return rc;
-        c->aov.pixels = nPixels;
-        c->aov.valid = true;
-        c->aov.rows = RowsOf{width, height, row0, rowStride, nRows};
-    }
-    const auto plane = [&](AovPlane k) { return d_out ? aov_plane(*d_out, k) : aov_plane(c->aov.buf.p, k, nPixels); };
-    const AovOut out{(float4*)plane(AOV_NORMAL_DEPTH), (float4*)plane(AOV_POSITION), (float4*)plane(AOV_ALBEDO), (float4*)plane(AOV_RAY_DIR), (uint4*)plane(AOV_IDS)};
+    Dispatch d;   // with the scene counts of this call
+    if ((rc = side_pass_begin(c, nPixels, dispatch_scene(c, pc->rayTraceParams), &d))) return rc;
+    if (!d_out && (rc = claim_planes(c, c->aov, nPixels, RowsOf{width, height, row0, rowStride, nRows}))) return rc;
+    const AovOut out = aov_out(d_out, c->aov.buf.p, nPixels);
     FrameParams fp = frame_camera(c, pc, width, height, row0, rowStride, nRows, nPixels);
     fp.nFrames = 1;
-    // this pass gets its scene counts, no per-pixel statistics and no phase statistics, and its launch is counted apart
-    Dispatch d = one_part(c, dispatch_scene(c, pc->rayTraceParams), false);
-    d.phaseStats = 0; d.launches = &c->rep.aovLaunches;
     const uint32_t blocks = (nPixels + RT_BLOCK - 1) / RT_BLOCK;
     hipLaunchKernelGGL(k_aov_rays, dim3(blocks), dim3(RT_BLOCK), 0, c->stream, d.sc, c->ps, fp);
     hipLaunchKernelGGL(k_init_counts, dim3(1), dim3(64), 0, c->stream, c->q.counts, nPixels);
@@ -1275,10 +1323,6 @@ int read_planes(rt_ctx* c, const OwnedPlane& pl, const char* fn, const char* nev
     RT_HIP(c, hipStreamSynchronize(c->stream));
     return 0;
 }
-AovOut aov_out(const RtAovBuffers* given, const void* owned, size_t nPixels) {   // given NULL: the ctx-owned set; both NULL: no plane
-    const auto plane = [&](AovPlane k) -> void* { return given ? aov_plane(*given, k) : owned ? aov_plane(owned, k, nPixels) : nullptr; };
-    return AovOut{(float4*)plane(AOV_NORMAL_DEPTH), (float4*)plane(AOV_POSITION), (float4*)plane(AOV_ALBEDO), (float4*)plane(AOV_RAY_DIR), (uint4*)plane(AOV_IDS)};
-}
 enum { GUIDE_COUNTS = 16 };   // words of guideCountBuf: [j] the rays of round j, j = 1 .. RT_GUIDE_MAX_BOUNCES + 1 (the last one stays 0)
 static_assert(RT_GUIDE_MAX_BOUNCES + 2 <= GUIDE_COUNTS, "a count per round");
 }  // namespace
@@ -1297,22 +1341,15 @@ int rt_render_guides(rt_ctx* c, const PushConstants* pc, uint32_t width, uint32_
     const std::string refusal = check_guides(pc->rayTraceParams, width, height, row0, rowStride, nRows, maxBounces, d_guides, d_firstHit, uploaded_scene(c));
     if (!refusal.empty()) return c->fail(refusal);
     const uint32_t nPixels = nRows * width;
-    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipSetDevice(c->device));   // (also for a tile without pixels)
     if (nPixels == 0) return 0;
     int rc;
-    if (c->capacity < nPixels || !c->stateBuf.p) RT_HIP(c, hipStreamSynchronize(c->stream));   // as rt_render_aovs
-    if ((rc = ensure_state(c, nPixels))) return rc;
+    Dispatch d;   // with the scene counts of this call
+    if ((rc = side_pass_begin(c, nPixels, dispatch_scene(c, pc->rayTraceParams), &d))) return rc;
     if ((rc = dev_alloc(c, c->guideCountBuf, GUIDE_COUNTS * sizeof(uint32_t)))) return rc;
-    if (!d_guides) {
-        if ((rc = dev_alloc(c, c->guide.buf, (size_t)nPixels * sizeof(float4) * AOV_PLANES))) return rc;
-        c->guide.pixels = nPixels;
-        c->guide.valid = true;
-        c->guide.rows = RowsOf{width, height, row0, rowStride, nRows};
-    }
+    if (!d_guides && (rc = claim_planes(c, c->guide, nPixels, RowsOf{width, height, row0, rowStride, nRows}))) return rc;
     FrameParams fp = frame_camera(c, pc, width, height, row0, rowStride, nRows, nPixels);
     fp.nFrames = 1;
-    Dispatch d = one_part(c, dispatch_scene(c, pc->rayTraceParams), false);
-    d.phaseStats = 0; d.launches = &c->rep.aovLaunches;
     const uint32_t blocks = (nPixels + RT_BLOCK - 1) / RT_BLOCK;
     uint32_t* const counts = (uint32_t*)c->guideCountBuf.p;
     GuideArgs ga{nullptr, nullptr, nullptr, nullptr, d.counts + 4, 0u, maxBounces, aov_out(d_guides, c->guide.buf.p, nPixels), aov_out(d_firstHit, nullptr, 0)};
@@ -1341,19 +1378,13 @@ int rt_read_guides(rt_ctx* c, const RtAovBuffers* out, size_t nPixels) {
 
 // ---- ray queries and the ambient-occlusion plane (ray_queries.h has the checks and the arithmetic; DESIGN.md, "Ray queries")
 namespace {
-// What the query passes share with rt_render_aovs: path-state slots [0, n) on the ctx stream (growing the state frees the old one,
-// so that waits for the device first), a queue of n entries, no phase statistics, launches and traversal work counted with the AOV
-// passes'
+// A side pass on the uploaded scene with a queue of n entries on top; a queue that grows waits for the device as the path state does
 int query_begin(rt_ctx* c, uint32_t n, Dispatch* d) {
-    RT_HIP(c, hipSetDevice(c->device));
-    const QueryShape qs = query_shape(n, RT_BLOCK);
-    if (c->capacity < n || !c->stateBuf.p || c->queryQueueBuf.bytes < qs.queueBytes) RT_HIP(c, hipStreamSynchronize(c->stream));
-    int rc = ensure_state(c, n);
+    const size_t queueBytes = query_shape(n, RT_BLOCK).queueBytes;
+    int rc = side_pass_begin(c, n, c->sc, d);
     if (rc) return rc;
-    if ((rc = dev_alloc(c, c->queryQueueBuf, qs.queueBytes))) return rc;
-    *d = one_part(c, c->sc, false);
-    d->phaseStats = 0; d->launches = &c->rep.aovLaunches;
-    return 0;
+    if (c->queryQueueBuf.bytes < queueBytes) RT_HIP(c, hipStreamSynchronize(c->stream));
+    return dev_alloc(c, c->queryQueueBuf, queueBytes);
 }
 // the traversal of the pass's queue: n entries, holes among them
 int query_trace(rt_ctx* c, const Dispatch& d, uint32_t n) {
@@ -1382,30 +1413,20 @@ int query_device(rt_ctx* c, const char* fn, const RtRayBatch* rays, void* d_out,
     return 0;
 }
 
-// The host-memory form: the batch's arrays go up into one ctx buffer (query_staging), the device form runs on the copies, the
-// output comes back; blocks. (The planes of `staged` all have one size; a batch's arrays do not.)
+// The host-memory form (staged)
 int query_host(rt_ctx* c, const char* fn, const RtRayBatch* rays, void* out, bool occlusion) {
     if (!c) return -1;
     const std::string refusal = check_ray_query(fn, c->sc.nodes != nullptr, rays, out);
     if (!refusal.empty()) return c->fail(refusal);
     const uint32_t n = rays->n;
     if (n == 0) return 0;
-    const size_t rec = occlusion ? sizeof(uint8_t) : sizeof(RtHit);
     const QueryShape qs = query_shape(n, RT_BLOCK);
-    const QueryStaging g = query_staging(n, rays->tmax != nullptr, rec);
-    RT_HIP(c, hipSetDevice(c->device));
-    if (c->queryHostBuf.bytes < g.bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees arrays a pass in flight may be using
-    int rc = dev_alloc(c, c->queryHostBuf, g.bytes);
-    if (rc) return rc;
-    char* const b = (char*)c->queryHostBuf.p;
-    RT_HIP(c, hipMemcpyAsync(b + g.origins, rays->origins, qs.vecBytes, hipMemcpyHostToDevice, c->stream));
-    RT_HIP(c, hipMemcpyAsync(b + g.dirs, rays->dirs, qs.vecBytes, hipMemcpyHostToDevice, c->stream));
-    if (rays->tmax) RT_HIP(c, hipMemcpyAsync(b + g.tmax, rays->tmax, qs.tmaxBytes, hipMemcpyHostToDevice, c->stream));
-    const RtRayBatch dev{(const float*)(b + g.origins), (const float*)(b + g.dirs), rays->tmax ? (const float*)(b + g.tmax) : nullptr, n};
-    if ((rc = query_device(c, fn, &dev, b + g.out, occlusion))) return rc;
-    RT_HIP(c, hipMemcpyAsync(out, b + g.out, (size_t)n * rec, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const StagePart parts[] = {{rays->origins, nullptr, qs.vecBytes}, {rays->dirs, nullptr, qs.vecBytes}, {rays->tmax, nullptr, rays->tmax ? qs.tmaxBytes : 0},
+                               {nullptr, out, occlusion ? qs.occludedBytes : qs.hitBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtRayBatch dev{(const float*)d[0], (const float*)d[1], (const float*)d[2], n};
+        return query_device(c, fn, &dev, d[3], occlusion);
+    });
 }
 }  // namespace
 
@@ -1442,8 +1463,7 @@ int nearest_device(rt_ctx* c, const char* fn, const RtPointBatch* pts, RtNearest
     return 0;
 }
 
-// The host-memory form: the batch's arrays go up into the staging buffer the ray queries' _host forms use (point_staging), the
-// device form runs on the copies, the records come back; blocks
+// The host-memory form (staged)
 int nearest_host(rt_ctx* c, const char* fn, const RtPointBatch* pts, RtNearest* out) {
     if (!c) return -1;
     const std::string refusal = check_point_query(fn, c->sc.nodes != nullptr, pts, out);
@@ -1451,19 +1471,11 @@ int nearest_host(rt_ctx* c, const char* fn, const RtPointBatch* pts, RtNearest* 
     const uint32_t n = pts->n;
     if (n == 0) return 0;
     const PointShape ps = point_shape(n, RT_BLOCK);
-    const PointStaging g = point_staging(n, pts->maxDist != nullptr);
-    RT_HIP(c, hipSetDevice(c->device));
-    if (c->queryHostBuf.bytes < g.bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees arrays a pass in flight may be using
-    int rc = dev_alloc(c, c->queryHostBuf, g.bytes);
-    if (rc) return rc;
-    char* const b = (char*)c->queryHostBuf.p;
-    RT_HIP(c, hipMemcpyAsync(b + g.points, pts->points, ps.pointBytes, hipMemcpyHostToDevice, c->stream));
-    if (pts->maxDist) RT_HIP(c, hipMemcpyAsync(b + g.limits, pts->maxDist, ps.limitBytes, hipMemcpyHostToDevice, c->stream));
-    const RtPointBatch dev{(const float*)(b + g.points), pts->maxDist ? (const float*)(b + g.limits) : nullptr, n};
-    if ((rc = nearest_device(c, fn, &dev, (RtNearest*)(b + g.out)))) return rc;
-    RT_HIP(c, hipMemcpyAsync(out, b + g.out, ps.outBytes, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const StagePart parts[] = {{pts->points, nullptr, ps.pointBytes}, {pts->maxDist, nullptr, pts->maxDist ? ps.limitBytes : 0}, {nullptr, out, ps.outBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtPointBatch dev{(const float*)d[0], (const float*)d[1], n};
+        return nearest_device(c, fn, &dev, (RtNearest*)d[2]);
+    });
 }
 }  // namespace
 
@@ -1504,16 +1516,11 @@ int radiance_device(rt_ctx* c, const char* fn, const RtRayBatch* rays, const uin
     if (!refusal.empty()) return c->fail(refusal);
     const uint32_t n = rays->n;
     if (n == 0) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
     const uint64_t maxSlots = radiance_max_slots(c);
-    const uint32_t cap = std::min(n, radiance_piece_cap(maxSlots));
-    // the pieces' paths live in slots [0, cap) on the ctx stream: growing the path state frees the old one, so that waits for the device first
-    if (c->capacity < cap || !c->stateBuf.p) RT_HIP(c, hipStreamSynchronize(c->stream));
-    int rc = ensure_state(c, cap);
+    Dispatch d;   // the pieces' paths live in slots [0, cap); the uploaded scene's counts; always the multi-kernel pipeline
+    int rc = side_pass_begin(c, std::min(n, radiance_piece_cap(maxSlots)), c->sc, &d);
     if (rc) return rc;
-    // no per-pixel statistics, no phase statistics, launches counted with the AOV passes'; the uploaded scene's counts
-    Dispatch d = one_part(c, c->sc, false);
-    d.phaseStats = 0; d.launches = &c->rep.aovLaunches; d.pipeline = 0;
+    d.pipeline = 0;
     FrameParams fp{};   // (the camera fields are unused: the rays are the caller's)
     fp.startingSeed = radiance_starting_seed(params->frameCount);
     fp.samples = params->samples;
@@ -1542,8 +1549,7 @@ int rt_query_radiance(rt_ctx* c, const RtRayBatch* d_rays, const uint32_t* d_ids
     return radiance_device(c, "rt_query_radiance", d_rays, d_ids, params, env, d_radiance);
 }
 
-// The host-memory form: the arrays go up into the ctx staging buffer (radiance_staging), with what `radiance` holds when the
-// result is blended with it, the device form runs on the copies, the result comes back; blocks.
+// The host-memory form (staged). What `radiance` holds goes up as well when the result is blended with it.
 int rt_query_radiance_host(rt_ctx* c, const RtRayBatch* rays, const uint32_t* ids, const RtRadianceParams* params, const EnvironmentData* env,
                            float* radiance) {
     if (!c) return -1;
@@ -1552,21 +1558,13 @@ int rt_query_radiance_host(rt_ctx* c, const RtRayBatch* rays, const uint32_t* id
     if (!refusal.empty()) return c->fail(refusal);
     const uint32_t n = rays->n;
     if (n == 0) return 0;
-    const RadianceStaging g = radiance_staging(n, ids != nullptr);
-    RT_HIP(c, hipSetDevice(c->device));
-    if (c->queryHostBuf.bytes < g.bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees arrays a pass in flight may be using
-    int rc = dev_alloc(c, c->queryHostBuf, g.bytes);
-    if (rc) return rc;
-    char* const b = (char*)c->queryHostBuf.p;
-    RT_HIP(c, hipMemcpyAsync(b + g.origins, rays->origins, g.vecBytes, hipMemcpyHostToDevice, c->stream));
-    RT_HIP(c, hipMemcpyAsync(b + g.dirs, rays->dirs, g.vecBytes, hipMemcpyHostToDevice, c->stream));
-    if (ids) RT_HIP(c, hipMemcpyAsync(b + g.ids, ids, g.idBytes, hipMemcpyHostToDevice, c->stream));
-    if (params->progressive) RT_HIP(c, hipMemcpyAsync(b + g.out, radiance, g.outBytes, hipMemcpyHostToDevice, c->stream));
-    const RtRayBatch dev{(const float*)(b + g.origins), (const float*)(b + g.dirs), nullptr, n};
-    if ((rc = radiance_device(c, fn, &dev, ids ? (const uint32_t*)(b + g.ids) : nullptr, params, env, (float*)(b + g.out)))) return rc;
-    RT_HIP(c, hipMemcpyAsync(radiance, b + g.out, g.outBytes, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const RadianceShape rs = radiance_shape(n, ids != nullptr);
+    const StagePart parts[] = {{rays->origins, nullptr, rs.vecBytes}, {rays->dirs, nullptr, rs.vecBytes}, {ids, nullptr, rs.idBytes},
+                               {params->progressive ? radiance : nullptr, radiance, rs.outBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtRayBatch dev{(const float*)d[0], (const float*)d[1], nullptr, n};
+        return radiance_device(c, fn, &dev, (const uint32_t*)d[2], params, env, (float*)d[3]);
+    });
 }
 
 // `samples` rounds of {k_ao_rays, the traversal, k_ao_count}, all enqueued without waiting for the device, then k_ao_resolve
@@ -1587,8 +1585,8 @@ int rt_render_ao(rt_ctx* c, uint32_t nPixels, const RtAovBuffers* d_aovs, const 
         if ((rc = dev_alloc(c, c->aoBuf, aoBytes))) return rc;
         c->aoPixels = nPixels;
     }
-    const auto plane = [&](AovPlane k) { return d_aovs ? aov_plane(*d_aovs, k) : aov_plane(c->aov.buf.p, k, nPixels); };
-    AoArgs a{(const float4*)plane(AOV_POSITION), (const float4*)plane(AOV_NORMAL_DEPTH), (const uint4*)plane(AOV_IDS), nPixels, 0u, p.samples, p.seed,
+    const AovOut in = aov_out(d_aovs, c->aov.buf.p, nPixels);
+    AoArgs a{in.position, in.normalDepth, in.ids, nPixels, 0u, p.samples, p.seed,
              p.radius, (uint32_t*)c->queryQueueBuf.p, (uint32_t*)c->aoCountBuf.p, d.counts + 4};
     const uint32_t blocks = query_shape(nPixels, RT_BLOCK).blocks;
     hipLaunchKernelGGL(k_init_counts, dim3(1), dim3(64), 0, c->stream, c->q.counts, nPixels);
@@ -1635,24 +1633,6 @@ int output_plane(rt_ctx* c, float* d_out, OwnedPlane& own, size_t n, float4** ou
     return 0;
 }
 
-// The host-memory form of a pass: the nIn input planes of `bytes` bytes go up into one ctx buffer, one behind the other, `pass` runs
-// on the device copies with the nOut planes behind them as its outputs, and those come back (a NULL host output is not wanted).
-template <typename Pass>
-int staged(rt_ctx* c, DevBuf& buf, size_t bytes, std::initializer_list<const void*> in, std::initializer_list<void*> out, Pass pass) {
-    const size_t nIn = in.size(), nOut = out.size();
-    RT_HIP(c, hipSetDevice(c->device));
-    if (buf.bytes < (nIn + nOut) * bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees planes a pass in flight may be using
-    int rc = dev_alloc(c, buf, (nIn + nOut) * bytes);
-    if (rc) return rc;
-    char* d = (char*)buf.p;
-    for (size_t k = 0; k < nIn; k++) RT_HIP(c, hipMemcpyAsync(d + k * bytes, in.begin()[k], bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = pass(d))) return rc;
-    for (size_t k = 0; k < nOut; k++)
-        if (out.begin()[k]) RT_HIP(c, hipMemcpyAsync(out.begin()[k], d + (nIn + k) * bytes, bytes, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 // The motion table onto the device, on the ctx stream: stream order keeps the copy behind the launch that still reads the table of
 // the call before, and the call stays asynchronous. The pinned staging copy is this call's until the event says the copy engine has
 // read it; only a second upload before that waits.
@@ -1666,7 +1646,7 @@ int upload_motion(rt_ctx* c, const MotionTable& mt, TemporalMotion& mo) {
         RT_HIP(c, hipHostMalloc((void**)&c->tpMotionHost, bytes, hipHostMallocDefault));
         c->tpMotionHostBytes = bytes;
     }
-    if (c->tpMotionBuf.bytes < bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees a table a launch may still read
+    if (c->tpMotionBuf.bytes < bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // a table that grows frees the one a launch may still read
     int rc = dev_alloc(c, c->tpMotionBuf, bytes);
     if (rc) return rc;
     memcpy(c->tpMotionHost, mt.objects.data(), ob);
@@ -1741,12 +1721,14 @@ int rt_denoise_host(rt_ctx* c, uint32_t width, uint32_t height, const float* rgb
     if (!rgba || !out) return c->fail("rt_denoise_host: rgba and out are required");
     if (!aovs || !aovs->normalDepth || !aovs->albedo || !aovs->ids) return c->fail("rt_denoise_host: aovs needs the normalDepth, albedo and ids planes");
     const size_t bytes = (size_t)width * height * sizeof(float4);
-    return staged(c, c->dnHostBuf, bytes, {rgba, aovs->normalDepth, aovs->albedo, aovs->ids}, {out}, [&](char* d) {
+    const StagePart parts[] = {{rgba, nullptr, bytes}, {aovs->normalDepth, nullptr, bytes}, {aovs->albedo, nullptr, bytes}, {aovs->ids, nullptr, bytes},
+                               {nullptr, out, bytes}};
+    return staged(c, parts, [&](void* const* d) {
         RtAovBuffers planes{};
-        planes.normalDepth = (float*)(d + bytes);
-        planes.albedo = (float*)(d + 2 * bytes);
-        planes.ids = (uint32_t*)(d + 3 * bytes);
-        return rt_denoise(c, width, height, (const float*)d, &planes, &p, (float*)(d + 4 * bytes));
+        planes.normalDepth = (float*)d[1];
+        planes.albedo = (float*)d[2];
+        planes.ids = (uint32_t*)d[3];
+        return rt_denoise(c, width, height, (const float*)d[0], &planes, &p, (float*)d[4]);
     });
 }
 
@@ -1835,13 +1817,16 @@ int rt_temporal_accumulate_host(rt_ctx* c, uint32_t width, uint32_t height, cons
     if (!aovs || !aovs->normalDepth || !aovs->position || !aovs->albedo || !aovs->ids)
         return c->fail("rt_temporal_accumulate_host: aovs needs the normalDepth, position, albedo and ids planes");
     const size_t bytes = (size_t)width * height * sizeof(float4);
-    return staged(c, c->tpHostBuf, bytes, {rgba, aovs->normalDepth, aovs->position, aovs->albedo, aovs->ids}, {out, moments}, [&](char* d) {
+    // (a NULL `moments` is not wanted back; the pass still writes the plane)
+    const StagePart parts[] = {{rgba, nullptr, bytes}, {aovs->normalDepth, nullptr, bytes}, {aovs->position, nullptr, bytes}, {aovs->albedo, nullptr, bytes},
+                               {aovs->ids, nullptr, bytes}, {nullptr, out, bytes}, {nullptr, moments, bytes}};
+    return staged(c, parts, [&](void* const* d) {
         RtAovBuffers planes{};
-        planes.normalDepth = (float*)(d + bytes);
-        planes.position = (float*)(d + 2 * bytes);
-        planes.albedo = (float*)(d + 3 * bytes);
-        planes.ids = (uint32_t*)(d + 4 * bytes);
-        return rt_temporal_accumulate(c, width, height, cam, (const float*)d, &planes, &p, (float*)(d + 5 * bytes), (float*)(d + 6 * bytes));
+        planes.normalDepth = (float*)d[1];
+        planes.position = (float*)d[2];
+        planes.albedo = (float*)d[3];
+        planes.ids = (uint32_t*)d[4];
+        return rt_temporal_accumulate(c, width, height, cam, (const float*)d[0], &planes, &p, (float*)d[5], (float*)d[6]);
     });
 }
 
@@ -1888,17 +1873,8 @@ int rt_build_sample_map_host(rt_ctx* c, uint32_t width, uint32_t height, const f
     const std::string m = check_sample_map(width, height, p, true, OwnedRows{}, "rt_build_sample_map_host");
     if (!m.empty()) return c->fail(m);
     const size_t n = (size_t)width * height;
-    RT_HIP(c, hipSetDevice(c->device));
-    if (c->smHostBuf.bytes < n * 20) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees planes a build in flight may be using
-    int rc = dev_alloc(c, c->smHostBuf, n * 20);
-    if (rc) return rc;
-    float* const dMom = (float*)c->smHostBuf.p;
-    uint32_t* const dMap = (uint32_t*)((char*)c->smHostBuf.p + n * 16);
-    RT_HIP(c, hipMemcpyAsync(dMom, moments, n * 16, hipMemcpyHostToDevice, c->stream));
-    if ((rc = rt_build_sample_map(c, width, height, dMom, &p, dMap))) return rc;
-    RT_HIP(c, hipMemcpyAsync(map, dMap, n * 4, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const StagePart parts[] = {{moments, nullptr, n * sizeof(float4)}, {nullptr, map, n * sizeof(uint32_t)}};
+    return staged(c, parts, [&](void* const* d) { return rt_build_sample_map(c, width, height, (const float*)d[0], &p, (uint32_t*)d[1]); });
 }
 
 int rt_get_counters(rt_ctx* c, RtCounters* out) {
@@ -2297,34 +2273,21 @@ int rt_deinterleave_strips(rt_ctx* c, const float* d_strips, uint32_t width, uin
 
 int rt_deinterleave_strips_host(rt_ctx* c, const float* strips, uint32_t width, uint32_t height, int nRanks, float* frame) {
     if (!c || !strips || !frame) return -1;
-    RT_HIP(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)width * height * 16;
-    int rc = dev_alloc(c, c->scratchBuf, 2 * bytes);
-    if (rc) return rc;
-    float* ds = (float*)c->scratchBuf.p;
-    float* df = (float*)((char*)c->scratchBuf.p + bytes);
-    RT_HIP(c, hipMemcpyAsync(ds, strips, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = rt_deinterleave_strips(c, ds, width, height, nRanks, df))) return rc;
-    RT_HIP(c, hipMemcpyAsync(frame, df, bytes, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    if (nRanks < 1 || width == 0 || height == 0) return c->fail("rt_deinterleave_strips: bad geometry");   // (the device form's words: an empty frame has no arrays to stage)
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    const StagePart parts[] = {{strips, nullptr, bytes}, {nullptr, frame, bytes}};
+    return staged(c, parts, [&](void* const* d) { return rt_deinterleave_strips(c, (const float*)d[0], width, height, nRanks, (float*)d[1]); });
 }
 
 int rt_device_math_probe(rt_ctx* c, uint32_t n, const float* in, float* out) {
     if (!c || !in || !out) return -1;
     if (n == 0) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    const size_t bi = (size_t)n * 32 * 4, bo = (size_t)n * 64 * 4;
-    int rc = dev_alloc(c, c->scratchBuf, bi + bo);
-    if (rc) return rc;
-    float* di = (float*)c->scratchBuf.p;
-    float* dout = di + (size_t)n * 32;
-    RT_HIP(c, hipMemcpyAsync(di, in, bi, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_math_probe, dim3((n + 63) / 64), dim3(64), 0, c->stream, di, dout, n);
-    RT_HIP(c, hipGetLastError());
-    RT_HIP(c, hipMemcpyAsync(out, dout, bo, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const StagePart parts[] = {{in, nullptr, (size_t)n * 32 * 4}, {nullptr, out, (size_t)n * 64 * 4}};
+    return staged(c, parts, [&](void* const* d) {
+        hipLaunchKernelGGL(k_math_probe, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const float*)d[0], (float*)d[1], n);
+        RT_HIP(c, hipGetLastError());
+        return 0;
+    });
 }
 
 int rt_measure_copy_bandwidth(rt_ctx* c, size_t bytes, int iters, double* gbps) {

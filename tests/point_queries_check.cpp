@@ -1,5 +1,5 @@
 // point_queries_check.cpp — what the point queries refuse (ray_tracer_amd/csrc/point_queries.h: check_point_query), in their order and
-// with their messages, the block and byte arithmetic of a batch (point_shape, point_staging), the stack choice (nearest_stack), the
+// with their messages, the block and byte arithmetic of a batch (point_shape), the stack choice (nearest_stack), the
 // identity object's pruning record, and the units of the rule (include/rt_point_query.h: rt_point_triangle in each of its seven
 // regions, on the plane, at a vertex, on zero-area triangles; rt_point_sphere; rt_nearest_exhaustive_host on a hand-made scene), on
 // the CPU, built with plain g++ by tests/test_point_queries_host.py. No array is ever dereferenced by the checks: the addresses are
@@ -60,23 +60,14 @@ void arithmetic() {
     CHECK(sizeof(RtNearest) == 48);
     const PointShape zero = point_shape(0, 256);
     CHECK(zero.blocks == 0 && zero.pointBytes == 0 && zero.limitBytes == 0 && zero.outBytes == 0);
-    CHECK(point_staging(0, true).bytes == 0 && point_staging(0, false).bytes == 0);
     struct Row { uint32_t n, blocks; } const rows[] = {{1, 1}, {63, 1}, {64, 1}, {65, 1}, {256, 1}, {257, 2}, {1024, 4}, {(1u << 30) - 1u, 1u << 22}};
     for (const Row& r : rows) {
         const PointShape s = point_shape(r.n, 256);
         CHECK(s.blocks == r.blocks);
         CHECK((uint64_t)s.blocks * 256 >= r.n && (uint64_t)(s.blocks - 1) * 256 < r.n);
         CHECK(s.pointBytes == (size_t)12 * r.n && s.limitBytes == (size_t)4 * r.n && s.outBytes == (size_t)48 * r.n);
-        for (int lim = 0; lim < 2; lim++) {
-            const PointStaging g = point_staging(r.n, lim != 0);
-            CHECK(g.points == 0 && g.limits % 256 == 0 && g.out % 256 == 0 && g.bytes % 256 == 0);
-            CHECK(g.limits >= s.pointBytes && g.limits < s.pointBytes + 256);
-            CHECK(lim ? g.out >= g.limits + s.limitBytes : g.out == g.limits);
-            CHECK(g.bytes >= g.out + s.outBytes && g.bytes < g.out + s.outBytes + 256);
-        }
     }
     CHECK(point_shape((1u << 30) - 1u, 256).outBytes == 51539607504ull);   // past 32 bits: size_t arithmetic
-    CHECK(point_staging((1u << 30) - 1u, true).bytes > 0xffffffffull);
 
     std::string e;
     CHECK(nearest_stack("f", 0, &e) == 24 && nearest_stack("f", 24, &e) == 24 && nearest_stack("f", 25, &e) == 64 && nearest_stack("f", 64, &e) == 64);

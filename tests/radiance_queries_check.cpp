@@ -1,6 +1,6 @@
 // radiance_queries_check.cpp — what the radiance queries refuse (ray_tracer_amd/csrc/radiance_queries.h: check_radiance_query), in
-// their order and with their messages, the pieces of a batch (radiance_piece_count, radiance_piece), the staging offsets of the _host
-// form (radiance_staging) and the frame's seed (radiance_starting_seed), on the CPU, built with plain g++ by
+// their order and with their messages, the pieces of a batch (radiance_piece_count, radiance_piece), the bytes of its arrays
+// (radiance_shape; where they lie in the staging buffer of the _host form: tests/host_staging_check.cpp) and the frame's seed (radiance_starting_seed), on the CPU, built with plain g++ by
 // tests/test_radiance_queries_host.py. No array is ever dereferenced by the checks: the addresses are made up. Prints
 // "seed <frameCount> <startingSeed>" for the frames the Python side compares with the oracle's random(), then "radiance queries ok".
 #include <cstdio>
@@ -106,20 +106,13 @@ void pieces() {
     cover((1u << 30) - 1u, (1ull << 20) << 10, 1);   // the knob's largest value
 }
 
-void staging() {
+void shape() {
     for (uint32_t n : {1u, 63u, 64u, 65u, 2299u, (1u << 30) - 1u})
         for (int ids = 0; ids < 2; ids++) {
-            const RadianceStaging g = radiance_staging(n, ids != 0);
+            const RadianceShape g = radiance_shape(n, ids != 0);
             CHECK(g.vecBytes == (size_t)12 * n && g.idBytes == (ids ? (size_t)4 * n : 0) && g.outBytes == (size_t)16 * n);
-            CHECK(g.origins == 0 && g.dirs % 256 == 0 && g.ids % 256 == 0 && g.out % 256 == 0 && g.bytes % 256 == 0);
-            // one behind the other: no array reaches into the next
-            CHECK(g.dirs >= g.origins + g.vecBytes && g.ids >= g.dirs + g.vecBytes);
-            CHECK(ids ? g.out >= g.ids + g.idBytes : g.out == g.ids);
-            CHECK(g.bytes >= g.out + g.outBytes && g.bytes < g.out + g.outBytes + 256);
         }
-    const RadianceStaging g = radiance_staging(65, true);
-    CHECK(g.dirs == 1024 && g.ids == 2048 && g.out == 2560 && g.bytes == 2560 + 1280);
-    const RadianceStaging top = radiance_staging((1u << 30) - 1u, true);
+    const RadianceShape top = radiance_shape((1u << 30) - 1u, true);
     CHECK(top.outBytes == 17179869168ull);   // past 32 bits: size_t arithmetic
 }
 
@@ -128,7 +121,7 @@ void staging() {
 int main() {
     refusals();
     pieces();
-    staging();
+    shape();
     for (uint32_t frame : {0u, 3u, 0xffffffffu}) printf("seed %u %u\n", frame, radiance_starting_seed(frame));
     if (failures) { printf("%d check(s) failed\n", failures); return 1; }
     printf("radiance queries ok\n");

@@ -1,7 +1,7 @@
 // ray_queries_check.cpp — what the ray queries and the ambient-occlusion pass refuse (ray_tracer_amd/csrc/ray_queries.h: check_ray_query,
-// check_ao), in their order and with their messages, and the slot and byte arithmetic of a batch (query_shape, query_staging), on
+// check_ao), in their order and with their messages, and the slot and byte arithmetic of a batch (query_shape), on
 // the CPU, built with plain g++ by tests/test_ray_queries_host.py. No array is ever dereferenced by the checks: the addresses are
-// made up. rt_ao_rays_host, which lives in the same host-only unit, runs on two real records. Prints "ray queries ok".
+// made up (where the arrays lie in the staging buffer of the _host forms: tests/host_staging_check.cpp). rt_ao_rays_host, which lives in the same host-only unit, runs on two real records. Prints "ray queries ok".
 #include <cmath>
 #include <cstdio>
 #include <limits>
@@ -66,20 +66,10 @@ void arithmetic() {
         CHECK(s.hitBytes == (size_t)60 * r.n && s.occludedBytes == (size_t)r.n);
         // every slot id fits a queue entry: slot * 4 + kind in 32 bits
         CHECK(((uint64_t)(r.n - 1) << 2 | 3u) <= 0xffffffffull);
-        for (int tm = 0; tm < 2; tm++)
-            for (size_t rec : {sizeof(RtHit), (size_t)1}) {
-                const QueryStaging g = query_staging(r.n, tm != 0, rec);
-                CHECK(g.origins == 0 && g.dirs % 256 == 0 && g.tmax % 256 == 0 && g.out % 256 == 0 && g.bytes % 256 == 0);
-                CHECK(g.dirs >= s.vecBytes && g.tmax >= g.dirs + s.vecBytes);
-                CHECK(tm ? g.out >= g.tmax + s.tmaxBytes : g.out == g.tmax);
-                CHECK(g.bytes >= g.out + (size_t)r.n * rec && g.bytes < g.out + (size_t)r.n * rec + 256);
-            }
     }
     CHECK(query_shape(64, 64).blocks == 1 && query_shape(65, 64).blocks == 2 && query_shape(63, 64).blocks == 1);
     const QueryShape top = query_shape((1u << 30) - 1u, 256);
     CHECK(top.hitBytes == 64424509380ull);   // past 32 bits: size_t arithmetic
-    const QueryStaging g = query_staging(65, true, sizeof(RtHit));
-    CHECK(g.dirs == 1024 && g.tmax == 2048 && g.out == 2560 && g.bytes == 2560 + 4096);
 }
 
 void ao_checks() {

@@ -2,7 +2,7 @@
 include/rt_point_query.h, and rt_nearest_exhaustive_host).
 
 tests/point_queries_check.cpp, built with plain g++, provokes every refusal with made-up addresses, in the stated order, with its
-message; covers the block, byte and staging arithmetic at n = 0, 1, ... and 2^30 - 1; the stack choice; rt_point_triangle in each of
+message; covers the block and byte arithmetic at n = 0, 1, ... and 2^30 - 1 (the staging offsets: tests/test_host_staging_host.py); the stack choice; rt_point_triangle in each of
 its seven regions, on the plane (dst exactly 0), at a vertex and on zero-area triangles; rt_point_sphere; and the exhaustive loop
 on a hand-made scene. It also prints the pruning record of the matrices this file hands it, and sMin is held against numpy's
 singular values: never above the true value, and within the stated margin below it.

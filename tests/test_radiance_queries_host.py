@@ -1,8 +1,8 @@
 """What the radiance queries (rt_query_radiance and its _host form) refuse before anything is allocated, the pieces a batch runs in,
-the staging offsets of the _host form and the frame's seed (ray_tracer_amd/csrc/radiance_queries.h), on the CPU:
+the bytes of its arrays and the frame's seed (ray_tracer_amd/csrc/radiance_queries.h), on the CPU:
 tests/radiance_queries_check.cpp provokes every refusal with made-up addresses, in the stated order, with its message, covers
-[0, n) with the pieces for n = 0, 1, 1023, 1024, 1025 and 3 x 1024 + 5 at "radiance_max_kslots" 1, checks that the staged arrays are
-aligned and do not overlap with and without ids, and prints startingSeed for frameCount 0, 3 and 2^32 - 1, which is compared here
+[0, n) with the pieces for n = 0, 1, 1023, 1024, 1025 and 3 x 1024 + 5 at "radiance_max_kslots" 1, checks the byte counts with and without ids
+(that the staged arrays are aligned and do not overlap: tests/test_host_staging_host.py), and prints startingSeed for frameCount 0, 3 and 2^32 - 1, which is compared here
 with the oracle's random() pushed through uint(random(frameCount) * 23892183.f)."""
 import os
 import re
