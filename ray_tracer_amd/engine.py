@@ -18,14 +18,11 @@ import os
 import numpy as np
 
 from . import _capi
+from .devmem import DeviceBuffer, RtError, hip as _hip   # noqa: F401  (engine.RtError and engine._hip are where callers know them)
 from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtNearest, RtPointBatch, RtRadianceParams, RtRayBatch,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
-
-
-class RtError(RuntimeError):
-    pass
 
 
 def placement(position=(0, 0, 0), rotation=(0, 0, 0), scale=(1, 1, 1), samplerIndex=0, frontOnly=False):
@@ -245,12 +242,12 @@ class Renderer:
         self._scene = None
         self._shape = None
         self._aov_shape = None
-        self._owned = {}                  # device buffers of this module, by name: (pointer, bytes) (_device_buffer)
+        self._owned = {}                  # device buffers of this module, by name (_device_buffer)
 
     def close(self):
         if getattr(self, "_h", None):
-            for p, _ in self._owned.values():
-                _hip().hipFree(p)
+            for b in self._owned.values():
+                b.free()
             self._owned = {}
             self._l.rt_destroy(self._h)
             self._h = None
@@ -317,31 +314,30 @@ class Renderer:
         """One dispatch. Returns an (nRows, width, 4) float32 array unless the
         caller supplied a device pointer."""
         if nRows is None:
-            nRows = (height - row0 + rowStride - 1) // rowStride
+            nRows = _tile_rows(height, row0, rowStride)
         self.fill_counts(pc)
         self._check(self._l.rt_render(self._h, C.byref(pc), width, height, row0, rowStride, nRows,
                                       C.c_void_p(out_ptr) if out_ptr else None), "rt_render")
-        self._shape = (nRows, width, 4)
-        if not sync:
-            return None
-        self.sync()
-        if out_ptr:
-            return None
-        return self.read_rgba()
+        return self._rendered(nRows, width, out_ptr, sync)
 
-    def render_frames(self, pc, width, height, nFrames, row0=0, rowStride=1, nRows=None, out_ptr=None, sync=True):
-        """nFrames progressive dispatches starting at pc.frameCount (rt_render_frames): the frames share launches where one
-        frame would leave the GPU short of pixels. Same pixels as nFrames render() calls."""
-        if nRows is None:
-            nRows = (height - row0 + rowStride - 1) // rowStride
-        self.fill_counts(pc)
-        self._check(self._l.rt_render_frames(self._h, C.byref(pc), width, height, row0, rowStride, nRows, int(nFrames),
-                                             C.c_void_p(out_ptr) if out_ptr else None), "rt_render_frames")
+    def _rendered(self, nRows, width, out_ptr, sync):
+        """The common end of render / render_frames / render_sampled: the tile's array, or None when the caller did not wait
+        (sync=False) or supplied the device pointer."""
         self._shape = (nRows, width, 4)
         if not sync:
             return None
         self.sync()
         return None if out_ptr else self.read_rgba()
+
+    def render_frames(self, pc, width, height, nFrames, row0=0, rowStride=1, nRows=None, out_ptr=None, sync=True):
+        """nFrames progressive dispatches starting at pc.frameCount (rt_render_frames): the frames share launches where one
+        frame would leave the GPU short of pixels. Same pixels as nFrames render() calls."""
+        if nRows is None:
+            nRows = _tile_rows(height, row0, rowStride)
+        self.fill_counts(pc)
+        self._check(self._l.rt_render_frames(self._h, C.byref(pc), width, height, row0, rowStride, nRows, int(nFrames),
+                                             C.c_void_p(out_ptr) if out_ptr else None), "rt_render_frames")
+        return self._rendered(nRows, width, out_ptr, sync)
 
     def render_sampled(self, pc, width, height, sample_map, nFrames=1, row0=0, rowStride=1, nRows=None, out_ptr=None, sync=True):
         """render_frames() with a sample count per pixel (rt_render_sampled): pixel p gets min(sample_map[p], S) samples, S being the
@@ -349,27 +345,21 @@ class Renderer:
         and costs nothing. `sample_map`: an (nRows, width) array of counts in the order of the rows rendered, or a device pointer (int)
         to such a plane, as build_sample_map(to_host=False) returns it; None: render_frames()."""
         if nRows is None:
-            nRows = (height - row0 + rowStride - 1) // rowStride
+            nRows = _tile_rows(height, row0, rowStride)
         d_map = None
         if sample_map is not None and not isinstance(sample_map, (int, np.integer)):
             m = np.ascontiguousarray(sample_map, np.uint32)
             if m.shape != (nRows, width):
                 raise ValueError(f"sample_map {m.shape}: not the ({nRows}, {width}) counts of the rows rendered")
             self.sync()   # (a dispatch still in flight may be reading the buffer this one reuses)
-            d_map = self._device_buffer("sample_map_in", m.nbytes)
-            if m.nbytes and _hip().hipMemcpy(d_map, m.ctypes.data, m.nbytes, 1) != 0:   # hipMemcpyHostToDevice
-                raise RtError("render_sampled: the sample map could not be copied to the device")
+            d_map = self._owned_buffer("sample_map_in", m.nbytes).upload(m, error="render_sampled: the sample map could not be copied to the device").ptr
         elif sample_map is not None:
             d_map = int(sample_map)
         self.fill_counts(pc)
         self._check(self._l.rt_render_sampled(self._h, C.byref(pc), width, height, row0, rowStride, nRows, int(nFrames),
                                               C.c_void_p(d_map) if d_map else None, C.c_void_p(out_ptr) if out_ptr else None),
                     "rt_render_sampled")
-        self._shape = (nRows, width, 4)
-        if not sync:
-            return None
-        self.sync()
-        return None if out_ptr else self.read_rgba()
+        return self._rendered(nRows, width, out_ptr, sync)
 
     def build_sample_map(self, moments=None, width=None, height=None, to_host=True, **params):
         """Sample counts for render_sampled() from the moments of temporal_accumulate() (rt_build_sample_map; DESIGN.md, "Per-pixel
@@ -395,15 +385,12 @@ class Renderer:
             return out
         H, W = (height, width) if width and height else (self._aov_shape or (0, 0))
         self.sync()   # (the plane this call reuses may still be read by a render_sampled() in flight)
-        d_map = self._device_buffer("sample_map_out", max(H * W, 1) * 4)
-        self._check(self._l.rt_build_sample_map(self._h, W, H, None, C.byref(p), C.c_void_p(d_map)), "rt_build_sample_map")
+        d_map = self._owned_buffer("sample_map_out", max(H * W, 1) * 4)
+        self._check(self._l.rt_build_sample_map(self._h, W, H, None, C.byref(p), C.c_void_p(d_map.ptr)), "rt_build_sample_map")
         if not to_host:
-            return d_map
+            return d_map.ptr
         self.sync()
-        out = np.empty((H, W), np.uint32)
-        if out.nbytes and _hip().hipMemcpy(out.ctypes.data, d_map, out.nbytes, 2) != 0:   # hipMemcpyDeviceToHost
-            raise RtError("build_sample_map: the map could not be copied back")
-        return out
+        return d_map.download((H, W), np.uint32, error="build_sample_map: the map could not be copied back")
 
     def sample_map_stats(self):
         """Of the last build_sample_map() (rt_sample_map_stats; blocks): samples, the sum of the counts; pixels; unknown, the pixels
@@ -413,17 +400,17 @@ class Renderer:
         return {n: getattr(st, n) for n, _ in RtSampleMapStats._fields_}
 
     def _device_buffer(self, name, need):
-        """Device memory of at least `need` bytes under a name, kept between calls and freed with the renderer."""
-        p, have = self._owned.get(name, (None, 0))
-        if have < need:
-            if p:
-                _hip().hipFree(p)
-                del self._owned[name]
-            q = C.c_void_p()
-            if _hip().hipMalloc(C.byref(q), need) != 0 or not q.value:
-                raise RtError(f"no device memory for {need} bytes ({name})")
-            self._owned[name] = (q.value, need)
-        return self._owned[name][0]
+        """Device memory of at least `need` bytes under a name, kept between calls and freed with the renderer: its address."""
+        return self._owned_buffer(name, need).ptr
+
+    def _owned_buffer(self, name, need):
+        """_device_buffer's DeviceBuffer, for the copies in and out."""
+        b = self._owned.get(name)
+        if b is None or b.nbytes < need:
+            if b is not None:
+                self._owned.pop(name).free()
+            b = self._owned[name] = DeviceBuffer(need, name)
+        return b
 
     def run_compute(self, pc, width, height, frames=1, **tile):
         """Frame semantics of draw()/run_compute (src/vk_engine.cpp:1782,1812-1814); `tile` = row0 / rowStride / nRows
@@ -478,8 +465,7 @@ class Renderer:
         """Both ray queries: numpy arrays through the _host entry points, device memory (objects with data_ptr(), or integer device
         pointers with n=) through the asynchronous ones."""
         rec = C.sizeof(RtHit) if what == "closest" else 1
-        on_device = [hasattr(x, "data_ptr") or isinstance(x, (int, np.integer)) for x in (origins, dirs)]
-        if not any(on_device):
+        if not _on_device(origins, dirs):
             o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
             d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
             if d.shape != o.shape:
@@ -494,17 +480,10 @@ class Renderer:
             fn = getattr(self._l, f"rt_query_{what}_host")
             self._check(fn(self._h, C.byref(batch), C.addressof(res) if what == "closest" else res.ctypes.data), f"rt_query_{what}_host")
             return res if what == "closest" else res.astype(bool)
-        if not all(on_device):
-            raise ValueError("origins and dirs must both be host arrays or both be device memory")
-        if out is None:
-            raise ValueError("device-pointer inputs need out=: device memory for the results")
-        if n is None:
-            if not hasattr(origins, "numel"):
-                raise ValueError("integer device pointers need n=")
-            n = int(origins.numel()) // 3
+        n = _device_count(origins, n, out)
         ptrs = [_device_ptr(origins, "origins", 12 * n), _device_ptr(dirs, "dirs", 12 * n),
                 None if tmax is None else _device_ptr(tmax, "tmax", 4 * n)]
-        batch = RtRayBatch(ptrs[0], ptrs[1], ptrs[2], int(n))
+        batch = RtRayBatch(ptrs[0], ptrs[1], ptrs[2], n)
         fn = getattr(self._l, f"rt_query_{what}")
         self._check(fn(self._h, C.byref(batch), C.c_void_p(_device_ptr(out, "out", rec * n, floats=False))), f"rt_query_{what}")
         if sync:
@@ -530,7 +509,7 @@ class Renderer:
         with n= goes through the asynchronous entry point, the RtNearest records are written to `out` (device memory, 16-byte
         aligned, 48 bytes per point) and sync=False is allowed."""
         rec = C.sizeof(RtNearest)
-        if not (hasattr(points, "data_ptr") or isinstance(points, (int, np.integer))):
+        if not _on_device(points):
             p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
             t = None if max_dist is None else np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
             if t is not None and t.shape[0] != p.shape[0]:
@@ -541,13 +520,8 @@ class Renderer:
             res = (RtNearest * p.shape[0])()
             self._check(self._l.rt_query_nearest_host(self._h, C.byref(batch), C.addressof(res)), "rt_query_nearest_host")
             return res
-        if out is None:
-            raise ValueError("device-pointer inputs need out=: device memory for the results")
-        if n is None:
-            if not hasattr(points, "numel"):
-                raise ValueError("integer device pointers need n=")
-            n = int(points.numel()) // 3
-        batch = RtPointBatch(_device_ptr(points, "points", 12 * n), None if max_dist is None else _device_ptr(max_dist, "max_dist", 4 * n), int(n))
+        n = _device_count(points, n, out)
+        batch = RtPointBatch(_device_ptr(points, "points", 12 * n), None if max_dist is None else _device_ptr(max_dist, "max_dist", 4 * n), n)
         self._check(self._l.rt_query_nearest(self._h, C.byref(batch), C.c_void_p(_device_ptr(out, "out", rec * n, floats=False))), "rt_query_nearest")
         if sync:
             self.sync()
@@ -569,8 +543,7 @@ class Renderer:
             raise ValueError("samples, bounces and frame are unsigned")
         p = RtRadianceParams(int(samples), int(bounces), 1 if progressive else 0, int(frame) & 0xFFFFFFFF)
         env = C.byref(environment) if environment is not None else None
-        on_device = [hasattr(x, "data_ptr") or isinstance(x, (int, np.integer)) for x in (origins, dirs)]
-        if not any(on_device):
+        if not _on_device(origins, dirs):
             o, d = np.asarray(origins), np.asarray(dirs)
             for name, a in (("origins", o), ("dirs", d)):
                 if a.dtype != np.float32:
@@ -608,17 +581,10 @@ class Renderer:
             self._check(self._l.rt_query_radiance_host(self._h, C.byref(batch), i.ctypes.data if i is not None else None, C.byref(p), env,
                                                        res.ctypes.data), "rt_query_radiance_host")
             return res
-        if not all(on_device):
-            raise ValueError("origins and dirs must both be host arrays or both be device memory")
-        if out is None:
-            raise ValueError("device-pointer inputs need out=: device memory for the results")
-        if n is None:
-            if not hasattr(origins, "numel"):
-                raise ValueError("integer device pointers need n=")
-            if hasattr(origins, "shape") and (len(origins.shape) != 2 or origins.shape[1] != 3):
-                raise ValueError(f"origins: shape {tuple(origins.shape)}, not (n, 3)")
-            n = int(origins.numel()) // 3
-        n = int(n)
+        counted = n is None
+        n = _device_count(origins, n, out)
+        if counted and hasattr(origins, "shape") and (len(origins.shape) != 2 or origins.shape[1] != 3):
+            raise ValueError(f"origins: shape {tuple(origins.shape)}, not (n, 3)")
         if hasattr(dirs, "shape") and hasattr(origins, "shape") and tuple(dirs.shape) != tuple(origins.shape):
             raise ValueError(f"origins {tuple(origins.shape)} and dirs {tuple(dirs.shape)}: not one (n, 3) pair")
         if ids is not None and hasattr(ids, "dtype") and not str(ids.dtype).endswith(("uint32", "int32")):
@@ -645,13 +611,11 @@ class Renderer:
             shape = aovs["depth"].shape
             n = int(np.prod(shape))
             self.sync()   # (a pass still in flight may be reading the buffer this one reuses)
-            d = self._device_buffer("ao_planes", max(n, 1) * 16 * 3)
+            d = self._owned_buffer("ao_planes", max(n, 1) * 16 * 3)
             b = RtAovBuffers()
             for i, k in enumerate(("position", "normalDepth", "ids")):
-                a = np.ascontiguousarray(planes[k])
-                if a.nbytes and _hip().hipMemcpy(d + i * n * 16, a.ctypes.data, a.nbytes, 1) != 0:   # hipMemcpyHostToDevice
-                    raise RtError("render_ao: the planes could not be copied to the device")
-                setattr(b, k, d + i * n * 16)
+                d.upload(planes[k], offset=i * n * 16, error="render_ao: the planes could not be copied to the device")
+                setattr(b, k, d.ptr + i * n * 16)
             self._check(self._l.rt_render_ao(self._h, n, C.byref(b), C.byref(p), None), "rt_render_ao")
         out = np.empty(shape, np.float32)
         self._check(self._l.rt_read_ao(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), "rt_read_ao")
@@ -662,7 +626,7 @@ class Renderer:
         aovs_to_numpy, arrays shaped (nRows, width[, 3]); with `out_ptrs` (device pointers keyed by the RtAovBuffers field names,
         e.g. a torch tensor's data_ptr(); planes left out are not written) the pass writes there and returns None."""
         if nRows is None:
-            nRows = (height - row0 + rowStride - 1) // rowStride
+            nRows = _tile_rows(height, row0, rowStride)
         d = None
         if out_ptrs is not None:
             unknown = set(out_ptrs) - set(AOV_PLANES)
@@ -682,8 +646,7 @@ class Renderer:
     def read_aovs(self):
         """The context's own planes of the last render_aovs() without `out_ptrs` (rt_read_aovs), as aovs_to_numpy gives them."""
         n, w = self._aov_shape or (0, 0)
-        planes = {k: np.empty((n, w, 4), np.uint32 if k == "ids" else np.float32) for k in AOV_PLANES}
-        b = RtAovBuffers(**{k: v.ctypes.data for k, v in planes.items()})
+        planes, b = _empty_planes(n, w)
         self._check(self._l.rt_read_aovs(self._h, C.byref(b), n * w), "rt_read_aovs")
         return aovs_to_numpy(planes)
 
@@ -695,26 +658,24 @@ class Renderer:
         (guides, first): `first` is what render_aovs() returns for the same tile, from the same traversal (the planes
         temporal_accumulate() takes). The context's own first-hit planes (render_aovs) are left as they are."""
         if nRows is None:
-            nRows = (height - row0 + rowStride - 1) // rowStride
+            nRows = _tile_rows(height, row0, rowStride)
         n = nRows * width
         first = None
         if first_hit:
-            d_first = self._device_buffer("first_hit", max(n, 1) * 16 * len(AOV_PLANES))   # what rt_render_guides fills beside the guides
-            first = RtAovBuffers(**{k: d_first + i * n * 16 for i, k in enumerate(AOV_PLANES)})
+            d_first = self._owned_buffer("first_hit", max(n, 1) * 16 * len(AOV_PLANES))   # what rt_render_guides fills beside the guides
+            first = RtAovBuffers(**{k: d_first.ptr + i * n * 16 for i, k in enumerate(AOV_PLANES)})
         self.fill_counts(pc)
         self._check(self._l.rt_render_guides(self._h, C.byref(pc), width, height, row0, rowStride, nRows, int(max_bounces), None,
                                              C.byref(first) if first is not None else None), "rt_render_guides")
-        planes = {k: np.empty((nRows, width, 4), np.uint32 if k == "ids" else np.float32) for k in AOV_PLANES}
-        b = RtAovBuffers(**{k: v.ctypes.data for k, v in planes.items()})
+        planes, b = _empty_planes(nRows, width)
         self._check(self._l.rt_read_guides(self._h, C.byref(b), n), "rt_read_guides")   # (blocks: the pass is over)
         g = aovs_to_numpy(planes)
         g["bounces"], g["cut"] = (planes["ids"][..., 3] >> 8) & 15, (planes["ids"][..., 3] & 8) != 0
         if first is None:
             return g
-        planes = {k: np.empty((nRows, width, 4), np.uint32 if k == "ids" else np.float32) for k in AOV_PLANES}
-        for k in AOV_PLANES:
-            if _hip().hipMemcpy(planes[k].ctypes.data, getattr(first, k), n * 16, 2) != 0:   # hipMemcpyDeviceToHost
-                raise RtError("render_guides: the first-hit planes could not be copied back")
+        planes, _ = _empty_planes(nRows, width)
+        for i, k in enumerate(AOV_PLANES):
+            d_first.download(into=planes[k], offset=i * n * 16, error="render_guides: the first-hit planes could not be copied back")
         return g, aovs_to_numpy(planes)
 
     def denoise(self, frame=None, aovs=None, iterations=5, sigma_luminance=4.0, sigma_normal=128.0, sigma_depth=1.0):
@@ -730,14 +691,7 @@ class Renderer:
             self._check(self._l.rt_read_denoised_rgba_f32(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size),
                         "rt_read_denoised_rgba_f32")
             return out
-        if frame is None or aovs is None:
-            raise ValueError("denoise() takes both a frame and its AOV planes, or neither (the context's own)")
-        frame = np.ascontiguousarray(frame, np.float32)
-        H, W = frame.shape[:2]
-        if frame.shape != (H, W, 4) or aovs["depth"].shape != (H, W):
-            raise ValueError(f"frame {frame.shape} and planes {aovs['depth'].shape}: not one (H, W, 4) frame and its (H, W) planes")
-        planes = numpy_to_aovs(aovs)
-        b = RtAovBuffers(**{k: v.ctypes.data for k, v in planes.items()})
+        frame, H, W, _planes, b = _frame_with_planes("denoise", frame, aovs)
         out = np.empty_like(frame)
         self._check(self._l.rt_denoise_host(self._h, W, H, frame.ctypes.data, C.byref(b), C.byref(p), out.ctypes.data),
                     "rt_denoise_host")
@@ -760,14 +714,7 @@ class Renderer:
             if moments:
                 self._check(self._l.rt_read_temporal_moments(self._h, mom.ctypes.data_as(fp), mom.size), "rt_read_temporal_moments")
             return (out, mom) if moments else out
-        if frame is None or aovs is None:
-            raise ValueError("temporal_accumulate() takes both a frame and its AOV planes, or neither (the context's own)")
-        frame = np.ascontiguousarray(frame, np.float32)
-        H, W = frame.shape[:2]
-        if frame.shape != (H, W, 4) or aovs["depth"].shape != (H, W):
-            raise ValueError(f"frame {frame.shape} and planes {aovs['depth'].shape}: not one (H, W, 4) frame and its (H, W) planes")
-        planes = numpy_to_aovs(aovs)
-        b = RtAovBuffers(**{k: v.ctypes.data for k, v in planes.items()})
+        frame, H, W, _planes, b = _frame_with_planes("temporal_accumulate", frame, aovs)
         out, mom = np.empty_like(frame), np.empty_like(frame)
         self._check(self._l.rt_temporal_accumulate_host(self._h, W, H, C.byref(cam), frame.ctypes.data, C.byref(b), C.byref(p), out.ctypes.data,
                                                         mom.ctypes.data), "rt_temporal_accumulate_host")
@@ -895,22 +842,52 @@ class Renderer:
 
 AOV_PLANES = ("normalDepth", "position", "albedo", "rayDir", "ids")   # the fields of RtAovBuffers
 
-_hip_handle = None
+
+def _tile_rows(height, row0, rowStride):
+    """How many of the rows row0, row0 + rowStride, ... lie in an image of `height` rows: a tile's nRows when the caller names none."""
+    return (height - row0 + rowStride - 1) // rowStride
 
 
-def _hip():
-    """The HIP runtime the library is bound to, for the few device buffers this module owns. Looked up through the library's own
-    handle (dlsym searches a library and then its dependencies), so that a second copy of the runtime in the process (a
-    framework's wheel bundles one) is never taken for it."""
-    global _hip_handle
-    if _hip_handle is None:
-        h = C.CDLL(_capi.LIB_PATH)
-        h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        h.hipFree.argtypes = [C.c_void_p]
-        _hip_handle = h
-    return _hip_handle
+def _plane_buffers(planes):
+    return RtAovBuffers(**{k: v.ctypes.data for k, v in planes.items()})
 
+
+def _empty_planes(n, w):
+    """An empty plane set of n rows of w records for the library to fill, and the RtAovBuffers that points into it."""
+    planes = {k: np.empty((n, w, 4), np.uint32 if k == "ids" else np.float32) for k in AOV_PLANES}
+    return planes, _plane_buffers(planes)
+
+
+def _frame_with_planes(who, frame, aovs):
+    """The host form of denoise() / temporal_accumulate(): one (H, W, 4) frame with the (H, W) planes of render_aovs() ->
+    (frame as contiguous float32, H, W, the planes (kept alive by the caller), the RtAovBuffers over them)."""
+    if frame is None or aovs is None:
+        raise ValueError(f"{who}() takes both a frame and its AOV planes, or neither (the context's own)")
+    frame = np.ascontiguousarray(frame, np.float32)
+    H, W = frame.shape[:2]
+    if frame.shape != (H, W, 4) or aovs["depth"].shape != (H, W):
+        raise ValueError(f"frame {frame.shape} and planes {aovs['depth'].shape}: not one (H, W, 4) frame and its (H, W) planes")
+    planes = numpy_to_aovs(aovs)
+    return frame, H, W, planes, _plane_buffers(planes)
+
+
+def _on_device(*inputs):
+    """Whether a query's inputs are device memory (objects with data_ptr(), or integer device pointers) rather than host arrays."""
+    on = [hasattr(x, "data_ptr") or isinstance(x, (int, np.integer)) for x in inputs]
+    if any(on) and not all(on):
+        raise ValueError("origins and dirs must both be host arrays or both be device memory")
+    return on[0]
+
+
+def _device_count(first, n, out):
+    """The rules of a query on device memory: out= is needed, and n= unless the first input can tell (numel() // 3)."""
+    if out is None:
+        raise ValueError("device-pointer inputs need out=: device memory for the results")
+    if n is None:
+        if not hasattr(first, "numel"):
+            raise ValueError("integer device pointers need n=")
+        n = int(first.numel()) // 3
+    return int(n)
 
 
 def _device_ptr(x, name, nbytes, floats=True):
@@ -966,12 +943,15 @@ def numpy_to_aovs(a):
     return planes
 
 
+def _record_words(recs, ctype):
+    """A ctypes array of records -> its 32-bit words, one row per record, as (float32 view, uint32 view)."""
+    raw = np.frombuffer(recs, dtype=np.uint8).reshape(len(recs), C.sizeof(ctype))
+    return raw.view(np.float32).reshape(len(recs), -1), raw.view(np.uint32).reshape(len(recs), -1)
+
+
 def hits_to_numpy(hits):
     """RtHit array -> dict of numpy arrays."""
-    n = len(hits)
-    raw = np.frombuffer(hits, dtype=np.uint8).reshape(n, C.sizeof(RtHit))
-    f = raw.view(np.float32).reshape(n, -1)
-    u = raw.view(np.uint32).reshape(n, -1)
+    f, u = _record_words(hits, RtHit)
     return dict(dst=f[:, 0].copy(), didHit=u[:, 1].copy(), isSphere=u[:, 2].copy(), objectHitIndex=u[:, 3].copy(),
                 triHitIndex=u[:, 4].copy(), materialIndex=u[:, 5].copy(), frontFace=u[:, 6].copy(),
                 hitPoint=f[:, 7:10].copy(), normal=f[:, 10:13].copy(), boxTests=u[:, 13].copy(),
@@ -980,10 +960,7 @@ def hits_to_numpy(hits):
 
 def nearest_to_numpy(recs):
     """RtNearest array -> dict of numpy arrays."""
-    n = len(recs)
-    raw = np.frombuffer(recs, dtype=np.uint8).reshape(n, C.sizeof(RtNearest))
-    f = raw.view(np.float32).reshape(n, -1)
-    u = raw.view(np.uint32).reshape(n, -1)
+    f, u = _record_words(recs, RtNearest)
     return dict(dst=f[:, 0].copy(), found=u[:, 1].copy(), isSphere=u[:, 2].copy(), objectIndex=u[:, 3].copy(), triIndex=u[:, 4].copy(),
                 uv=f[:, 5:7].copy(), point=f[:, 7:10].copy())
 

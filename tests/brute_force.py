@@ -145,7 +145,8 @@ DECODE_ULP = 8        # tests/test_glsl_builtins.py holds the float32 decode to 
 # ---------------------------------------------------------------- camera rays (moved here from tests/test_aovs.py)
 def camera_dirs(pc, W, H):
     """raytrace.comp:547-556 in float64: a plane of nearPlane * tan(fov / 2) * 2 by aspectRatio times that, at depth 0.1 (not
-    nearPlane), uv = pixel / image size, dir = normalize(point), (cameraRotation * vec4(dir, 1)).xyz."""
+    nearPlane), uv = pixel / image size, dir = normalize(point), (cameraRotation * vec4(dir, 1)).xyz.
+    The depth is the double 0.1, the shader's literal as written: temporal_float64.primary_dirs takes float32(0.1) instead."""
     cam = pc.camInfo
     ph = np.float64(np.float32(cam.nearPlane)) * np.tan(np.radians(np.float64(np.float32(cam.fov)) * 0.5)) * 2.0
     pw = ph * np.float64(np.float32(cam.aspectRatio))

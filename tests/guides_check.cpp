@@ -6,14 +6,9 @@
 #include <string>
 
 #include "post_passes.h"
+#include "check.h"
 
 namespace {
-
-int failures = 0;
-#define CHECK(x)                                                              \
-    do {                                                                      \
-        if (!(x)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } \
-    } while (0)
 
 template <typename T> T* at(uintptr_t a) { return (T*)a; }
 
@@ -112,7 +107,5 @@ void guide_checks() {
 int main() {
     tile_checks();
     guide_checks();
-    if (failures) { printf("%d check(s) failed\n", failures); return 1; }
-    printf("guides ok\n");
-    return 0;
+    return check_finish("guides ok");
 }

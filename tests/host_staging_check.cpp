@@ -9,14 +9,9 @@
 
 #include "host_staging.h"
 #include "rt_amd.h"
+#include "check.h"
 
 namespace {
-
-int failures = 0;
-#define CHECK(x)                                                              \
-    do {                                                                      \
-        if (!(x)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } \
-    } while (0)
 
 static_assert(sizeof(size_t) >= 8, "the layout of 2^30 - 1 records is past 32 bits");
 
@@ -159,7 +154,5 @@ int main() {
     the_queries();
     the_planes();
     the_edges();
-    if (failures) { printf("%d check(s) failed\n", failures); return 1; }
-    printf("host staging ok\n");
-    return 0;
+    return check_finish("host staging ok");
 }

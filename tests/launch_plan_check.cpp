@@ -11,19 +11,7 @@
 #include <vector>
 
 #include "scene_layout.h"   // RT_MAP_*
-
-static long g_checks = 0, g_failed = 0;
-#define CHECK(cond, ...)                                                        \
-    do {                                                                        \
-        g_checks++;                                                             \
-        if (!(cond)) {                                                          \
-            if (g_failed++ < 40) {                                              \
-                fprintf(stderr, "FAIL line %d: %s: ", __LINE__, #cond);         \
-                fprintf(stderr, __VA_ARGS__);                                   \
-                fprintf(stderr, "\n");                                          \
-            }                                                                   \
-        }                                                                       \
-    } while (0)
+#include "check.h"
 
 static Measured measured(double boxPerRay, double segPerPath = -1.0) { Measured m; m.boxPerRay = boxPerRay; m.segPerPath = segPerPath; return m; }
 static DispatchFacts slots(uint32_t nPixels, uint32_t nFrames = 1, uint32_t samples = 1) { DispatchFacts d; d.nPixels = nPixels; d.nFrames = nFrames; d.samples = samples; return d; }
@@ -542,10 +530,5 @@ int main() {
     check_fused_shape();
     check_measured();
     check_tuning();
-    if (g_failed) {
-        fprintf(stderr, "%ld of %ld checks failed\n", g_failed, g_checks);
-        return 1;
-    }
-    printf("launch plan ok (%ld checks)\n", g_checks);
-    return 0;
+    return check_finish("launch plan ok");
 }

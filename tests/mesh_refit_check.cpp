@@ -13,20 +13,7 @@
 #include <set>
 #include <string>
 #include <vector>
-
-static long g_checks = 0, g_failed = 0;
-static std::string g_where;
-#define CHECK(cond, ...)                                                                 \
-    do {                                                                                 \
-        g_checks++;                                                                      \
-        if (!(cond)) {                                                                   \
-            if (g_failed++ < 40) {                                                       \
-                fprintf(stderr, "FAIL [%s] line %d: %s: ", g_where.c_str(), __LINE__, #cond); \
-                fprintf(stderr, __VA_ARGS__);                                            \
-                fprintf(stderr, "\n");                                                   \
-            }                                                                            \
-        }                                                                                \
-    } while (0)
+#include "check.h"
 
 static std::string g_assets, g_out;
 
@@ -375,7 +362,5 @@ int main(int argc, char** argv) {
     }
     g_where = "refusals";
     check_refusals();
-    printf("%ld checks, %ld failed\n", g_checks, g_failed);
-    if (g_failed == 0) printf("mesh refit ok\n");
-    return g_failed ? 1 : 0;
+    return check_finish("mesh refit ok");
 }

@@ -7,7 +7,7 @@ arithmetic is fixed (tests/test_glsl_builtins.py and tests/test_oracle_kat.py pi
 holds, in both modes below. Pixels are vectorised: one array row per pixel, bounce by bounce, under masks. The debug heat maps
 (debug >= 0) are not restated: they count boxes.
 
-TWO MODES (as tests/test_temporal.py's Restatement has)
+TWO MODES (as tests/temporal_float64.py's Restatement has)
   exact     every operation in float64. closest_hit reads its rays as float32 holds them (that is its contract), so a query sees the
             path's ray rounded once; the path itself goes on unrounded.
   rounded   the path arithmetic in np.float32, numpy's own elementary functions (sin, cos, log2, exp2, sqrt: a different
@@ -46,6 +46,8 @@ FRAGILE PIXELS are left out of every comparison. A pixel is fragile if
 import numpy as np
 
 import brute_force as bf
+from ray_tracer_amd import engine
+from denoise_float64 import _checker_scene
 
 MARGIN = 1e-4            # hard decisions
 FLOOR = 1e-3             # |got - ref| <= T * max(|ref|, FLOOR), the floor tests/test_denoise.py and tests/test_temporal.py use
@@ -457,3 +459,37 @@ def study(brute, pcs, W, H, maps=False, chain=False, seeds=SIGN_SEEDS):
         if chain:
             prev, inherited = [r.image for r in runs], fr.fragile
     return frames
+
+
+T = 4e-2                # 4 x T_MEASURED, rounded up to one significant figure
+
+
+MAX_FRAGILE = 0.10
+
+
+def _spheres_scene(materials, spheres):
+    s = engine.Scene()
+    for m in materials:
+        s.add_material(engine.default_material(**m))
+    for i, (c, r, m) in enumerate(spheres):
+        s.set_sphere(i, c, r, m)
+    return s
+
+
+def _sky_scene():
+    """Spheres under an open sky: a large diffuse one as the ground, a mirror, glass and a diffuse one on it."""
+    mats = [dict(albedo=(0.7, 0.7, 0.6)), dict(reflectance=1.0), dict(ior=1.5), dict(albedo=(0.3, 0.6, 0.9))]
+    sph = [((0.0, 3.5, 0.0), 3.0, 0), ((-0.9, 0.0, 0.3), 0.5, 1), ((0.3, 0.05, -0.4), 0.45, 2), ((1.2, 0.1, 0.6), 0.4, 3)]
+    return _spheres_scene(mats, sph)
+
+
+def _maps_scene():
+    """tests/denoise_float64.py's checker quad, its material binding a metalness map besides the albedo map: every other row of texels a mirror."""
+    s, m, tex = _checker_scene()
+    mat = s.material(m)
+    mat.metalnessIndex = 1
+    s.set_material(m, mat)
+    metal = np.zeros((4, 4, 4), np.uint8)
+    metal[..., 1:] = 99                                   # noise in the channels that must not matter
+    metal[::2, :, 0] = (255, 3, 1, 90)
+    return s, [tex, metal]

@@ -14,14 +14,9 @@
 
 #include "point_queries.h"
 #include "rt_point_query.h"
+#include "check.h"
 
 namespace {
-
-int failures = 0;
-#define CHECK(x)                                                              \
-    do {                                                                      \
-        if (!(x)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } \
-    } while (0)
 
 template <typename T> T* at(uintptr_t a) { return (T*)a; }
 
@@ -214,7 +209,5 @@ int main(int argc, char** argv) {
         }
         fclose(f);
     }
-    if (failures) { printf("%d checks failed\n", failures); return 1; }
-    printf("point queries ok\n");
-    return 0;
+    return check_finish("point queries ok");
 }

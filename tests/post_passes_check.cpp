@@ -11,14 +11,9 @@
 
 #include "post_passes.h"
 #include "rt_det_math.h"
+#include "check.h"
 
 namespace {
-
-int failures = 0;
-#define CHECK(x)                                                              \
-    do {                                                                      \
-        if (!(x)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } \
-    } while (0)
 
 bool has(const std::string& m, const char* part) { return m.find(part) != std::string::npos; }
 template <typename T> T* at(uintptr_t a) { return (T*)a; }
@@ -214,7 +209,7 @@ struct Replay {
         const uint32_t* m = h.moved_counts();
         if (s.read != (history ? lastWrite : -1) || s.write != 1 - lastWrite || s.motion.any() != table || m[0] != mo || m[1] != ro || m[2] != ms) {
             printf("FAILED %s:%d: read %d write %d table %d moved %u %u %u\n", __FILE__, line, s.read, s.write, (int)s.motion.any(), m[0], m[1], m[2]);
-            failures++;
+            g_failed++;
         }
         h.commit(cam);
         lastWrite = s.write;
@@ -348,7 +343,5 @@ int main() {
     history_without_tracking();
     history_with_tracking();
     camera_planes();
-    if (failures) { printf("%d check(s) failed\n", failures); return 1; }
-    printf("post passes ok\n");
-    return 0;
+    return check_finish("post passes ok");
 }

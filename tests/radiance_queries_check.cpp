@@ -7,14 +7,9 @@
 #include <string>
 
 #include "radiance_queries.h"
+#include "check.h"
 
 namespace {
-
-int failures = 0;
-#define CHECK(x)                                                              \
-    do {                                                                      \
-        if (!(x)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } \
-    } while (0)
 
 template <typename T> T* at(uintptr_t a) { return (T*)a; }
 
@@ -123,7 +118,5 @@ int main() {
     pieces();
     shape();
     for (uint32_t frame : {0u, 3u, 0xffffffffu}) printf("seed %u %u\n", frame, radiance_starting_seed(frame));
-    if (failures) { printf("%d check(s) failed\n", failures); return 1; }
-    printf("radiance queries ok\n");
-    return 0;
+    return check_finish("radiance queries ok");
 }

@@ -8,14 +8,9 @@
 #include <string>
 
 #include "ray_queries.h"
+#include "check.h"
 
 namespace {
-
-int failures = 0;
-#define CHECK(x)                                                              \
-    do {                                                                      \
-        if (!(x)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } \
-    } while (0)
 
 template <typename T> T* at(uintptr_t a) { return (T*)a; }
 
@@ -146,7 +141,5 @@ int main() {
     arithmetic();
     ao_checks();
     ao_rays();
-    if (failures) { printf("%d check(s) failed\n", failures); return 1; }
-    printf("ray queries ok\n");
-    return 0;
+    return check_finish("ray queries ok");
 }

@@ -7,14 +7,9 @@
 #include <string>
 
 #include "post_passes.h"
+#include "check.h"
 
 namespace {
-
-int failures = 0;
-#define CHECK(x)                                                              \
-    do {                                                                      \
-        if (!(x)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } \
-    } while (0)
 
 bool has(const std::string& m, const char* part) { return m.find(part) != std::string::npos; }
 const float NaN = std::numeric_limits<float>::quiet_NaN(), Inf = std::numeric_limits<float>::infinity();
@@ -82,7 +77,5 @@ int main() {
     parameter_checks();
     owned_moments();
     sampled_render();
-    if (failures) { printf("%d check(s) failed\n", failures); return 1; }
-    printf("sample map ok\n");
-    return 0;
+    return check_finish("sample map ok");
 }

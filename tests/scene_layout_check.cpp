@@ -13,20 +13,7 @@
 #include <vector>
 
 #include "rt_det_math.h"
-
-static long g_checks = 0, g_failed = 0;
-static std::string g_where;
-#define CHECK(cond, ...)                                                                 \
-    do {                                                                                 \
-        g_checks++;                                                                      \
-        if (!(cond)) {                                                                   \
-            if (g_failed++ < 40) {                                                       \
-                fprintf(stderr, "FAIL [%s] line %d: %s: ", g_where.c_str(), __LINE__, #cond); \
-                fprintf(stderr, __VA_ARGS__);                                            \
-                fprintf(stderr, "\n");                                                   \
-            }                                                                            \
-        }                                                                                \
-    } while (0)
+#include "check.h"
 
 static uint32_t bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 static bool same3(const float4& v, float x, float y, float z) { return bits(v.x) == bits(x) && bits(v.y) == bits(y) && bits(v.z) == bits(z); }
@@ -566,7 +553,5 @@ int main(int argc, char** argv) {
     check_refusals();
     check_small_tables();
 
-    if (g_failed) { fprintf(stderr, "%ld of %ld checks failed\n", g_failed, g_checks); return 1; }
-    printf("scene layout ok: %ld checks\n", g_checks);
-    return 0;
+    return check_finish("scene layout ok");
 }

@@ -10,14 +10,9 @@
 #include <cstring>
 
 #include "temporal_motion.h"
+#include "check.h"
 
 namespace {
-
-int failures = 0;
-#define CHECK(x)                                                              \
-    do {                                                                      \
-        if (!(x)) { printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); failures++; } \
-    } while (0)
 
 uint32_t bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 float from_bits(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
@@ -168,7 +163,5 @@ int from_file(const char* in, const char* out) {
 int main(int argc, char** argv) {
     if (argc == 3) return from_file(argv[1], argv[2]);
     worked_cases();
-    if (failures) return 1;
-    printf("temporal motion ok\n");
-    return 0;
+    return check_finish("temporal motion ok");
 }

@@ -15,12 +15,11 @@ from oracle import pyoracle
 from ray_tracer_amd import _capi, engine, render, scenes
 from ray_tracer_amd.session import InteractiveSession
 
-from test_instantiations import build_scene, skewed, soup
-from util import EditedScene, assert_hits_equal, cornell_scene, model_scene
+from aov_cases import _albedos, _as_hits, _check_misses, _upload, PLANES
+from instantiation_scenes import build_scene, skewed, soup
+from util import EditedScene, assert_hits_equal, cornell_scene, device_buffers, frames_between_passes, model_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MISS_DST = np.float32(99999999.0)   # RT_MISS_DST
-PLANES = ("depth", "normal", "position", "albedo", "ray_dir", "object", "triangle", "material", "hit", "sphere", "front_face")
 ULP1 = 2.0 ** -23   # one float32 ulp of a unit component
 
 
@@ -55,36 +54,6 @@ def test_planes_decode():
 def test_aov_out_flag():
     assert render.build_parser().parse_args([]).aov_out is None
     assert render.build_parser().parse_args(["--aov-out", "planes.npz"]).aov_out == "planes.npz"
-
-
-# ---------------------------------------------------------------- GPU helpers
-def _upload(renderer, s):
-    if isinstance(s, EditedScene):
-        renderer.upload_scene(s.scene)
-        for what in ("objects", "materials", "spheres"):
-            s.push(renderer, what)
-    else:
-        renderer.upload_scene(s)
-
-
-def _as_hits(a):
-    """The planes as the RtHit fields of rt_trace_rays (a miss: zeros beside dst)."""
-    h = a["hit"].reshape(-1)
-    z = lambda x: np.where(h, x.reshape(-1), 0).astype(np.uint32)   # noqa: E731
-    return dict(dst=a["depth"].reshape(-1), didHit=h.astype(np.uint32), isSphere=a["sphere"].reshape(-1).astype(np.uint32),
-                objectHitIndex=z(a["object"]), triHitIndex=z(a["triangle"]), materialIndex=z(a["material"]),
-                frontFace=a["front_face"].reshape(-1).astype(np.uint32), hitPoint=a["position"].reshape(-1, 3),
-                normal=a["normal"].reshape(-1, 3))
-
-
-def _check_misses(a):
-    m = ~a["hit"]
-    assert np.all(a["depth"][m] == MISS_DST)
-    for k in ("normal", "position", "albedo"):
-        assert not a[k][m].any()
-    for k in ("object", "triangle", "material"):
-        assert np.all(a[k][m] == 0xFFFFFFFF)
-    assert not (a["sphere"][m].any() or a["front_face"][m].any())
 
 
 def _raw_pass(renderer, pc, W, H, row0=0, rowStride=1, nRows=None, objectCount=None):
@@ -207,7 +176,7 @@ def test_parity_sponza_rows_at_1080p(renderer):
 
 @pytest.mark.gpu
 def test_parity_alpha_and_bump_maps(renderer, tmp_path):
-    from test_textures import _bound, _map_set
+    from texture_cases import _bound, _map_set
     tex = _map_set()
     W, H = 72, 54
     pc = engine.push_constants(W, H)
@@ -251,12 +220,6 @@ def test_camera_rays_against_a_float64_restatement(renderer):
     pc.camInfo.cameraRotation[12], pc.camInfo.cameraRotation[13], pc.camInfo.cameraRotation[14] = 0.25, -0.5, 0.125
     err = np.abs(renderer.render_aovs(pc, 24, 16)["ray_dir"].astype(np.float64) - _camera_dirs(pc, 24, 16)).max()
     assert err <= 16 * ULP1, err
-
-
-# ---------------------------------------------------------------- 3. albedo
-def _albedos(s):
-    arr = s.arrays()
-    return np.array([list(arr.materials[i].albedo) for i in range(arr.materialCount)], np.float32)
 
 
 @pytest.mark.gpu
@@ -372,80 +335,38 @@ def test_strips_and_rows_equal_the_full_frame(renderer, W, H):
         same(renderer.render_aovs(pc, W, H, row0=y, nRows=1), slice(y, y + 1), f"row {y}")
 
 
-def _hip_runtime():
-    """The HIP runtime the library itself is bound to, for device buffers without a framework. The symbols are looked up through
-    the library's handle (dlsym searches the library and then its own dependencies), not by the runtime's file name: a process
-    may hold a second copy of the runtime (a framework's wheel bundles one), and memory from that copy is not the library's."""
-    h = C.CDLL(_capi.LIB_PATH)
-    h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    h.hipFree.argtypes = [C.c_void_p]
-    return h
-
-
 @pytest.mark.gpu
 def test_device_planes(renderer):
-    import torch  # noqa: F401  (its wheel's copy of the HIP runtime now sits beside the library's: _hip_runtime must not take it)
-    hip = _hip_runtime()
+    import torch  # noqa: F401  (its wheel's copy of the HIP runtime now sits beside the library's: devmem.hip must not take it)
     renderer.upload_scene(cornell_scene(True))
     W, H = 40, 30
     pc = engine.push_constants(W, H)
     ref = renderer.render_aovs(pc, W, H)
     nbytes = H * W * 16
-    bufs = {k: C.c_void_p() for k in list(engine.AOV_PLANES) + ["only"]}
-    try:
-        for b in bufs.values():
-            assert hip.hipMalloc(C.byref(b), nbytes) == 0
-            assert hip.hipMemset(b, 7, nbytes) == 0
-        assert hip.hipDeviceSynchronize() == 0
-
-        def fetch(b, dtype):
-            out = np.empty((H, W, 4), dtype)
-            assert hip.hipMemcpy(out.ctypes.data, b, nbytes, 2) == 0   # hipMemcpyDeviceToHost
-            return out
-
-        assert renderer.render_aovs(pc, W, H, out_ptrs={k: bufs[k].value for k in engine.AOV_PLANES}) is None
-        got = engine.aovs_to_numpy({k: fetch(bufs[k], np.uint32 if k == "ids" else np.float32) for k in engine.AOV_PLANES})
+    with device_buffers(list(engine.AOV_PLANES) + ["only"], nbytes, fill=7) as bufs:
+        assert renderer.render_aovs(pc, W, H, out_ptrs={k: bufs[k].ptr for k in engine.AOV_PLANES}) is None
+        got = engine.aovs_to_numpy({k: bufs[k].download((H, W, 4), np.uint32 if k == "ids" else np.float32) for k in engine.AOV_PLANES})
         for k in PLANES:
             assert np.array_equal(got[k].view(np.uint8), ref[k].view(np.uint8)), k
-        renderer.render_aovs(pc, W, H, out_ptrs={"ids": bufs["only"].value, "position": 0})   # one plane only
-        assert np.array_equal(fetch(bufs["only"], np.uint32)[..., 0], ref["object"])
-    finally:
-        for b in bufs.values():
-            if b.value:
-                hip.hipFree(b)
+        renderer.render_aovs(pc, W, H, out_ptrs={"ids": bufs["only"].ptr, "position": 0})   # one plane only
+        assert np.array_equal(bufs["only"].download((H, W, 4), np.uint32)[..., 0], ref["object"])
 
 
 # ---------------------------------------------------------------- 5. no side effects on rendering
-def _render_sequence(renderer, s, W, H, passes):
-    renderer.upload_scene(s)
-    renderer.clear_framebuffer()
-    pc = engine.push_constants(W, H, progressive=1, raysPerPixel=2)
-    other = engine.push_constants(W + 24, H + 16, cameraAngles=(15.0, 40.0, 0.0), pos=(0.2, -0.6, -2.5))
-    frames, deltas = [], []
-    for k in range(3):
-        if passes:   # another camera, a bigger image: the path state grows
-            renderer.render_aovs(other, W + 24, H + 16)
-            renderer.render_aovs(other, W + 24, H + 16, row0=1, rowStride=2, sync=False)
-        pc.frameCount = k
-        before = renderer.counters()
-        frames.append(renderer.render(pc, W, H))
-        after = renderer.counters()
-        deltas.append({n: after[n] - before[n] for n in after})
-    renderer.sync()
-    return frames, deltas, (renderer.ray_cost(), renderer.last_pipeline(), renderer.last_parts())
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("pipeline", [-1, 0])
 def test_passes_leave_rendering_untouched(renderer, pipeline):
     s = model_scene("bunny.obj", spheres=True)
     W, H = 64, 48
     renderer.set_tuning("pipeline", pipeline)
+
+    def aov_passes(other, w, h):
+        renderer.render_aovs(other, w, h)
+        renderer.render_aovs(other, w, h, row0=1, rowStride=2, sync=False)
+
     try:
-        a = _render_sequence(renderer, s, W, H, False)
-        b = _render_sequence(renderer, s, W, H, True)
+        a = frames_between_passes(renderer, s, W, H)
+        b = frames_between_passes(renderer, s, W, H, aov_passes)
     finally:
         renderer.set_tuning("pipeline", -1)
     for fa, fb in zip(a[0], b[0]):

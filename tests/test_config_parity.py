@@ -22,6 +22,8 @@ import pytest
 from oracle import pyoracle
 from ray_tracer_amd import engine, scenes
 
+from util import bits
+
 pytestmark = pytest.mark.gpu
 
 MODES = [("multikernel", 0, 0), ("fused", 1, 64), ("fused-refill", 1, 8)]
@@ -51,10 +53,6 @@ def _set_mode(r, pipeline, refill):
     r.set_tuning("pixel_refill", refill)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def test_c1_cornell_512_whole_frame(renderer):
     """C1: Cornell + dielectric / mirror / diffuse spheres, 512x512, 4 spp — every pixel and every counter."""
     s, _ = scenes.cornell(True)
@@ -68,7 +66,7 @@ def test_c1_cornell_512_whole_frame(renderer):
             renderer.reset_counters()
             img = renderer.render(pc, W, H)
             cnt = renderer.counters()
-            assert np.array_equal(_bits(img), _bits(ref)), f"{name}: pixels differ from the oracle"
+            assert np.array_equal(bits(img), bits(ref)), f"{name}: pixels differ from the oracle"
             assert {k: cnt[k] for k in KEYS} == {k: rc[k] for k in KEYS}, name
     finally:
         _set_mode(renderer, -1, 0)
@@ -94,13 +92,13 @@ def test_config_at_full_size_on_sampled_rows(renderer, config):
         _set_mode(r, -1, 0)
         full = r.render(pc, W, H)             # the whole frame, as bench.py dispatches it
         assert full.shape == (H, W, 4)
-        assert np.array_equal(_bits(full[rows][:8]), _bits(ref)), "full-frame dispatch differs from the oracle on the sampled rows"
+        assert np.array_equal(bits(full[rows][:8]), bits(ref)), "full-frame dispatch differs from the oracle on the sampled rows"
         for name, pipe, refill in MODES:
             _set_mode(r, pipe, refill)
             r.reset_counters()
             img = r.render(pc, W, H, **tile)
             cnt = r.counters()
-            assert np.array_equal(_bits(img), _bits(ref)), f"{name}: tile pixels differ from the oracle"
+            assert np.array_equal(bits(img), bits(ref)), f"{name}: tile pixels differ from the oracle"
             assert {k: cnt[k] for k in KEYS} == {k: rc[k] for k in KEYS}, name
         # ---- 64 serial samples on two rows
         pc = cam(W, H, singleRender=1, sampleLimit=64)
@@ -111,7 +109,7 @@ def test_config_at_full_size_on_sampled_rows(renderer, config):
             r.reset_counters()
             img = r.render(pc, W, H, **tile)
             cnt = r.counters()
-            assert np.array_equal(_bits(img), _bits(ref)), f"{name}: 64-spp rows differ from the oracle"
+            assert np.array_equal(bits(img), bits(ref)), f"{name}: 64-spp rows differ from the oracle"
             assert {k: cnt[k] for k in KEYS} == {k: rc[k] for k in KEYS}, name
     finally:
         _set_mode(r, -1, 0)

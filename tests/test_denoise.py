@@ -13,103 +13,16 @@ import sys
 import numpy as np
 import pytest
 
-from ray_tracer_amd import _capi, engine, render, scenes
+from ray_tracer_amd import _capi, devmem, engine, render, scenes
 
-from util import cornell_scene, model_scene
+from denoise_float64 import _checker_scene, _shift, planes_of, restate
+from temporal_float64 import emission_of, filtered_set
+from util import cornell_scene, device_buffers, model_scene, progressive_frames
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LUM = np.array([0.2126, 0.7152, 0.0722])
-H5 = np.array([1.0, 4.0, 6.0, 4.0, 1.0]) / 16.0
 DEFAULTS = dict(iterations=5, sigma_luminance=4.0, sigma_normal=128.0, sigma_depth=1.0)
 OTHER = dict(sigma_luminance=1.5, sigma_normal=0.0, sigma_depth=0.25)   # sigma_normal 0: normals do not stop the filter
 REL = 1e-4   # |gpu - ref| <= REL * max(|ref|, 1e-3): an estimate from fp32 rounding (rt_exp2, rt_pow and the divisions against float64)
-
-
-# ---------------------------------------------------------------- the float64 restatement
-def _shift(a, dy, dx, fill):
-    """b[y, x] = a[y + dy, x + dx] where that is inside the image, `fill` elsewhere."""
-    H, W = a.shape[:2]
-    b = np.full_like(a, fill)
-    if abs(dy) < H and abs(dx) < W:
-        b[max(0, -dy):H - max(0, dy), max(0, -dx):W - max(0, dx)] = a[max(0, dy):H - max(0, -dy), max(0, dx):W - max(0, -dx)]
-    return b
-
-
-def filtered_set(ids, emission):
-    """F: a hit (ids.w & 1) on a material index below the table's size whose emissionStrength is 0."""
-    emission = np.asarray(emission, np.float64)
-    m = ids[..., 2]
-    ok = ((ids[..., 3] & 1) == 1) & (m < len(emission))
-    return ok & (emission[np.where(ok, m, 0)] == 0.0)
-
-
-def _gradient(z, F, dy, dx):
-    """The depth gradient along (dy, dx): the forward or the backward difference to a neighbour in F, the smaller in magnitude
-    (forward on a tie), 0 without either. The differences are taken in float32, as the kernel takes them, so that a near-tie
-    picks the same side; they are exact where the depths are within a factor of two (Sterbenz)."""
-    hf, hb = _shift(F, dy, dx, False), _shift(F, -dy, -dx, False)
-    f = _shift(z, dy, dx, np.float32(0)) - z
-    b = z - _shift(z, -dy, -dx, np.float32(0))
-    g = np.where(hf & hb, np.where(np.abs(b) < np.abs(f), b, f), np.where(hf, f, np.where(hb, b, np.float32(0))))
-    return g.astype(np.float64)
-
-
-def restate(rgba, nd, albedo, ids, emission, iterations=5, sigma_luminance=4.0, sigma_normal=128.0, sigma_depth=1.0, blind=False):
-    """The filter of rt_denoise in float64 on (H, W, 4) planes: returns the output (float64; kept pixels hold their input) and F.
-    blind: a plain B3 a-trous filter (h weights only) over the same demodulated pixels, kept pixels still excluded."""
-    F = filtered_set(ids, emission)
-    out = rgba.astype(np.float64)
-    if iterations == 0 or not F.any():
-        return out, F
-    d = np.maximum(albedo[..., :3].astype(np.float64), 1e-3)
-    e = rgba[..., :3].astype(np.float64) / d
-    lum = e @ LUM
-    taps = [(dy, dx) for dy in range(-2, 3) for dx in range(-2, 3)]
-    cnt = sum(_shift(F, dy, dx, False).astype(np.float64) for dy, dx in taps)
-    mu = sum(np.where(_shift(F, dy, dx, False), _shift(lum, dy, dx, 0.0), 0.0) for dy, dx in taps) / np.maximum(cnt, 1)
-    v = sum(np.where(_shift(F, dy, dx, False), (_shift(lum, dy, dx, 0.0) - mu) ** 2, 0.0) for dy, dx in taps) / np.maximum(cnt, 1)
-    z32 = np.ascontiguousarray(nd[..., 3], np.float32)
-    gx, gy = _gradient(z32, F, 0, 1), _gradient(z32, F, 1, 0)
-    n, z = nd[..., :3].astype(np.float64), z32.astype(np.float64)
-    for k in range(iterations):
-        s = 2 ** k
-        lum_den = sigma_luminance * np.sqrt(v) + 1e-4
-        sw, se, sv = np.zeros(F.shape), np.zeros(e.shape), np.zeros(F.shape)
-        for j in range(-2, 3):
-            for i in range(-2, 3):
-                dy, dx = s * j, s * i
-                Fq = _shift(F, dy, dx, False)
-                eq = _shift(e, dy, dx, 0.0)
-                w = np.full(F.shape, H5[i + 2] * H5[j + 2])
-                if not blind:
-                    if sigma_normal != 0.0:
-                        w = w * np.maximum(0.0, (n * _shift(n, dy, dx, 0.0)).sum(-1)) ** sigma_normal
-                    dz = np.abs(z - _shift(z, dy, dx, 0.0))
-                    with np.errstate(divide="ignore", invalid="ignore"):
-                        az = np.where(dz == 0.0, 0.0, dz / (sigma_depth * np.abs(gx * dx + gy * dy) + 1e-4 * z))
-                    al = np.abs(lum - eq @ LUM) / lum_den
-                    w = w * np.exp(-(az + al))
-                w = np.where(Fq, w, 0.0)
-                sw += w
-                se += w[..., None] * eq
-                sv += w * w * _shift(v, dy, dx, 0.0)
-        safe = np.where(F, sw, 1.0)
-        e = np.where(F[..., None], se / safe[..., None], e)
-        v = np.where(F, sv / (safe * safe), v)
-        lum = e @ LUM
-    out[..., :3] = np.where(F[..., None], e * d, out[..., :3])
-    return out, F
-
-
-def emission_of(scene):
-    a = scene.arrays()
-    return np.array([a.materials[i].emissionStrength for i in range(a.materialCount)], np.float64)
-
-
-def planes_of(a):
-    """render_aovs()'s dict -> the (H, W, 4) normalDepth, albedo and ids planes."""
-    p = engine.numpy_to_aovs(a)
-    return p["normalDepth"], p["albedo"], p["ids"]
 
 
 def assert_matches(got, rgba, ref, F, what):
@@ -221,17 +134,6 @@ def _denoise_host(r, rgba, nd, albedo, ids, **kw):
     return out
 
 
-def _hip_runtime():
-    """The HIP runtime the library itself is bound to, looked up through the library's handle (as tests/test_aovs.py does): a
-    process may hold a second copy of the runtime, and memory from that copy is not the library's."""
-    h = C.CDLL(_capi.LIB_PATH)
-    h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    h.hipFree.argtypes = [C.c_void_p]
-    return h
-
-
 def _render_frame(r, scene, pc, W, H):
     """One frame and its planes into the context's own buffers; returns both as numpy."""
     r.upload_scene(scene)
@@ -322,8 +224,7 @@ def test_misses_and_emitters_do_not_leak(renderer):
 # ---------------------------------------------------------------- 6. one result by every route
 @pytest.mark.gpu
 def test_every_route_gives_the_same_frame(renderer):
-    import torch  # noqa: F401  (its wheel's copy of the HIP runtime now sits beside the library's: _hip_runtime must not take it)
-    hip = _hip_runtime()
+    import torch  # noqa: F401  (its wheel's copy of the HIP runtime now sits beside the library's: devmem.hip must not take it)
     s = model_scene("bunny.obj", spheres=True)
     W, H = 72, 40
     pc = engine.push_constants(W, H, singleRender=1, sampleLimit=4)
@@ -332,24 +233,13 @@ def test_every_route_gives_the_same_frame(renderer):
     assert np.array_equal(renderer.denoise().view(np.uint32), first.view(np.uint32))   # two calls in a row
     assert np.array_equal(renderer.denoise(frame, a).view(np.uint32), first.view(np.uint32))   # host path
     nbytes = H * W * 16
-    bufs = {k: C.c_void_p() for k in ("frame", "out") + engine.AOV_PLANES}
-    try:
-        for b in bufs.values():
-            assert hip.hipMalloc(C.byref(b), nbytes) == 0
-            assert hip.hipMemset(b, 7, nbytes) == 0
-        assert hip.hipDeviceSynchronize() == 0
-        renderer.render(pc, W, H, out_ptr=bufs["frame"].value)
-        renderer.render_aovs(pc, W, H, out_ptrs={k: bufs[k].value for k in engine.AOV_PLANES})
-        d = _capi.RtAovBuffers(**{k: bufs[k].value for k in engine.AOV_PLANES})
-        renderer._check(renderer._l.rt_denoise(renderer._h, W, H, bufs["frame"].value, C.byref(d), None, bufs["out"].value), "rt_denoise")
+    with device_buffers(("frame", "out") + engine.AOV_PLANES, nbytes, fill=7) as bufs:
+        renderer.render(pc, W, H, out_ptr=bufs["frame"].ptr)
+        renderer.render_aovs(pc, W, H, out_ptrs={k: bufs[k].ptr for k in engine.AOV_PLANES})
+        d = _capi.RtAovBuffers(**{k: bufs[k].ptr for k in engine.AOV_PLANES})
+        renderer._check(renderer._l.rt_denoise(renderer._h, W, H, bufs["frame"].ptr, C.byref(d), None, bufs["out"].ptr), "rt_denoise")
         renderer.sync()
-        out, dev_frame = np.empty((H, W, 4), np.float32), np.empty((H, W, 4), np.float32)
-        assert hip.hipMemcpy(out.ctypes.data, bufs["out"], nbytes, 2) == 0   # hipMemcpyDeviceToHost
-        assert hip.hipMemcpy(dev_frame.ctypes.data, bufs["frame"], nbytes, 2) == 0
-    finally:
-        for b in bufs.values():
-            if b.value:
-                hip.hipFree(b)
+        out, dev_frame = bufs["out"].download((H, W, 4), np.float32), bufs["frame"].download((H, W, 4), np.float32)
     assert np.array_equal(dev_frame.view(np.uint32), frame.view(np.uint32))
     assert np.array_equal(out.view(np.uint32), first.view(np.uint32))
     assert np.array_equal(renderer.denoise().view(np.uint32), first.view(np.uint32))   # the context's planes are still its own
@@ -373,34 +263,20 @@ def test_denoise_leaves_the_context_untouched(renderer):
         assert np.array_equal(again[k].view(np.uint8), a[k].view(np.uint8)), k
 
 
-def _progressive(renderer, s, W, H, denoise):
-    renderer.upload_scene(s)
-    renderer.clear_framebuffer()
-    pc = engine.push_constants(W, H, progressive=1, raysPerPixel=2)
-    renderer.render_aovs(pc, W, H)
-    frames, deltas = [], []
-    for k in range(3):
-        pc.frameCount = k
-        before = renderer.counters()
-        frames.append(renderer.render(pc, W, H))
-        after = renderer.counters()
-        deltas.append({n: after[n] - before[n] for n in after})
-        if denoise:
-            renderer.denoise()
-            renderer.denoise(iterations=2, **OTHER)
-    renderer.sync()
-    return frames, deltas, (renderer.ray_cost(), renderer.last_pipeline(), renderer.last_parts(), renderer.last_kernel())
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("pipeline", [0, 1])
 def test_progressive_history_is_untouched(renderer, pipeline):
     s = model_scene("bunny.obj", spheres=True)
     W, H = 64, 48
     renderer.set_tuning("pipeline", pipeline)
+
+    def denoise(pc):
+        renderer.denoise()
+        renderer.denoise(iterations=2, **OTHER)
+
     try:
-        a = _progressive(renderer, s, W, H, False)
-        b = _progressive(renderer, s, W, H, True)
+        a = progressive_frames(renderer, s, W, H)
+        b = progressive_frames(renderer, s, W, H, denoise)
     finally:
         renderer.set_tuning("pipeline", -1)
     assert a[2][1] == pipeline
@@ -408,20 +284,6 @@ def test_progressive_history_is_untouched(renderer, pipeline):
         assert np.array_equal(fa.view(np.uint32), fb.view(np.uint32))
     assert a[1] == b[1]
     assert a[2] == b[2]
-
-
-# ---------------------------------------------------------------- 8. quality
-def _checker_scene():
-    """The Cornell box without spheres and a quad in front of its back wall whose material binds texture slot 0."""
-    s = cornell_scene(False)
-    m = s.add_material(engine.default_material(albedo=(0.9, 0.9, 0.9), albedoIndex=0))
-    x0, x1, y0, y1, z = -0.7, 0.7, -1.3, 0.3, 0.6
-    P = np.array([[[x0, y0, z], [x1, y0, z], [x1, y1, z]], [[x0, y0, z], [x1, y1, z], [x0, y1, z]]], np.float32)
-    UV = np.stack([(P[..., 0] - x0) / (x1 - x0), (P[..., 1] - y0) / (y1 - y0)], -1).astype(np.float32)
-    s.add_mesh("checker", P, np.tile(np.array([0, 0, -1], np.float32), (2, 3, 1)), engine.placement(), m, uvs=UV)
-    tex = np.full((8, 8, 4), 255, np.uint8)
-    tex[..., :3] = np.where(((np.arange(8)[:, None] + np.arange(8)[None, :]) % 2 == 0)[..., None], 230, 40)
-    return s, m, tex
 
 
 def _edges(a):
@@ -498,9 +360,8 @@ def test_cli_denoise_on_one_and_two_ranks(tmp_path):
 # ---------------------------------------------------------------- 10. errors
 @pytest.mark.gpu
 def test_errors(built):
-    hip = _hip_runtime()
     r = engine.Renderer(0)
-    buf = C.c_void_p()
+    buf = devmem.DeviceBuffer(8 * 8 * 16)
     try:
         def fails(match, W=8, H=8, rgba=None, aovs=None, params=None, out=None):
             rc = r._l.rt_denoise(r._h, W, H, rgba, C.byref(aovs) if aovs is not None else None,
@@ -533,10 +394,9 @@ def test_errors(built):
             fails(what, params=_params(**bad))
             with pytest.raises(engine.RtError, match=what):
                 r.denoise(**bad)
-        assert hip.hipMalloc(C.byref(buf), 8 * 8 * 16) == 0
-        fails("d_out overlaps an input", rgba=buf.value, out=buf.value)
-        planes = _capi.RtAovBuffers(normalDepth=buf.value, albedo=buf.value + 64, ids=buf.value + 128)
-        fails("d_out overlaps an input", aovs=planes, out=buf.value + 512)
+        fails("d_out overlaps an input", rgba=buf.ptr, out=buf.ptr)
+        planes = _capi.RtAovBuffers(normalDepth=buf.ptr, albedo=buf.ptr + 64, ids=buf.ptr + 128)
+        fails("d_out overlaps an input", aovs=planes, out=buf.ptr + 512)
         nd, albedo, ids = (np.zeros((8, 8, 4), t) for t in (np.float32, np.float32, np.uint32))
         b = _capi.RtAovBuffers(normalDepth=nd.ctypes.data, albedo=albedo.ctypes.data)
         assert r._l.rt_denoise_host(r._h, 8, 8, host.ctypes.data, C.byref(b), None, host.ctypes.data) != 0
@@ -553,6 +413,5 @@ def test_errors(built):
         assert "size mismatch" in r._l.rt_last_error(r._h).decode()
         assert np.array_equal(r.denoise().view(np.uint32), out.view(np.uint32))
     finally:
-        if buf.value:
-            hip.hipFree(buf)
+        buf.free()
         r.close()

@@ -6,16 +6,14 @@ k_render_fused_maps: the fused kernel's loop with the alpha look-up in the trave
 configuration for every map scene (24 LDS stack entries + the overflow buffer, object culling, no top-level table). Every case
 here is HIP == oracle bit for bit, pixels and the eight counters, on the kernel the case names, with pixels replaced a block at
 a time (pixel_refill 64) and at 8 free lanes."""
-import re
-import subprocess
-
 import numpy as np
 import pytest
 
 from oracle import pyoracle
-from ray_tracer_amd import _capi, engine
+from ray_tracer_amd import engine
 
-from test_textures import KEYS, _bound, _checker, _grey, _map_set, _plane_material, _same_as_oracle
+from texture_cases import KEYS, _bound, _grey, _map_set, _plane_material, _same_as_oracle
+from util import kernel_instantiations
 
 pytestmark = pytest.mark.gpu
 
@@ -25,8 +23,7 @@ LAUNCHED = set()   # k_render_fused_maps<...> instantiations the cases below ran
 
 
 def maps_instantiations():
-    out = subprocess.run(["nm", "-C", _capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    return set(re.findall(r"__device_stub__(k_render_fused_maps<[^>]*>)", out))
+    return kernel_instantiations("k_render_fused_maps")
 
 
 @pytest.fixture
@@ -108,7 +105,7 @@ def test_fused_maps_heat_maps(fused, tmp_path, refill):
 def _deep_scene():
     """A lopsided mesh of BVH depth > 24 with uvs and all three maps, beside two placed copies of a small mesh under general
     transforms (test_textures.test_alpha_map_on_a_deep_bvh_with_placed_objects): the overflow buffer and object culling."""
-    from test_instantiations import skewed, soup
+    from instantiation_scenes import skewed, soup
     rng = np.random.default_rng(9)
     s = engine.Scene()
     glow = s.add_material(engine.default_material(albedo=(0, 0, 0), emissionColor=(1, 0.9, 0.8), emissionStrength=3.0))

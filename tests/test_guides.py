@@ -11,13 +11,13 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle
-from ray_tracer_amd import _capi, engine, render
+from ray_tracer_amd import _capi, devmem, engine, render
 from ray_tracer_amd.session import InteractiveSession
 
-from test_aovs import PLANES, _albedos, _as_hits, _check_misses, _hip_runtime, _upload
-from test_denoise import emission_of, planes_of, restate
-from test_temporal import camera_path, primary_dirs
-from util import EditedScene, assert_hits_equal, cornell_scene, model_scene
+from aov_cases import PLANES, _albedos, _as_hits, _check_misses, _upload
+from denoise_float64 import planes_of, restate
+from temporal_float64 import camera_path, emission_of, primary_dirs
+from util import EditedScene, assert_hits_equal, cornell_scene, device_buffers, frames_between_passes, model_scene
 
 MISS_DST = np.float32(99999999.0)   # RT_MISS_DST
 MIRROR = 4                          # the built-in mirror material (reflectance 1)
@@ -336,28 +336,19 @@ def test_small_frames_and_tiles(renderer, W, H):
 # ---------------------------------------------------------------- GPU: routes and side effects
 @pytest.mark.gpu
 def test_device_ctx_owned_and_null_field_routes_agree(renderer):
-    import torch  # noqa: F401  (as tests/test_aovs.py: a second copy of the HIP runtime in the process must not be taken)
-    hip = _hip_runtime()
+    import torch  # noqa: F401  (as tests/test_aovs.py: devmem.hip must not take the second copy of the HIP runtime now in the process)
     renderer.upload_scene(cornell_scene(True))
     W, H = 40, 30
     pc = engine.push_constants(W, H)
     ref, first = renderer.render_guides(pc, W, H, 4, first_hit=True)
     nbytes = H * W * 16
     names = [f"g_{k}" for k in engine.AOV_PLANES] + [f"f_{k}" for k in engine.AOV_PLANES]
-    bufs = {k: C.c_void_p() for k in names}
-    try:
-        for b in bufs.values():
-            assert hip.hipMalloc(C.byref(b), nbytes) == 0
-            assert hip.hipMemset(b, 7, nbytes) == 0
-        assert hip.hipDeviceSynchronize() == 0
-
+    with device_buffers(names, nbytes, fill=7) as bufs:
         def fetch(b, dtype):
-            out = np.empty((H, W, 4), dtype)
-            assert hip.hipMemcpy(out.ctypes.data, b, nbytes, 2) == 0   # hipMemcpyDeviceToHost
-            return out
+            return b.download((H, W, 4), dtype)
 
         def planes(prefix, only=engine.AOV_PLANES):
-            return _capi.RtAovBuffers(**{k: bufs[f"{prefix}_{k}"].value for k in only})
+            return _capi.RtAovBuffers(**{k: bufs[f"{prefix}_{k}"].ptr for k in only})
 
         def run(guides, first_hit):
             renderer.fill_counts(pc)
@@ -375,8 +366,8 @@ def test_device_ctx_owned_and_null_field_routes_agree(renderer):
             assert np.array_equal(got_first[k].view(np.uint8), first[k].view(np.uint8)), k
         # NULL fields are skipped: one guide plane and one first-hit plane, the others keep their fill
         for b in bufs.values():
-            assert hip.hipMemset(b, 7, nbytes) == 0
-        assert hip.hipDeviceSynchronize() == 0
+            b.fill(7)
+        devmem.synchronize()
         run(planes("g", ["normalDepth"]), planes("f", ["ids"]))
         assert np.array_equal(fetch(bufs["g_normalDepth"], np.float32)[..., 3], ref["depth"])
         assert np.array_equal(fetch(bufs["f_ids"], np.uint32)[..., 0], first["object"])
@@ -391,30 +382,6 @@ def test_device_ctx_owned_and_null_field_routes_agree(renderer):
         own = engine.aovs_to_numpy(own)
         for k in PLANES:
             assert np.array_equal(own[k].view(np.uint8), ref[k].view(np.uint8)), k
-    finally:
-        for b in bufs.values():
-            if b.value:
-                hip.hipFree(b)
-
-
-def _render_sequence(renderer, s, W, H, passes):
-    """tests/test_aovs.py's sequence with guide passes between the progressive frames."""
-    renderer.upload_scene(s)
-    renderer.clear_framebuffer()
-    pc = engine.push_constants(W, H, progressive=1, raysPerPixel=2)
-    other = engine.push_constants(W + 24, H + 16, cameraAngles=(15.0, 40.0, 0.0), pos=(0.2, -0.6, -2.5))
-    frames, deltas = [], []
-    for k in range(3):
-        if passes:   # another camera, a bigger image: the path state grows
-            renderer.render_guides(other, W + 24, H + 16, 4)
-            renderer.render_guides(other, W + 24, H + 16, 8, first_hit=True, row0=1, rowStride=2)
-        pc.frameCount = k
-        before = renderer.counters()
-        frames.append(renderer.render(pc, W, H))
-        after = renderer.counters()
-        deltas.append({n: after[n] - before[n] for n in after})
-    renderer.sync()
-    return frames, deltas, (renderer.ray_cost(), renderer.last_pipeline(), renderer.last_parts())
 
 
 @pytest.mark.gpu
@@ -423,9 +390,14 @@ def test_passes_leave_rendering_untouched(renderer, pipeline):
     s = model_scene("bunny.obj", material=MIRROR, spheres=True)
     W, H = 64, 48
     renderer.set_tuning("pipeline", pipeline)
+
+    def guide_passes(other, w, h):
+        renderer.render_guides(other, w, h, 4)
+        renderer.render_guides(other, w, h, 8, first_hit=True, row0=1, rowStride=2)
+
     try:
-        a = _render_sequence(renderer, s, W, H, False)
-        b = _render_sequence(renderer, s, W, H, True)
+        a = frames_between_passes(renderer, s, W, H)
+        b = frames_between_passes(renderer, s, W, H, guide_passes)
     finally:
         renderer.set_tuning("pipeline", -1)
     for fa, fb in zip(a[0], b[0]):

@@ -19,7 +19,7 @@ import pytest
 
 from ray_tracer_amd import _capi, engine
 
-from util import cornell_scene
+from util import bits, cornell_scene
 
 W, H = 64, 48
 
@@ -31,9 +31,7 @@ def _words(x):
     if isinstance(x, tuple):
         return np.concatenate([_words(v) for v in x])
     a = np.ascontiguousarray(x)
-    if a.dtype == np.bool_:
-        a = a.astype(np.uint32)
-    return a.view(np.uint32).reshape(-1)
+    return bits(a.astype(np.uint32) if a.dtype == np.bool_ else a).reshape(-1)
 
 
 def _fresh():

@@ -12,20 +12,7 @@ import pytest
 from oracle import pyoracle
 from ray_tracer_amd import engine, scenes
 
-from util import cornell_scene, model_scene
-
-
-def emitters_scene():
-    """Cornell with an emissive sphere, glass right under the ceiling light and a second light coplanar with the ceiling (also the
-    "emitters" case of tests/test_paths_float64.py)."""
-    s = cornell_scene(True)
-    glow = s.add_material(engine.default_material(albedo=(0.1, 0.1, 0.1), emissionColor=(0.3, 0.6, 1.0), emissionStrength=1.2))
-    s.set_sphere(3, (-0.6, -0.9, 0.4), 0.2, glow)
-    s.set_sphere(4, (0.1, -1.3, 0.0), 0.25, 5)       # glass right under the ceiling light
-    quad = np.array([[[-0.2, -1.5, 0.5], [0.2, -1.5, 0.5], [0.2, -1.5, 0.8]], [[-0.2, -1.5, 0.5], [0.2, -1.5, 0.8], [-0.2, -1.5, 0.8]]], np.float32)
-    nq = np.zeros_like(quad); nq[..., 1] = 1
-    s.add_mesh("coplanar_light", quad, nq, engine.placement(), glow)   # in the plane of the ceiling: equal distances
-    return s
+from util import cornell_scene, emitters_scene, model_scene
 
 
 def _scenes():

@@ -10,8 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import hostcheck
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ray_tracer_amd", "csrc")
 SCENES = ("cornell", "cornell_cube", "cornell_bunny", "two_bunnies")
 
 NODE = np.dtype([("box", np.float32, (3, 2)), ("index", np.uint32), ("triCount", np.uint32)])   # BVHNode: (min, max) per axis
@@ -33,26 +34,15 @@ def numpy_refit(nodes, tri, pos, root):
     nodes[root]["box"][:, 0], nodes[root]["box"][:, 1] = lo, hi
 
 
-def _compile(built, exe, extra):
-    rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(built.HIPCC))), "include")
-    cc = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + rocm_include,
-          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, os.path.join(CSRC, "scene.cpp"), os.path.join(CSRC, "scene_layout.cpp"),
-          os.path.join(CSRC, "mesh_refit.cpp"), os.path.join(ROOT, "tests", "mesh_refit_check.cpp"), "-o", exe]
-    return subprocess.run(cc + extra, capture_output=True, text=True, timeout=600)
+def _build(directory, name, **how):
+    return hostcheck.build(directory, name, ["scene.cpp", "scene_layout.cpp", "mesh_refit.cpp"], "mesh_refit_check.cpp", opt="-O1", **how)
 
 
 @pytest.fixture(scope="module")
 def checked(tmp_path_factory, built):
     """The check program, built without sanitizers and run once: its output directory."""
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
     d = tmp_path_factory.mktemp("mesh_refit")
-    exe = str(d / "mesh_refit_check")
-    b = _compile(built, exe, ["-O1"])
-    assert b.returncode == 0, b.stderr[-3000:]
-    p = subprocess.run([exe, os.path.join(ROOT, "assets"), str(d)], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, (p.stdout + p.stderr)[-4000:]
-    assert "mesh refit ok" in p.stdout
+    hostcheck.run(_build(d, "mesh_refit_check", sanitize=None), [os.path.join(ROOT, "assets"), d], ok="mesh refit ok")
     return d
 
 
@@ -76,12 +66,8 @@ def _sanitizers_installed(tmp_path):
 def test_the_check_program_under_asan_and_ubsan(tmp_path, built):
     if not _sanitizers_installed(tmp_path):
         pytest.skip("the sanitizer runtimes are not installed")
-    exe = str(tmp_path / "mesh_refit_check_san")
-    b = _compile(built, exe, ["-O1", "-g"] + SANITIZE)
-    assert b.returncode == 0, b.stderr[-3000:]
-    p = subprocess.run([exe, os.path.join(ROOT, "assets"), str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, (p.stdout + p.stderr)[-4000:]
-    assert "mesh refit ok" in p.stdout
+    exe = _build(tmp_path, "mesh_refit_check_san", fallback=False, extra=["-g"])
+    hostcheck.run(exe, [os.path.join(ROOT, "assets"), tmp_path], ok="mesh refit ok", timeout=300)
 
 
 @pytest.mark.parametrize("kind", (0, 1, 2), ids=("all_points", "sub_range", "straddles_two_meshes"))

@@ -46,15 +46,12 @@ from ray_tracer_amd import engine
 from oracle import pyoracle
 import brute_force as bf
 import paths_float64 as pf
-from util import cornell_scene, model_scene
-from test_denoise import _checker_scene
-from test_light_queries_oracle import emitters_scene
+from paths_float64 import MAX_FRAGILE, T, _maps_scene, _sky_scene, _spheres_scene
+from util import cornell_scene, emitters_scene, model_scene
 
 T_MEASURED = 7.7e-3     # largest rounded-to-exact distance of the restatement over the cases that share T (the table above)
-T = 4e-2                # 4 x T_MEASURED, rounded up to one significant figure
 T_MEASURED_OWN = dict(emitters_b3=1.17e-1, sphere_cave=6.1e-2)    # the two cases whose own distance would loosen the rest
 T_OWN = dict(emitters_b3=5e-1, sphere_cave=3e-1)
-MAX_FRAGILE = 0.10
 W, H = 64, 48
 SKY = dict(environmentOn=True)
 
@@ -72,15 +69,6 @@ FLOORS = {
 CASES = list(FLOORS)
 
 
-def _spheres_scene(materials, spheres):
-    s = engine.Scene()
-    for m in materials:
-        s.add_material(engine.default_material(**m))
-    for i, (c, r, m) in enumerate(spheres):
-        s.set_sphere(i, c, r, m)
-    return s
-
-
 def _cave_scene():
     """A diffuse sphere of radius 3 seen from inside; in it an emissive sphere around the hard-wired light's rectangle (y = -1.5:
     surfaces below it see it with a positive PDF, the cave's small cap above it with a negative one), a mirror, two glass spheres, and
@@ -91,25 +79,6 @@ def _cave_scene():
     sph = [((0.0, 0.8, 0.0), 3.0, 0), ((0.0, -1.5, 0.0), 0.5, 1), ((-1.0, 0.9, 0.6), 0.6, 2), ((0.9, 0.8, -0.2), 0.6, 3),
            ((0.0, 1.1, -1.2), 0.45, 4), ((1.05, 0.9, -0.25), 0.3, 5)]
     return _spheres_scene(mats, sph)
-
-
-def _sky_scene():
-    """Spheres under an open sky: a large diffuse one as the ground, a mirror, glass and a diffuse one on it."""
-    mats = [dict(albedo=(0.7, 0.7, 0.6)), dict(reflectance=1.0), dict(ior=1.5), dict(albedo=(0.3, 0.6, 0.9))]
-    sph = [((0.0, 3.5, 0.0), 3.0, 0), ((-0.9, 0.0, 0.3), 0.5, 1), ((0.3, 0.05, -0.4), 0.45, 2), ((1.2, 0.1, 0.6), 0.4, 3)]
-    return _spheres_scene(mats, sph)
-
-
-def _maps_scene():
-    """tests/test_denoise.py's checker quad, its material binding a metalness map besides the albedo map: every other row of texels a mirror."""
-    s, m, tex = _checker_scene()
-    mat = s.material(m)
-    mat.metalnessIndex = 1
-    s.set_material(m, mat)
-    metal = np.zeros((4, 4, 4), np.uint8)
-    metal[..., 1:] = 99                                   # noise in the channels that must not matter
-    metal[::2, :, 0] = (255, 3, 1, 90)
-    return s, [tex, metal]
 
 
 def _constants(name):

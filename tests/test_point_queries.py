@@ -15,7 +15,7 @@ import pytest
 from ray_tracer_amd import _capi, engine
 
 import point_query_cases as pq
-from test_update_points import _deformed_bunny
+from util import _deformed_bunny, to_device
 
 pytestmark = pytest.mark.gpu
 
@@ -25,25 +25,18 @@ REC = C.sizeof(_capi.RtNearest)
 SHALLOW, DEEP = "k_nearest_points<24, true>", "k_nearest_points<64, false>"
 
 
-def _to_device(renderer, name, a):
-    p = renderer._device_buffer(name, max(a.nbytes, 1))
-    if a.nbytes:
-        assert engine._hip().hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0   # hipMemcpyHostToDevice
-    return p
-
-
 def _device_query(renderer, points, T=None, guard=0):
     """Through the device entry point: (the records' bytes [n, 48], the kernel that ran, the `guard` bytes behind them)."""
     n = len(points)
     renderer.sync()
-    pp = _to_device(renderer, "n_points", points)
-    pt = None if T is None else _to_device(renderer, "n_limits", T)
+    pp = to_device(renderer, "n_points", points)
+    pt = None if T is None else to_device(renderer, "n_limits", T)
     raw = np.full(n * REC + guard, 0xA5, np.uint8)
-    po = _to_device(renderer, "n_out", raw)
+    po = to_device(renderer, "n_out", raw)
     renderer.query_nearest(pp, pt, n=n, out=po, sync=False)
     kernel = renderer.last_kernel()
     renderer.sync()
-    assert engine._hip().hipMemcpy(raw.ctypes.data, po, raw.nbytes, 2) == 0   # hipMemcpyDeviceToHost
+    renderer._owned["n_out"].download(into=raw)
     return raw[:n * REC].reshape(n, REC), kernel, raw[n * REC:]
 
 
@@ -139,8 +132,8 @@ def test_empty_batch_and_refusals(renderer):
     l, h = renderer._l, renderer._h
     guard = np.full(4096, 0x5A, np.uint8)
     renderer.sync()
-    po = _to_device(renderer, "n_out", guard)
-    pp = _to_device(renderer, "n_points", c["sets"]["uniform"][:16])
+    po = to_device(renderer, "n_out", guard)
+    pp = to_device(renderer, "n_points", c["sets"]["uniform"][:16])
     empty = _capi.RtPointBatch(None, None, 0)
     assert l.rt_query_nearest(h, C.byref(empty), None) == 0 and l.rt_query_nearest_host(h, C.byref(empty), None) == 0
     for fn in ("rt_query_nearest", "rt_query_nearest_host"):
@@ -157,7 +150,7 @@ def test_empty_batch_and_refusals(renderer):
             assert l.rt_last_error(h).decode() == f"{fn}: {message}"
         assert not np.frombuffer(out_host, np.uint8).any()
     renderer.sync()
-    assert engine._hip().hipMemcpy(guard.ctypes.data, po, guard.nbytes, 2) == 0
+    renderer._owned["n_out"].download(into=guard)
     assert (guard == 0x5A).all(), "a refused call wrote to its output"
     fresh = engine.Renderer(renderer.device)
     try:

@@ -11,21 +11,16 @@ rt_nearest_exhaustive_host is then held against the float64 brute force (tests/n
 tests/point_query_cases.py, by the rules of check_records there; the largest |dst - ref| / bound(C = 1) per set is printed, and
 C must be at least twice the worst. The limits T = 0.5, 0.999, 1.001 and 2 x the float64 distance run on the uniform sets: found iff
 dst < T, no point within the bound of its limit (the exempt share is 0)."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 from ray_tracer_amd import engine
 
 import brute_force as bf
+import hostcheck
 import nearest_float64 as nf
 import point_query_cases as pq
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ray_tracer_amd", "csrc")
 FACTORS = (0.5, 0.999, 1.001, 2.0)
 SMIN_MARGIN = 1e-6     # RT_NEAREST_SMIN_MARGIN
 
@@ -51,26 +46,13 @@ def _matrices():
 def checked(tmp_path_factory, built):
     """The check program built with plain g++ (no hipcc, no HIP runtime, no device), under ASan and UBSan where they are installed,
     and run once on the matrices: its output."""
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
     d = tmp_path_factory.mktemp("point_queries")
-    exe = str(d / "point_queries_check")
-    rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(built.HIPCC))), "include")
-    cc = ["g++", "-std=c++17", "-O1", "-Wall", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + rocm_include,
-          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, os.path.join(CSRC, "point_queries.cpp"),
-          os.path.join(ROOT, "tests", "point_queries_check.cpp"), "-o", exe]
-    b = subprocess.run(cc + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True, timeout=600)
-    if b.returncode != 0 and ("asan" in b.stderr.lower() or "ubsan" in b.stderr.lower()):
-        b = subprocess.run(cc, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    assert "warning" not in b.stderr, b.stderr[-3000:]
+    exe = hostcheck.build(d, "point_queries_check", ["point_queries.cpp"], "point_queries_check.cpp", opt="-O1")
     mats = _matrices()
     path = d / "matrices.bin"
     np.stack([m.T.reshape(-1) for m in mats.values()]).astype(np.float32).tofile(path)    # column-major
-    p = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, (p.stdout + p.stderr)[-4000:]
-    assert "point queries ok" in p.stdout
-    rows = [tuple(float(x) for x in line.split()[1:]) for line in p.stdout.splitlines() if line.startswith("prune ")]
+    out = hostcheck.run(exe, [path], ok="point queries ok")
+    rows = [tuple(float(x) for x in line.split()[1:]) for line in out.splitlines() if line.startswith("prune ")]
     assert len(rows) == len(mats)
     return dict(zip(mats, rows))
 

@@ -29,7 +29,7 @@ from ray_tracer_amd import engine
 import brute_force as bf
 import paths_float64 as pf
 import radiance_fans as fans
-from test_paths_float64 import MAX_FRAGILE, T as T_SHARED
+from paths_float64 import MAX_FRAGILE, T as T_SHARED
 
 T_MEASURED = 4.75e-3    # largest rounded-to-exact distance of the restatement over the compared rays of both runs
 T = 4e-2                # T_MEASURED <= 7.7e-3: the shared T of tests/test_paths_float64.py

@@ -12,11 +12,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from ray_tracer_amd import _capi, engine
+from ray_tracer_amd import _capi, devmem, engine
 
 import radiance_fans as fans
-from test_paths_float64 import _maps_scene, _sky_scene
-from util import cornell_scene
+from paths_float64 import _maps_scene, _sky_scene
+from util import bits, cornell_scene
 
 W, H = 64, 48
 DEFAULTS = dict(pipeline=-1, camera_reuse=1, light_queries=1, lanes=0, lanes_min_kslots=1024, radiance_max_kslots=0, fused_maps=0)
@@ -34,13 +34,9 @@ def gpu(renderer):
             renderer.set_tuning(k, v)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def _same(got, want, what):
     got, want = np.asarray(got).reshape(-1, 4), np.asarray(want).reshape(-1, 4)
-    bad = np.flatnonzero((_bits(got) != _bits(want)).any(axis=1))
+    bad = np.flatnonzero((bits(got) != bits(want)).any(axis=1))
     assert not len(bad), f"{what}: {len(bad)} of {len(got)} rays differ from rt_render, first at {bad[:5].tolist()}: {got[bad[:2]].tolist()} against {want[bad[:2]].tolist()}"
 
 
@@ -146,7 +142,7 @@ def test_map_scene_equals_rt_render(gpu):
     o, d = _camera_rays(gpu, pc, W, H)
     want = _render0(gpu, pc, W, H)
     _same(gpu.query_radiance(o, d, samples=3, bounces=3), want, "maps")
-    assert len(np.unique(_bits(want).reshape(-1, 4)[:, :3])) > 100, "the frame is not flat"
+    assert len(np.unique(bits(want).reshape(-1, 4)[:, :3])) > 100, "the frame is not flat"
 
 
 @pytest.mark.gpu
@@ -197,40 +193,26 @@ def test_device_form_equals_host_form(gpu):
         gpu.query_radiance(to, td.double(), out=out)
 
 
-def _hip_runtime():
-    """The HIP runtime the library itself is bound to (as tests/test_aovs.py looks it up): device buffers without a framework."""
-    h = C.CDLL(_capi.LIB_PATH)
-    h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    h.hipFree.argtypes = [C.c_void_p]
-    return h
-
-
 @pytest.mark.gpu
 def test_device_pointers_equal_host_form(gpu):
     """The asynchronous form on device memory the test owns (integer pointers with n=), where no framework is needed: sync=False,
     then rt_sync, equals the host form; then a progressive frame on top of the result in `out`."""
-    hip = _hip_runtime()
     o, d, ids, _ = _fan_batch(gpu)
     host = gpu.query_radiance(o, d, samples=3, bounces=4, ids=ids)
     bufs = []
 
     def device(a):
-        p = C.c_void_p()
-        assert hip.hipMalloc(C.byref(p), a.nbytes) == 0
-        bufs.append(p)
-        assert hip.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0   # hipMemcpyHostToDevice
-        return p.value
+        bufs.append(devmem.DeviceBuffer(a.nbytes).upload(a))
+        return bufs[-1].ptr
 
     try:
         d_o, d_d, d_i, d_out = device(o), device(d), device(ids), device(np.full((fans.N, 4), 7.0, np.float32))
-        got = np.empty((fans.N, 4), np.float32)
         assert gpu.query_radiance(d_o, d_d, samples=3, bounces=4, ids=d_i, n=fans.N, out=d_out, sync=False) is None
         gpu.sync()
-        assert hip.hipMemcpy(got.ctypes.data, d_out, got.nbytes, 2) == 0   # hipMemcpyDeviceToHost
+        got = bufs[-1].download((fans.N, 4), np.float32)
         _same(got, host, "device pointers, sync=False")
         gpu.query_radiance(d_o, d_d, samples=3, bounces=4, ids=d_i, n=fans.N, progressive=True, frame=1, out=d_out)
-        assert hip.hipMemcpy(got.ctypes.data, d_out, got.nbytes, 2) == 0
+        got = bufs[-1].download((fans.N, 4), np.float32)
         _same(got, gpu.query_radiance(o, d, samples=3, bounces=4, ids=ids, progressive=True, frame=1, out=host), "progressive on the device")
         with pytest.raises(ValueError):
             gpu.query_radiance(d_o, d_d, out=d_out)             # integer pointers need n=
@@ -238,8 +220,8 @@ def test_device_pointers_equal_host_form(gpu):
             gpu.query_radiance(d_o, d_d, n=fans.N)              # ... and out=
     finally:
         gpu.sync()
-        for p in bufs:
-            hip.hipFree(p)
+        for b in bufs:
+            b.free()
 
 
 # ---------------------------------------------------------------------------------------------------------------- what it leaves alone

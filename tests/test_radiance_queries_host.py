@@ -4,37 +4,22 @@ tests/radiance_queries_check.cpp provokes every refusal with made-up addresses, 
 [0, n) with the pieces for n = 0, 1, 1023, 1024, 1025 and 3 x 1024 + 5 at "radiance_max_kslots" 1, checks the byte counts with and without ids
 (that the staged arrays are aligned and do not overlap: tests/test_host_staging_host.py), and prints startingSeed for frameCount 0, 3 and 2^32 - 1, which is compared here
 with the oracle's random() pushed through uint(random(frameCount) * 23892183.f)."""
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
 from oracle import pyoracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ray_tracer_amd", "csrc")
+import hostcheck
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_radiance_query_checks_on_the_cpu(tmp_path, built):
     """radiance_queries.cpp + the checker with plain g++ (no hipcc, no HIP runtime, no device), under ASan and UBSan where they
     are installed."""
-    exe = str(tmp_path / "radiance_queries_check")
-    cc = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-          os.path.join(CSRC, "radiance_queries.cpp"), os.path.join(ROOT, "tests", "radiance_queries_check.cpp"), "-o", exe]
-    b = subprocess.run(cc + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True, timeout=600)
-    if b.returncode != 0 and ("asan" in b.stderr.lower() or "ubsan" in b.stderr.lower()):
-        b = subprocess.run(cc, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    assert "warning" not in b.stderr, b.stderr[-3000:]
-    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, (p.stdout + p.stderr)[-4000:]
-    assert "radiance queries ok" in p.stdout
-    seeds = {int(f): int(s) for f, s in re.findall(r"^seed (\d+) (\d+)$", p.stdout, re.M)}
-    assert sorted(seeds) == [0, 3, 2**32 - 1], p.stdout
+    exe = hostcheck.build(tmp_path, "radiance_queries_check", ["radiance_queries.cpp"], "radiance_queries_check.cpp", rocm=False)
+    out = hostcheck.run(exe, ok="radiance queries ok")
+    seeds = {int(f): int(s) for f, s in re.findall(r"^seed (\d+) (\d+)$", out, re.M)}
+    assert sorted(seeds) == [0, 3, 2**32 - 1], out
     for frame, seed in seeds.items():
         _, r = pyoracle.random(frame)
         assert seed == int(np.uint32(np.float32(r) * np.float32(23892183.0))), (frame, seed, r)

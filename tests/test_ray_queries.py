@@ -20,9 +20,9 @@ from oracle import pyoracle
 from ray_tracer_amd import _capi, engine
 
 import brute_force as bf
-import test_closest_hit_float64 as chf
-import test_texture_maps_float64 as tmf
-from util import assert_hits_equal, cornell_scene, model_scene
+import closest_hit_cases as chf
+import texture_map_cases as tmf
+from util import assert_hits_equal, cornell_scene, model_scene, to_device
 
 MISS_DST = np.float32(99999999.0)   # RT_MISS_DST
 FACTORS = np.array([0.5, 0.999, 1.001, 2.0], np.float32)
@@ -157,19 +157,12 @@ def test_ray_batch_layout_matches_the_header():
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU half
-def _to_device(renderer, name, a):
-    p = renderer._device_buffer(name, max(a.nbytes, 1))
-    if a.nbytes:
-        assert engine._hip().hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0   # hipMemcpyHostToDevice
-    return p
-
-
 def _device_queries(renderer, o, d, T):
     """Both queries through the device entry points: the rays start as numpy arrays and get there through device buffers."""
     n = len(o)
     renderer.sync()
-    po, pd = _to_device(renderer, "q_origins", o), _to_device(renderer, "q_dirs", d)
-    pt = None if T is None else _to_device(renderer, "q_tmax", T)
+    po, pd = to_device(renderer, "q_origins", o), to_device(renderer, "q_dirs", d)
+    pt = None if T is None else to_device(renderer, "q_tmax", T)
     ph = renderer._device_buffer("q_hits", n * C.sizeof(_capi.RtHit))
     pb = renderer._device_buffer("q_occluded", n)
     renderer.query_closest(po, pd, pt, n=n, out=ph, sync=False)
@@ -178,9 +171,8 @@ def _device_queries(renderer, o, d, T):
     assert renderer.last_kernel() == kernel
     renderer.sync()
     hits = (_capi.RtHit * n)()
-    occ = np.zeros(n, np.uint8)
-    assert engine._hip().hipMemcpy(C.addressof(hits), ph, C.sizeof(hits), 2) == 0   # hipMemcpyDeviceToHost
-    assert engine._hip().hipMemcpy(occ.ctypes.data, pb, n, 2) == 0
+    renderer._owned["q_hits"].download(into=np.frombuffer(hits, np.uint8))
+    occ = renderer._owned["q_occluded"].download(n, np.uint8)
     assert set(np.unique(occ)) <= {0, 1}
     return engine.hits_to_numpy(hits), occ.astype(bool), kernel
 
@@ -277,9 +269,9 @@ def test_batch_sizes(renderer, n):
     # nothing past the batch is written
     guard = np.full(n + 64, 7, np.uint8)
     renderer.sync()
-    pb = _to_device(renderer, "q_guard", guard)
-    renderer.query_occluded(_to_device(renderer, "q_origins", o), _to_device(renderer, "q_dirs", d), None, n=n, out=pb)
-    assert engine._hip().hipMemcpy(guard.ctypes.data, pb, guard.nbytes, 2) == 0
+    pb = to_device(renderer, "q_guard", guard)
+    renderer.query_occluded(to_device(renderer, "q_origins", o), to_device(renderer, "q_dirs", d), None, n=n, out=pb)
+    renderer._owned["q_guard"].download(into=guard)
     assert np.array_equal(guard[:n].astype(bool), oracle["didHit"].astype(bool)) and np.all(guard[n:] == 7)
 
 

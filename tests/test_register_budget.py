@@ -7,26 +7,20 @@ phase statistics fits the 72 registers that leave room for a k_shade wave beside
 (five waves per SIMD), and the fused kernels spill a third of what they did. profiles/r05_registers.txt has both columns for all
 kernels; the fused kernels' limits below are its parent column. A compiler or a source change that takes the registers back
 shows here, on the CPU, before it shows as a slower frame."""
-import importlib.util
 import os
 import re
 
 import pytest
 
+from util import code_object
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH_KERNEL = "_Z10k_trace_pwILi20ELb0ELb0ELb0ELb0ELi144ELi5EEv8DevScene9PathState11TracePwArgs"   # k_trace_pw<20, 0, 0, 0, 0, 144, 5>
 
 
-def _code_object():
-    spec = importlib.util.spec_from_file_location("code_object", os.path.join(ROOT, "tools", "code_object.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
 @pytest.fixture(scope="module")
 def kernels(built):
-    return _code_object().kernels(built.LIB)
+    return code_object().kernels(built.LIB)
 
 
 def _parent_column():
@@ -71,6 +65,6 @@ def test_fused_kernels_spill_no_more_than_the_parent_build(kernels):
 def test_bench_kernel_keeps_its_packed_slab_test(built):
     """box_intersect_pair is packed by hand (ext_vector_type): six v_pk_add_f32 and six v_pk_mul_f32 per copy of the interior step.
     The vectorizer switch must not take them away."""
-    ops = _code_object().disassembly(built.LIB)[BENCH_KERNEL]
+    ops = code_object().disassembly(built.LIB)[BENCH_KERNEL]
     packed = sum(op in ("v_pk_add_f32", "v_pk_mul_f32") for op in ops)
     assert packed > 0 and packed % 12 == 0, f"{packed} packed fp32 instructions in the bench kernel"

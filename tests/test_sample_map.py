@@ -20,7 +20,7 @@ import pytest
 from oracle import pyoracle
 from ray_tracer_amd import _capi, engine, session
 
-from util import cornell_scene, model_scene
+from util import bits, cornell_scene, model_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -127,10 +127,6 @@ def tune(r, knobs):
         r.set_tuning(k, v)
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def expected(uniform, counts, untouched):
     """Pixel p of image min(counts[p], S), or of `untouched` where the count is 0. uniform[n - 1]: the image at n samples."""
     n = np.minimum(counts, S)
@@ -163,7 +159,7 @@ def upload_bunny(r, tmp_path):
 
 def upload_maps(r, tmp_path):
     """The plane scene with an alpha, a metalness and a bump map bound, as tests/test_fused_maps.py builds it."""
-    from test_textures import _bound, _map_set
+    from texture_cases import _bound, _map_set
     s = _bound(tmp_path / "maps", 1, 2.5, alphaIndex=1, metalnessIndex=2, bumpIndex=3)
     r.upload_scene(s.scene)
     s.push(r, "objects")

@@ -1,34 +1,18 @@
 """The host logic of the per-pixel sample counts on the CPU: tests/sample_map_check.cpp provokes every parameter refusal of
 rt_build_sample_map, the rule for the ctx-owned moments plane (none yet, another size) and rt_render_sampled's refusal of a map with
 the debug heat maps (ray_tracer_amd/csrc/post_passes.h); and the tiling helper that cuts a whole-frame map into a rank's rows."""
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ray_tracer_amd", "csrc")
+import hostcheck
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_sample_map_checks_on_the_cpu(tmp_path, built):
     """post_passes.cpp + temporal_motion.cpp + the checker with plain g++ (no hipcc, no HIP runtime, no device), under ASan and UBSan
     where they are installed."""
-    exe = str(tmp_path / "sample_map_check")
-    rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(built.HIPCC))), "include")
-    cc = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + rocm_include,
-          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, os.path.join(CSRC, "post_passes.cpp"), os.path.join(CSRC, "temporal_motion.cpp"),
-          os.path.join(ROOT, "tests", "sample_map_check.cpp"), "-o", exe]
-    b = subprocess.run(cc + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True, timeout=600)
-    if b.returncode != 0 and ("asan" in b.stderr.lower() or "ubsan" in b.stderr.lower()):
-        b = subprocess.run(cc, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    assert "warning" not in b.stderr, b.stderr[-3000:]
-    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, (p.stdout + p.stderr)[-4000:]
-    assert "sample map ok" in p.stdout
+    exe = hostcheck.build(tmp_path, "sample_map_check", ["post_passes.cpp", "temporal_motion.cpp"], "sample_map_check.cpp")
+    hostcheck.run(exe, ok="sample map ok")
 
 
 @pytest.mark.parametrize("H,world", [(33, 1), (33, 2), (33, 4), (33, 8), (8, 8), (5, 8), (1, 3), (1080, 7)])

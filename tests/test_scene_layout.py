@@ -4,33 +4,21 @@ object hierarchy, spheres, emitters, maps and every refusal against the scene. O
 as it was."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from ray_tracer_amd import _capi, engine
 
+import hostcheck
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ray_tracer_amd", "csrc")
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_scene_tables_on_the_cpu(tmp_path, built):
     """scene.cpp + scene_layout.cpp + the checker with plain g++ (no hipcc, no device), under UBSan where it is installed."""
-    exe = str(tmp_path / "scene_layout_check")
-    rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(built.HIPCC))), "include")
-    cc = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + rocm_include,
-          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, os.path.join(CSRC, "scene.cpp"), os.path.join(CSRC, "scene_layout.cpp"),
-          os.path.join(ROOT, "tests", "scene_layout_check.cpp"), "-o", exe]
-    b = subprocess.run(cc + ["-fsanitize=undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True, timeout=600)
-    if b.returncode != 0 and "ubsan" in b.stderr.lower():
-        b = subprocess.run(cc, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    p = subprocess.run([exe, os.path.join(ROOT, "assets")], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, (p.stdout + p.stderr)[-4000:]
-    assert "scene layout ok" in p.stdout
+    exe = hostcheck.build(tmp_path, "scene_layout_check", ["scene.cpp", "scene_layout.cpp"], "scene_layout_check.cpp", sanitize="undefined")
+    hostcheck.run(exe, [os.path.join(ROOT, "assets")], ok="scene layout ok")
 
 
 class _WithNodes:

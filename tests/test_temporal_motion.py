@@ -4,7 +4,7 @@ k_tp_accumulate_motion, Renderer.temporal_track_motion, InteractiveSession(track
 The contract is DESIGN.md's "Temporal accumulation" with the addition "Moved objects and spheres": a pixel of F on a moved object
 sends P~ = D P and n~ = G n / |G n| through the previous camera and the tap tests in place of P and n, one on a moved sphere
 P~ = c' + (P - c) r' / r, one on a replaced object or sphere has no history, and what is stored is the frame's own n, z and ids.
-`MotionRestatement` restates that in numpy on top of tests/test_temporal.py's `Restatement` (which is imported, not edited); it
+`MotionRestatement` restates that in numpy on top of tests/temporal_float64.py's `Restatement` (which is imported, not edited); it
 computes D = Fwd' Inv and G = Inv'^T Fwd^T itself from the fp32 transformMatrix of the two calls (float64: numpy's float64 inverse;
 float32: numpy's float32 inverse and products rounded once to fp32, as the library's tables are) and takes nothing from the library.
 
@@ -46,9 +46,10 @@ import os
 import numpy as np
 import pytest
 
-from ray_tracer_amd import _capi, engine, session
+from ray_tracer_amd import _capi, devmem, engine, session
 
-from test_temporal import FRAGILE_CAP, Restatement, T, T_COLOUR, T_COLOUR_MEASURED, T_MEASURED, camera_of, filtered_set, paths, rel, synthetic
+from temporal_float64 import (EMISSION_TOY, FRAGILE_CAP, Restatement, T, T_COLOUR, T_COLOUR_MEASURED, T_MEASURED, cam, camera_of, distances, emission_of, filtered_set,
+                              paths, planes_of, primary_dirs, rel, synthetic)
 from util import EditedScene, cornell_scene, model_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,7 +62,6 @@ MOTION_T_COLOUR_RENDERED = 9e-3
 MOTION_T_COLOUR_FIXED, MOTION_T_FIXED = 3e-1, 6e-1
 RENDERED_FOV = 20.0
 SIZES = [(1, 1), (67, 1), (1, 67), (37, 23), (130, 70)]
-EMISSION_TOY = np.array([0.0, 0.0, 5.0, 0.0])
 
 
 # ---------------------------------------------------------------- placements and the motion between two of them
@@ -159,14 +159,6 @@ def med(x):
     return round(float(np.median(x)), 3)
 
 
-def distances(got, mom, out, m, cmp):
-    """Over the pixels `cmp`: the largest relative difference of (rgb, m1, m2, N) and of the variance."""
-    if not cmp.any():
-        return 0.0, 0.0
-    colour = max(float(rel(got[cmp][:, :3], out[cmp][:, :3]).max()), float(rel(mom[cmp][:, [0, 1, 3]], m[cmp][:, [0, 1, 3]]).max()))
-    return colour, float(rel(mom[cmp][:, 2], m[cmp][:, 2]).max())
-
-
 class MotionChecker:
     """One sequence: every call's result against the float64 motion restatement, and the float32 one beside it."""
 
@@ -216,19 +208,6 @@ class MotionChecker:
 
 # ---------------------------------------------------------------- synthetic planes of moved bodies
 SPHERE_BASE = {1: np.array([2.0, 0.0, 6.0, 1.0], np.float32), 3: np.array([2.0, 0.0, -6.0, 1.0], np.float32)}   # bands' own space
-
-
-def cam(W, H, yaw=0.0, pos=(0.0, 0.0, 0.0), pitch=0.0):
-    """tests/test_temporal.py's synthetic camera: 20 degrees of vertical field of view."""
-    return engine.push_constants(W, H, cameraAngles=(pitch, yaw, 0.0), pos=pos, fov=20.0, aspectRatio=min(W / H, 2.0)).camInfo
-
-
-def primary_dirs(ci, W, H):
-    c = camera_of(ci)
-    gy, gx = np.mgrid[0:H, 0:W].astype(np.float64)
-    pt = np.stack([c["bl"][0] + c["pw"] * (gx / W), c["bl"][1] + c["ph"] * (gy / H), np.full((H, W), c["bl"][2])], -1)
-    d = pt / np.linalg.norm(pt, axis=-1, keepdims=True)
-    return d @ c["M"].T + c["t"]
 
 
 def sphere_affine(s, base):
@@ -509,40 +488,25 @@ def _host(r, ci, rgba, nd, position, albedo, ids):
     return out, mom
 
 
-def _hip_runtime():
-    """The HIP runtime the library itself is bound to (as tests/test_temporal.py looks it up)."""
-    h = C.CDLL(_capi.LIB_PATH)
-    h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    h.hipFree.argtypes = [C.c_void_p]
-    return h
-
-
 class _DeviceRoute:
     """rt_temporal_accumulate on device planes the test owns: seven planes of one frame."""
 
     def __init__(self, W, H):
-        self.hip, self.W, self.H, self.nbytes = _hip_runtime(), W, H, W * H * 16
-        self.bufs = [C.c_void_p() for _ in range(7)]
-        for b in self.bufs:
-            assert self.hip.hipMalloc(C.byref(b), self.nbytes) == 0
+        self.W, self.H = W, H
+        self.bufs = [devmem.DeviceBuffer(W * H * 16) for _ in range(7)]
 
     def call(self, r, ci, rgba, nd, position, albedo, ids):
         for b, a in zip(self.bufs, (rgba, nd, position, albedo, ids)):
-            assert self.hip.hipMemcpy(b, np.ascontiguousarray(a).ctypes.data, self.nbytes, 1) == 0   # hipMemcpyHostToDevice
-        v = [b.value for b in self.bufs]
+            b.upload(a)
+        v = [b.ptr for b in self.bufs]
         d = _capi.RtAovBuffers(normalDepth=v[1], position=v[2], albedo=v[3], ids=v[4])
         r._check(r._l.rt_temporal_accumulate(r._h, self.W, self.H, C.byref(ci), v[0], C.byref(d), None, v[5], v[6]), "rt_temporal_accumulate")
         r.sync()
-        out, mom = np.empty((self.H, self.W, 4), np.float32), np.empty((self.H, self.W, 4), np.float32)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.bufs[5], self.nbytes, 2) == 0                # hipMemcpyDeviceToHost
-        assert self.hip.hipMemcpy(mom.ctypes.data, self.bufs[6], self.nbytes, 2) == 0
-        return out, mom
+        return self.bufs[5].download((self.H, self.W, 4), np.float32), self.bufs[6].download((self.H, self.W, 4), np.float32)
 
     def close(self):
         for b in self.bufs:
-            if b.value:
-                self.hip.hipFree(b)
+            b.free()
 
 
 def _place(e, now):
@@ -569,11 +533,6 @@ def tracking(renderer):
     renderer.temporal_track_motion(True)
     yield renderer
     renderer.temporal_track_motion(False)
-
-
-def emission_of(scene):
-    a = scene.arrays()
-    return np.array([a.materials[i].emissionStrength for i in range(a.materialCount)], np.float64)
 
 
 # ---------------------------------------------------------------- 1. synthetic planes against the restatement
@@ -618,11 +577,6 @@ def test_synthetic_planes_against_the_restatement(tracking, W, H):
 
 
 # ---------------------------------------------------------------- 2. rendered sequences against the restatement
-def planes_of(a):
-    p = engine.numpy_to_aovs(a)
-    return p["normalDepth"], p["position"], p["albedo"], p["ids"]
-
-
 def camera_path(W, H, k, moving, **params):
     """Frame k: tests/test_temporal.py's path (a small yaw plus a translation) or its first camera, with a 20-degree field of view
     (module docstring, "Fragile share"); consecutive frameCounts."""

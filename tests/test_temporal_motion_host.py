@@ -4,37 +4,21 @@ translated, rescaled and re-pointed objects, growing and shrinking counts, spher
 snapshot pairs this file writes into tables, whose flags, counts and matrices are checked here: D = Fwd' Inv and
 G = Inv'^T Fwd^T against a numpy float64 product of the same fp32 rows, each entry within 2^-23 x the sum of the magnitudes of
 its terms (one rounding to fp32 of a sum accumulated exactly, with room for the double accumulation's own last bits)."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ray_tracer_amd", "csrc")
+import hostcheck
+
 UNMOVED, MOVED, REPLACED = 0, 1, 2
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory, built):
-    if shutil.which("g++") is None:
-        pytest.skip("needs g++")
-    exe = str(tmp_path_factory.mktemp("temporal_motion") / "temporal_motion_check")
-    rocm_include = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(built.HIPCC))), "include")
-    cc = ["g++", "-std=c++17", "-Wall", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I" + rocm_include, "-I" + os.path.join(ROOT, "include"),
-          "-I" + CSRC, os.path.join(CSRC, "temporal_motion.cpp"), os.path.join(ROOT, "tests", "temporal_motion_check.cpp"), "-o", exe]
-    b = subprocess.run(cc + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True, timeout=600)
-    if b.returncode != 0 and ("asan" in b.stderr.lower() or "ubsan" in b.stderr.lower()):
-        b = subprocess.run(cc, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    return exe
+    return hostcheck.build(tmp_path_factory.mktemp("temporal_motion"), "temporal_motion_check", ["temporal_motion.cpp"], "temporal_motion_check.cpp")
 
 
 def test_worked_cases(checker):
-    p = subprocess.run([checker], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0, (p.stdout + p.stderr)[-4000:]
-    assert "temporal motion ok" in p.stdout
+    hostcheck.run(checker, ok="temporal motion ok")
 
 
 def rotation(rng):
@@ -122,8 +106,7 @@ def test_random_snapshots_against_float64(checker, tmp_path):
     with open(src, "w") as fh:
         for prev, now, what, sprev, snow, swhat in cases:
             write_case(fh, prev, now, sprev, snow)
-    p = subprocess.run([checker, str(src), str(out)], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0 and f"{len(cases)} cases" in p.stdout, (p.stdout + p.stderr)[-4000:]
+    hostcheck.run(checker, [src, out], ok=f"{len(cases)} cases")
     lines = iter(open(out).read().splitlines())
     worst = 0.0
     seen = set()

@@ -13,8 +13,8 @@ import pytest
 from ray_tracer_amd import engine, scenes
 from oracle import pyoracle
 import brute_force as bf
-from util import assert_hits_equal, cornell_scene, model_scene, seeded_rays
-from test_closest_hit_float64 import ON_SURFACE, _aimed_rays, _compare, _conditions, _corners_of
+from closest_hit_cases import ON_SURFACE, _aimed_rays, _compare, _conditions, _corners_of
+from util import _deformed_bunny, _mesh_points, _mesh_triangles, _smooth, assert_hits_equal, cornell_scene, model_scene, same_bits, seeded_rays
 
 pytestmark = pytest.mark.gpu
 
@@ -80,40 +80,6 @@ def _widest_level(scene, obj):
     return widest
 
 
-def _mesh_triangles(scene, obj):
-    """The point indices (n, 3) of the triangles of the mesh of object `obj`."""
-    a = scene.numpy()
-    nodes = a["bvhNodes"].view(np.uint32).reshape(-1, 8)
-    tri = a["triangles"].view(np.uint32).reshape(-1, 12)[:, :3]
-    root = int(a["objects"].view(np.uint32).reshape(-1, 20)[obj, 17])
-    stack, used = [root], []
-    while stack:
-        n = stack.pop()
-        index, count = int(nodes[n, 6]), int(nodes[n, 7])
-        if count:
-            used.append(tri[index:index + count])
-        else:
-            stack += [index, index + 1]
-    return np.concatenate(used)
-
-
-def _mesh_points(scene, obj):
-    """The point indices the mesh of object `obj` uses, as a range [lo, hi)."""
-    used = _mesh_triangles(scene, obj)
-    return int(used.min()), int(used.max()) + 1
-
-
-def _smooth(points, seed, amp):
-    """A seeded smooth displacement of positions (and a tilt of the normals and a shift of the uvs)."""
-    rng = np.random.default_rng(seed)
-    k, ph = rng.uniform(2.0, 7.0, (3, 3)), rng.uniform(0, 6.28, 3)
-    p = points.copy()
-    p[:, :3] += (amp * np.sin(points[:, :3].astype(np.float64) @ k.T + ph)).astype(np.float32)
-    p[:, 4:7] += (0.2 * np.cos(points[:, :3].astype(np.float64) @ k + ph)).astype(np.float32)
-    p[:, 3] += np.float32(0.01)
-    return p
-
-
 def _updates(scene, deformation, seed):
     """The (points, first) updates of a deformation, and the object whose mesh it grows (or None)."""
     pts = scene.points()
@@ -174,10 +140,6 @@ def _everything(r, o, d):
     return out
 
 
-def _same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
 @pytest.mark.parametrize("deformation", DEFORMATIONS)
 @pytest.mark.parametrize("name", SCENES)
 def test_refit_tables_equal_a_fresh_upload_and_the_oracle(renderer, name, deformation):
@@ -210,20 +172,13 @@ def test_refit_tables_equal_a_fresh_upload_and_the_oracle(renderer, name, deform
     assert_hits_equal(A["hits"], ref_hits)
     ref_img, ref_cnt = pyoracle.render(scene, _pc(), W, H)
     for cfg, fa, fb, ca, cb in zip(CONFIGS, A["frames"], B["frames"], A["counters"], B["counters"]):
-        assert _same_bits(fa, fb), f"{cfg}: the frame after update_points differs from a fresh upload's"
-        assert _same_bits(fa, ref_img), f"{cfg}: the frame after update_points differs from the oracle's"
+        assert same_bits(fa, fb), f"{cfg}: the frame after update_points differs from a fresh upload's"
+        assert same_bits(fa, ref_img), f"{cfg}: the frame after update_points differs from the oracle's"
         assert ca == cb, f"{cfg}: counters {ca} against a fresh upload's {cb}"
         for k in COUNTERS:
             assert ca[k] == ref_cnt[k], f"{cfg}: counter {k}: {ca[k]}, oracle {ref_cnt[k]}"
     for k in A["aovs"]:
-        assert _same_bits(A["aovs"][k], B["aovs"][k]), f"render_aovs plane {k}"
-
-
-# ---------------------------------------------------------------------------------------------------------------- float64
-def _deformed_bunny():
-    s = model_scene("bunny.obj")
-    lo, hi = _mesh_points(s, s.counts()["objects"] - 1)
-    return s, _smooth(s.points()[lo:hi], 31, 0.06), lo
+        assert same_bits(A["aovs"][k], B["aovs"][k]), f"render_aovs plane {k}"
 
 
 def _float64_case(scene):
@@ -263,11 +218,11 @@ def test_noop_updates_leave_frames_bit_equal(renderer):
     img0, cnt0 = _frame(renderer)
     renderer.update_points(scene.points(), 0)                        # the original points again: every box refit to what it was
     img1, cnt1 = _frame(renderer)
-    assert _same_bits(img0, img1) and cnt0 == cnt1
+    assert same_bits(img0, img1) and cnt0 == cnt1
     renderer.update_points(np.zeros((0, 8), np.float32), 5)          # count = 0
     renderer._check(renderer._l.rt_update_points(renderer._h, None, 0, 0), "rt_update_points")
     img2, cnt2 = _frame(renderer)
-    assert _same_bits(img0, img2) and cnt0 == cnt2
+    assert same_bits(img0, img2) and cnt0 == cnt2
 
 
 def test_refusals_through_the_abi(renderer):
@@ -288,7 +243,7 @@ def test_refusals_through_the_abi(renderer):
     with pytest.raises(engine.RtError, match=f"the position of point {n // 2} is not finite"):
         renderer.update_points(bad, 0)
     img1, cnt1 = _frame(renderer)
-    assert _same_bits(img0, img1) and cnt0 == cnt1, "a refused update changed the next frame"
+    assert same_bits(img0, img1) and cnt0 == cnt1, "a refused update changed the next frame"
     with pytest.raises(engine.RtError, match="is not finite"):
         scene.update_points(bad, 0)
     renderer.upload_scene(scene)                                     # a plain upload drops what the dynamic one kept
@@ -328,10 +283,10 @@ def test_a_refused_dynamic_upload_leaves_the_context_as_it_was(renderer):
         renderer.upload_scene(shared, dynamic=True)
     renderer._counts = scene.counts()
     img1, cnt1 = _frame(renderer)
-    assert _same_bits(img0, img1) and cnt0 == cnt1
+    assert same_bits(img0, img1) and cnt0 == cnt1
     renderer.update_points(scene.points(), 0)                        # and it is still the dynamic scene it was
     img2, cnt2 = _frame(renderer)
-    assert _same_bits(img0, img2) and cnt0 == cnt2
+    assert same_bits(img0, img2) and cnt0 == cnt2
 
 
 # ---------------------------------------------------------------------------------------------------------------- temporal

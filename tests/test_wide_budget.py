@@ -5,25 +5,19 @@ Two work-groups of 768 threads per CU are 24 waves, six per SIMD. That holds onl
 VGPRs (allocated in eights) without scratch, at most 112 SGPRs (a SIMD's 800 hold floor(800 / (ceil(sgpr / 16) * 16 + 16)) waves)
 and a work-group at most half of a CU's 160 KiB of LDS. A compiler or a source change that takes one of them away costs the sixth
 wave, or the second work-group, silently: it shows here, on the CPU."""
-import importlib.util
 import os
 import re
 
 import pytest
 
+from util import code_object
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _code_object():
-    spec = importlib.util.spec_from_file_location("code_object", os.path.join(ROOT, "tools", "code_object.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
 
 
 @pytest.fixture(scope="module")
 def wide(built):
-    found = {n: k for n, k in _code_object().kernels(built.LIB).items() if re.match(r"void k_trace_pw_wide<", n)}
+    found = {n: k for n, k in code_object().kernels(built.LIB).items() if re.match(r"void k_trace_pw_wide<", n)}
     assert list(found) == ["void k_trace_pw_wide<20, 192, 768>"], f"the wide kernels in the library: {sorted(found)}"
     return found["void k_trace_pw_wide<20, 192, 768>"]
 
@@ -45,6 +39,6 @@ def test_two_wide_groups_fit_a_cu(wide):
 
 def test_wide_kernel_keeps_its_packed_slab_test(built):
     """box_intersect_pair is packed by hand: six v_pk_add_f32 and six v_pk_mul_f32 per copy of the interior step."""
-    ops = _code_object().disassembly(built.LIB)["_Z15k_trace_pw_wideILi20ELi192ELi768EEv8DevScene9PathState11TracePwArgs"]
+    ops = code_object().disassembly(built.LIB)["_Z15k_trace_pw_wideILi20ELi192ELi768EEv8DevScene9PathState11TracePwArgs"]
     packed = sum(op in ("v_pk_add_f32", "v_pk_mul_f32") for op in ops)
     assert packed > 0 and packed % 12 == 0, f"{packed} packed fp32 instructions in the wide kernel"

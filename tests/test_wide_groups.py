@@ -13,7 +13,7 @@ import pytest
 from oracle import pyoracle
 from ray_tracer_amd import engine, scenes
 
-from test_instantiations import _same, build_scene, soup
+from instantiation_scenes import _same, build_scene, soup
 
 pytestmark = pytest.mark.gpu
 

@@ -1,7 +1,9 @@
 """Shared helpers for the parity tests."""
+import contextlib
+
 import numpy as np
 
-from ray_tracer_amd import engine, scenes
+from ray_tracer_amd import devmem, engine, scenes
 
 
 def cornell_scene(spheres=True):
@@ -33,14 +35,46 @@ def seeded_rays(n, seed, box=1.2):
     return o, d.astype(np.float32)
 
 
+def bits(a):
+    """An array as uint32 words: what bit-for-bit comparisons are taken on (NaNs and signed zeros compare by their bits)."""
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def same_bits(a, b):
+    """Whether two arrays (of any dtype) have one dtype, one shape and the same bytes."""
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def assert_same_bits(a, b, what="arrays"):
+    assert a.dtype == b.dtype and a.shape == b.shape, f"{what}: {a.dtype}{a.shape} against {b.dtype}{b.shape}"
+    if not same_bits(a, b):
+        x, y = (bits(a), bits(b)) if a.dtype == np.float32 else (a, b)
+        raise AssertionError(f"{what} differs at {np.argwhere(x != y)[:5].tolist()}")
+
+
 def assert_hits_equal(a, b):
     """Two RtHit dict-of-arrays must agree bit for bit."""
     for k in a:
-        x, y = a[k], b[k]
-        if x.dtype == np.float32:
-            assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), f"field {k} differs at {np.argwhere(x.view(np.uint32) != y.view(np.uint32))[:5].tolist()}"
-        else:
-            assert np.array_equal(x, y), f"field {k} differs at {np.argwhere(x != y)[:5].tolist()}"
+        assert_same_bits(a[k], b[k], f"field {k}")
+
+
+def code_object():
+    """tools/code_object.py (what the library's gfx950 code object says about its kernels) as a module."""
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("code_object", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "code_object.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def kernel_instantiations(names):
+    """The instantiations in the library of the kernel templates `names` (a regular expression), read from its symbol table."""
+    import re
+    import subprocess
+    from ray_tracer_amd import _capi
+    out = subprocess.run(["nm", "-C", _capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    return set(re.findall(rf"__device_stub__({names}<[^>]*>)", out))
 
 
 class EditedScene:
@@ -116,3 +150,124 @@ def random_emitter_scene(seed):
     W, H = 80, 60
     pc = engine.push_constants(W, H, singleRender=1, sampleLimit=2, bounceLimit=int(rng.integers(2, 9)), environmentOn=bool(seed % 2))
     return s, pc, W, H
+
+
+def _mesh_triangles(scene, obj):
+    """The point indices (n, 3) of the triangles of the mesh of object `obj`."""
+    a = scene.numpy()
+    nodes = a["bvhNodes"].view(np.uint32).reshape(-1, 8)
+    tri = a["triangles"].view(np.uint32).reshape(-1, 12)[:, :3]
+    root = int(a["objects"].view(np.uint32).reshape(-1, 20)[obj, 17])
+    stack, used = [root], []
+    while stack:
+        n = stack.pop()
+        index, count = int(nodes[n, 6]), int(nodes[n, 7])
+        if count:
+            used.append(tri[index:index + count])
+        else:
+            stack += [index, index + 1]
+    return np.concatenate(used)
+
+
+def _mesh_points(scene, obj):
+    """The point indices the mesh of object `obj` uses, as a range [lo, hi)."""
+    used = _mesh_triangles(scene, obj)
+    return int(used.min()), int(used.max()) + 1
+
+
+def _smooth(points, seed, amp):
+    """A seeded smooth displacement of positions (and a tilt of the normals and a shift of the uvs)."""
+    rng = np.random.default_rng(seed)
+    k, ph = rng.uniform(2.0, 7.0, (3, 3)), rng.uniform(0, 6.28, 3)
+    p = points.copy()
+    p[:, :3] += (amp * np.sin(points[:, :3].astype(np.float64) @ k.T + ph)).astype(np.float32)
+    p[:, 4:7] += (0.2 * np.cos(points[:, :3].astype(np.float64) @ k + ph)).astype(np.float32)
+    p[:, 3] += np.float32(0.01)
+    return p
+
+
+# ---------------------------------------------------------------------------------------------------------------- float64
+def _deformed_bunny():
+    s = model_scene("bunny.obj")
+    lo, hi = _mesh_points(s, s.counts()["objects"] - 1)
+    return s, _smooth(s.points()[lo:hi], 31, 0.06), lo
+
+
+def emitters_scene():
+    """Cornell with an emissive sphere, glass right under the ceiling light and a second light coplanar with the ceiling (also the
+    "emitters" case of tests/test_paths_float64.py)."""
+    s = cornell_scene(True)
+    glow = s.add_material(engine.default_material(albedo=(0.1, 0.1, 0.1), emissionColor=(0.3, 0.6, 1.0), emissionStrength=1.2))
+    s.set_sphere(3, (-0.6, -0.9, 0.4), 0.2, glow)
+    s.set_sphere(4, (0.1, -1.3, 0.0), 0.25, 5)       # glass right under the ceiling light
+    quad = np.array([[[-0.2, -1.5, 0.5], [0.2, -1.5, 0.5], [0.2, -1.5, 0.8]], [[-0.2, -1.5, 0.5], [0.2, -1.5, 0.8], [-0.2, -1.5, 0.8]]], np.float32)
+    nq = np.zeros_like(quad); nq[..., 1] = 1
+    s.add_mesh("coplanar_light", quad, nq, engine.placement(), glow)   # in the plane of the ceiling: equal distances
+    return s
+
+
+@contextlib.contextmanager
+def device_buffers(names, nbytes, fill=None):
+    """name -> a devmem.DeviceBuffer of `nbytes` the test owns, every byte set to `fill` first (so that what the library did not
+    write shows) and that fill waited for; freed when the block ends."""
+    bufs = {}
+    try:
+        for k in names:
+            bufs[k] = devmem.DeviceBuffer(nbytes)
+            if fill is not None:
+                bufs[k].fill(fill)
+        devmem.synchronize()
+        yield bufs
+    finally:
+        for b in bufs.values():
+            b.free()
+
+
+def to_device(renderer, name, a):
+    """The array in a named device buffer of the renderer's own (Renderer._device_buffer: kept and freed with it): its address.
+    renderer._owned[name] is the buffer, for reading it back."""
+    a = np.ascontiguousarray(a)
+    p = renderer._device_buffer(name, max(a.nbytes, 1))
+    renderer._owned[name].upload(a)
+    return p
+
+
+def progressive_frames(renderer, s, W, H, after_frame=None):
+    """Three progressive frames after a render_aovs() of the same image, with `after_frame(pc)` (a post pass, or nothing) run
+    behind each: the frames, the counters each one added, and the state of the launch policy at the end. A pass that leaves
+    rendering alone gives the same three with and without it."""
+    renderer.upload_scene(s)
+    renderer.clear_framebuffer()
+    pc = engine.push_constants(W, H, progressive=1, raysPerPixel=2)
+    renderer.render_aovs(pc, W, H)
+    frames, deltas = [], []
+    for k in range(3):
+        pc.frameCount = k
+        before = renderer.counters()
+        frames.append(renderer.render(pc, W, H))
+        after = renderer.counters()
+        deltas.append({n: after[n] - before[n] for n in after})
+        if after_frame:
+            after_frame(pc)
+    renderer.sync()
+    return frames, deltas, (renderer.ray_cost(), renderer.last_pipeline(), renderer.last_parts(), renderer.last_kernel())
+
+
+def frames_between_passes(renderer, s, W, H, passes=None):
+    """Three progressive frames with `passes(other, W + 24, H + 16)` run before each: side passes of another camera over a bigger
+    image, so that the path state grows. Returns what progressive_frames returns, without the kernel's name."""
+    renderer.upload_scene(s)
+    renderer.clear_framebuffer()
+    pc = engine.push_constants(W, H, progressive=1, raysPerPixel=2)
+    other = engine.push_constants(W + 24, H + 16, cameraAngles=(15.0, 40.0, 0.0), pos=(0.2, -0.6, -2.5))
+    frames, deltas = [], []
+    for k in range(3):
+        if passes:
+            passes(other, W + 24, H + 16)
+        pc.frameCount = k
+        before = renderer.counters()
+        frames.append(renderer.render(pc, W, H))
+        after = renderer.counters()
+        deltas.append({n: after[n] - before[n] for n in after})
+    renderer.sync()
+    return frames, deltas, (renderer.ray_cost(), renderer.last_pipeline(), renderer.last_parts())

@@ -10,19 +10,7 @@
 #include <string>
 
 #include "scene_layout.h"   // RT_MAP_*, RT_HOT_PAIRS
-
-static long g_checks = 0, g_failed = 0;
-#define CHECK(cond, ...)                                                        \
-    do {                                                                        \
-        g_checks++;                                                             \
-        if (!(cond)) {                                                          \
-            if (g_failed++ < 40) {                                              \
-                fprintf(stderr, "FAIL line %d: %s: ", __LINE__, #cond);         \
-                fprintf(stderr, __VA_ARGS__);                                   \
-                fprintf(stderr, "\n");                                          \
-            }                                                                   \
-        }                                                                       \
-    } while (0)
+#include "check.h"
 
 static DispatchFacts slots(uint32_t nPixels, uint32_t nFrames = 1) { DispatchFacts d; d.nPixels = nPixels; d.nFrames = nFrames; d.samples = 1; return d; }
 static Tuning tuned(const char* key, int value) {
@@ -155,10 +143,5 @@ int main() {
     check_wide_key();
     check_knob();
     check_wide_shape();
-    if (g_failed) {
-        fprintf(stderr, "%ld of %ld checks failed\n", g_failed, g_checks);
-        return 1;
-    }
-    printf("wide plan ok (%ld checks)\n", g_checks);
-    return 0;
+    return check_finish("wide plan ok");
 }

@@ -11,9 +11,8 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import ctypes as C  # noqa: E402
 
-from ray_tracer_amd import _capi, engine, scenes  # noqa: E402
+from ray_tracer_amd import devmem, engine, scenes  # noqa: E402
 
 runs = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "aov_timing.json")
@@ -21,18 +20,13 @@ CASES = [("sponza stand-in", lambda: scenes.sponza(0)[0], scenes.sponza_camera, 
          ("cornell + spheres", lambda: scenes.cornell(True)[0], engine.push_constants, 1728, 1117)]
 
 r = engine.Renderer(0)
-hip = C.CDLL(_capi.LIB_PATH)   # device buffers from the HIP runtime the library is bound to (dlsym through its handle)
-hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-hip.hipFree.argtypes = [C.c_void_p]
 rows = []
 for label, make, camera, W, H in CASES:
     r.upload_scene(make())
     pc = camera(W, H, singleRender=1, sampleLimit=8)
-    bufs = [C.c_void_p() for _ in range(6)]
-    for b in bufs:
-        assert hip.hipMalloc(C.byref(b), W * H * 16) == 0
-    frame = bufs[0].value
-    ptrs = {k: b.value for k, b in zip(engine.AOV_PLANES, bufs[1:])}
+    bufs = [devmem.DeviceBuffer(W * H * 16) for _ in range(6)]
+    frame = bufs[0].ptr
+    ptrs = {k: b.ptr for k, b in zip(engine.AOV_PLANES, bufs[1:])}
 
     def timed(fn):
         t = time.perf_counter()
@@ -63,7 +57,7 @@ for label, make, camera, W, H in CASES:
                frame_box_tests_per_ray=round(r.ray_cost(), 1))
     rows.append(row)
     for b in bufs:
-        hip.hipFree(b)
+        b.free()
     print(json.dumps(row), flush=True)
 r.close()
 with open(out, "w") as f:

@@ -16,7 +16,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ctypes as C  # noqa: E402
 
-from ray_tracer_amd import _capi, engine, scenes  # noqa: E402
+from ray_tracer_amd import _capi, devmem, engine, scenes  # noqa: E402
 
 runs = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "denoise_timing.json")
@@ -24,20 +24,15 @@ CASES = [("sponza stand-in", lambda: scenes.sponza(0)[0], scenes.sponza_camera, 
          ("cornell + spheres", lambda: scenes.cornell(True)[0], engine.push_constants, 1728, 1117)]
 
 r = engine.Renderer(0)
-hip = C.CDLL(_capi.LIB_PATH)   # device buffers from the HIP runtime the library is bound to (dlsym through its handle)
-hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-hip.hipFree.argtypes = [C.c_void_p]
 params = _capi.RtDenoiseParams()
 r._l.rt_denoise_params_default(C.byref(params))
 rows = []
 for label, make, camera, W, H in CASES:
     r.upload_scene(make())
     pc = camera(W, H, singleRender=1, sampleLimit=8)
-    bufs = [C.c_void_p() for _ in range(7)]
-    for b in bufs:
-        assert hip.hipMalloc(C.byref(b), W * H * 16) == 0
-    frame, dout = bufs[0].value, bufs[6].value
-    ptrs = {k: b.value for k, b in zip(engine.AOV_PLANES, bufs[1:6])}
+    bufs = [devmem.DeviceBuffer(W * H * 16) for _ in range(7)]
+    frame, dout = bufs[0].ptr, bufs[6].ptr
+    ptrs = {k: b.ptr for k, b in zip(engine.AOV_PLANES, bufs[1:6])}
     planes = _capi.RtAovBuffers(**ptrs)
 
     def timed(fn):
@@ -71,10 +66,11 @@ for label, make, camera, W, H in CASES:
                denoise_share_of_frame=round(med(td) / med(tf), 4), denoise_mpixels_per_s=round(W * H / med(td) / 1e3, 1))
     rows.append(row)
     for b in bufs:
-        hip.hipFree(b)
+        b.free()
     print(json.dumps(row), flush=True)
 
-from test_denoise import _checker_scene, quality  # noqa: E402
+from denoise_float64 import _checker_scene  # noqa: E402
+from test_denoise import quality  # noqa: E402
 
 W, H = 160, 120
 s, _, tex = _checker_scene()

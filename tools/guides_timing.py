@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import ctypes as C  # noqa: E402
 
-from ray_tracer_amd import _capi, engine, scenes  # noqa: E402
+from ray_tracer_amd import _capi, devmem, engine, scenes  # noqa: E402
 
 runs = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "guides_timing.json")
@@ -24,19 +24,14 @@ CASES = [("sponza stand-in", lambda: scenes.sponza(0)[0], scenes.sponza_camera, 
 BOUNCES = (0, 1, 4, 8)
 
 r = engine.Renderer(0)
-hip = C.CDLL(_capi.LIB_PATH)   # device buffers from the HIP runtime the library is bound to (dlsym through its handle)
-hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-hip.hipFree.argtypes = [C.c_void_p]
 rows = []
 for label, make, camera, W, H in CASES:
     r.upload_scene(make())
     pc = r.fill_counts(camera(W, H))
-    bufs = [C.c_void_p() for _ in range(10)]
-    for b in bufs:
-        assert hip.hipMalloc(C.byref(b), W * H * 16) == 0
-    ptrs = {k: b.value for k, b in zip(engine.AOV_PLANES, bufs[:5])}
+    bufs = [devmem.DeviceBuffer(W * H * 16) for _ in range(10)]
+    ptrs = {k: b.ptr for k, b in zip(engine.AOV_PLANES, bufs[:5])}
     guides = _capi.RtAovBuffers(**ptrs)
-    first = _capi.RtAovBuffers(**{k: b.value for k, b in zip(engine.AOV_PLANES, bufs[5:])})
+    first = _capi.RtAovBuffers(**{k: b.ptr for k, b in zip(engine.AOV_PLANES, bufs[5:])})
 
     def timed(fn):
         t = time.perf_counter()
@@ -75,7 +70,7 @@ for label, make, camera, W, H in CASES:
     row["guides_8_over_aov"] = round(med(tg[(8, False)]) / med(ta), 4)
     rows.append(row)
     for b in bufs:
-        hip.hipFree(b)
+        b.free()
     print(json.dumps(row), flush=True)
 r.close()
 with open(out, "w") as f:

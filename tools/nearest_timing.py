@@ -18,7 +18,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ray_tracer_amd import _capi, engine, scenes  # noqa: E402
+from ray_tracer_amd import _capi, devmem, engine, scenes  # noqa: E402
 
 runs = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "nearest_timing.json")
@@ -27,17 +27,15 @@ N = W * H
 G = 128
 
 r = engine.Renderer(0)
-hip = C.CDLL(_capi.LIB_PATH)   # device buffers from the HIP runtime the library is bound to (dlsym through its handle)
-hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+BUFS = {}   # device address -> the devmem.DeviceBuffer that owns it
 
 
 def device(nbytes, host=None):
-    p = C.c_void_p()
-    assert hip.hipMalloc(C.byref(p), nbytes) == 0
+    b = devmem.DeviceBuffer(nbytes)
     if host is not None:
-        assert hip.hipMemcpy(p, host.ctypes.data, host.nbytes, 1) == 0   # hipMemcpyHostToDevice
-    return p.value
+        b.upload(host)
+    BUFS[b.ptr] = b
+    return b.ptr
 
 
 def timed(fn):
@@ -53,7 +51,7 @@ ptrs = {k: device(N * 16) for k in engine.AOV_PLANES}
 r.render_aovs(pc, W, H, out_ptrs=ptrs)
 planes = {k: np.empty((N, 4), np.float32) for k in ("position", "normalDepth", "rayDir")}
 for k, a in planes.items():
-    assert hip.hipMemcpy(a.ctypes.data, ptrs[k], a.nbytes, 2) == 0   # hipMemcpyDeviceToHost
+    BUFS[ptrs[k]].download(into=a)
 offset = np.ascontiguousarray(planes["position"][:, :3] + np.float32(0.05) * planes["normalDepth"][:, :3])
 pos = scene.numpy()["triPoints"].view(np.float32).reshape(-1, 8)[:, :3]
 lo, hi = pos.min(axis=0), pos.max(axis=0)

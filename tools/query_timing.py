@@ -19,7 +19,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ray_tracer_amd import _capi, engine, scenes  # noqa: E402
+from ray_tracer_amd import _capi, devmem, engine, scenes  # noqa: E402
 
 runs = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "query_timing.json")
@@ -29,18 +29,15 @@ N = W * H
 
 r = engine.Renderer(0)
 have_queries = hasattr(r, "query_closest")
-hip = C.CDLL(_capi.LIB_PATH)   # device buffers from the HIP runtime the library is bound to (dlsym through its handle)
-hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-hip.hipFree.argtypes = [C.c_void_p]
+BUFS = {}   # device address -> the devmem.DeviceBuffer that owns it
 
 
 def device(nbytes, host=None):
-    p = C.c_void_p()
-    assert hip.hipMalloc(C.byref(p), nbytes) == 0
+    b = devmem.DeviceBuffer(nbytes)
     if host is not None:
-        assert hip.hipMemcpy(p, host.ctypes.data, host.nbytes, 1) == 0   # hipMemcpyHostToDevice
-    return p.value
+        b.upload(host)
+    BUFS[b.ptr] = b
+    return b.ptr
 
 
 def timed(fn):
@@ -59,7 +56,7 @@ kernels["aov"] = r.last_kernel()
 if have_queries:
     planes = {k: np.empty((N, 4), np.float32) for k in ("rayDir", "normalDepth")}
     for k, a in planes.items():
-        assert hip.hipMemcpy(a.ctypes.data, ptrs[k], a.nbytes, 2) == 0   # hipMemcpyDeviceToHost
+        BUFS[ptrs[k]].download(into=a)
     dirs = np.ascontiguousarray(planes["rayDir"][:, :3])
     origins = np.ascontiguousarray(np.tile(np.array(list(pc.camInfo.pos), np.float32), (N, 1)))
     half = np.ascontiguousarray(planes["normalDepth"][:, 3] * np.float32(0.5))
@@ -90,7 +87,7 @@ for k, v in ms.items():
 if have_queries:
     occ = np.empty(N, np.uint8)
     passes["occluded"]()
-    assert hip.hipMemcpy(occ.ctypes.data, d_occ, N, 2) == 0
+    BUFS[d_occ].download(into=occ)
     row["hit_share"] = round(float(occ.mean()), 4)
 if baseline:
     with open(baseline) as f:

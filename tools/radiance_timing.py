@@ -8,7 +8,6 @@ from what the entry point costs. Everything reads and writes device buffers (no 
 the enqueue and an rt_sync; two warm-ups of each, then `runs` of each, interleaved; median, min, max and the ratio of the medians.
 The three images are compared bit for bit before anything is timed.
 usage: tools/radiance_timing.py [runs] [out.json]   (default: 9, profiles/radiance_timing.json)"""
-import ctypes as C
 import json
 import os
 import statistics
@@ -22,7 +21,7 @@ import numpy as np  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from ray_tracer_amd import _capi, engine, scenes  # noqa: E402
+from ray_tracer_amd import devmem, engine, scenes  # noqa: E402
 
 runs = int(sys.argv[1]) if len(sys.argv) > 1 else 9
 out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "radiance_timing.json")
@@ -30,22 +29,20 @@ W, H, SAMPLES, BOUNCES = 1920, 1080, 8, 8
 N = W * H
 
 r = engine.Renderer(0)
-hip = C.CDLL(_capi.LIB_PATH)   # device buffers from the HIP runtime the library is bound to (dlsym through its handle)
-hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+BUFS = {}   # device address -> the devmem.DeviceBuffer that owns it
 
 
 def device(nbytes, host=None):
-    p = C.c_void_p()
-    assert hip.hipMalloc(C.byref(p), nbytes) == 0
+    b = devmem.DeviceBuffer(nbytes)
     if host is not None:
-        assert hip.hipMemcpy(p, host.ctypes.data, host.nbytes, 1) == 0   # hipMemcpyHostToDevice
-    return p.value
+        b.upload(host)
+    BUFS[b.ptr] = b
+    return b.ptr
 
 
 def host(ptr, shape, dtype=np.float32):
     a = np.empty(shape, dtype)
-    assert hip.hipMemcpy(a.ctypes.data, ptr, a.nbytes, 2) == 0   # hipMemcpyDeviceToHost
+    BUFS[ptr].download(into=a)
     return a
 
 

@@ -20,25 +20,22 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
-from ray_tracer_amd import _capi, engine, scenes  # noqa: E402
+from ray_tracer_amd import devmem, engine, scenes  # noqa: E402
 
 runs = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "sample_map_timing.json")
 W, H, S = 1920, 1080, 8
 
 r = engine.Renderer(0)
-hip = C.CDLL(_capi.LIB_PATH)   # device buffers from the HIP runtime the library is bound to (dlsym through its handle)
-hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-hip.hipFree.argtypes = [C.c_void_p]
+BUFS = {}   # device address -> the devmem.DeviceBuffer that owns it
 
 
 def device(nbytes, host=None):
-    p = C.c_void_p()
-    assert hip.hipMalloc(C.byref(p), nbytes) == 0
+    b = devmem.DeviceBuffer(nbytes)
     if host is not None:
-        assert hip.hipMemcpy(p, host.ctypes.data, nbytes, 1) == 0   # hipMemcpyHostToDevice
-    return p.value
+        b.upload(host)
+    BUFS[b.ptr] = b
+    return b.ptr
 
 
 def timed(call):
@@ -119,5 +116,5 @@ with open(out, "w") as f:
     json.dump(result, f, indent=1)
     f.write("\n")
 for p in [frame, d_mom, d_map] + list(d_maps.values()):
-    hip.hipFree(C.c_void_p(p))
+    BUFS.pop(p).free()
 r.close()

@@ -26,7 +26,7 @@ import ctypes as C  # noqa: E402
 
 import numpy as np  # noqa: E402
 
-from ray_tracer_amd import _capi, engine, scenes  # noqa: E402
+from ray_tracer_amd import _capi, devmem, engine, scenes  # noqa: E402
 
 MOVING = "--moving-object" in sys.argv
 argv = [a for a in sys.argv if a != "--moving-object"]
@@ -38,10 +38,6 @@ CASES = [("sponza stand-in", lambda: scenes.sponza(0)[0], scenes.sponza_camera, 
 BYTES_PER_PIXEL = (5 + 4 * 3 + 2 + 3) * 16
 
 r = engine.Renderer(0)
-hip = C.CDLL(_capi.LIB_PATH)   # device buffers from the HIP runtime the library is bound to (dlsym through its handle)
-hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-hip.hipFree.argtypes = [C.c_void_p]
 rows = []
 
 
@@ -53,11 +49,9 @@ def moving_object_mode():
         scene = make()
         e = EditedScene(scene)
         r.upload_scene(scene)
-        bufs = [C.c_void_p() for _ in range(8)]
-        for b in bufs:
-            assert hip.hipMalloc(C.byref(b), W * H * 16) == 0
-        frame, acc, mom = bufs[0].value, bufs[6].value, bufs[7].value
-        ptrs = {k: b.value for k, b in zip(engine.AOV_PLANES, bufs[1:6])}
+        bufs = [devmem.DeviceBuffer(W * H * 16) for _ in range(8)]
+        frame, acc, mom = bufs[0].ptr, bufs[6].ptr, bufs[7].ptr
+        ptrs = {k: b.ptr for k, b in zip(engine.AOV_PLANES, bufs[1:6])}
         planes = _capi.RtAovBuffers(**ptrs)
         state = dict(k=0, edits=0)
 
@@ -86,7 +80,7 @@ def moving_object_mode():
         target, x0 = ("sphere", 2), 0.0
         frame_of(False)
         ids = np.empty((H, W, 4), np.uint32)
-        assert hip.hipMemcpy(ids.ctypes.data, ptrs["ids"], W * H * 16, 2) == 0   # hipMemcpyDeviceToHost
+        bufs[5].download(into=ids)   # (the ids plane)
         if label.startswith("sponza"):
             mesh = ids[..., 0][(ids[..., 3] & 3) == 1]
             target = ("object", int(np.bincount(mesh).argmax()))
@@ -104,8 +98,8 @@ def moving_object_mode():
             assert not any(st.values()), st
             t_static.append(ms)
         m = np.empty((H, W, 4), np.float32)
-        assert hip.hipMemcpy(m.ctypes.data, mom, W * H * 16, 2) == 0
-        assert hip.hipMemcpy(ids.ctypes.data, ptrs["ids"], W * H * 16, 2) == 0
+        bufs[7].download(into=m)
+        bufs[5].download(into=ids)
         N = m[..., 3]
         on_target = (ids[..., 0] == target[1]) & ((ids[..., 3] & 3) == (1 if target[0] == "object" else 3))
         med = statistics.median
@@ -118,7 +112,7 @@ def moving_object_mode():
                    history_share_of_filtered=round(float((N > 1).sum() / max((N > 0).sum(), 1)), 4))
         rows.append(row)
         for b in bufs:
-            hip.hipFree(b)
+            b.free()
         print(json.dumps(row), flush=True)
     r.temporal_track_motion(False)
     r.close()
@@ -132,11 +126,9 @@ if MOVING:
     sys.exit(0)
 for label, make, camera, angles, W, H in CASES:
     r.upload_scene(make())
-    bufs = [C.c_void_p() for _ in range(9)]
-    for b in bufs:
-        assert hip.hipMalloc(C.byref(b), W * H * 16) == 0
-    frame, acc, mom, dout = bufs[0].value, bufs[6].value, bufs[7].value, bufs[8].value
-    ptrs = {k: b.value for k, b in zip(engine.AOV_PLANES, bufs[1:6])}
+    bufs = [devmem.DeviceBuffer(W * H * 16) for _ in range(9)]
+    frame, acc, mom, dout = bufs[0].ptr, bufs[6].ptr, bufs[7].ptr, bufs[8].ptr
+    ptrs = {k: b.ptr for k, b in zip(engine.AOV_PLANES, bufs[1:6])}
     planes = _capi.RtAovBuffers(**ptrs)
     state = dict(k=0, pc=None)
 
@@ -171,7 +163,7 @@ for label, make, camera, angles, W, H in CASES:
             ts.append(timed(fn))
     med = statistics.median
     m = np.empty((H, W, 4), np.float32)
-    assert hip.hipMemcpy(m.ctypes.data, mom, W * H * 16, 2) == 0   # hipMemcpyDeviceToHost
+    bufs[7].download(into=m)
     N = m[..., 3]
     row = dict(scene=label, width=W, height=H, spp=1, yaw_deg_per_frame=0.5, runs=runs,
                frame_ms=round(med(t[0]), 3), frame_ms_min=round(min(t[0]), 3), frame_pipeline=r.last_pipeline(),
@@ -184,7 +176,7 @@ for label, make, camera, angles, W, H in CASES:
                longest_history=float(N.max()))
     rows.append(row)
     for b in bufs:
-        hip.hipFree(b)
+        b.free()
     print(json.dumps(row), flush=True)
 
 from test_temporal import quality  # noqa: E402
