@@ -578,6 +578,63 @@ int  rt_query_nearest(rt_ctx* ctx, const RtPointBatch* d_points, RtNearest* d_ou
 int  rt_query_nearest_host(rt_ctx* ctx, const RtPointBatch* points, RtNearest* out);
 int  rt_nearest_exhaustive_host(const RtSceneArrays* scene, const RtPointBatch* points, RtNearest* out);
 
+/* Signed point queries ("Signed point queries"; include/rt_point_side.h states the rule, both sides compile it): the
+ * record of rt_query_nearest, bit for bit, and one byte side[i]: +1 outside, -1 inside, 0 unknown or nothing found.
+ *  - A sphere: l = |q - c| as rt_point_sphere computes it: +1 when l > r, -1 when l < r, 0 when l == r.
+ *  - A triangle: relative to the closed COMPONENT the reported triangle belongs to: the triangles of one mesh connected through
+ *    shared edges, after the mesh's points are welded by equal position (equal float values: -0 == +0, NaN welds with nothing).
+ *    A component is signable when every edge of it is shared by exactly two non-degenerate triangles, it is orientable and its
+ *    signed volume in object space is not zero. Orientation is repaired, never the geometry: a walk over the edges winds each
+ *    signable component consistently and then so that its volume is positive (normals outward); a triangle whose stored winding
+ *    disagrees carries a FLIP bit. Cavities (inner shells) are not modelled, overlapping solids are not a union: the sign is
+ *    relative to the nearest component alone.
+ *  - side = sign(dot(q - p, N)) x the object's orientation (+1, or -1 when det(fwd 3x3) < 0), p = rt_bary_point(a, b, c, u, v),
+ *    N the angle-weighted pseudo-normal (Baerentzen and Aanaes) of the feature p lies on (rt_point_triangle_feature): the face's
+ *    normal, the sum of the two unit face normals at an edge, the sum of corner angle x unit face normal over the fan of a vertex;
+ *    normals and angles from the world corners rt_xform_point(fwd, v) in fp32, as the nearest kernel places them.
+ *  - 0 for: a component that is not signable (open quads, non-manifold or non-orientable meshes); a degenerate triangle; a vertex
+ *    whose fan is not one closed cycle of at most RT_SIDE_MAX_FAN triangles; a matrix with a zero or non-finite determinant;
+ *    a pseudo-normal that is not finite; a dot product of exactly 0.
+ * rt_scene_topology: per object (the first nObjects) the statistics of its mesh's table and its orientation; no ctx, no GPU.
+ * -1: a NULL argument, 2^30 triangles or more, or arrays that index out of range.
+ * rt_nearest_side_host: the rule applied to GIVEN records in a plain loop, no ctx, no GPU: fed rt_query_nearest_signed's own
+ * records it reproduces its side byte for byte (the side is a function of the point and the reported record alone). -1: a NULL
+ * argument with n > 0, n >= 2^30, a record or arrays that index out of range.
+ * rt_upload_topology: builds the table and the per-object orientations from the host arrays of the uploaded scene and uploads
+ * them; explicit, so rt_upload_scene keeps its cost. A later rt_upload_scene or rt_upload_scene_dynamic drops them.
+ * rt_update_points keeps the table (the topology is kept by contract: the caller keeps coincident points coincident);
+ * rt_update_objects keeps it and refreshes the orientations. Refused: before rt_upload_scene; 2^30 triangles or more.
+ * rt_query_nearest_signed: rt_query_nearest, then the side pass (k_nearest_side, one lane per point) on the same stream;
+ * asynchronous as rt_query_nearest is; d_side is n bytes of device memory. rt_last_kernel names k_nearest_side<256>. The pass adds
+ * what rt_query_nearest adds to the AOV passes' counter block and, in its `segments` field (which no ray or point query writes
+ * and the ray-cost measurement never reads), the points it gave a sign other than 0. It changes nothing a later render or query
+ * produces. Refused with a message, nothing written, in this order: no uploaded scene; "no topology uploaded"; "topology does not
+ * match the uploaded scene" (the object, triangle or node counts differ); a NULL batch; points, the output or side NULL with
+ * n > 0; n >= 2^30. n == 0 succeeds and does nothing. rt_query_nearest_signed_host takes host arrays and blocks. */
+/* (RT_SIDE_MAX_FAN is 256: include/rt_point_side.h) */
+typedef struct RtMeshTopology {
+    uint32_t triangles;            /* of the object's mesh */
+    uint32_t weldedVertices;       /* distinct positions among the points its triangles use */
+    uint32_t components;           /* edge-connected sets of non-degenerate triangles */
+    uint32_t signableComponents;
+    uint32_t signableTriangles;
+    uint32_t boundaryEdges;        /* edges with one triangle */
+    uint32_t nonManifoldEdges;     /* edges with three or more */
+    uint32_t flippedTriangles;     /* FLIP bits among the signable triangles */
+    uint32_t degenerateTriangles;
+    int32_t orientation;           /* +1, -1, or 0: the sign of det(transformMatrix 3x3); 0 when it is zero or not finite */
+} RtMeshTopology;
+int  rt_scene_topology(const RtSceneArrays* scene, RtMeshTopology* out, uint32_t nObjects);
+int  rt_nearest_side_host(const RtSceneArrays* scene, const RtPointBatch* points, const RtNearest* recs, int8_t* side);
+/* the same loop, and beside side what the rule met (either array may be NULL): feature[i], the region code of
+ * rt_point_triangle_feature (0 face, 1-3 vertices a b c, 4-6 edges ab ac bc; 255: a sphere, nothing found, or a triangle the rule
+ * left unsigned before classifying it), and fan[i], the triangles walked around a vertex (0 otherwise). For measurements. */
+int  rt_nearest_side_features_host(const RtSceneArrays* scene, const RtPointBatch* points, const RtNearest* recs, int8_t* side,
+                                   uint8_t* feature, uint16_t* fan);
+int  rt_upload_topology(rt_ctx* ctx, const RtSceneArrays* scene);
+int  rt_query_nearest_signed(rt_ctx* ctx, const RtPointBatch* d_points, RtNearest* d_out, int8_t* d_side);
+int  rt_query_nearest_signed_host(rt_ctx* ctx, const RtPointBatch* points, RtNearest* out, int8_t* side);
+
 /* Ambient occlusion from first-hit planes ("Ray queries", "Ambient-occlusion plane"). Record i of the planes with
  * ids.w & 1 shoots `samples` occlusion queries: origin position + (normal * 1) * 0.00001 (the next-ray origin of shading),
  * direction the shader's cosineHemisphereDir about normalDepth.xyz (raytrace.comp:405-424, the arithmetic of the diffuse branch of

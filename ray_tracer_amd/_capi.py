@@ -115,6 +115,11 @@ class RtNearest(C.Structure):
                 ("triIndex", C.c_uint32), ("uv", C.c_float * 2), ("point", C.c_float * 3), ("_pad", C.c_uint32 * 2)]
 
 
+class RtMeshTopology(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("triangles", "weldedVertices", "components", "signableComponents", "signableTriangles", "boundaryEdges",
+                                          "nonManifoldEdges", "flippedTriangles", "degenerateTriangles")] + [("orientation", C.c_int32)]
+
+
 class RtRadianceParams(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("bounceLimit", C.c_uint32), ("progressive", C.c_uint32), ("frameCount", C.c_uint32)]
 
@@ -201,6 +206,12 @@ SYMBOLS = {
     "rt_query_nearest": (C.c_int, [_vp, _P(RtPointBatch), _vp]),
     "rt_query_nearest_host": (C.c_int, [_vp, _P(RtPointBatch), _vp]),
     "rt_nearest_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtPointBatch), _vp]),
+    "rt_scene_topology": (C.c_int, [_P(RtSceneArrays), _P(RtMeshTopology), C.c_uint32]),
+    "rt_nearest_side_host": (C.c_int, [_P(RtSceneArrays), _P(RtPointBatch), _vp, _vp]),
+    "rt_nearest_side_features_host": (C.c_int, [_P(RtSceneArrays), _P(RtPointBatch), _vp, _vp, _vp, _vp]),
+    "rt_upload_topology": (C.c_int, [_vp, _P(RtSceneArrays)]),
+    "rt_query_nearest_signed": (C.c_int, [_vp, _P(RtPointBatch), _vp, _vp]),
+    "rt_query_nearest_signed_host": (C.c_int, [_vp, _P(RtPointBatch), _vp, _vp]),
     "rt_radiance_params_default": (None, [_P(RtRadianceParams)]),
     "rt_query_radiance": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),
     "rt_query_radiance_host": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),

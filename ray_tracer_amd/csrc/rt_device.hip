@@ -15,7 +15,9 @@
 #include "radiance_queries.h"   // ... and for the radiance queries: their checks, pieces, byte counts and seed
 #include "host_staging.h"       // ... and for every _host form: where its arrays lie in the staging buffer
 #include "rt_nearest.hip.h"     // the kernel of the point queries; point_queries.h: their checks, the arithmetic of a batch, the pruning table
+#include "rt_nearest_side.hip.h"  // the side pass of the signed point queries; mesh_topology.h: its table, checks and host form
 #include "point_queries.h"
+#include "mesh_topology.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -120,6 +122,13 @@ struct rt_ctx {
     // rt_render_ao(..., d_ao = NULL) with its pixel count (0: never written)
     DevBuf queryQueueBuf, aoCountBuf, aoBuf;
     DevBuf objNearBuf;      // point queries: the per-object pruning table (layout_nearest), which follows the object tables (set_objects)
+    // signed point queries: the topology table and the per-object orientations (rt_upload_topology), with the counts of the scene
+    // they were made for. A scene upload drops them; set_objects refreshes the orientations beside objNearBuf
+    struct Topology {
+        bool on = false;
+        TopologyCounts counts;
+        DevBuf rows, orient;
+    } topo;
     size_t aoPixels = 0;
     DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
     // the denoiser (rt_denoise): its work planes and the ctx-owned output
@@ -625,6 +634,11 @@ int set_objects(rt_ctx* c, const ObjectLayout& l, const RenderObject* o, uint32_
     if ((rc = upload_table(c, c->objCostBuf, l.cost, c->sc.objCost))) return rc;
     const std::vector<float4> nearTable = layout_nearest(l, o, n, c->rootOf);
     if ((rc = upload(c, c->objNearBuf, nearTable.data(), nearTable.size() * sizeof(float4)))) return rc;
+    if (c->topo.on) {
+        const std::vector<int32_t> orient = layout_orientation(o, n);
+        if ((rc = upload(c, c->topo.orient, orient.data(), orient.size() * sizeof(int32_t)))) return rc;
+        c->topo.counts.objects = n;
+    }
     for (int k = 0; k <= RT_OBJTREE_LEVELS; k++) c->sc.objTreeOff[k] = l.treeOff[k];
     c->sc.objTreeLevels = l.treeLevels;
     c->sc.reachCount = l.reachCount;
@@ -797,6 +811,8 @@ int upload_scene(rt_ctx* c, const RtSceneArrays* s, bool dynamic) {
     c->sc.mapFlags = 0;
     c->sc.texCount = 0;  // texture slots belong to the scene's materials: rt_upload_textures follows a new scene
     release_dynamic(c);
+    c->topo.on = false;   // the table belongs to the scene it was made for: rt_upload_topology follows a new scene
+    c->topo.rows.release(); c->topo.orient.release();
     c->sceneBufs.clear();
     c->sceneBufs.resize(5);
     int rc;
@@ -1482,6 +1498,69 @@ int nearest_host(rt_ctx* c, const char* fn, const RtPointBatch* pts, RtNearest* 
 extern "C" {
 int rt_query_nearest(rt_ctx* c, const RtPointBatch* d_points, RtNearest* d_out) { return nearest_device(c, "rt_query_nearest", d_points, d_out); }
 int rt_query_nearest_host(rt_ctx* c, const RtPointBatch* points, RtNearest* out) { return nearest_host(c, "rt_query_nearest_host", points, out); }
+}  // extern "C"
+
+// ---- signed point queries (mesh_topology.h has the table, the checks and the host form; DESIGN.md, "Signed point queries")
+namespace {
+std::string signed_refusal(const rt_ctx* c, const char* fn, const RtPointBatch* pts, const void* out, const void* side) {
+    const TopologyCounts scene{c->sc.objectCount, c->sc.triCount, (uint32_t)c->rootOf.size()};   // (rootOf: one entry per node of the host arrays)
+    return check_signed_query(fn, c->sc.nodes != nullptr, c->topo.on, c->topo.counts, scene, pts, out, side);
+}
+
+// the search, then the side pass on what it wrote
+int signed_device(rt_ctx* c, const char* fn, const RtPointBatch* pts, RtNearest* d_out, int8_t* d_side) {
+    if (!c) return -1;
+    const std::string refusal = signed_refusal(c, fn, pts, d_out, d_side);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = pts->n;
+    if (n == 0) return 0;
+    int rc = nearest_device(c, fn, pts, d_out);
+    if (rc) return rc;
+    const SideArgs sa{pts->points, n, (const float4*)d_out, (const uint4*)c->topo.rows.p, (const int32_t*)c->topo.orient.p, d_side, (DevCounters*)c->aovCounterBuf.p};
+    hipLaunchKernelGGL(k_nearest_side<RT_BLOCK>, dim3(point_shape(n, RT_BLOCK).blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, sa);
+    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_nearest_side<%d>", (int)RT_BLOCK);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The host-memory form (staged): the point query's parts and one more, the bytes of side
+int signed_host(rt_ctx* c, const char* fn, const RtPointBatch* pts, RtNearest* out, int8_t* side) {
+    if (!c) return -1;
+    const std::string refusal = signed_refusal(c, fn, pts, out, side);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = pts->n;
+    if (n == 0) return 0;
+    const PointShape ps = point_shape(n, RT_BLOCK);
+    const StagePart parts[] = {{pts->points, nullptr, ps.pointBytes}, {pts->maxDist, nullptr, pts->maxDist ? ps.limitBytes : 0}, {nullptr, out, ps.outBytes}, {nullptr, side, (size_t)n}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtPointBatch dev{(const float*)d[0], (const float*)d[1], n};
+        return signed_device(c, fn, &dev, (RtNearest*)d[2], (int8_t*)d[3]);
+    });
+}
+}  // namespace
+
+extern "C" {
+int rt_upload_topology(rt_ctx* c, const RtSceneArrays* s) {
+    if (!c || !s) return -1;
+    if (!c->sc.nodes) return c->fail("rt_upload_topology before rt_upload_scene");
+    const TopologyTables t = build_topology("rt_upload_topology", *s);
+    if (!t.error.empty()) return c->fail(t.error);
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipStreamSynchronize(c->stream));   // a side pass in flight may be reading the tables this replaces
+    c->topo.on = false;
+    int rc;
+    if ((rc = upload(c, c->topo.rows, t.rows.data(), t.rows.size() * sizeof(uint4)))) return rc;
+    if ((rc = upload(c, c->topo.orient, t.orientation.data(), t.orientation.size() * sizeof(int32_t)))) return rc;
+    c->topo.counts = TopologyCounts{s->objectCount, s->triangleCount, s->bvhNodeCount};
+    c->topo.on = true;
+    return 0;
+}
+int rt_query_nearest_signed(rt_ctx* c, const RtPointBatch* d_points, RtNearest* d_out, int8_t* d_side) {
+    return signed_device(c, "rt_query_nearest_signed", d_points, d_out, d_side);
+}
+int rt_query_nearest_signed_host(rt_ctx* c, const RtPointBatch* points, RtNearest* out, int8_t* side) {
+    return signed_host(c, "rt_query_nearest_signed_host", points, out, side);
+}
 }  // extern "C"
 
 // ---- radiance queries (radiance_queries.h has the checks and the arithmetic; DESIGN.md, "Radiance queries")

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .devmem import DeviceBuffer, RtError, hip as _hip   # noqa: F401  (engine.RtError and engine._hip are where callers know them)
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtNearest, RtPointBatch, RtRadianceParams, RtRayBatch,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtMeshTopology, RtNearest, RtPointBatch, RtRadianceParams, RtRayBatch,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -218,6 +218,11 @@ class Scene:
             "objects": self._view(a.objects, a.objectCount, RenderObject).copy(),
             "bvhNodes": self._view(a.bvhNodes, a.bvhNodeCount, BVHNode).copy(),
         }
+
+    def topology(self):
+        """Per object, the statistics of its mesh's topology table and its orientation (rt_scene_topology; DESIGN.md, "Signed point
+        queries"; no GPU): a list of dicts with RtMeshTopology's fields."""
+        return scene_topology(self.arrays())
 
     def counts(self):
         a = self.arrays()
@@ -501,6 +506,39 @@ class Renderer:
         """Whether each ray hits anything nearer than its limit (rt_query_occluded): a bool array for numpy inputs, one byte per ray
         in `out` for device memory, as query_closest takes it."""
         return self._query("occluded", origins, dirs, tmax, n, out, sync)
+
+    def upload_topology(self, scene):
+        """Builds the topology table of `scene` (the one uploaded) and uploads it: what query_nearest_signed needs (rt_upload_topology).
+        upload_scene drops it again; update_points and update_objects keep it."""
+        a = scene.arrays()
+        self._check(self._l.rt_upload_topology(self._h, C.byref(a)), "rt_upload_topology")
+
+    def query_nearest_signed(self, points, max_dist=None, n=None, out=None, side=None, sync=True):
+        """query_nearest, and for each point on which side of the reported surface it lies (rt_query_nearest_signed; DESIGN.md, "Signed
+        point queries"): +1 outside, -1 inside, 0 unknown or nothing found. Host arrays come back as (RtNearest array, int8 array);
+        device memory (as query_nearest takes it) needs out= and side= (n bytes) and returns None."""
+        rec = C.sizeof(RtNearest)
+        if not _on_device(points):
+            p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+            t = None if max_dist is None else np.ascontiguousarray(max_dist, dtype=np.float32).reshape(-1)
+            if t is not None and t.shape[0] != p.shape[0]:
+                raise ValueError(f"max_dist has {t.shape[0]} limits for {p.shape[0]} points")
+            if out is not None or side is not None or not sync:
+                raise ValueError("out=, side= and sync=False go with device-pointer inputs")
+            batch = RtPointBatch(p.ctypes.data, t.ctypes.data if t is not None else None, p.shape[0])
+            res = (RtNearest * p.shape[0])()
+            sd = np.zeros(p.shape[0], np.int8)
+            self._check(self._l.rt_query_nearest_signed_host(self._h, C.byref(batch), C.addressof(res), sd.ctypes.data), "rt_query_nearest_signed_host")
+            return res, sd
+        n = _device_count(points, n, out)
+        if side is None:
+            raise ValueError("device-pointer inputs need side=: n bytes of device memory")
+        batch = RtPointBatch(_device_ptr(points, "points", 12 * n), None if max_dist is None else _device_ptr(max_dist, "max_dist", 4 * n), n)
+        self._check(self._l.rt_query_nearest_signed(self._h, C.byref(batch), C.c_void_p(_device_ptr(out, "out", rec * n, floats=False)),
+                                                    C.c_void_p(_device_ptr(side, "side", n, floats=False))), "rt_query_nearest_signed")
+        if sync:
+            self.sync()
+        return None
 
     def query_nearest(self, points, max_dist=None, n=None, out=None, sync=True):
         """The closest surface point of each of the caller's points within its limit (rt_query_nearest; DESIGN.md, "Point queries").
@@ -977,6 +1015,41 @@ def nearest_exhaustive(scene_arrays, points, max_dist=None):
     if _capi.lib().rt_nearest_exhaustive_host(C.byref(scene_arrays), C.byref(batch), C.addressof(res)) != 0:
         raise RtError("rt_nearest_exhaustive_host refused its arguments (NULL arrays, n >= 2^30, or indices out of range)")
     return (RtNearest * p.shape[0]).from_buffer(res) if p.shape[0] else (RtNearest * 0)()
+
+
+def scene_topology(scene_arrays):
+    """rt_scene_topology on Scene.arrays() (or an edited copy of them): one dict of RtMeshTopology's fields per object."""
+    n = scene_arrays.objectCount
+    st = (RtMeshTopology * max(n, 1))()
+    if _capi.lib().rt_scene_topology(C.byref(scene_arrays), st, n) != 0:
+        raise RtError("rt_scene_topology refused its arguments (2^30 triangles or more, or indices out of range)")
+    return [{k: getattr(st[i], k) for k, _ in RtMeshTopology._fields_} for i in range(n)]
+
+
+def nearest_side_host(scene_arrays, points, records, features=False):
+    """The side rule of the signed point queries applied to given records in a plain loop (rt_nearest_side_host; no GPU): `records`
+    is an RtNearest array (query_nearest's, query_nearest_signed's or nearest_exhaustive's) for `points`; returns an int8 array.
+    With `features` (rt_nearest_side_features_host): (side, feature uint8, fan uint16), the region code each point's rule met
+    (255: none) and the triangles it walked around a vertex."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    if len(records) != p.shape[0]:
+        raise ValueError(f"{len(records)} records for {p.shape[0]} points")
+    batch = RtPointBatch(p.ctypes.data, None, p.shape[0])
+    side, feat, fan = np.zeros(p.shape[0], np.int8), np.full(p.shape[0], 255, np.uint8), np.zeros(p.shape[0], np.uint16)
+    if p.shape[0] and _capi.lib().rt_nearest_side_features_host(C.byref(scene_arrays), C.byref(batch), C.addressof(records), side.ctypes.data,
+                                                                 feat.ctypes.data if features else None, fan.ctypes.data if features else None) != 0:
+        raise RtError("rt_nearest_side_host refused its arguments (n >= 2^30, or records or arrays that index out of range)")
+    return (side, feat, fan) if features else side
+
+
+def signed_distance(records, side):
+    """dst x side where side != 0; NaN where something was found and side == 0; RT_MISS_DST where nothing was found. `records`: an
+    RtNearest array or nearest_to_numpy's dict."""
+    r = records if isinstance(records, dict) else nearest_to_numpy(records)
+    s = np.asarray(side, np.int8)
+    d = r["dst"].astype(np.float32) * s.astype(np.float32)
+    d = np.where(s == 0, np.float32(np.nan), d)
+    return np.where(r["found"] == 0, np.float32(99999999.0), d).astype(np.float32)
 
 
 def load_textures(scene):
