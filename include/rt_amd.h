@@ -491,6 +491,49 @@ int  rt_query_occluded(rt_ctx* ctx, const RtRayBatch* d_rays, uint8_t* d_occlude
 int  rt_query_closest_host(rt_ctx* ctx, const RtRayBatch* rays, RtHit* hits);
 int  rt_query_occluded_host(rt_ctx* ctx, const RtRayBatch* rays, uint8_t* occluded);
 
+/* All-hit ray queries ("All-hit ray queries"; include/rt_ray_hits.h states the rule, both sides compile it): every
+ * surface a ray crosses below its limit, the first k of them in order, and how many there are.
+ * Contract. Ray i has the limit T (tmax[i]; RT_MISS_DST when tmax is NULL). Its candidate set C is what calculateIntersections
+ * (raytrace.comp:276-353) accepts when its bound is the constant T and never shrinks:
+ *  - spheres: sphereIntersection's arithmetic, both roots. The entry root (b - sqrtd) / a counts when it is >= 0: a front face, the
+ *    record the reference gives. The exit root (b + sqrtd) / a counts when it is >= 0: a back face, normal -normalize(p - c). Each
+ *    must also be < T. From inside a sphere only the exit exists, as in the reference.
+ *  - objects in index order, the ray taken to object space as ever, the object's root entered untested; a child box is entered
+ *    when boxIntersection(...) < T; a triangle is a candidate when triangleIntersection says didHit, dst < T and its alpha texel
+ *    does not cut it out (as in rendering).
+ * The bound is constant, so C does not depend on the order anything is visited in: not on the kernel, the stack, the knobs or the
+ * device's node numbering.
+ *  - d_counts[i] = |C|, exact whatever k is.
+ *  - d_hits[i * k .. i * k + k - 1]: the first min(k, |C|) members of C in ascending order of the key (dst as an fp32 compare;
+ *    spheres before triangles; the lower sphere or object index; the lower triHitIndex; a sphere's entry before its exit), then
+ *    the miss record (dst == RT_MISS_DST, everything else 0) in the remaining slots.
+ *  - A member's record is the RtHit rt_query_closest builds for that primitive (hitPoint and normal through the forward matrix,
+ *    bump maps as in rendering, materialIndex and frontFace as ever, boxTests and triTests 0): for the primitive rt_query_closest
+ *    reports it equals rt_query_closest's record byte for byte.
+ *  - The closest hit is always a member of C: every box the shrinking search enters passes d < best <= T.
+ *  - hits[0].dst <= closest.dst on every ray. It can be strictly less: a shrinking bound can prune a box whose fp32 distance
+ *    rounds above the dst of a triangle inside it, and the constant bound does not.
+ *  - k == 0 is allowed: counts only, d_hits may be NULL. A limit that is NaN or <= 0 gives count 0 and miss records without a
+ *    search. n == 0 succeeds and does nothing.
+ * rt_query_hits: the struct is read on the host, its arrays, d_hits and d_counts are device pointers, asynchronous on the ctx
+ * stream (the arrays stay valid and unchanged until the stream has passed it). rt_query_hits_host takes host arrays, stages them
+ * through a ctx buffer and blocks. One lane per ray, no path state: the search (k_ray_hits) and, with k > 0, a resolve pass of
+ * one lane per slot (k_ray_hits_resolve). rt_last_kernel names the search that ran: k_ray_hits<24, false> while the scene's
+ * deepest BVH leaf is at most 24 levels down, k_ray_hits<64, true> beyond (its list lives in a ctx buffer instead of LDS; a scene
+ * deeper than 64 is refused). The pass adds to the AOV passes' counter block: boxTests, triTests, raysTraced (the rays searched),
+ * raysHit (the rays with count > 0), and changes nothing a later render or query produces or chooses.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch; (n == 0 succeeds here;) origins or
+ * dirs NULL; k > RT_HITS_MAX_K; d_counts NULL, or d_hits NULL with k > 0; n >= 2^30.
+ * rt_hits_walk_host: the definition as a plain loop over the host arrays (bvhNodes in the host's numbering, an explicit stack, the
+ * constant bound), no ctx, no GPU; sphereCount and objectCount as rayTraceParams gives them (at most the arrays' counts);
+ * textures as rt_upload_textures takes them (NULL, 0: no maps). -1: a NULL argument, k > RT_HITS_MAX_K, n >= 2^30, or arrays
+ * that index out of range. */
+#define RT_HITS_MAX_K 8
+int  rt_query_hits(rt_ctx* ctx, const RtRayBatch* d_rays, uint32_t k, RtHit* d_hits, uint32_t* d_counts);
+int  rt_query_hits_host(rt_ctx* ctx, const RtRayBatch* rays, uint32_t k, RtHit* hits, uint32_t* counts);
+int  rt_hits_walk_host(const RtSceneArrays* scene, uint32_t sphereCount, uint32_t objectCount, const RtTexture* textures,
+                       uint32_t nTextures, const RtRayBatch* rays, uint32_t k, RtHit* hits, uint32_t* counts);
+
 /* Radiance queries: the path-traced radiance along the caller's own rays ("Radiance queries"): what rt_render
  * estimates for the pinhole camera's rays, for any batch of rays: baking, probes, other camera models, jittered pixels, rays
  * made on the device. */

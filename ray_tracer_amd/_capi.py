@@ -203,6 +203,9 @@ SYMBOLS = {
     "rt_query_occluded": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
     "rt_query_closest_host": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
     "rt_query_occluded_host": (C.c_int, [_vp, _P(RtRayBatch), _vp]),
+    "rt_query_hits": (C.c_int, [_vp, _P(RtRayBatch), C.c_uint32, _vp, _vp]),
+    "rt_query_hits_host": (C.c_int, [_vp, _P(RtRayBatch), C.c_uint32, _vp, _vp]),
+    "rt_hits_walk_host": (C.c_int, [_P(RtSceneArrays), C.c_uint32, C.c_uint32, _P(RtTexture), C.c_uint32, _P(RtRayBatch), C.c_uint32, _vp, _vp]),
     "rt_query_nearest": (C.c_int, [_vp, _P(RtPointBatch), _vp]),
     "rt_query_nearest_host": (C.c_int, [_vp, _P(RtPointBatch), _vp]),
     "rt_nearest_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtPointBatch), _vp]),

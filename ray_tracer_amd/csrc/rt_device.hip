@@ -18,6 +18,8 @@
 #include "rt_nearest_side.hip.h"  // the side pass of the signed point queries; mesh_topology.h: its table, checks and host form
 #include "point_queries.h"
 #include "mesh_topology.h"
+#include "rt_ray_hits.hip.h"      // the kernels of the all-hit ray queries; ray_hits.h: their checks, the arithmetic of a batch, the stack choice
+#include "ray_hits.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -129,6 +131,7 @@ struct rt_ctx {
         TopologyCounts counts;
         DevBuf rows, orient;
     } topo;
+    DevBuf hitsListBuf;     // all-hit ray queries: the lists of k_ray_hits<64, true>, whose stack leaves no LDS for them
     size_t aoPixels = 0;
     DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
     // the denoiser (rt_denoise): its work planes and the ctx-owned output
@@ -1560,6 +1563,66 @@ int rt_query_nearest_signed(rt_ctx* c, const RtPointBatch* d_points, RtNearest* 
 }
 int rt_query_nearest_signed_host(rt_ctx* c, const RtPointBatch* points, RtNearest* out, int8_t* side) {
     return signed_host(c, "rt_query_nearest_signed_host", points, out, side);
+}
+}  // extern "C"
+
+// ---- all-hit ray queries (ray_hits.h has the checks, the arithmetic and the stack choice; DESIGN.md, "All-hit ray queries")
+namespace {
+template <int STACK, bool GLIST>
+void launch_ray_hits(rt_ctx* c, uint32_t blocks, const RayHitsArgs& ha) {
+    hipLaunchKernelGGL((k_ray_hits<STACK, GLIST>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, ha);
+    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_ray_hits<%d, %s>", STACK, tf(GLIST));
+}
+
+// the search, then with k > 0 the resolve pass on what it left in the records
+int hits_device(rt_ctx* c, const char* fn, const RtRayBatch* rays, uint32_t k, RtHit* d_hits, uint32_t* d_counts) {
+    if (!c) return -1;
+    const std::string refusal = check_hits_query(fn, c->sc.nodes != nullptr, rays, k, d_hits, d_counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = rays->n;
+    if (n == 0) return 0;
+    std::string deep;
+    const uint32_t stack = hits_stack(fn, c->maxLeafDepth, &deep);
+    if (!stack) return c->fail(deep);
+    RT_HIP(c, hipSetDevice(c->device));
+    const HitsShape hs = hits_shape(n, k, RT_BLOCK);
+    const bool glist = stack != (uint32_t)RT_HITS_STACK;
+    if (glist && k) {
+        if (c->hitsListBuf.bytes < hs.listBytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees lists a search in flight may be using
+        int rc = dev_alloc(c, c->hitsListBuf, hs.listBytes);
+        if (rc) return rc;
+    }
+    const RayHitsArgs ha{rays->origins, rays->dirs, rays->tmax, n, k, (uint32_t*)d_hits, d_counts, (uint32_t*)c->hitsListBuf.p, (DevCounters*)c->aovCounterBuf.p};
+    if (glist) launch_ray_hits<RT_HITS_STACK_DEEP, true>(c, hs.searchBlocks, ha);
+    else launch_ray_hits<RT_HITS_STACK, false>(c, hs.searchBlocks, ha);
+    if (k) hipLaunchKernelGGL(k_ray_hits_resolve<RT_BLOCK>, dim3(hs.resolveBlocks), dim3(RT_BLOCK), 0, c->stream, c->sc, ha);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The host-memory form (staged): origins, dirs, tmax, hits, counts
+int hits_host(rt_ctx* c, const char* fn, const RtRayBatch* rays, uint32_t k, RtHit* hits, uint32_t* counts) {
+    if (!c) return -1;
+    const std::string refusal = check_hits_query(fn, c->sc.nodes != nullptr, rays, k, hits, counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = rays->n;
+    if (n == 0) return 0;
+    const HitsShape hs = hits_shape(n, k, RT_BLOCK);
+    const StagePart parts[] = {{rays->origins, nullptr, hs.vecBytes}, {rays->dirs, nullptr, hs.vecBytes}, {rays->tmax, nullptr, rays->tmax ? hs.tmaxBytes : 0},
+                               {nullptr, hits, hs.hitBytes}, {nullptr, counts, hs.countBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtRayBatch dev{(const float*)d[0], (const float*)d[1], (const float*)d[2], n};
+        return hits_device(c, fn, &dev, k, (RtHit*)d[3], (uint32_t*)d[4]);
+    });
+}
+}  // namespace
+
+extern "C" {
+int rt_query_hits(rt_ctx* c, const RtRayBatch* d_rays, uint32_t k, RtHit* d_hits, uint32_t* d_counts) {
+    return hits_device(c, "rt_query_hits", d_rays, k, d_hits, d_counts);
+}
+int rt_query_hits_host(rt_ctx* c, const RtRayBatch* rays, uint32_t k, RtHit* hits, uint32_t* counts) {
+    return hits_host(c, "rt_query_hits_host", rays, k, hits, counts);
 }
 }  // extern "C"
 

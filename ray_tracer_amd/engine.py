@@ -507,6 +507,34 @@ class Renderer:
         in `out` for device memory, as query_closest takes it."""
         return self._query("occluded", origins, dirs, tmax, n, out, sync)
 
+    def query_hits(self, origins, dirs, k, tmax=None, n=None, out=None, counts=None, sync=True):
+        """Every surface each ray crosses below its limit: the first `k` (0..8) in order, and how many there are (rt_query_hits;
+        DESIGN.md, "All-hit ray queries"). (n, 3) numpy arrays and an optional (n,) `tmax` go through rt_query_hits_host and come
+        back as (RtHit array of n * k records, ray i's at [i * k, i * k + k); uint32 array of n counts); device memory, as
+        query_closest takes it, needs counts= (4 bytes per ray) and, with k > 0, out= (60 bytes per slot), and returns None."""
+        k = int(k)
+        if not _on_device(origins, dirs):
+            o, d, t = _ray_arrays(origins, dirs, tmax)
+            if out is not None or counts is not None or not sync:
+                raise ValueError("out=, counts= and sync=False go with device-pointer inputs")
+            batch = RtRayBatch(o.ctypes.data, d.ctypes.data, t.ctypes.data if t is not None else None, o.shape[0])
+            res = (RtHit * max(o.shape[0] * k, 1))()
+            cnt = np.zeros(o.shape[0], np.uint32)
+            self._check(self._l.rt_query_hits_host(self._h, C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data), "rt_query_hits_host")
+            return _hit_rows(res, o.shape[0], k), cnt
+        if counts is None:
+            raise ValueError("device-pointer inputs need counts=: device memory for the n counts")
+        n = _device_count(origins, n, counts)
+        if out is None and k > 0:
+            raise ValueError("device-pointer inputs need out=: device memory for the n * k records")
+        batch = RtRayBatch(_device_ptr(origins, "origins", 12 * n), _device_ptr(dirs, "dirs", 12 * n),
+                           None if tmax is None else _device_ptr(tmax, "tmax", 4 * n), n)
+        self._check(self._l.rt_query_hits(self._h, C.byref(batch), k, None if out is None else C.c_void_p(_device_ptr(out, "out", C.sizeof(RtHit) * n * k, floats=False)),
+                                          C.c_void_p(_device_ptr(counts, "counts", 4 * n, floats=False))), "rt_query_hits")
+        if sync:
+            self.sync()
+        return None
+
     def upload_topology(self, scene):
         """Builds the topology table of `scene` (the one uploaded) and uploads it: what query_nearest_signed needs (rt_upload_topology).
         upload_scene drops it again; update_points and update_objects keep it."""
@@ -994,6 +1022,48 @@ def hits_to_numpy(hits):
                 triHitIndex=u[:, 4].copy(), materialIndex=u[:, 5].copy(), frontFace=u[:, 6].copy(),
                 hitPoint=f[:, 7:10].copy(), normal=f[:, 10:13].copy(), boxTests=u[:, 13].copy(),
                 triTests=u[:, 14].copy())
+
+
+def _ray_arrays(origins, dirs, tmax):
+    """Host rays as the entry points take them: (n, 3) float32 origins and dirs and (n,) limits or None."""
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    if d.shape != o.shape:
+        raise ValueError(f"origins {o.shape} and dirs {d.shape}: not one (n, 3) pair")
+    t = None if tmax is None else np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+    if t is not None and t.shape[0] != o.shape[0]:
+        raise ValueError(f"tmax has {t.shape[0]} limits for {o.shape[0]} rays")
+    return o, d, t
+
+
+def _hit_rows(res, n, k):
+    """The n * k records of an all-hit query out of the (never empty) ctypes array they were written to."""
+    return (RtHit * (n * k)).from_buffer(res) if n * k else (RtHit * 0)()
+
+
+def hits_walk(scene_arrays, origins, dirs, k, tmax=None, textures=None, spheres=None, objects=None):
+    """The definition of the all-hit ray queries as a plain loop over the host arrays (rt_hits_walk_host; no GPU): `scene_arrays`
+    is Scene.arrays(), `textures` a list of uint8 [h, w, 4] arrays in slot order as upload_textures takes them (None: no maps);
+    `spheres` / `objects`: how many of the arrays' entries take part (None: all). Returns (RtHit array of n * k records, uint32
+    counts), as Renderer.query_hits does for numpy inputs."""
+    o, d, t = _ray_arrays(origins, dirs, tmax)
+    k = int(k)
+    images = [np.ascontiguousarray(im, dtype=np.uint8) for im in (textures or [])]
+    tex = (RtTexture * max(len(images), 1))()
+    for i, im in enumerate(images):
+        if im.ndim != 3 or im.shape[2] != 4:
+            raise ValueError("textures are [height, width, 4] uint8 (RGBA)")
+        tex[i].width, tex[i].height = im.shape[1], im.shape[0]
+        tex[i].rgba8 = im.ctypes.data_as(C.POINTER(C.c_uint8))
+    batch = RtRayBatch(o.ctypes.data, d.ctypes.data, t.ctypes.data if t is not None else None, o.shape[0])
+    res = (RtHit * max(o.shape[0] * k, 1))()
+    cnt = np.zeros(o.shape[0], np.uint32)
+    rc = _capi.lib().rt_hits_walk_host(C.byref(scene_arrays), scene_arrays.sphereCount if spheres is None else int(spheres),
+                                       scene_arrays.objectCount if objects is None else int(objects), tex if images else None, len(images),
+                                       C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data)
+    if rc != 0:
+        raise RtError("rt_hits_walk_host refused its arguments (k > 8, n >= 2^30, or arrays that index out of range)")
+    return _hit_rows(res, o.shape[0], k), cnt
 
 
 def nearest_to_numpy(recs):
