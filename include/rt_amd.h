@@ -678,6 +678,52 @@ int  rt_upload_topology(rt_ctx* ctx, const RtSceneArrays* scene);
 int  rt_query_nearest_signed(rt_ctx* ctx, const RtPointBatch* d_points, RtNearest* d_out, int8_t* d_side);
 int  rt_query_nearest_signed_host(rt_ctx* ctx, const RtPointBatch* points, RtNearest* out, int8_t* side);
 
+/* Radius point queries ("Radius point queries"; include/rt_point_within.h states the rule, both sides compile it): every
+ * surface within reach of a point, the first k of them nearest first, and how many there are: the point side's counterpart of
+ * rt_query_hits.
+ * Contract. Point i has the reach R (maxDist[i]; none when maxDist is NULL: every surface is a member) and the bound
+ * R2 = rt_nearest_start(...), the very function rt_query_nearest starts with: fl(R * R), or +inf without a reach. A reach that
+ * is NaN or <= 0 means no search. Its member set C:
+ *  - every sphere with rt_sphere_is_surface(r) whose rt_point_sphere squared distance is STRICTLY < R2;
+ *  - every triangle of every object whose rt_point_triangle squared distance is < R2, its world corners placed through the
+ *    forward matrix in fp32 exactly as rt_query_nearest places them.
+ * Nothing else plays a part: no frontOnly, no materials, no alpha maps. R2 never shrinks, so C is a function of the point and the
+ * scene alone: not of the visiting order, the BVH, the kernel, the stack or any knob.
+ *  - d_counts[i] = |C|, exact whatever k is.
+ *  - d_out[i * k .. i * k + k - 1]: the first min(k, |C|) members in ascending order of the key, then the not-found record
+ *    (dst == RT_MISS_DST, everything else 0) in the remaining slots. The key, compared lexicographically: the squared distance as
+ *    an fp32 compare; spheres before triangles; the lower sphere or object index; the lower triangle index (rt_hits_before of
+ *    include/rt_ray_hits.h on {d2, primitive word, triangle}).
+ *  - A member's record is an RtNearest with found = 1, dst = rt_sqrt(d2), and uv, point and the indices exactly as
+ *    rt_query_nearest builds them for that primitive; 48 bytes, padding 0.
+ *  - The key is total, so unlike rt_query_nearest the reported primitives are particular ones, and rt_query_within equals
+ *    rt_within_exhaustive_host in every byte of every record and count.
+ *  - Hence, bit for bit: counts[i] > 0 iff rt_query_nearest with maxDist = R has found; out[i * k].dst has the bits of its dst;
+ *    the primitive it reports is a member and, with count <= k, is in the list with its record byte for byte; counts are the same
+ *    for every k; the list at a smaller k is the head of the list at a larger one; for R1 < R2 the list at R1 is the prefix of the
+ *    list at R2 whose squared distances are < fl(R1 * R1).
+ *  - k runs from 0 to RT_WITHIN_MAX_K. k == 0: counts only, d_out may be NULL. n == 0 succeeds and does nothing.
+ * rt_query_within: the struct is read on the host, its arrays, d_out (16-byte aligned) and d_counts are device pointers,
+ * asynchronous on the ctx stream (the arrays stay valid and unchanged until the stream has passed it). rt_query_within_host takes
+ * host arrays, stages them through a ctx buffer and blocks. One lane per point, no path state: the search (k_points_within,
+ * pruned as k_nearest_points prunes, with the bound held constant) and, with k > 0, a resolve pass of one lane per slot
+ * (k_points_within_resolve). rt_last_kernel names the search that ran: k_points_within<24, false> while the scene's deepest BVH
+ * leaf is at most 24 levels down, k_points_within<64, true> beyond (its lists live in a ctx buffer instead of LDS; a scene deeper
+ * than 64 is refused). The pass adds to the AOV passes' counter block: boxTests (box distances evaluated), triTests
+ * (rt_point_triangle calls), raysTraced (points searched), raysHit (points with count > 0), and changes nothing a later render
+ * or query produces or chooses. It reads the tables of the scene as they are: after rt_update_objects or rt_update_points, the
+ * moved and the refit ones.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch; (n == 0 succeeds here;) points NULL
+ * ("points and the output are required"); k > RT_WITHIN_MAX_K; d_counts NULL, or d_out NULL with k > 0 ("counts and, with k > 0,
+ * the output are required"); n >= 2^30.
+ * rt_within_exhaustive_host: the definition as a plain loop over the host arrays: every sphere in index order, then every
+ * triangle of every object in index order, no pruning; no ctx, no GPU. -1: what rt_nearest_exhaustive_host refuses, and
+ * k > RT_WITHIN_MAX_K. */
+#define RT_WITHIN_MAX_K 8
+int  rt_query_within(rt_ctx* ctx, const RtPointBatch* d_points, uint32_t k, RtNearest* d_out, uint32_t* d_counts);
+int  rt_query_within_host(rt_ctx* ctx, const RtPointBatch* points, uint32_t k, RtNearest* out, uint32_t* counts);
+int  rt_within_exhaustive_host(const RtSceneArrays* scene, const RtPointBatch* points, uint32_t k, RtNearest* out, uint32_t* counts);
+
 /* Ambient occlusion from first-hit planes ("Ray queries", "Ambient-occlusion plane"). Record i of the planes with
  * ids.w & 1 shoots `samples` occlusion queries: origin position + (normal * 1) * 0.00001 (the next-ray origin of shading),
  * direction the shader's cosineHemisphereDir about normalDepth.xyz (raytrace.comp:405-424, the arithmetic of the diffuse branch of

@@ -215,6 +215,9 @@ SYMBOLS = {
     "rt_upload_topology": (C.c_int, [_vp, _P(RtSceneArrays)]),
     "rt_query_nearest_signed": (C.c_int, [_vp, _P(RtPointBatch), _vp, _vp]),
     "rt_query_nearest_signed_host": (C.c_int, [_vp, _P(RtPointBatch), _vp, _vp]),
+    "rt_query_within": (C.c_int, [_vp, _P(RtPointBatch), C.c_uint32, _vp, _vp]),
+    "rt_query_within_host": (C.c_int, [_vp, _P(RtPointBatch), C.c_uint32, _vp, _vp]),
+    "rt_within_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtPointBatch), C.c_uint32, _vp, _vp]),
     "rt_radiance_params_default": (None, [_P(RtRadianceParams)]),
     "rt_query_radiance": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),
     "rt_query_radiance_host": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),

@@ -190,31 +190,26 @@ std::vector<float4> layout_nearest(const ObjectLayout& l, const RenderObject* o,
     return t;
 }
 
-extern "C" {
-
-int rt_nearest_exhaustive_host(const RtSceneArrays* s, const RtPointBatch* points, RtNearest* out) {
-    if (!s || !points) return -1;
-    const uint32_t n = points->n;
-    if (n == 0) return 0;
-    if (!points->points || !out || n >= (uint32_t)RT_NEAREST_MAX_POINTS) return -1;
-    // the triangles of every object: the leaf ranges under its root, in index order (the BVH only says which triangles a mesh has)
-    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> rangesOf(s->objectCount);
-    for (uint32_t i = 0; i < s->objectCount; i++) {
-        const uint32_t root = s->objects[i].bvhIndex;
-        if (root >= s->bvhNodeCount) return -1;
+// (the BVH only says which triangles a mesh has)
+bool object_triangle_ranges(const RtSceneArrays& s, std::vector<TriangleRanges>* out) {
+    std::vector<TriangleRanges>& rangesOf = *out;
+    rangesOf.assign(s.objectCount, TriangleRanges());
+    for (uint32_t i = 0; i < s.objectCount; i++) {
+        const uint32_t root = s.objects[i].bvhIndex;
+        if (root >= s.bvhNodeCount) return false;
         bool shared = false;
         for (uint32_t k = 0; k < i && !shared; k++)
-            if (s->objects[k].bvhIndex == root) { rangesOf[i] = rangesOf[k]; shared = true; }
+            if (s.objects[k].bvhIndex == root) { rangesOf[i] = rangesOf[k]; shared = true; }
         if (shared) continue;
         std::vector<uint32_t> st(1, root);
         size_t visited = 0;
         while (!st.empty()) {
             const uint32_t nidx = st.back();
             st.pop_back();
-            if (nidx >= s->bvhNodeCount || ++visited > (size_t)s->bvhNodeCount + 1) return -1;
-            const BVHNode& b = s->bvhNodes[nidx];
+            if (nidx >= s.bvhNodeCount || ++visited > (size_t)s.bvhNodeCount + 1) return false;
+            const BVHNode& b = s.bvhNodes[nidx];
             if (b.triCount) {
-                if ((uint64_t)b.index + b.triCount > s->triangleCount) return -1;
+                if ((uint64_t)b.index + b.triCount > s.triangleCount) return false;
                 rangesOf[i].emplace_back(b.index, b.triCount);
             } else {
                 st.push_back(b.index);
@@ -223,15 +218,28 @@ int rt_nearest_exhaustive_host(const RtSceneArrays* s, const RtPointBatch* point
         }
         std::sort(rangesOf[i].begin(), rangesOf[i].end());
     }
-    for (uint32_t t = 0; t < s->triangleCount; t++)
-        if (s->triangles[t].v0 >= s->triPointCount || s->triangles[t].v1 >= s->triPointCount || s->triangles[t].v2 >= s->triPointCount) return -1;
-    // rows 0..2 of the matrix are the identity's (what RT_OBJ_FWD_IDENTITY says on the device)
-    auto is_identity = [](const float* m) {
-        bool is = true;
-        for (int c = 0; c < 4; c++)
-            for (int r = 0; r < 3; r++) is = is && m[c * 4 + r] == (r == c ? 1.f : 0.f);
-        return is;
-    };
+    for (uint32_t t = 0; t < s.triangleCount; t++)
+        if (s.triangles[t].v0 >= s.triPointCount || s.triangles[t].v1 >= s.triPointCount || s.triangles[t].v2 >= s.triPointCount) return false;
+    return true;
+}
+
+// (what RT_OBJ_FWD_IDENTITY says on the device)
+bool matrix_rows_identity(const float* m) {
+    bool is = true;
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 3; r++) is = is && m[c * 4 + r] == (r == c ? 1.f : 0.f);
+    return is;
+}
+
+extern "C" {
+
+int rt_nearest_exhaustive_host(const RtSceneArrays* s, const RtPointBatch* points, RtNearest* out) {
+    if (!s || !points) return -1;
+    const uint32_t n = points->n;
+    if (n == 0) return 0;
+    if (!points->points || !out || n >= (uint32_t)RT_NEAREST_MAX_POINTS) return -1;
+    std::vector<TriangleRanges> rangesOf;
+    if (!object_triangle_ranges(*s, &rangesOf)) return -1;
     for (uint32_t i = 0; i < n; i++) {
         RtNearest r;
         memset(&r, 0, sizeof r);
@@ -250,7 +258,7 @@ int rt_nearest_exhaustive_host(const RtSceneArrays* s, const RtPointBatch* point
             }
             for (uint32_t k = 0; k < s->objectCount; k++) {
                 const float* m = s->objects[k].transformMatrix;
-                const bool isIdent = is_identity(m);
+                const bool isIdent = matrix_rows_identity(m);
                 for (const auto& range : rangesOf[k])
                     for (uint32_t t = range.first; t < range.first + range.second; t++) {
                         const Triangle& tr = s->triangles[t];

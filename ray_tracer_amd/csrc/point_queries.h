@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rt_amd.h"
@@ -52,3 +53,10 @@ NearestPrune nearest_prune(const float* transformMatrix, bool fwdIdentity);
 // (-inf, +inf) for anything else (never skipped). mag bounds |M| |[v; 1]| over the root box's corners and the world box's own
 // coordinates: the scale the fp32 rounding of the object's world corners goes with (+inf where that is not finite).
 std::vector<float4> layout_nearest(const ObjectLayout& l, const RenderObject* o, uint32_t n, const std::vector<RootInfo>& rootOf);
+
+// The triangles of every object of the host arrays, for the exhaustive loops: the leaf ranges {first, count} under its root, in
+// index order. false: a root, a node, a leaf range or a triangle's point index lies outside its array, or the nodes are no tree.
+typedef std::vector<std::pair<uint32_t, uint32_t>> TriangleRanges;
+bool object_triangle_ranges(const RtSceneArrays& s, std::vector<TriangleRanges>* rangesOf);
+// rows 0..2 of the column-major matrix are the identity's: the object's corners are used as they are
+bool matrix_rows_identity(const float* m);

@@ -20,6 +20,8 @@
 #include "mesh_topology.h"
 #include "rt_ray_hits.hip.h"      // the kernels of the all-hit ray queries; ray_hits.h: their checks, the arithmetic of a batch, the stack choice
 #include "ray_hits.h"
+#include "rt_point_within.hip.h"  // the kernels of the radius point queries; point_within.h: their checks, the arithmetic of a batch, the stack choice
+#include "point_within.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -132,6 +134,7 @@ struct rt_ctx {
         DevBuf rows, orient;
     } topo;
     DevBuf hitsListBuf;     // all-hit ray queries: the lists of k_ray_hits<64, true>, whose stack leaves no LDS for them
+    DevBuf withinListBuf;   // radius point queries: the lists of k_points_within<64, true>, likewise
     size_t aoPixels = 0;
     DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
     // the denoiser (rt_denoise): its work planes and the ctx-owned output
@@ -1623,6 +1626,65 @@ int rt_query_hits(rt_ctx* c, const RtRayBatch* d_rays, uint32_t k, RtHit* d_hits
 }
 int rt_query_hits_host(rt_ctx* c, const RtRayBatch* rays, uint32_t k, RtHit* hits, uint32_t* counts) {
     return hits_host(c, "rt_query_hits_host", rays, k, hits, counts);
+}
+}  // extern "C"
+
+// ---- radius point queries (point_within.h has the checks, the arithmetic and the stack choice; DESIGN.md, "Radius point queries")
+namespace {
+template <int STACK, bool GLIST>
+void launch_points_within(rt_ctx* c, uint32_t blocks, const WithinArgs& wa) {
+    hipLaunchKernelGGL((k_points_within<STACK, GLIST>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, wa);
+    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_points_within<%d, %s>", STACK, tf(GLIST));
+}
+
+// the search, then with k > 0 the resolve pass on what it left in the records
+int within_device(rt_ctx* c, const char* fn, const RtPointBatch* pts, uint32_t k, RtNearest* d_out, uint32_t* d_counts) {
+    if (!c) return -1;
+    const std::string refusal = check_within_query(fn, c->sc.nodes != nullptr, pts, k, d_out, d_counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = pts->n;
+    if (n == 0) return 0;
+    std::string deep;
+    const uint32_t stack = within_stack(fn, c->maxLeafDepth, &deep);
+    if (!stack) return c->fail(deep);
+    RT_HIP(c, hipSetDevice(c->device));
+    const WithinShape ws = within_shape(n, k, RT_BLOCK);
+    const bool glist = stack != (uint32_t)RT_WITHIN_STACK;
+    if (glist && k) {
+        if (c->withinListBuf.bytes < ws.listBytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees lists a search in flight may be using
+        int rc = dev_alloc(c, c->withinListBuf, ws.listBytes);
+        if (rc) return rc;
+    }
+    const WithinArgs wa{pts->points, pts->maxDist, n, k, (const float4*)c->objNearBuf.p, (uint32_t*)d_out, d_counts, (uint32_t*)c->withinListBuf.p, (DevCounters*)c->aovCounterBuf.p};
+    if (glist) launch_points_within<RT_WITHIN_STACK_DEEP, true>(c, ws.searchBlocks, wa);
+    else launch_points_within<RT_WITHIN_STACK, false>(c, ws.searchBlocks, wa);
+    if (k) hipLaunchKernelGGL(k_points_within_resolve<RT_BLOCK>, dim3(ws.resolveBlocks), dim3(RT_BLOCK), 0, c->stream, c->sc, wa);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The host-memory form (staged): points, maxDist, out, counts
+int within_host(rt_ctx* c, const char* fn, const RtPointBatch* pts, uint32_t k, RtNearest* out, uint32_t* counts) {
+    if (!c) return -1;
+    const std::string refusal = check_within_query(fn, c->sc.nodes != nullptr, pts, k, out, counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = pts->n;
+    if (n == 0) return 0;
+    const WithinShape ws = within_shape(n, k, RT_BLOCK);
+    const StagePart parts[] = {{pts->points, nullptr, ws.pointBytes}, {pts->maxDist, nullptr, pts->maxDist ? ws.limitBytes : 0}, {nullptr, out, ws.outBytes}, {nullptr, counts, ws.countBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtPointBatch dev{(const float*)d[0], (const float*)d[1], n};
+        return within_device(c, fn, &dev, k, (RtNearest*)d[2], (uint32_t*)d[3]);
+    });
+}
+}  // namespace
+
+extern "C" {
+int rt_query_within(rt_ctx* c, const RtPointBatch* d_points, uint32_t k, RtNearest* d_out, uint32_t* d_counts) {
+    return within_device(c, "rt_query_within", d_points, k, d_out, d_counts);
+}
+int rt_query_within_host(rt_ctx* c, const RtPointBatch* points, uint32_t k, RtNearest* out, uint32_t* counts) {
+    return within_host(c, "rt_query_within_host", points, k, out, counts);
 }
 }  // extern "C"
 

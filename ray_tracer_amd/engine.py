@@ -593,6 +593,35 @@ class Renderer:
             self.sync()
         return None
 
+    def query_within(self, points, radius, k, n=None, out=None, counts=None, sync=True):
+        """Every surface within `radius` of each point: the first `k` (0..8) nearest first, and how many there are (rt_query_within;
+        DESIGN.md, "Radius point queries"). An (n, 3) numpy array and an (n,) `radius` (None: no reach, every surface counts) go
+        through rt_query_within_host and come back as (RtNearest array of n * k records, point i's at [i * k, i * k + k);
+        uint32 array of n counts); device memory, as query_nearest takes it, needs counts= (4 bytes per point) and, with k > 0,
+        out= (48 bytes per slot, 16-byte aligned), and returns None."""
+        k = int(k)
+        rec = C.sizeof(RtNearest)
+        if not _on_device(points):
+            p, t = _point_arrays(points, radius, "radius")
+            if out is not None or counts is not None or not sync:
+                raise ValueError("out=, counts= and sync=False go with device-pointer inputs")
+            batch = RtPointBatch(p.ctypes.data, t.ctypes.data if t is not None else None, p.shape[0])
+            res = (RtNearest * max(p.shape[0] * k, 1))()
+            cnt = np.zeros(p.shape[0], np.uint32)
+            self._check(self._l.rt_query_within_host(self._h, C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data), "rt_query_within_host")
+            return _nearest_rows(res, p.shape[0], k), cnt
+        if counts is None:
+            raise ValueError("device-pointer inputs need counts=: device memory for the n counts")
+        n = _device_count(points, n, counts)
+        if out is None and k > 0:
+            raise ValueError("device-pointer inputs need out=: device memory for the n * k records")
+        batch = RtPointBatch(_device_ptr(points, "points", 12 * n), None if radius is None else _device_ptr(radius, "radius", 4 * n), n)
+        self._check(self._l.rt_query_within(self._h, C.byref(batch), k, None if out is None else C.c_void_p(_device_ptr(out, "out", rec * n * k, floats=False)),
+                                            C.c_void_p(_device_ptr(counts, "counts", 4 * n, floats=False))), "rt_query_within")
+        if sync:
+            self.sync()
+        return None
+
     def query_radiance(self, origins, dirs, samples=1, bounces=8, ids=None, progressive=False, frame=0, environment=None, n=None, out=None,
                        sync=True):
         """The path-traced radiance along each of the caller's rays (rt_query_radiance; DESIGN.md, "Radiance queries"): `samples`
@@ -1085,6 +1114,34 @@ def nearest_exhaustive(scene_arrays, points, max_dist=None):
     if _capi.lib().rt_nearest_exhaustive_host(C.byref(scene_arrays), C.byref(batch), C.addressof(res)) != 0:
         raise RtError("rt_nearest_exhaustive_host refused its arguments (NULL arrays, n >= 2^30, or indices out of range)")
     return (RtNearest * p.shape[0]).from_buffer(res) if p.shape[0] else (RtNearest * 0)()
+
+
+def _point_arrays(points, limits, name):
+    """Host points as the entry points take them: (n, 3) float32 points and (n,) limits or None."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    t = None if limits is None else np.ascontiguousarray(limits, dtype=np.float32).reshape(-1)
+    if t is not None and t.shape[0] != p.shape[0]:
+        raise ValueError(f"{name} has {t.shape[0]} limits for {p.shape[0]} points")
+    return p, t
+
+
+def _nearest_rows(res, n, k):
+    """The n * k records of a radius query out of the (never empty) ctypes array they were written to."""
+    return (RtNearest * (n * k)).from_buffer(res) if n * k else (RtNearest * 0)()
+
+
+def within_exhaustive(scene_arrays, points, radius, k):
+    """The definition of the radius point queries as a plain loop over the host arrays (rt_within_exhaustive_host; no GPU, no
+    pruning): `scene_arrays` is Scene.arrays(), `radius` an (n,) array or None (no reach). Returns (RtNearest array of n * k
+    records (nearest_to_numpy), uint32 counts), as Renderer.query_within does for numpy inputs."""
+    p, t = _point_arrays(points, radius, "radius")
+    k = int(k)
+    batch = RtPointBatch(p.ctypes.data, t.ctypes.data if t is not None else None, p.shape[0])
+    res = (RtNearest * max(p.shape[0] * k, 1))()
+    cnt = np.zeros(p.shape[0], np.uint32)
+    if _capi.lib().rt_within_exhaustive_host(C.byref(scene_arrays), C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data) != 0:
+        raise RtError("rt_within_exhaustive_host refused its arguments (k > 8, NULL arrays, n >= 2^30, or indices out of range)")
+    return _nearest_rows(res, p.shape[0], k), cnt
 
 
 def scene_topology(scene_arrays):
