@@ -724,6 +724,60 @@ int  rt_query_within(rt_ctx* ctx, const RtPointBatch* d_points, uint32_t k, RtNe
 int  rt_query_within_host(rt_ctx* ctx, const RtPointBatch* points, uint32_t k, RtNearest* out, uint32_t* counts);
 int  rt_within_exhaustive_host(const RtSceneArrays* scene, const RtPointBatch* points, uint32_t k, RtNearest* out, uint32_t* counts);
 
+/* Sphere sweeps ("Sphere sweeps"; include/rt_sweep.h states the rule, both sides compile it): a ball of radius
+ * radius[i] whose centre moves along origins[i] + t dirs[i]; does it touch the scene, when and where? Sphere casts, thick rays,
+ * continuous collision, the clearance of a path.
+ * Contract. The surfaces are rt_query_nearest's: every sphere with rt_sphere_is_surface(r), every triangle of every object, its
+ * world corners placed through the forward matrix in fp32 exactly as rt_query_nearest places them. Surfaces, not solids: a sweep
+ * that starts inside a closed mesh or a scene sphere without touching it meets the surface from inside (for a scene sphere of
+ * radius r > R, the shell r - R). frontOnly, materials and alpha maps play no part. dirs are not renormalised: t is in units of
+ * |dir|, as in the ray queries. Ray i asks for the least t in [0, T) at which the centre is within R of a surface, T = tmax[i],
+ * +inf when tmax is NULL. No search, and the not-found record, when the radius is NaN, infinite or <= 0, the limit NaN or <= 0,
+ * or dot(d, d) not finite or not > 0.
+ *  - Per primitive the rule gives one time or none (the slab of the triangle's plane, its vertex balls and edge cylinders; the
+ *    balls r + R and r - R of a sphere), every quadratic solved about the point of the line nearest the primitive, and a time
+ *    counts only when the point queries' own distance from the centre fl(o + t d) to that primitive is <= fl((R + sigma)^2),
+ *    sigma = RT_SWEEP_SIGMA (48 x 2^-24) x the largest |coordinate| of the centre, the primitive and the step t d.
+ *  - The answer is the primitive with the least key {t, spheres before triangles, the lower sphere or object index, the lower
+ *    triangle index} (rt_hits_before) among those with t < T. The key is total and the device's pruning conservative by
+ *    derivation, so rt_query_sweep equals rt_sweep_exhaustive_host in every byte of every record, whatever the BVH, the kernel
+ *    or the visiting order.
+ *  - The record: t; the primitive as in RtNearest; uv, point and gap (rt_sqrt of the squared distance) exactly as the point
+ *    queries measure that primitive from the centre fl(o + t d), so rt_query_nearest at that centre returns dst <= gap;
+ *    normal = normalize(centre - point), -normalize(dir) where they coincide; startsInContact = 1 when t == 0.
+ *  - A sweep that starts in contact reports t = 0 and the lowest-keyed primitive it touches, not the nearest or the deepest:
+ *    rt_query_nearest at the origin answers that.
+ * rt_query_sweep: the struct is read on the host, its arrays and d_out (16-byte aligned) are device pointers, asynchronous on
+ * the ctx stream. rt_query_sweep_host takes host arrays, stages them through a ctx buffer and blocks. One lane per ray, no path
+ * state. rt_last_kernel names the instantiation that ran: k_sweep_spheres<24, true> while the scene's deepest BVH leaf is at most
+ * 24 levels down, k_sweep_spheres<64, false> beyond (a scene deeper than 64 is refused). The pass adds to the AOV passes'
+ * counter block: boxTests (grown boxes tested), triTests (calls of the triangle rule), raysTraced (rays searched), raysHit (rays
+ * found), and changes nothing a later render or query produces or chooses. It reads the tables of the scene as they are: after
+ * rt_update_objects or rt_update_points, the moved and the refit ones.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch; (n == 0 succeeds here and does
+ * nothing;) origins, dirs, radius or the output NULL; n >= 2^30.
+ * rt_sweep_exhaustive_host: the definition as a plain loop over the host arrays: every sphere in index order, then every triangle
+ * of every object in index order, no pruning; no ctx, no GPU. -1: what rt_nearest_exhaustive_host refuses. */
+typedef struct RtSweepBatch {
+    const float* origins;  /* n x 3, packed: the centre at t = 0 */
+    const float* dirs;     /* n x 3; not renormalised: t is in units of |dir| */
+    const float* radius;   /* n floats, required */
+    const float* tmax;     /* n floats, or NULL: no limit */
+    uint32_t n;
+} RtSweepBatch;
+typedef struct RtSweep {           /* 64 bytes, four 16-byte stores, output 16-byte aligned */
+    float t;                       /* RT_MISS_DST when found == 0 */
+    uint32_t found, isSphere, objectIndex;
+    uint32_t triIndex; float uv[2]; float gap;   /* gap: distance from the centre at t to the surface, as the rule measured it */
+    float point[3];                /* the contact point on the surface, world space */
+    uint32_t startsInContact;      /* 1: already touching at t = 0 (then t == 0) */
+    float normal[3];               /* unit, from point towards the centre at t; -normalize(dir) when they coincide */
+    uint32_t _pad;                 /* 0 */
+} RtSweep;                         /* not found: t = RT_MISS_DST, everything else 0 */
+int  rt_query_sweep(rt_ctx* ctx, const RtSweepBatch* d_batch, RtSweep* d_out);
+int  rt_query_sweep_host(rt_ctx* ctx, const RtSweepBatch* batch, RtSweep* out);
+int  rt_sweep_exhaustive_host(const RtSceneArrays* scene, const RtSweepBatch* batch, RtSweep* out);
+
 /* Ambient occlusion from first-hit planes ("Ray queries", "Ambient-occlusion plane"). Record i of the planes with
  * ids.w & 1 shoots `samples` occlusion queries: origin position + (normal * 1) * 0.00001 (the next-ray origin of shading),
  * direction the shader's cosineHemisphereDir about normalDepth.xyz (raytrace.comp:405-424, the arithmetic of the diffuse branch of

@@ -115,6 +115,16 @@ class RtNearest(C.Structure):
                 ("triIndex", C.c_uint32), ("uv", C.c_float * 2), ("point", C.c_float * 3), ("_pad", C.c_uint32 * 2)]
 
 
+class RtSweepBatch(C.Structure):
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("radius", C.c_void_p), ("tmax", C.c_void_p), ("n", C.c_uint32)]
+
+
+class RtSweep(C.Structure):
+    _fields_ = [("t", C.c_float), ("found", C.c_uint32), ("isSphere", C.c_uint32), ("objectIndex", C.c_uint32),
+                ("triIndex", C.c_uint32), ("uv", C.c_float * 2), ("gap", C.c_float), ("point", C.c_float * 3),
+                ("startsInContact", C.c_uint32), ("normal", C.c_float * 3), ("_pad", C.c_uint32)]
+
+
 class RtMeshTopology(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("triangles", "weldedVertices", "components", "signableComponents", "signableTriangles", "boundaryEdges",
                                           "nonManifoldEdges", "flippedTriangles", "degenerateTriangles")] + [("orientation", C.c_int32)]
@@ -218,6 +228,9 @@ SYMBOLS = {
     "rt_query_within": (C.c_int, [_vp, _P(RtPointBatch), C.c_uint32, _vp, _vp]),
     "rt_query_within_host": (C.c_int, [_vp, _P(RtPointBatch), C.c_uint32, _vp, _vp]),
     "rt_within_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtPointBatch), C.c_uint32, _vp, _vp]),
+    "rt_query_sweep": (C.c_int, [_vp, _P(RtSweepBatch), _vp]),
+    "rt_query_sweep_host": (C.c_int, [_vp, _P(RtSweepBatch), _vp]),
+    "rt_sweep_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtSweepBatch), _vp]),
     "rt_radiance_params_default": (None, [_P(RtRadianceParams)]),
     "rt_query_radiance": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),
     "rt_query_radiance_host": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),

@@ -22,6 +22,8 @@
 #include "ray_hits.h"
 #include "rt_point_within.hip.h"  // the kernels of the radius point queries; point_within.h: their checks, the arithmetic of a batch, the stack choice
 #include "point_within.h"
+#include "rt_sweep.hip.h"         // the kernel of the sphere sweeps; sweep_queries.h: their checks, the arithmetic of a batch, the stack choice
+#include "sweep_queries.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -1686,6 +1688,54 @@ int rt_query_within(rt_ctx* c, const RtPointBatch* d_points, uint32_t k, RtNeare
 int rt_query_within_host(rt_ctx* c, const RtPointBatch* points, uint32_t k, RtNearest* out, uint32_t* counts) {
     return within_host(c, "rt_query_within_host", points, k, out, counts);
 }
+}  // extern "C"
+
+// ---- sphere sweeps (sweep_queries.h has the checks, the arithmetic and the stack choice; DESIGN.md, "Sphere sweeps")
+namespace {
+template <int STACK, bool RETEST>
+void launch_sweep(rt_ctx* c, uint32_t blocks, const SweepArgs& sa) {
+    hipLaunchKernelGGL((k_sweep_spheres<STACK, RETEST>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, sa);
+    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_sweep_spheres<%d, %s>", STACK, tf(RETEST));
+}
+
+int sweep_device(rt_ctx* c, const char* fn, const RtSweepBatch* b, RtSweep* d_out) {
+    if (!c) return -1;
+    const std::string refusal = check_sweep_query(fn, c->sc.nodes != nullptr, b, d_out);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = b->n;
+    if (n == 0) return 0;
+    std::string deep;
+    const uint32_t stack = sweep_stack(fn, c->maxLeafDepth, &deep);
+    if (!stack) return c->fail(deep);
+    RT_HIP(c, hipSetDevice(c->device));
+    const SweepArgs sa{b->origins, b->dirs, b->radius, b->tmax, n, (const float4*)c->objNearBuf.p, (float4*)d_out, (DevCounters*)c->aovCounterBuf.p};
+    const uint32_t blocks = sweep_shape(n, RT_BLOCK).blocks;
+    if (stack == (uint32_t)RT_SWEEP_STACK) launch_sweep<RT_SWEEP_STACK, true>(c, blocks, sa);
+    else launch_sweep<RT_SWEEP_STACK_DEEP, false>(c, blocks, sa);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The host-memory form (staged): origins, dirs, radius, tmax, out
+int sweep_host(rt_ctx* c, const char* fn, const RtSweepBatch* b, RtSweep* out) {
+    if (!c) return -1;
+    const std::string refusal = check_sweep_query(fn, c->sc.nodes != nullptr, b, out);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = b->n;
+    if (n == 0) return 0;
+    const SweepShape ss = sweep_shape(n, RT_BLOCK);
+    const StagePart parts[] = {{b->origins, nullptr, ss.vecBytes}, {b->dirs, nullptr, ss.vecBytes}, {b->radius, nullptr, ss.scalarBytes},
+                               {b->tmax, nullptr, b->tmax ? ss.scalarBytes : 0}, {nullptr, out, ss.outBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtSweepBatch dev{(const float*)d[0], (const float*)d[1], (const float*)d[2], (const float*)d[3], n};
+        return sweep_device(c, fn, &dev, (RtSweep*)d[4]);
+    });
+}
+}  // namespace
+
+extern "C" {
+int rt_query_sweep(rt_ctx* c, const RtSweepBatch* d_batch, RtSweep* d_out) { return sweep_device(c, "rt_query_sweep", d_batch, d_out); }
+int rt_query_sweep_host(rt_ctx* c, const RtSweepBatch* batch, RtSweep* out) { return sweep_host(c, "rt_query_sweep_host", batch, out); }
 }  // extern "C"
 
 // ---- radiance queries (radiance_queries.h has the checks and the arithmetic; DESIGN.md, "Radiance queries")

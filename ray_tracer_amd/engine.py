@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .devmem import DeviceBuffer, RtError, hip as _hip   # noqa: F401  (engine.RtError and engine._hip are where callers know them)
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtMeshTopology, RtNearest, RtPointBatch, RtRadianceParams, RtRayBatch,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtMeshTopology, RtNearest, RtPointBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -622,6 +622,28 @@ class Renderer:
             self.sync()
         return None
 
+    def query_sweep(self, origins, dirs, radius, tmax=None, n=None, out=None, sync=True):
+        """The first contact of a ball of `radius` whose centre moves along each ray (rt_query_sweep; DESIGN.md, "Sphere sweeps"):
+        the least t in [0, tmax) at which the centre origins + t dirs is within radius of a surface, and where. (n, 3) numpy
+        origins and dirs, an (n,) `radius` and an optional (n,) `tmax` go through rt_query_sweep_host and come back as an RtSweep
+        array (sweep_to_numpy); device memory, as query_closest takes it, needs out= (64 bytes per ray, 16-byte aligned), returns
+        None, and sync=False is allowed."""
+        if not _on_device(origins, dirs):
+            o, d, rad, t = _sweep_arrays(origins, dirs, radius, tmax)
+            if out is not None or not sync:
+                raise ValueError("out= and sync=False go with device-pointer inputs")
+            batch = RtSweepBatch(o.ctypes.data, d.ctypes.data, rad.ctypes.data, t.ctypes.data if t is not None else None, o.shape[0])
+            res = (RtSweep * max(o.shape[0], 1))()
+            self._check(self._l.rt_query_sweep_host(self._h, C.byref(batch), C.addressof(res)), "rt_query_sweep_host")
+            return _sweep_rows(res, o.shape[0])
+        n = _device_count(origins, n, out)
+        batch = RtSweepBatch(_device_ptr(origins, "origins", 12 * n), _device_ptr(dirs, "dirs", 12 * n), _device_ptr(radius, "radius", 4 * n),
+                             None if tmax is None else _device_ptr(tmax, "tmax", 4 * n), n)
+        self._check(self._l.rt_query_sweep(self._h, C.byref(batch), C.c_void_p(_device_ptr(out, "out", C.sizeof(RtSweep) * n, floats=False))), "rt_query_sweep")
+        if sync:
+            self.sync()
+        return None
+
     def query_radiance(self, origins, dirs, samples=1, bounces=8, ids=None, progressive=False, frame=0, environment=None, n=None, out=None,
                        sync=True):
         """The path-traced radiance along each of the caller's rays (rt_query_radiance; DESIGN.md, "Radiance queries"): `samples`
@@ -1142,6 +1164,40 @@ def within_exhaustive(scene_arrays, points, radius, k):
     if _capi.lib().rt_within_exhaustive_host(C.byref(scene_arrays), C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data) != 0:
         raise RtError("rt_within_exhaustive_host refused its arguments (k > 8, NULL arrays, n >= 2^30, or indices out of range)")
     return _nearest_rows(res, p.shape[0], k), cnt
+
+
+def _sweep_arrays(origins, dirs, radius, tmax):
+    """Host sweeps as the entry points take them: _ray_arrays' three and the (n,) radii."""
+    o, d, t = _ray_arrays(origins, dirs, tmax)
+    if radius is None:
+        raise ValueError("a sweep needs its radii")
+    rad = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+    if rad.shape[0] != o.shape[0]:
+        raise ValueError(f"radius has {rad.shape[0]} entries for {o.shape[0]} rays")
+    return o, d, rad, t
+
+
+def _sweep_rows(res, n):
+    """The n records of a sweep out of the (never empty) ctypes array they were written to."""
+    return (RtSweep * n).from_buffer(res) if n else (RtSweep * 0)()
+
+
+def sweep_to_numpy(recs):
+    """RtSweep array -> dict of numpy arrays."""
+    f, u = _record_words(recs, RtSweep)
+    return dict(t=f[:, 0].copy(), found=u[:, 1].copy(), isSphere=u[:, 2].copy(), objectIndex=u[:, 3].copy(), triIndex=u[:, 4].copy(),
+                uv=f[:, 5:7].copy(), gap=f[:, 7].copy(), point=f[:, 8:11].copy(), startsInContact=u[:, 11].copy(), normal=f[:, 12:15].copy())
+
+
+def sweep_exhaustive(scene_arrays, origins, dirs, radius, tmax=None):
+    """The definition of the sphere sweeps as a plain loop over the host arrays (rt_sweep_exhaustive_host; no GPU, no pruning):
+    `scene_arrays` is Scene.arrays(). Returns an RtSweep array (sweep_to_numpy), as Renderer.query_sweep does for numpy inputs."""
+    o, d, rad, t = _sweep_arrays(origins, dirs, radius, tmax)
+    batch = RtSweepBatch(o.ctypes.data, d.ctypes.data, rad.ctypes.data, t.ctypes.data if t is not None else None, o.shape[0])
+    res = (RtSweep * max(o.shape[0], 1))()
+    if _capi.lib().rt_sweep_exhaustive_host(C.byref(scene_arrays), C.byref(batch), C.addressof(res)) != 0:
+        raise RtError("rt_sweep_exhaustive_host refused its arguments (NULL arrays, n >= 2^30, or indices out of range)")
+    return _sweep_rows(res, o.shape[0])
 
 
 def scene_topology(scene_arrays):
