@@ -574,6 +574,74 @@ int  rt_query_radiance(rt_ctx* ctx, const RtRayBatch* d_rays, const uint32_t* d_
 int  rt_query_radiance_host(rt_ctx* ctx, const RtRayBatch* rays, const uint32_t* ids, const RtRadianceParams* params,
                             const EnvironmentData* env, float* radiance);
 
+/* Baked light at points ("Irradiance and SH probes"; include/rt_irradiance.h states the rule, both sides compile it):
+ * the irradiance at surface points with normals (a lightmap texel, a baked vertex colour), and the spherical-harmonic
+ * coefficients of the radiance around free points (the probes of an irradiance volume). Each point shoots `samples` rays by a
+ * fixed rule, rt_query_radiance's pipeline estimates the radiance along each with one path, and the records are summed in a
+ * fixed order. */
+typedef struct RtPointNormalBatch {
+    const float* points;   /* n x 3 floats, packed */
+    const float* normals;  /* n x 3; used as given (unit length is assumed); the probe form ignores it, may be NULL */
+    uint32_t n;
+} RtPointNormalBatch;
+typedef struct RtIrradianceParams {
+    uint32_t samples;      /* S, rays per point: 1 .. 2^24 - 1, and at most one radiance piece ("radiance_max_kslots" x 1024) */
+    uint32_t bounceLimit;  /* as rayTraceParams.bounceLimit; < 2^28 - 1 */
+    uint32_t progressive;  /* 0: the estimate; 1: blended with what the output holds, weight 1 / (frameCount + 1), as rt_render */
+    uint32_t frameCount;   /* seeds the directions and the paths, and weighs the blend */
+    float bias;            /* irradiance form: the origin is p + (n * 1) * bias; finite, >= 0 */
+} RtIrradianceParams;
+void rt_irradiance_params_default(RtIrradianceParams* p);   /* 64, 8, 0, 0, 0.00001f (the next-ray origin of shading) */
+/* Contract. Point i has the id pid = d_ids ? d_ids[i] : i. Its sample s (0 <= s < S) is a ray:
+ *  - directions, a shifted Hammersley set per point: st = rt_ao_state(pid, 0, frameCount); u1 = rt_random(&st), u2 = rt_random(&st);
+ *    r1 = ((float)s + u1) / (float)S; r2 = v + u2, minus 1 when >= 1, v = (float)(bitreverse32(s) >> 8) * 2^-24.
+ *    Irradiance form: cosineHemisphereDir's arithmetic (raytrace.comp:405-424, as rt_cosine_hemisphere_dir evaluates it) about the
+ *    normal, r1 under the square roots and r2 the azimuth: density cos / pi over the hemisphere.
+ *    Probe form: z = 1 - 2 r1, rho = rt_sqrt(rt_max(0, 1 - z z)), phi = 2 pi r2, dir = (rho cos phi, rho sin phi, z) in world axes:
+ *    density 1 / (4 pi) over the sphere.
+ *  - origin: p + (n * 1) * bias (irradiance form), p itself (probe form).
+ *  - L_s: the rgb rt_query_radiance gives that ray with the RNG id pid * S + s (32 bits, wrapping), one sample, `bounceLimit`,
+ *    `frameCount`, not blended, under `env`: (1, 0, 1) where the path's radiance is NaN or Inf.
+ *  - rt_query_irradiance: d_out[4 i .. 4 i + 2] = E = pi * (sum of L_s) / (float)S, d_out[4 i + 3] = 1.
+ *  - rt_query_sh_probes: d_out[27 i + 3 j + c] = 4 pi * (sum of L_s[c] * Y_j(dir_s)) / (float)S for the nine real spherical
+ *    harmonics of bands 0 to 2 in the order 1, y, z, x, xy, yz, 3 z^2 - 1, x z, x^2 - y^2, with the constants 0.282095, 0.488603,
+ *    1.092548, 0.315392, 0.546274, in world axes (the scene's "up" is -y).
+ *  - the sum's order is part of the rule: partial[l] = the terms with s = l (mod 64) in ascending s, from +0; then 64 -> 1 by halves,
+ *    partial[l] += partial[l + 32], then 16, ..., 1. The host forms below evaluate the same text in the same order, so
+ *    rt_irradiance_gather_host(rt_query_radiance(rt_irradiance_rays_host(...))) equals the device's answer in every bit.
+ *  - with `progressive` every output float but the alpha is old * (1 - w) + new * w, w = 1 / ((float)frameCount + 1).
+ *  - a point's answer depends on (position, normal, pid, params, env, scene) only: not on n, its place in the batch, or the chunks.
+ * The batch runs in chunks of whole points, as many as keep chunk x S within one radiance piece ("radiance_max_kslots" x 1024
+ * rays; by default what "frames_max_mslots" allows): k_irradiance_rays<SPHERE> writes the chunk's rays into a ctx buffer (44 bytes
+ * per ray: origin, direction, id, radiance record), the radiance pipeline runs them as rt_query_radiance would, and
+ * k_irradiance_gather<SPHERE> sums, one wave per point. The struct, the params and env are read on the host. With the plain
+ * names the arrays, d_ids and d_out (16-byte aligned for the irradiance form) are device pointers and the call is asynchronous on
+ * the ctx stream: the arrays stay valid and unchanged until the stream has passed it. The _host names take host arrays, stage
+ * them through a ctx buffer and block.
+ * The pass changes nothing a later render or query produces or chooses: not the ctx framebuffer or its progressive history, not
+ * rt_last_pipeline, rt_last_parts or rt_ray_cost. Its counters go to the AOV passes' block (paths grows by n x S). rt_last_kernel
+ * names the traversal kernel that ran.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch or NULL params; (n == 0 succeeds here
+ * and does nothing;) points, normals (irradiance form) or the output NULL; samples 0 or >= 2^24; bounceLimit >= 2^28 - 1; bias
+ * not finite or < 0; samples above the rays of one piece; n >= 2^30. */
+int  rt_query_irradiance(rt_ctx* ctx, const RtPointNormalBatch* d_batch, const uint32_t* d_ids, const RtIrradianceParams* params,
+                         const EnvironmentData* env, float* d_out);
+int  rt_query_irradiance_host(rt_ctx* ctx, const RtPointNormalBatch* batch, const uint32_t* ids, const RtIrradianceParams* params,
+                              const EnvironmentData* env, float* out);
+int  rt_query_sh_probes(rt_ctx* ctx, const RtPointNormalBatch* d_batch, const uint32_t* d_ids, const RtIrradianceParams* params,
+                        const EnvironmentData* env, float* d_out);
+int  rt_query_sh_probes_host(rt_ctx* ctx, const RtPointNormalBatch* batch, const uint32_t* ids, const RtIrradianceParams* params,
+                             const EnvironmentData* env, float* out);
+/* The host forms of the rule: no ctx, no GPU. `sphere` != 0: the probe form. rt_irradiance_rays_host: the rays of points
+ * [first, first + count) of the batch, ray (i - first) * S + s at origins / dirs [3 ray ..] and rayIds[ray] (count x S of each).
+ * rt_irradiance_gather_host: radiance holds 4 floats per ray of the whole batch (ray i * S + s), out 4 n or 27 n floats, read as
+ * the previous result when `progressive`; the probe form reads no array of the batch. -1: a NULL argument, samples 0 or
+ * >= 2^24, a bias that is not finite or < 0, first + count > n. */
+int  rt_irradiance_rays_host(const RtPointNormalBatch* batch, const uint32_t* ids, const RtIrradianceParams* params, int sphere,
+                             uint32_t first, uint32_t count, float* origins, float* dirs, uint32_t* rayIds);
+int  rt_irradiance_gather_host(const RtPointNormalBatch* batch, const uint32_t* ids, const RtIrradianceParams* params, int sphere,
+                               const float* radiance, float* out);
+
 /* Point queries ("Point queries"): how far each of the caller's points is from the scene, and where the nearest surface
  * is. The search is not a ray's: a best-first descent pruned by box distance, in a kernel of its own (k_nearest_points) over the
  * tables the scene already has on the device. */

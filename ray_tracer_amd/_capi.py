@@ -134,6 +134,15 @@ class RtRadianceParams(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("bounceLimit", C.c_uint32), ("progressive", C.c_uint32), ("frameCount", C.c_uint32)]
 
 
+class RtPointNormalBatch(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("normals", C.c_void_p), ("n", C.c_uint32)]
+
+
+class RtIrradianceParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("bounceLimit", C.c_uint32), ("progressive", C.c_uint32), ("frameCount", C.c_uint32),
+                ("bias", C.c_float)]
+
+
 class RtAoParams(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32)]
 
@@ -234,6 +243,13 @@ SYMBOLS = {
     "rt_radiance_params_default": (None, [_P(RtRadianceParams)]),
     "rt_query_radiance": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),
     "rt_query_radiance_host": (C.c_int, [_vp, _P(RtRayBatch), _vp, _P(RtRadianceParams), _P(EnvironmentData), _vp]),
+    "rt_irradiance_params_default": (None, [_P(RtIrradianceParams)]),
+    "rt_query_irradiance": (C.c_int, [_vp, _P(RtPointNormalBatch), _vp, _P(RtIrradianceParams), _P(EnvironmentData), _vp]),
+    "rt_query_irradiance_host": (C.c_int, [_vp, _P(RtPointNormalBatch), _vp, _P(RtIrradianceParams), _P(EnvironmentData), _vp]),
+    "rt_query_sh_probes": (C.c_int, [_vp, _P(RtPointNormalBatch), _vp, _P(RtIrradianceParams), _P(EnvironmentData), _vp]),
+    "rt_query_sh_probes_host": (C.c_int, [_vp, _P(RtPointNormalBatch), _vp, _P(RtIrradianceParams), _P(EnvironmentData), _vp]),
+    "rt_irradiance_rays_host": (C.c_int, [_P(RtPointNormalBatch), _vp, _P(RtIrradianceParams), C.c_int, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "rt_irradiance_gather_host": (C.c_int, [_P(RtPointNormalBatch), _vp, _P(RtIrradianceParams), C.c_int, _vp, _vp]),
     "rt_ao_params_default": (None, [_P(RtAoParams)]),
     "rt_render_ao": (C.c_int, [_vp, C.c_uint32, _P(RtAovBuffers), _P(RtAoParams), _vp]),
     "rt_read_ao": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),

@@ -24,6 +24,8 @@
 #include "point_within.h"
 #include "rt_sweep.hip.h"         // the kernel of the sphere sweeps; sweep_queries.h: their checks, the arithmetic of a batch, the stack choice
 #include "sweep_queries.h"
+#include "rt_irradiance.hip.h"    // the two kernels of the baked-light queries around the radiance pipeline; irradiance_queries.h: their checks, chunks and byte counts
+#include "irradiance_queries.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -137,6 +139,7 @@ struct rt_ctx {
     } topo;
     DevBuf hitsListBuf;     // all-hit ray queries: the lists of k_ray_hits<64, true>, whose stack leaves no LDS for them
     DevBuf withinListBuf;   // radius point queries: the lists of k_points_within<64, true>, likewise
+    DevBuf irradianceBuf;   // baked-light queries: a chunk's rays, ray ids and radiance records (irradiance_scratch), at most 44 bytes x the piece cap
     size_t aoPixels = 0;
     DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
     // the denoiser (rt_denoise): its work planes and the ctx-owned output
@@ -1820,7 +1823,89 @@ int rt_query_radiance_host(rt_ctx* c, const RtRayBatch* rays, const uint32_t* id
         return radiance_device(c, fn, &dev, (const uint32_t*)d[2], params, env, (float*)d[3]);
     });
 }
+}  // extern "C"
 
+// ---- baked-light queries (irradiance_queries.h has the checks, the chunks and the byte counts; include/rt_irradiance.h the rule;
+// DESIGN.md, "Irradiance and SH probes")
+namespace {
+// Chunk by chunk: k_irradiance_rays into the ctx scratch, the chunk's rays through radiance_device() as one piece (one path per
+// ray, not blended), k_irradiance_gather into the caller's array. Everything is enqueued on the ctx stream; the only wait is the
+// one before the scratch grows.
+template <bool SPHERE>
+int irradiance_device(rt_ctx* c, const char* fn, const RtPointNormalBatch* b, const uint32_t* d_ids, const RtIrradianceParams* params,
+                      const EnvironmentData* env, float* d_out) {
+    if (!c) return -1;
+    const uint64_t maxSlots = radiance_max_slots(c);
+    const std::string refusal = check_irradiance_query(fn, SPHERE, c->sc.nodes != nullptr, b, params, d_out, maxSlots);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = b->n, S = params->samples;
+    if (n == 0) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    const uint32_t most = std::min(n, irradiance_chunk_points(S, maxSlots));   // points of the largest chunk
+    const IrradianceScratch sl = irradiance_scratch(most * S);
+    if (c->irradianceBuf.bytes < sl.bytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees arrays a pass in flight may be using
+    int rc = dev_alloc(c, c->irradianceBuf, sl.bytes);
+    if (rc) return rc;
+    char* const base = (char*)c->irradianceBuf.p;
+    IrradianceArgs a{b->points, b->normals, d_ids, 0u, 0u, S, params->frameCount, params->bias, (float*)(base + sl.origins),
+                     (float*)(base + sl.dirs), (uint32_t*)(base + sl.ids), (const float4*)(base + sl.radiance), d_out,
+                     params->progressive, params->frameCount};
+    const RtRadianceParams rp{1u, params->bounceLimit, 0u, params->frameCount};
+    const uint32_t chunks = irradiance_chunk_count(n, S, maxSlots);
+    for (uint32_t k = 0; k < chunks; k++) {
+        const IrradianceChunk ch = irradiance_chunk(n, S, maxSlots, k);
+        a.first = ch.first; a.count = ch.n;
+        const uint32_t rays = ch.n * S;
+        hipLaunchKernelGGL((k_irradiance_rays<SPHERE>), dim3((rays + RT_IRR_BLOCK - 1) / RT_IRR_BLOCK), dim3(RT_IRR_BLOCK), 0, c->stream, a);
+        RT_HIP(c, hipGetLastError());
+        const RtRayBatch rb{a.origins, a.dirs, nullptr, rays};
+        if ((rc = radiance_device(c, fn, &rb, a.rayIds, &rp, env, (float*)(base + sl.radiance)))) return rc;
+        const uint32_t groups = (ch.n + RT_IRR_BLOCK / 64 - 1) / (RT_IRR_BLOCK / 64);
+        hipLaunchKernelGGL((k_irradiance_gather<SPHERE>), dim3(groups), dim3(RT_IRR_BLOCK), 0, c->stream, a);
+        RT_HIP(c, hipGetLastError());
+    }
+    return 0;
+}
+
+// The host-memory form (staged): points, normals, ids, and the result, which goes up as well when it is blended with
+template <bool SPHERE>
+int irradiance_host(rt_ctx* c, const char* fn, const RtPointNormalBatch* b, const uint32_t* ids, const RtIrradianceParams* params,
+                    const EnvironmentData* env, float* out) {
+    if (!c) return -1;
+    const std::string refusal = check_irradiance_query(fn, SPHERE, c->sc.nodes != nullptr, b, params, out, radiance_max_slots(c));
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = b->n;
+    if (n == 0) return 0;
+    const IrradianceShape g = irradiance_shape(n, ids != nullptr, SPHERE);
+    const StagePart parts[] = {{b->points, nullptr, g.vecBytes}, {b->normals, nullptr, !SPHERE ? g.vecBytes : 0}, {ids, nullptr, g.idBytes},
+                               {params->progressive ? out : nullptr, out, g.outBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtPointNormalBatch dev{(const float*)d[0], (const float*)d[1], n};
+        return irradiance_device<SPHERE>(c, fn, &dev, (const uint32_t*)d[2], params, env, (float*)d[3]);
+    });
+}
+}  // namespace
+
+extern "C" {
+int rt_query_irradiance(rt_ctx* c, const RtPointNormalBatch* d_batch, const uint32_t* d_ids, const RtIrradianceParams* params,
+                        const EnvironmentData* env, float* d_out) {
+    return irradiance_device<false>(c, "rt_query_irradiance", d_batch, d_ids, params, env, d_out);
+}
+int rt_query_irradiance_host(rt_ctx* c, const RtPointNormalBatch* batch, const uint32_t* ids, const RtIrradianceParams* params,
+                             const EnvironmentData* env, float* out) {
+    return irradiance_host<false>(c, "rt_query_irradiance_host", batch, ids, params, env, out);
+}
+int rt_query_sh_probes(rt_ctx* c, const RtPointNormalBatch* d_batch, const uint32_t* d_ids, const RtIrradianceParams* params,
+                       const EnvironmentData* env, float* d_out) {
+    return irradiance_device<true>(c, "rt_query_sh_probes", d_batch, d_ids, params, env, d_out);
+}
+int rt_query_sh_probes_host(rt_ctx* c, const RtPointNormalBatch* batch, const uint32_t* ids, const RtIrradianceParams* params,
+                            const EnvironmentData* env, float* out) {
+    return irradiance_host<true>(c, "rt_query_sh_probes_host", batch, ids, params, env, out);
+}
+}  // extern "C"
+
+extern "C" {
 // `samples` rounds of {k_ao_rays, the traversal, k_ao_count}, all enqueued without waiting for the device, then k_ao_resolve
 int rt_render_ao(rt_ctx* c, uint32_t nPixels, const RtAovBuffers* d_aovs, const RtAoParams* params, float* d_ao) {
     if (!c) return -1;

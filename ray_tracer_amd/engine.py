@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .devmem import DeviceBuffer, RtError, hip as _hip   # noqa: F401  (engine.RtError and engine._hip are where callers know them)
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtMeshTopology, RtNearest, RtPointBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -714,6 +714,90 @@ class Renderer:
             self.sync()
         return None
 
+    def query_irradiance(self, points, normals, samples=64, bounces=8, ids=None, progressive=False, frame=0, bias=1e-5, environment=None,
+                         n=None, out=None, sync=True):
+        """The irradiance at surface points with normals (rt_query_irradiance; DESIGN.md, "Irradiance and SH probes"): E = pi x the
+        mean radiance of `samples` cosine-distributed rays per point, each one path of at most `bounces` bounces, the directions
+        and the paths seeded from ids[i] (or i) and `frame`; rgb and alpha 1 per point. The normals are used as given (unit
+        length is assumed); the rays start at p + n * bias. (n, 3) float32 numpy arrays (and (n,) uint32 ids) go through
+        rt_query_irradiance_host and come back as an (n, 4) float32 array; with `progressive`, `out` is the previous result the new
+        one is blended with, and is not modified. Torch tensors on the device (anything with data_ptr(): fp32, contiguous; ids
+        uint32 or int32) or integer device pointers with n= go through the asynchronous entry point into `out` (device memory, 16
+        bytes per point), and sync=False is allowed. A wrong dtype or shape raises before the library is called."""
+        return self._query_baked(False, points, normals, samples, bounces, ids, progressive, frame, bias, environment, n, out, sync)
+
+    def query_sh_probes(self, points, samples=64, bounces=8, ids=None, progressive=False, frame=0, environment=None, n=None, out=None,
+                        sync=True):
+        """The spherical-harmonic coefficients of the radiance around free points (rt_query_sh_probes): c_j = 4 pi x the mean of
+        L Y_j over `samples` rays spread on the sphere, for the nine real SH of bands 0..2 in the order 1, y, z, x, xy, yz,
+        3z^2 - 1, xz, x^2 - y^2, in world axes: (n, 9, 3) float32, [j][rgb] (device form: 108 bytes per point in `out`). The
+        arguments are query_irradiance's without the normals and the bias; sh9_irradiance() turns the result into irradiance."""
+        return self._query_baked(True, points, None, samples, bounces, ids, progressive, frame, 0.0, environment, n, out, sync)
+
+    def _query_baked(self, sphere, points, normals, samples, bounces, ids, progressive, frame, bias, environment, n, out, sync):
+        what = "rt_query_sh_probes" if sphere else "rt_query_irradiance"
+        width = 27 if sphere else 4
+        if environment is not None and not isinstance(environment, _capi.EnvironmentData):
+            raise TypeError("environment: an EnvironmentData (PushConstants.environment) or None")
+        if int(samples) < 0 or int(bounces) < 0 or int(frame) < 0:
+            raise ValueError("samples, bounces and frame are unsigned")
+        p = RtIrradianceParams(int(samples), int(bounces), 1 if progressive else 0, int(frame) & 0xFFFFFFFF, float(bias))
+        env = C.byref(environment) if environment is not None else None
+        inputs = [("points", points)] + ([] if sphere else [("normals", normals)])
+        if not _on_device(*[a for _, a in inputs]):
+            arrays = [(name, np.asarray(a)) for name, a in inputs]
+            for name, a in arrays:
+                if a.dtype != np.float32:
+                    raise TypeError(f"{name}: {a.dtype}, not float32")
+                if a.ndim != 2 or a.shape[1] != 3:
+                    raise ValueError(f"{name}: shape {a.shape}, not (n, 3)")
+            if arrays[-1][1].shape != arrays[0][1].shape:
+                raise ValueError(f"points {arrays[0][1].shape} and normals {arrays[-1][1].shape}: not one (n, 3) pair")
+            count = arrays[0][1].shape[0]
+            i = None
+            if ids is not None:
+                i = np.asarray(ids)
+                if i.dtype != np.uint32:
+                    raise TypeError(f"ids: {i.dtype}, not uint32")
+                if i.shape != (count,):
+                    raise ValueError(f"ids: shape {i.shape}, not ({count},)")
+                i = np.ascontiguousarray(i)
+            if not sync:
+                raise ValueError("sync=False goes with device-pointer inputs")
+            if out is not None and not progressive:
+                raise ValueError("out= with host arrays is the previous result of a progressive query")
+            shape = (count, 9, 3) if sphere else (count, 4)
+            if progressive:
+                if out is None:
+                    raise ValueError("progressive needs out=: the previous result")
+                prev = np.asarray(out)
+                if prev.dtype != np.float32:
+                    raise TypeError(f"out: {prev.dtype}, not float32")
+                if prev.shape != shape:
+                    raise ValueError(f"out: shape {prev.shape}, not {shape}")
+                res = np.array(prev, dtype=np.float32, order="C", copy=True)
+            else:
+                res = np.zeros(shape, np.float32)
+            held = [np.ascontiguousarray(a) for _, a in arrays]
+            batch = RtPointNormalBatch(held[0].ctypes.data, None if sphere else held[1].ctypes.data, count)
+            self._check(getattr(self._l, what + "_host")(self._h, C.byref(batch), i.ctypes.data if i is not None else None, C.byref(p), env,
+                                                         res.ctypes.data), what + "_host")
+            return res
+        counted = n is None
+        n = _device_count(points, n, out)
+        if counted and hasattr(points, "shape") and (len(points.shape) != 2 or points.shape[1] != 3):
+            raise ValueError(f"points: shape {tuple(points.shape)}, not (n, 3)")
+        if not sphere and hasattr(normals, "shape") and hasattr(points, "shape") and tuple(normals.shape) != tuple(points.shape):
+            raise ValueError(f"points {tuple(points.shape)} and normals {tuple(normals.shape)}: not one (n, 3) pair")
+        if ids is not None and hasattr(ids, "dtype") and not str(ids.dtype).endswith(("uint32", "int32")):
+            raise TypeError(f"ids: {ids.dtype}, not uint32 (or int32)")
+        batch = RtPointNormalBatch(_device_ptr(points, "points", 12 * n), None if sphere else _device_ptr(normals, "normals", 12 * n), n)
+        d_ids = None if ids is None else _device_ptr(ids, "ids", 4 * n, floats=False)
+        self._check(getattr(self._l, what)(self._h, C.byref(batch), d_ids, C.byref(p), env, C.c_void_p(_device_ptr(out, "out", 4 * width * n))), what)
+        if sync:
+            self.sync()
+        return None
+
     def render_ao(self, aovs=None, samples=4, radius=0.5, seed=0):
         """The ambient-occlusion plane of first-hit planes (rt_render_ao): `samples` cosine-weighted occlusion queries of reach
         `radius` per hit record. Without `aovs`: the context's own planes of the last render_aovs(); else the dict render_aovs()
@@ -1035,6 +1119,82 @@ def ao_rays(aovs, sample, samples=4, radius=0.5, seed=0):
                                    v.ctypes.data_as(C.POINTER(C.c_uint8))) != 0:
         raise RtError("rt_ao_rays_host refused its arguments (samples 1..64, radius finite and > 0, sample < samples, at least one pixel)")
     return o, d, v.astype(bool)
+
+
+def _baked_batch(points, normals, ids, samples, frame, bias, progressive=False):
+    """The host structs of the baked-light rule's host forms; normals None: the probe form. Returns (batch, ids, params, held)."""
+    pts = np.ascontiguousarray(points, np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points: shape {pts.shape}, not (n, 3)")
+    nrm = None
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, np.float32)
+        if nrm.shape != pts.shape:
+            raise ValueError(f"points {pts.shape} and normals {nrm.shape}: not one (n, 3) pair")
+    i = None
+    if ids is not None:
+        i = np.ascontiguousarray(ids, np.uint32)
+        if i.shape != (len(pts),):
+            raise ValueError(f"ids: shape {i.shape}, not ({len(pts)},)")
+    batch = RtPointNormalBatch(pts.ctypes.data, None if nrm is None else nrm.ctypes.data, len(pts))
+    params = RtIrradianceParams(int(samples), 0, 1 if progressive else 0, int(frame) & 0xFFFFFFFF, float(bias))
+    return batch, i, params, (pts, nrm)
+
+
+def irradiance_rays(points, normals=None, samples=64, ids=None, frame=0, bias=1e-5, first=0, count=None):
+    """The rays query_irradiance() (normals given) or query_sh_probes() (normals None) shoots for points [first, first + count) of
+    the batch, computed on the host by the rule the device compiles (rt_irradiance_rays_host; no GPU): (origins (count * samples,
+    3), dirs likewise, rayIds (count * samples,) uint32), ray (i - first) * samples + s being sample s of point i."""
+    batch, i, params, held = _baked_batch(points, normals, ids, samples, frame, bias)
+    count = batch.n - int(first) if count is None else int(count)
+    rays = max(count, 0) * int(samples)
+    o, d, r = np.zeros((rays, 3), np.float32), np.zeros((rays, 3), np.float32), np.zeros(rays, np.uint32)
+    if _capi.lib().rt_irradiance_rays_host(C.byref(batch), None if i is None else i.ctypes.data, C.byref(params), 0 if normals is not None else 1,
+                                           int(first), count, o.ctypes.data, d.ctypes.data, r.ctypes.data) != 0:
+        raise RtError("rt_irradiance_rays_host refused its arguments (samples 1 .. 2^24 - 1, bias finite and >= 0, first + count <= n)")
+    return o, d, r
+
+
+def irradiance_gather(radiance, n, samples=64, ids=None, frame=0, sphere=False, progressive=False, out=None):
+    """What the device makes of the radiance records of a batch's rays ((n * samples, 4) float32, as query_radiance() returns them
+    for irradiance_rays()' rays), by the rule's weights and summation order on the host (rt_irradiance_gather_host; no GPU):
+    (n, 4) irradiance, or with `sphere` (n, 9, 3) SH coefficients; with `progressive` blended with the previous result `out`
+    (not modified) at weight 1 / (frame + 1)."""
+    n = int(n)
+    rad = np.ascontiguousarray(radiance, np.float32)
+    if rad.shape != (n * int(samples), 4):
+        raise ValueError(f"radiance: shape {rad.shape}, not ({n * int(samples)}, 4)")
+    shape = (n, 9, 3) if sphere else (n, 4)
+    if progressive:
+        if out is None or np.asarray(out).shape != shape:
+            raise ValueError(f"progressive needs out=: the previous result {shape}")
+        res = np.array(out, dtype=np.float32, order="C", copy=True)
+    else:
+        res = np.zeros(shape, np.float32)
+    i = None if ids is None else np.ascontiguousarray(ids, np.uint32)
+    if i is not None and i.shape != (n,):
+        raise ValueError(f"ids: shape {i.shape}, not ({n},)")
+    batch = RtPointNormalBatch(None, None, n)
+    params = RtIrradianceParams(int(samples), 0, 1 if progressive else 0, int(frame) & 0xFFFFFFFF, 0.0)
+    if _capi.lib().rt_irradiance_gather_host(C.byref(batch), None if i is None else i.ctypes.data, C.byref(params), 1 if sphere else 0,
+                                             rad.ctypes.data, res.ctypes.data) != 0:
+        raise RtError("rt_irradiance_gather_host refused its arguments (samples 1 .. 2^24 - 1)")
+    return res
+
+
+def sh9_irradiance(coeffs, normals):
+    """The irradiance on a surface of normal `normals` ((n, 3), or (3,) for all) under the radiance whose SH coefficients are
+    `coeffs` ((n, 9, 3), query_sh_probes' order): the convolution with the clamped cosine lobe, band weights pi, 2 pi / 3, pi / 4.
+    numpy, float64: (n, 3)."""
+    c = np.asarray(coeffs, np.float64)
+    if c.ndim != 3 or c.shape[1:] != (9, 3):
+        raise ValueError(f"coeffs: shape {c.shape}, not (n, 9, 3)")
+    nn = np.broadcast_to(np.asarray(normals, np.float64), (c.shape[0], 3))
+    x, y, z = nn[:, 0], nn[:, 1], nn[:, 2]
+    basis = np.stack([0.282095 * np.ones_like(x), 0.488603 * y, 0.488603 * z, 0.488603 * x, 1.092548 * x * y, 1.092548 * y * z,
+                      0.315392 * (3.0 * z * z - 1.0), 1.092548 * x * z, 0.546274 * (x * x - y * y)], axis=1)
+    band = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+    return np.einsum("nj,njc->nc", basis * band, c)
 
 
 def aovs_to_numpy(planes):
