@@ -642,6 +642,69 @@ int  rt_irradiance_rays_host(const RtPointNormalBatch* batch, const uint32_t* id
 int  rt_irradiance_gather_host(const RtPointNormalBatch* batch, const uint32_t* ids, const RtIrradianceParams* params, int sphere,
                                const float* radiance, float* out);
 
+/* Lightmap texels ("Lightmap texels"; include/rt_texels.h states the rule, both sides compile it): the surface point
+ * and shading normal behind every texel of a W x H map laid over one object's uv layout, the batch rt_query_irradiance takes, the
+ * way back into the map, and gutter texels around the charts. */
+typedef struct RtTexel {
+    float point[3];  uint32_t state;     /* world position; state: 0 empty, 1 covered, 3 covered and overlapped */
+    float normal[3]; uint32_t triIndex;  /* the shading normal; the owner, as RtHit.triHitIndex numbers triangles */
+    float uv[2];     uint32_t _pad[2];   /* the owner's barycentrics (u, v) at the texel's centre; 0 */
+} RtTexel;                               /* 48 bytes, three 16-byte stores; an empty record is all 0 */
+typedef struct RtTexelStats {
+    uint32_t covered;           /* records with state != 0 */
+    uint32_t overlapped;        /* records with state == 3 */
+    uint32_t skippedTriangles;  /* triangles of the object that cover nothing by the rule: a uv that is not finite, |X| or |Y| >= 2^27, area 0 */
+    uint32_t degenerateTexels;  /* texels whose owner gives no finite normal: left empty */
+} RtTexelStats;
+/* Contract (the rule in full: include/rt_texels.h).
+ *  - The map is width x height, each 1 .. 8192, rows top to bottom; record y * width + x is texel (x, y), whose centre is
+ *    u = (x + 0.5) / W, v = 1 - (y + 0.5) / H: the texel rt_tex_index(u, W), rt_tex_index(1 - v, H) picks for that uv.
+ *  - Coverage in exact integers on a grid of 256 sub-texels: a uv corner snaps to X = rint(u * 256 W), Y = rint((1 - v) * 256 H) in
+ *    doubles, ties to even; a centre (256 x + 128, 256 y + 128) is covered by a triangle when its three edge functions, normalised to
+ *    the winding that makes the doubled area A positive, are > 0, or == 0 on a top or left edge. Either winding works; a centre on
+ *    an edge two triangles share belongs to exactly one of them. Triangles with a uv that is not finite, |X| or |Y| >= 2^27, or A = 0
+ *    are skipped and counted.
+ *  - The owner is the lowest triangle index that covers the centre, `overlapped` (state 3) when two or more do: functions of the
+ *    scene alone.
+ *  - uv = (u, v) = ((float)(E1 / A), (float)(E2 / A)) in doubles, w = (1 - u) - v; point = rt_bary_point of the world corners as
+ *    rt_query_nearest places them; normal = rt_normalize(fwd x ((n0 w + n1 u) + n2 v)), reconstruct_hit's for a front-face hit
+ *    without the bump map; where that is not finite the normalised world face normal on the side of the vertex normals' sum; where
+ *    that is not finite either the texel stays empty and is counted in degenerateTexels.
+ * rt_bake_texels: d_texels is device memory, 16-byte aligned, 48 bytes per texel; asynchronous on the ctx stream, except that a
+ * statsOut (host memory) makes the call wait for them. Kernels: k_texel_bins (one lane per triangle: the 8 x 8-texel blocks its
+ * box touches), an exclusive scan, k_texel_cover (one wave per (triangle, block), one lane per texel, atomicMin on an owner plane
+ * in ctx scratch), k_texel_resolve (one lane per texel: the record). rt_bake_texels_host: host memory, blocks. They read the
+ * scene tables as they are (after rt_update_objects and rt_update_points too) and change nothing a later render or query
+ * produces or chooses. rt_texels_exhaustive_host: the same rule in plain loops over the host arrays, no ctx, no GPU; -1: a NULL
+ * argument, an object, a size or indices out of range, or a mesh whose triangles are not one contiguous range.
+ * rt_texels_compact: the covered texels in ascending texel index (by a scan, not by atomics) as packed points and normals
+ * (RtPointNormalBatch's layout) and d_index[j] = y * W + x, which rt_query_irradiance takes as ids, so a texel's light depends on
+ * its place in the map and never on which other texels are covered; d_countOut[0] (device) = how many. Each array holds nTexels
+ * entries' worth.
+ * rt_texels_scatter: d_rgba[d_index[j]] = d_values4[j] (4 floats) and d_fill[d_index[j]] = 1 for j < nCovered; every other texel
+ * (0, 0, 0, 0) and fill 0.
+ * rt_dilate_texels: `passes` (<= 254) passes in ping-pong through a ctx plane; pass k (from 1): a texel with fill 0 and at least
+ * one 8-neighbour (no wrap) with fill != 0 gets the sum of those neighbours' rgb, in the order (-1,-1), (0,-1), (1,-1), (-1,0),
+ * (1,0), (-1,1), (0,1), (1,1) from +0, divided by (float)count, alpha 0, fill 1 + k. rt_dilate_texels_host: the same, host memory,
+ * no ctx, no GPU; -1: a NULL plane, a size out of range, passes > 254.
+ * rt_bake_lightmap: rt_bake_texels, rt_texels_compact, rt_query_irradiance(ids = index), rt_texels_scatter, rt_dilate_texels,
+ * in that order through ctx scratch, equal to the composition by hand in every bit; d_rgba (16-byte aligned, 16 bytes per texel)
+ * and d_fill (1 byte per texel) are device memory. It waits once, for the count of covered texels. One shot: params->progressive
+ * != 0 is refused.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL output; object >= the object count; width or
+ * height 0 or > 8192; an object whose mesh's triangles are not one contiguous range; then, for rt_bake_lightmap, NULL params,
+ * progressive, dilatePasses > 254 and rt_query_irradiance's own refusals. rt_texels_compact / _scatter / rt_dilate_texels refuse
+ * NULL arrays and nTexels (width x height) 0 or > 8192 x 8192, nCovered > nTexels, passes > 254. */
+int  rt_bake_texels(rt_ctx* ctx, uint32_t object, uint32_t width, uint32_t height, RtTexel* d_texels, RtTexelStats* statsOut);
+int  rt_bake_texels_host(rt_ctx* ctx, uint32_t object, uint32_t width, uint32_t height, RtTexel* texels, RtTexelStats* stats);
+int  rt_texels_exhaustive_host(const RtSceneArrays* scene, uint32_t object, uint32_t width, uint32_t height, RtTexel* texels, RtTexelStats* stats);
+int  rt_texels_compact(rt_ctx* ctx, uint32_t nTexels, const RtTexel* d_texels, float* d_points, float* d_normals, uint32_t* d_index, uint32_t* d_countOut);
+int  rt_texels_scatter(rt_ctx* ctx, uint32_t nTexels, uint32_t nCovered, const uint32_t* d_index, const float* d_values4, float* d_rgba, uint8_t* d_fill);
+int  rt_dilate_texels(rt_ctx* ctx, uint32_t width, uint32_t height, uint32_t passes, float* d_rgba, uint8_t* d_fill);
+int  rt_dilate_texels_host(uint32_t width, uint32_t height, uint32_t passes, float* rgba, uint8_t* fill);
+int  rt_bake_lightmap(rt_ctx* ctx, uint32_t object, uint32_t width, uint32_t height, const RtIrradianceParams* params, const EnvironmentData* env,
+                      uint32_t dilatePasses, float* d_rgba, uint8_t* d_fill, RtTexelStats* statsOut);
+
 /* Point queries ("Point queries"): how far each of the caller's points is from the scene, and where the nearest surface
  * is. The search is not a ray's: a best-first descent pruned by box distance, in a kernel of its own (k_nearest_points) over the
  * tables the scene already has on the device. */

@@ -143,6 +143,15 @@ class RtIrradianceParams(C.Structure):
                 ("bias", C.c_float)]
 
 
+class RtTexel(C.Structure):
+    _fields_ = [("point", C.c_float * 3), ("state", C.c_uint32), ("normal", C.c_float * 3), ("triIndex", C.c_uint32),
+                ("uv", C.c_float * 2), ("_pad", C.c_uint32 * 2)]
+
+
+class RtTexelStats(C.Structure):
+    _fields_ = [("covered", C.c_uint32), ("overlapped", C.c_uint32), ("skippedTriangles", C.c_uint32), ("degenerateTexels", C.c_uint32)]
+
+
 class RtAoParams(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("radius", C.c_float), ("seed", C.c_uint32)]
 
@@ -250,6 +259,15 @@ SYMBOLS = {
     "rt_query_sh_probes_host": (C.c_int, [_vp, _P(RtPointNormalBatch), _vp, _P(RtIrradianceParams), _P(EnvironmentData), _vp]),
     "rt_irradiance_rays_host": (C.c_int, [_P(RtPointNormalBatch), _vp, _P(RtIrradianceParams), C.c_int, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "rt_irradiance_gather_host": (C.c_int, [_P(RtPointNormalBatch), _vp, _P(RtIrradianceParams), C.c_int, _vp, _vp]),
+    "rt_bake_texels": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _P(RtTexelStats)]),
+    "rt_bake_texels_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _P(RtTexelStats)]),
+    "rt_texels_exhaustive_host": (C.c_int, [_P(RtSceneArrays), C.c_uint32, C.c_uint32, C.c_uint32, _vp, _P(RtTexelStats)]),
+    "rt_texels_compact": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "rt_texels_scatter": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "rt_dilate_texels": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "rt_dilate_texels_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "rt_bake_lightmap": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _P(RtIrradianceParams), _P(EnvironmentData), C.c_uint32, _vp, _vp,
+                                   _P(RtTexelStats)]),
     "rt_ao_params_default": (None, [_P(RtAoParams)]),
     "rt_render_ao": (C.c_int, [_vp, C.c_uint32, _P(RtAovBuffers), _P(RtAoParams), _vp]),
     "rt_read_ao": (C.c_int, [_vp, _P(C.c_float), C.c_size_t]),

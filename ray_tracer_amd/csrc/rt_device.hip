@@ -26,6 +26,8 @@
 #include "sweep_queries.h"
 #include "rt_irradiance.hip.h"    // the two kernels of the baked-light queries around the radiance pipeline; irradiance_queries.h: their checks, chunks and byte counts
 #include "irradiance_queries.h"
+#include "rt_texels.hip.h"        // the kernels of the lightmap texel passes; texel_queries.h: their checks, launch shapes, scan levels and byte counts
+#include "texel_queries.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -140,6 +142,9 @@ struct rt_ctx {
     DevBuf hitsListBuf;     // all-hit ray queries: the lists of k_ray_hits<64, true>, whose stack leaves no LDS for them
     DevBuf withinListBuf;   // radius point queries: the lists of k_points_within<64, true>, likewise
     DevBuf irradianceBuf;   // baked-light queries: a chunk's rays, ray ids and radiance records (irradiance_scratch), at most 44 bytes x the piece cap
+    // lightmap texels: a bake's planes and scan (texel_scratch), the compaction's block sums, the dilation's second plane, and
+    // rt_bake_lightmap's records, batch and values (lightmap_scratch)
+    DevBuf bakeTexelBuf, bakeScanBuf, bakeDilateBuf, lightmapBuf;
     size_t aoPixels = 0;
     DevBuf shadeStatBuf;                  // k_shade's striped statistics (ShadeStatStripe), zero between dispatches
     // the denoiser (rt_denoise): its work planes and the ctx-owned output
@@ -1902,6 +1907,210 @@ int rt_query_sh_probes(rt_ctx* c, const RtPointNormalBatch* d_batch, const uint3
 int rt_query_sh_probes_host(rt_ctx* c, const RtPointNormalBatch* batch, const uint32_t* ids, const RtIrradianceParams* params,
                             const EnvironmentData* env, float* out) {
     return irradiance_host<true>(c, "rt_query_sh_probes_host", batch, ids, params, env, out);
+}
+}  // extern "C"
+
+// ---- lightmap texels (texel_queries.h has the checks, the launch shapes, the scan's levels and the byte counts; include/rt_texels.h
+// the rule; DESIGN.md, "Lightmap texels")
+namespace {
+// a ctx scratch of at least `bytes`; growing frees memory a pass in flight may be using, so it waits first
+int texel_buffer(rt_ctx* c, DevBuf& b, size_t bytes) {
+    if (b.bytes < bytes) RT_HIP(c, hipStreamSynchronize(c->stream));
+    return dev_alloc(c, b, bytes);
+}
+
+// The exclusive scan of n values (load(i)) into excl (NULL: only the scanned block sums are wanted), level by level through
+// `sums` (scan_levels(n).elems values). Afterwards sums[0 .. ceil(n / 256)) holds what precedes each block of level 0.
+template <typename T, typename LOAD>
+int scan_exclusive(rt_ctx* c, LOAD load, uint64_t n, T* excl, T* sums) {
+    const ScanLevels L = scan_levels(n);
+    hipLaunchKernelGGL((k_scan_local<T, LOAD>), dim3(texel_groups(L.count[0], RT_TEXEL_GROUP)), dim3(RT_TEXEL_GROUP), 0, c->stream, load,
+                       (unsigned long long)L.count[0], excl, sums + L.offset[0]);
+    for (int l = 1; l < L.levels; l++) {
+        T* const vals = sums + L.offset[l - 1];
+        hipLaunchKernelGGL((k_scan_local<T, ScanLoadSame<T>>), dim3(texel_groups(L.count[l], RT_TEXEL_GROUP)), dim3(RT_TEXEL_GROUP), 0, c->stream,
+                           ScanLoadSame<T>{vals}, (unsigned long long)L.count[l], vals, sums + L.offset[l]);
+    }
+    for (int l = L.levels - 2; l >= 1; l--)
+        hipLaunchKernelGGL((k_scan_add<T>), dim3(texel_groups(L.count[l], RT_TEXEL_GROUP)), dim3(RT_TEXEL_GROUP), 0, c->stream, sums + L.offset[l - 1],
+                           (unsigned long long)L.count[l], (const T*)(sums + L.offset[l]));
+    if (excl)
+        hipLaunchKernelGGL((k_scan_add<T>), dim3(texel_groups(L.count[0], RT_TEXEL_GROUP)), dim3(RT_TEXEL_GROUP), 0, c->stream, excl,
+                           (unsigned long long)L.count[0], (const T*)(sums + L.offset[0]));
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+uint32_t texel_tri_total(const rt_ctx* c, uint32_t object) {
+    return object < c->hostObjects.size() && c->hostObjects[object].bvhIndex < c->rootOf.size() ? c->rootOf[c->hostObjects[object].bvhIndex].triTotal : 0u;
+}
+
+// Enqueues the bake; the statistics stay in the ctx scratch (*d_stats) for whoever wants them
+int bake_texels_device(rt_ctx* c, const char* fn, uint32_t object, uint32_t width, uint32_t height, RtTexel* d_texels, const uint32_t** d_stats) {
+    if (!c) return -1;
+    const std::string refusal = check_texel_bake(fn, c->sc.nodes != nullptr, d_texels, object, c->sc.objectCount, width, height, texel_tri_total(c, object));
+    if (!refusal.empty()) return c->fail(refusal);
+    if (object >= c->hostObjects.size()) return c->fail(std::string(fn) + ": object " + std::to_string(object) + " is not among the uploaded objects");
+    RT_HIP(c, hipSetDevice(c->device));
+    const RootInfo& root = c->rootOf[c->hostObjects[object].bvhIndex];
+    const TexelScratch sl = texel_scratch(root.triTotal, width, height);
+    int rc = texel_buffer(c, c->bakeTexelBuf, sl.bytes);
+    if (rc) return rc;
+    char* const base = (char*)c->bakeTexelBuf.p;
+    const size_t n = (size_t)width * height;
+    TexelArgs a{object, root.triFirst, root.triTotal, width, height, (uint32_t*)(base + sl.owner), (uint8_t*)(base + sl.overlapped),
+                (uint32_t*)(base + sl.counts), (unsigned long long*)(base + sl.offsets), (uint32_t*)(base + sl.stats), (float4*)d_texels};
+    RT_HIP(c, hipMemsetAsync(a.stats, 0, sizeof(RtTexelStats), c->stream));
+    RT_HIP(c, hipMemsetAsync(a.owner, 0xff, 4 * n, c->stream));
+    RT_HIP(c, hipMemsetAsync(a.overlapped, 0, n, c->stream));
+    hipLaunchKernelGGL(k_texel_bins, dim3(texel_groups((uint64_t)root.triTotal + 1, RT_TEXEL_GROUP)), dim3(RT_TEXEL_GROUP), 0, c->stream, c->sc, a);
+    RT_HIP(c, hipGetLastError());
+    if ((rc = scan_exclusive<unsigned long long>(c, ScanLoadU32{a.counts}, (uint64_t)root.triTotal + 1, a.offsets, (unsigned long long*)(base + sl.sums)))) return rc;
+    hipLaunchKernelGGL(k_texel_cover, dim3((uint32_t)c->numCUs * 8u), dim3(RT_TEXEL_GROUP), 0, c->stream, c->sc, a);
+    RT_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(k_texel_resolve, dim3(texel_groups(n, RT_TEXEL_RESOLVE * RT_TEXEL_RESOLVE_RUNS)), dim3(RT_TEXEL_RESOLVE), 0, c->stream, c->sc, a);
+    RT_HIP(c, hipGetLastError());
+    if (d_stats) *d_stats = a.stats;
+    return 0;
+}
+
+int texels_compact_device(rt_ctx* c, const char* fn, uint32_t nTexels, const RtTexel* d_texels, float* d_points, float* d_normals, uint32_t* d_index,
+                          uint32_t* d_countOut) {
+    if (!c) return -1;
+    if (!c->sc.nodes) return c->fail(std::string(fn) + " before rt_upload_scene");
+    const std::string refusal = check_texel_pass(fn, d_texels && d_points && d_normals && d_index && d_countOut, nTexels, 0u, 0u);
+    if (!refusal.empty()) return c->fail(refusal);
+    RT_HIP(c, hipSetDevice(c->device));
+    int rc = texel_buffer(c, c->bakeScanBuf, sizeof(uint32_t) * (size_t)scan_levels(nTexels).elems);
+    if (rc) return rc;
+    uint32_t* const sums = (uint32_t*)c->bakeScanBuf.p;
+    if ((rc = scan_exclusive<uint32_t>(c, ScanLoadCovered{(const float4*)d_texels}, nTexels, (uint32_t*)nullptr, sums))) return rc;
+    const TexelCompactArgs a{nTexels, (const float4*)d_texels, sums, d_points, d_normals, d_index, d_countOut};
+    hipLaunchKernelGGL(k_texel_compact, dim3(texel_groups(nTexels, RT_TEXEL_GROUP)), dim3(RT_TEXEL_GROUP), 0, c->stream, a);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+int texels_scatter_device(rt_ctx* c, const char* fn, uint32_t nTexels, uint32_t nCovered, const uint32_t* d_index, const float* d_values4, float* d_rgba,
+                          uint8_t* d_fill) {
+    if (!c) return -1;
+    if (!c->sc.nodes) return c->fail(std::string(fn) + " before rt_upload_scene");
+    const std::string refusal = check_texel_pass(fn, d_rgba && d_fill && (nCovered == 0 || (d_index && d_values4)), nTexels, nCovered, 0u);
+    if (!refusal.empty()) return c->fail(refusal);
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipMemsetAsync(d_rgba, 0, 16 * (size_t)nTexels, c->stream));
+    RT_HIP(c, hipMemsetAsync(d_fill, 0, nTexels, c->stream));
+    if (nCovered) {
+        hipLaunchKernelGGL(k_texel_scatter, dim3(texel_groups(nCovered, RT_TEXEL_GROUP)), dim3(RT_TEXEL_GROUP), 0, c->stream, nCovered, d_index,
+                           (const float4*)d_values4, (float4*)d_rgba, d_fill, nTexels);
+        RT_HIP(c, hipGetLastError());
+    }
+    return 0;
+}
+
+// `passes` passes in ping-pong between the caller's planes and a ctx pair; an odd count ends with a copy back
+int dilate_texels_device(rt_ctx* c, const char* fn, uint32_t width, uint32_t height, uint32_t passes, float* d_rgba, uint8_t* d_fill) {
+    if (!c) return -1;
+    if (!c->sc.nodes) return c->fail(std::string(fn) + " before rt_upload_scene");
+    std::string refusal = check_texel_pass(fn, d_rgba && d_fill, 1u, 0u, passes);
+    if (refusal.empty()) refusal = check_texel_size(fn, width, height);
+    if (!refusal.empty()) return c->fail(refusal);
+    if (passes == 0) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)width * height;
+    int rc = texel_buffer(c, c->bakeDilateBuf, 17 * n);
+    if (rc) return rc;
+    float* planes[2] = {d_rgba, (float*)c->bakeDilateBuf.p};
+    uint8_t* fills[2] = {d_fill, (uint8_t*)c->bakeDilateBuf.p + 16 * n};
+    for (uint32_t k = 1; k <= passes; k++) {
+        const int from = (int)((k - 1u) & 1u), to = from ^ 1;
+        hipLaunchKernelGGL(k_texel_dilate, dim3(texel_groups(n, RT_TEXEL_GROUP)), dim3(RT_TEXEL_GROUP), 0, c->stream, width, height, k,
+                           (const float*)planes[from], (const uint8_t*)fills[from], (float4*)planes[to], fills[to]);
+        RT_HIP(c, hipGetLastError());
+    }
+    if (passes & 1u) {
+        RT_HIP(c, hipMemcpyAsync(d_rgba, planes[1], 16 * n, hipMemcpyDeviceToDevice, c->stream));
+        RT_HIP(c, hipMemcpyAsync(d_fill, fills[1], n, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+int rt_bake_texels(rt_ctx* c, uint32_t object, uint32_t width, uint32_t height, RtTexel* d_texels, RtTexelStats* statsOut) {
+    const uint32_t* d_stats = nullptr;
+    const int rc = bake_texels_device(c, "rt_bake_texels", object, width, height, d_texels, &d_stats);
+    if (rc || !statsOut) return rc;
+    RT_HIP(c, hipMemcpyAsync(statsOut, d_stats, sizeof(RtTexelStats), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int rt_bake_texels_host(rt_ctx* c, uint32_t object, uint32_t width, uint32_t height, RtTexel* texels, RtTexelStats* stats) {
+    if (!c) return -1;
+    const char* fn = "rt_bake_texels_host";
+    const std::string refusal = check_texel_bake(fn, c->sc.nodes != nullptr, texels, object, c->sc.objectCount, width, height, texel_tri_total(c, object));
+    if (!refusal.empty()) return c->fail(refusal);
+    const StagePart parts[] = {{nullptr, texels, sizeof(RtTexel) * (size_t)width * height}, {nullptr, stats, stats ? sizeof(RtTexelStats) : 0}};
+    return staged(c, parts, [&](void* const* d) {
+        const uint32_t* d_stats = nullptr;
+        const int rc = bake_texels_device(c, fn, object, width, height, (RtTexel*)d[0], &d_stats);
+        if (rc || !d[1]) return rc;
+        RT_HIP(c, hipMemcpyAsync(d[1], d_stats, sizeof(RtTexelStats), hipMemcpyDeviceToDevice, c->stream));
+        return 0;
+    });
+}
+
+int rt_texels_compact(rt_ctx* c, uint32_t nTexels, const RtTexel* d_texels, float* d_points, float* d_normals, uint32_t* d_index, uint32_t* d_countOut) {
+    return texels_compact_device(c, "rt_texels_compact", nTexels, d_texels, d_points, d_normals, d_index, d_countOut);
+}
+int rt_texels_scatter(rt_ctx* c, uint32_t nTexels, uint32_t nCovered, const uint32_t* d_index, const float* d_values4, float* d_rgba, uint8_t* d_fill) {
+    return texels_scatter_device(c, "rt_texels_scatter", nTexels, nCovered, d_index, d_values4, d_rgba, d_fill);
+}
+int rt_dilate_texels(rt_ctx* c, uint32_t width, uint32_t height, uint32_t passes, float* d_rgba, uint8_t* d_fill) {
+    return dilate_texels_device(c, "rt_dilate_texels", width, height, passes, d_rgba, d_fill);
+}
+
+// The five passes in order through lightmapBuf. The one wait is for the count of covered texels: the irradiance query's batch
+// size is read on the host.
+int rt_bake_lightmap(rt_ctx* c, uint32_t object, uint32_t width, uint32_t height, const RtIrradianceParams* params, const EnvironmentData* env,
+                     uint32_t dilatePasses, float* d_rgba, uint8_t* d_fill, RtTexelStats* statsOut) {
+    if (!c) return -1;
+    const char* fn = "rt_bake_lightmap";
+    std::string refusal = check_texel_bake(fn, c->sc.nodes != nullptr, d_rgba, object, c->sc.objectCount, width, height, texel_tri_total(c, object));
+    if (refusal.empty()) refusal = check_lightmap(fn, params, dilatePasses, d_fill);
+    if (refusal.empty()) {
+        const RtPointNormalBatch any{(const float*)d_rgba, (const float*)d_rgba, 1u};   // (never read: the refusals that do not depend on the batch)
+        refusal = check_irradiance_query(fn, false, true, &any, params, d_rgba, radiance_max_slots(c));
+    }
+    if (!refusal.empty()) return c->fail(refusal);
+    RT_HIP(c, hipSetDevice(c->device));
+    const LightmapScratch sl = lightmap_scratch(width, height);
+    int rc = texel_buffer(c, c->lightmapBuf, sl.bytes);
+    if (rc) return rc;
+    char* const base = (char*)c->lightmapBuf.p;
+    const uint32_t nTexels = width * height;
+    RtTexel* const texels = (RtTexel*)(base + sl.texels);
+    float* const points = (float*)(base + sl.points);
+    float* const normals = (float*)(base + sl.normals);
+    uint32_t* const index = (uint32_t*)(base + sl.index);
+    uint32_t* const count = (uint32_t*)(base + sl.count);
+    float* const values = (float*)(base + sl.values);
+    const uint32_t* d_stats = nullptr;
+    if ((rc = bake_texels_device(c, fn, object, width, height, texels, &d_stats))) return rc;
+    if ((rc = texels_compact_device(c, fn, nTexels, texels, points, normals, index, count))) return rc;
+    uint32_t nCovered = 0;
+    RtTexelStats stats;
+    RT_HIP(c, hipMemcpyAsync(&nCovered, count, sizeof nCovered, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipMemcpyAsync(&stats, d_stats, sizeof stats, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    if (nCovered > nTexels) return c->fail(std::string(fn) + ": internal: " + std::to_string(nCovered) + " covered texels of " + std::to_string(nTexels));
+    const RtPointNormalBatch batch{points, normals, nCovered};
+    if ((rc = irradiance_device<false>(c, fn, &batch, index, params, env, values))) return rc;
+    if ((rc = texels_scatter_device(c, fn, nTexels, nCovered, index, values, d_rgba, d_fill))) return rc;
+    if ((rc = dilate_texels_device(c, fn, width, height, dilatePasses, d_rgba, d_fill))) return rc;
+    if (statsOut) *statsOut = stats;
+    return 0;
 }
 }  // extern "C"
 

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .devmem import DeviceBuffer, RtError, hip as _hip   # noqa: F401  (engine.RtError and engine._hip are where callers know them)
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch, RtTexel, RtTexelStats,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -798,6 +798,93 @@ class Renderer:
             self.sync()
         return None
 
+    def bake_texels(self, object, width, height, out=None, stats=True, sync=True):
+        """The surface point and shading normal behind every texel of a width x height map over object `object`'s uv layout
+        (rt_bake_texels; DESIGN.md, "Lightmap texels"). Without `out` the records come back through rt_bake_texels_host as
+        (RtTexel array of height * width records (texels_to_numpy), statistics dict). With `out` (a torch tensor on the device or
+        an integer device pointer: 48 bytes per texel, 16-byte aligned) the asynchronous entry point writes there; the statistics
+        dict is returned when `stats` (which waits for them), else None, and sync=False is allowed."""
+        object, width, height = int(object), int(width), int(height)
+        if object < 0 or width < 0 or height < 0:
+            raise ValueError("object, width and height are unsigned")
+        st = RtTexelStats()
+        if out is None:
+            if not sync:
+                raise ValueError("sync=False goes with out=: device memory")
+            res = (RtTexel * max(width * height, 1))()
+            self._check(self._l.rt_bake_texels_host(self._h, object, width, height, C.addressof(res), C.byref(st)), "rt_bake_texels_host")
+            return (RtTexel * (width * height)).from_buffer(res), _texel_stats(st)
+        ptr = _device_ptr(out, "out", C.sizeof(RtTexel) * width * height, floats=False)
+        self._check(self._l.rt_bake_texels(self._h, object, width, height, C.c_void_p(ptr), C.byref(st) if stats else None), "rt_bake_texels")
+        if sync:
+            self.sync()
+        return _texel_stats(st) if stats else None
+
+    def texels_compact(self, texels, n_texels, points, normals, index, count, sync=True):
+        """The covered records of `texels` in ascending texel index as packed points, normals and their texel indices, and how
+        many (rt_texels_compact): device memory throughout (tensors or integer pointers), n_texels entries' worth per array and
+        one word for `count`."""
+        n = int(n_texels)
+        self._check(self._l.rt_texels_compact(self._h, n, C.c_void_p(_device_ptr(texels, "texels", 48 * n, floats=False)),
+                                              C.c_void_p(_device_ptr(points, "points", 12 * n)), C.c_void_p(_device_ptr(normals, "normals", 12 * n)),
+                                              C.c_void_p(_device_ptr(index, "index", 4 * n, floats=False)),
+                                              C.c_void_p(_device_ptr(count, "count", 4, floats=False))), "rt_texels_compact")
+        if sync:
+            self.sync()
+
+    def texels_scatter(self, n_texels, n_covered, index, values, rgba, fill, sync=True):
+        """values[j] (4 floats) to rgba[index[j]] and fill[index[j]] = 1 for j < n_covered, every other texel 0 (rt_texels_scatter):
+        device memory throughout."""
+        n, k = int(n_texels), int(n_covered)
+        self._check(self._l.rt_texels_scatter(self._h, n, k, C.c_void_p(_device_ptr(index, "index", 4 * k, floats=False)),
+                                              C.c_void_p(_device_ptr(values, "values", 16 * k)), C.c_void_p(_device_ptr(rgba, "rgba", 16 * n)),
+                                              C.c_void_p(_device_ptr(fill, "fill", n, floats=False))), "rt_texels_scatter")
+        if sync:
+            self.sync()
+
+    def dilate_texels(self, width, height, passes, rgba, fill, sync=True):
+        """`passes` gutter passes over a map and its fill plane in device memory, in place (rt_dilate_texels)."""
+        n = int(width) * int(height)
+        self._check(self._l.rt_dilate_texels(self._h, int(width), int(height), int(passes), C.c_void_p(_device_ptr(rgba, "rgba", 16 * n)),
+                                             C.c_void_p(_device_ptr(fill, "fill", n, floats=False))), "rt_dilate_texels")
+        if sync:
+            self.sync()
+
+    def bake_lightmap(self, object, width, height, params=None, env=None, dilate=2, out=None, fill=None, sync=True):
+        """The lightmap of object `object`: the irradiance at every covered texel of a width x height map over its uv layout and
+        `dilate` passes of gutter texels (rt_bake_lightmap: rt_bake_texels, rt_texels_compact, rt_query_irradiance with the texel
+        indices as ids, rt_texels_scatter, rt_dilate_texels). `params`: an RtIrradianceParams (None: the defaults), `env`: an
+        EnvironmentData or None. Without `out` / `fill`: ((height, width, 4) float32, (height, width) uint8 fill plane,
+        statistics dict). With both (torch tensors on the device or integer device pointers, 16 bytes and 1 byte per texel) the
+        map is written there and the statistics dict is returned."""
+        object, width, height = int(object), int(width), int(height)
+        if object < 0 or width < 0 or height < 0 or int(dilate) < 0:
+            raise ValueError("object, width, height and dilate are unsigned")
+        if env is not None and not isinstance(env, _capi.EnvironmentData):
+            raise TypeError("env: an EnvironmentData (PushConstants.environment) or None")
+        if params is None:
+            params = RtIrradianceParams()
+            self._l.rt_irradiance_params_default(C.byref(params))
+        if (out is None) != (fill is None):
+            raise ValueError("out= and fill= go together")
+        st = RtTexelStats()
+        n = width * height
+        e = C.byref(env) if env is not None else None
+        if out is None:
+            if not sync:
+                raise ValueError("sync=False goes with out= and fill=: device memory")
+            with DeviceBuffer(16 * n, "lightmap") as d_rgba, DeviceBuffer(n, "lightmap fill") as d_fill:
+                self._check(self._l.rt_bake_lightmap(self._h, object, width, height, C.byref(params), e, int(dilate), C.c_void_p(d_rgba.ptr),
+                                                     C.c_void_p(d_fill.ptr), C.byref(st)), "rt_bake_lightmap")
+                self.sync()
+                return d_rgba.download((height, width, 4), np.float32), d_fill.download((height, width), np.uint8), _texel_stats(st)
+        self._check(self._l.rt_bake_lightmap(self._h, object, width, height, C.byref(params), e, int(dilate),
+                                             C.c_void_p(_device_ptr(out, "out", 16 * n)), C.c_void_p(_device_ptr(fill, "fill", n, floats=False)),
+                                             C.byref(st)), "rt_bake_lightmap")
+        if sync:
+            self.sync()
+        return _texel_stats(st)
+
     def render_ao(self, aovs=None, samples=4, radius=0.5, seed=0):
         """The ambient-occlusion plane of first-hit planes (rt_render_ao): `samples` cosine-weighted occlusion queries of reach
         `radius` per hit record. Without `aovs`: the context's own planes of the last render_aovs(); else the dict render_aovs()
@@ -1195,6 +1282,47 @@ def sh9_irradiance(coeffs, normals):
                       0.315392 * (3.0 * z * z - 1.0), 1.092548 * x * z, 0.546274 * (x * x - y * y)], axis=1)
     band = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
     return np.einsum("nj,njc->nc", basis * band, c)
+
+
+def _texel_stats(st):
+    return dict(covered=int(st.covered), overlapped=int(st.overlapped), skippedTriangles=int(st.skippedTriangles),
+                degenerateTexels=int(st.degenerateTexels))
+
+
+def texels_to_numpy(recs, width=None, height=None):
+    """RtTexel array (or an (n, 12) uint32 array of record words) -> dict of numpy arrays; with width and height shaped (height, width[, k])."""
+    if isinstance(recs, np.ndarray):
+        u = np.ascontiguousarray(recs).view(np.uint32).reshape(-1, 12)
+        f = u.view(np.float32)
+    else:
+        f, u = _record_words(recs, RtTexel)
+    d = dict(point=f[:, 0:3].copy(), state=u[:, 3].copy(), normal=f[:, 4:7].copy(), triIndex=u[:, 7].copy(), uv=f[:, 8:10].copy(), pad=u[:, 10:12].copy())
+    if width is not None and height is not None:
+        d = {k: v.reshape((int(height), int(width)) + v.shape[1:]) for k, v in d.items()}
+    return d
+
+
+def texels_exhaustive(scene_arrays, object, width, height):
+    """The rule of the texel bake in plain loops over the host arrays (rt_texels_exhaustive_host; no GPU): `scene_arrays` is
+    Scene.arrays(); returns (RtTexel array of height * width records (texels_to_numpy), statistics dict)."""
+    width, height = int(width), int(height)
+    res = (RtTexel * max(width * height, 1))()
+    st = RtTexelStats()
+    if _capi.lib().rt_texels_exhaustive_host(C.byref(scene_arrays), int(object), width, height, C.addressof(res), C.byref(st)) != 0:
+        raise RtError("rt_texels_exhaustive_host refused its arguments (an object, a size or indices out of range, or a mesh whose triangles are not one range)")
+    return (RtTexel * (width * height)).from_buffer(res), _texel_stats(st)
+
+
+def dilate_texels(rgba, fill, passes):
+    """`passes` gutter passes over an (H, W, 4) float32 map and its (H, W) uint8 fill plane on the host, by the rule the device
+    compiles (rt_dilate_texels_host; no GPU): new arrays, the inputs are not modified."""
+    out = np.array(rgba, dtype=np.float32, order="C", copy=True)
+    f = np.array(fill, dtype=np.uint8, order="C", copy=True)
+    if out.ndim != 3 or out.shape[2] != 4 or f.shape != out.shape[:2]:
+        raise ValueError(f"rgba {out.shape} and fill {f.shape}: not one (H, W, 4) map and its (H, W) plane")
+    if _capi.lib().rt_dilate_texels_host(out.shape[1], out.shape[0], int(passes), out.ctypes.data, f.ctypes.data) != 0:
+        raise RtError("rt_dilate_texels_host refused its arguments (a size outside 1 .. 8192, passes > 254)")
+    return out, f
 
 
 def aovs_to_numpy(planes):

@@ -38,7 +38,7 @@ import numpy as np
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # before the first HIP call: the renderer's three streams beside torch's and RCCL's (rt_amd.h, "lane_grid_pct")
 
-from . import engine, scenes  # noqa: E402
+from . import _capi, engine, scenes  # noqa: E402
 
 
 def build_parser():
@@ -103,6 +103,12 @@ def build_parser():
     ap.add_argument("--sun-direction", type=float, nargs=3, default=None)
     ap.add_argument("--sun-focus", type=float, default=None)
     ap.add_argument("--sun-intensity", type=float, default=None)
+    ap.add_argument("--bake-object", type=int, default=None, metavar="I",
+                    help="instead of rendering: the lightmap of object I over its uv layout (rt_bake_lightmap: --rays-per-pixel samples per texel, "
+                         "--bounce-limit bounces, the environment options' sky), written to --bake-out")
+    ap.add_argument("--bake-size", type=int, nargs=2, default=(256, 256), metavar=("W", "H"))
+    ap.add_argument("--bake-dilate", type=int, default=2, metavar="N", help="gutter passes around the charts")
+    ap.add_argument("--bake-out", metavar="FILE.npy", help="with --bake-object: the (H, W, 4) fp32 map; FILE.fill.npy gets the (H, W) uint8 fill plane")
     return ap
 
 
@@ -187,6 +193,8 @@ def main(argv=None):
         raise SystemExit("--adaptive takes its sample counts from the temporal pass: it needs --temporal-frames")
     if args.adaptive is not None and not args.adaptive > 0:
         raise SystemExit("--adaptive must be > 0")
+    if args.bake_object is not None and (world > 1 or not args.bake_out or not args.bake_out.endswith(".npy")):
+        raise SystemExit("--bake-object is a single-process job and needs --bake-out FILE.npy")
     if args.temporal_frames and world > 1:   # before any rank waits for another
         raise SystemExit(f"--temporal-frames needs the whole frame on one GPU: launched on {world} ranks, run it as a single process")
     if world > 1:
@@ -211,6 +219,16 @@ def main(argv=None):
         textured = True
     elif paths and rank == 0:
         print(f"{len(paths)} texture map(s) named by the scene are not sampled (the reference's shader samples none; --textures applies this build's declared semantics)")
+    if args.bake_object is not None:
+        p = _capi.RtIrradianceParams(max(args.rays_per_pixel, 1), args.bounce_limit, 0, 0, 1e-5)
+        bw, bh = args.bake_size
+        t0 = time.perf_counter()
+        rgba, fill, st = r.bake_lightmap(args.bake_object, bw, bh, params=p, env=pc.environment, dilate=args.bake_dilate)
+        print(f"{label}: lightmap of object {args.bake_object}, {bw}x{bh}, {p.samples} samples per texel, {time.perf_counter() - t0:.3f} s, {st}")
+        np.save(args.bake_out, rgba)
+        np.save(args.bake_out[:-4] + ".fill.npy", fill)
+        print("wrote", args.bake_out)
+        return 0
     W, H = args.width, args.height
     tile = dict(row0=rank, rowStride=world) if world > 1 else {}
     t0 = time.perf_counter()
