@@ -855,6 +855,58 @@ int  rt_query_within(rt_ctx* ctx, const RtPointBatch* d_points, uint32_t k, RtNe
 int  rt_query_within_host(rt_ctx* ctx, const RtPointBatch* points, uint32_t k, RtNearest* out, uint32_t* counts);
 int  rt_within_exhaustive_host(const RtSceneArrays* scene, const RtPointBatch* points, uint32_t k, RtNearest* out, uint32_t* counts);
 
+/* Box queries ("Box queries"; include/rt_box_overlap.h states the rule, both sides compile it): every surface that an
+ * axis-aligned box touches, the first k of them in index order, and how many there are: voxelisation, broad-phase candidates,
+ * selection by a volume.
+ * Contract. Box i is [lo[3 i .. 3 i + 2], hi[3 i .. 3 i + 2]], closed. It is valid when its six numbers are finite and lo <= hi on
+ * every axis; flat and point boxes are valid. Any other box is not searched: count 0, empty records, not counted in raysTraced.
+ * The surfaces are rt_query_nearest's: every sphere with rt_sphere_is_surface(r), and every triangle of every object, its world
+ * corners rt_xform_point(fwd, v) in fp32 (an identity object's corners as they are). No frontOnly, no materials, no alpha maps.
+ * Touching counts: every "separated" decision is a strict inequality, an axis that comes out zero separates nothing, and a
+ * comparison with a NaN operand is false. The member set C of a valid box:
+ *  - every triangle that rt_box_triangle keeps: the 13-axis separating-axis test in a fixed order: the three box axes by
+ *    comparisons alone (out when max(a_i, b_i, c_i) < lo_i or min(a_i, b_i, c_i) > hi_i; exact); then, with the centre
+ *    fl(lo 0.5 + hi 0.5), the half-extent fl(hi 0.5 - lo 0.5) and the corners relative to the centre, the plane axis e0 x e1; then
+ *    the nine axes e_j x unit_i, each a two-term projection against h . |axis|. A triangle with two equal corners is its segment,
+ *    with three its point;
+ *  - every sphere that rt_box_sphere keeps: the surface is the shell: d2min <= fl(r r) <= d2max, d2min = rt_point_box2(centre,
+ *    lo, hi), d2max the squared distance to the farthest corner summed in x, y, z order. A box wholly inside a ball is no member.
+ * C is a function of the box and the scene alone: not of the visiting order, the BVH, the kernel, the stack or any knob.
+ *  - d_counts[i] = |C|, exact whatever k is.
+ *  - d_out[i * k .. i * k + k - 1]: the first min(k, |C|) members in ascending order of the key, then empty records (all 0). The
+ *    key: spheres before triangles; the lower sphere or object index; the lower triangle index (rt_hits_before of
+ *    include/rt_ray_hits.h with a constant first word). A member's record: found = 1, isSphere, objectIndex (the sphere's or
+ *    the object's index), triIndex (0 for a sphere).
+ *  - The key is total, so rt_query_boxes equals rt_boxes_exhaustive_host in every byte of every record and count. Counts are the
+ *    same for every k, and the list at a smaller k is the head of the list at a larger one.
+ *  - k runs from 0 to RT_BOXES_MAX_K; the count says when a box must be subdivided. k == 0: counts only, d_out may be NULL.
+ *    n == 0 succeeds and does nothing.
+ * rt_query_boxes: the struct is read on the host, its arrays, d_out (16-byte aligned) and d_counts are device pointers,
+ * asynchronous on the ctx stream (the arrays stay valid and unchanged until the stream has passed it). rt_query_boxes_host takes
+ * host arrays, stages its four parts through a ctx buffer and blocks. One lane per box, no path state, one kernel
+ * (k_boxes_overlap; it writes the records itself): the descent discards a subtree by box-against-box overlap only, exact for an
+ * identity object and padded by a derived multiple of the rounding unit for a placed one. rt_last_kernel names the search that
+ * ran: k_boxes_overlap<24, false> while the scene's deepest BVH leaf is at most 24 levels down, k_boxes_overlap<64, true> beyond
+ * (its lists live in a ctx buffer instead of LDS; a scene deeper than 64 is refused). The pass adds to the AOV passes' counter
+ * block: boxTests (box-against-box tests, the object boxes among them), triTests (rt_box_triangle calls), raysTraced (boxes
+ * searched), raysHit (boxes with count > 0), and changes nothing a later render or query produces or chooses. It reads the tables
+ * of the scene as they are: after rt_update_objects or rt_update_points, the moved and the refit ones.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch; (n == 0 succeeds here;) lo or hi NULL
+ * ("lo and hi are required"); k > RT_BOXES_MAX_K; d_counts NULL, or d_out NULL with k > 0 ("counts and, with k > 0, the output
+ * are required"); n >= 2^30.
+ * rt_boxes_exhaustive_host: the definition as a plain loop over the host arrays: every sphere in index order, then every
+ * triangle of every object in index order, no pruning; no ctx, no GPU. -1: what rt_within_exhaustive_host refuses. */
+typedef struct RtBoxBatch {
+    const float* lo;   /* n x 3, packed */
+    const float* hi;   /* n x 3, packed */
+    uint32_t n;
+} RtBoxBatch;
+typedef struct RtOverlap { uint32_t found, isSphere, objectIndex, triIndex; } RtOverlap;   /* 16 bytes, one 16-byte store; no member: all 0 */
+#define RT_BOXES_MAX_K 8
+int  rt_query_boxes(rt_ctx* ctx, const RtBoxBatch* d_boxes, uint32_t k, RtOverlap* d_out, uint32_t* d_counts);
+int  rt_query_boxes_host(rt_ctx* ctx, const RtBoxBatch* boxes, uint32_t k, RtOverlap* out, uint32_t* counts);
+int  rt_boxes_exhaustive_host(const RtSceneArrays* scene, const RtBoxBatch* boxes, uint32_t k, RtOverlap* out, uint32_t* counts);
+
 /* Sphere sweeps ("Sphere sweeps"; include/rt_sweep.h states the rule, both sides compile it): a ball of radius
  * radius[i] whose centre moves along origins[i] + t dirs[i]; does it touch the scene, when and where? Sphere casts, thick rays,
  * continuous collision, the clearance of a path.

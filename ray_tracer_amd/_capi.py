@@ -110,6 +110,14 @@ class RtPointBatch(C.Structure):
     _fields_ = [("points", C.c_void_p), ("maxDist", C.c_void_p), ("n", C.c_uint32)]
 
 
+class RtBoxBatch(C.Structure):
+    _fields_ = [("lo", C.c_void_p), ("hi", C.c_void_p), ("n", C.c_uint32)]
+
+
+class RtOverlap(C.Structure):
+    _fields_ = [("found", C.c_uint32), ("isSphere", C.c_uint32), ("objectIndex", C.c_uint32), ("triIndex", C.c_uint32)]
+
+
 class RtNearest(C.Structure):
     _fields_ = [("dst", C.c_float), ("found", C.c_uint32), ("isSphere", C.c_uint32), ("objectIndex", C.c_uint32),
                 ("triIndex", C.c_uint32), ("uv", C.c_float * 2), ("point", C.c_float * 3), ("_pad", C.c_uint32 * 2)]
@@ -246,6 +254,9 @@ SYMBOLS = {
     "rt_query_within": (C.c_int, [_vp, _P(RtPointBatch), C.c_uint32, _vp, _vp]),
     "rt_query_within_host": (C.c_int, [_vp, _P(RtPointBatch), C.c_uint32, _vp, _vp]),
     "rt_within_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtPointBatch), C.c_uint32, _vp, _vp]),
+    "rt_query_boxes": (C.c_int, [_vp, _P(RtBoxBatch), C.c_uint32, _vp, _vp]),
+    "rt_query_boxes_host": (C.c_int, [_vp, _P(RtBoxBatch), C.c_uint32, _vp, _vp]),
+    "rt_boxes_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtBoxBatch), C.c_uint32, _vp, _vp]),
     "rt_query_sweep": (C.c_int, [_vp, _P(RtSweepBatch), _vp]),
     "rt_query_sweep_host": (C.c_int, [_vp, _P(RtSweepBatch), _vp]),
     "rt_sweep_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtSweepBatch), _vp]),

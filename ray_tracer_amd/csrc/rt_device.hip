@@ -28,6 +28,8 @@
 #include "irradiance_queries.h"
 #include "rt_texels.hip.h"        // the kernels of the lightmap texel passes; texel_queries.h: their checks, launch shapes, scan levels and byte counts
 #include "texel_queries.h"
+#include "rt_box_overlap.hip.h"   // the kernel of the box queries; box_queries.h: their checks, the arithmetic of a batch, the stack choice
+#include "box_queries.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -141,6 +143,7 @@ struct rt_ctx {
     } topo;
     DevBuf hitsListBuf;     // all-hit ray queries: the lists of k_ray_hits<64, true>, whose stack leaves no LDS for them
     DevBuf withinListBuf;   // radius point queries: the lists of k_points_within<64, true>, likewise
+    DevBuf boxesListBuf;    // box queries: the lists of k_boxes_overlap<64, true>, likewise
     DevBuf irradianceBuf;   // baked-light queries: a chunk's rays, ray ids and radiance records (irradiance_scratch), at most 44 bytes x the piece cap
     // lightmap texels: a bake's planes and scan (texel_scratch), the compaction's block sums, the dilation's second plane, and
     // rt_bake_lightmap's records, batch and values (lightmap_scratch)
@@ -2865,4 +2868,62 @@ int rt_measure_copy_bandwidth(rt_ctx* c, size_t bytes, int iters, double* gbps) 
     return 0;
 }
 
+}  // extern "C"
+
+// ---- box queries (box_queries.h has the checks, the arithmetic and the stack choice; DESIGN.md, "Box queries")
+namespace {
+template <int STACK, bool GLIST>
+void launch_boxes_overlap(rt_ctx* c, uint32_t blocks, const BoxesArgs& ba) {
+    hipLaunchKernelGGL((k_boxes_overlap<STACK, GLIST>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, ba);
+    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_boxes_overlap<%d, %s>", STACK, tf(GLIST));
+}
+
+// the search; it writes the records itself
+int boxes_device(rt_ctx* c, const char* fn, const RtBoxBatch* boxes, uint32_t k, RtOverlap* d_out, uint32_t* d_counts) {
+    if (!c) return -1;
+    const std::string refusal = check_boxes_query(fn, c->sc.nodes != nullptr, boxes, k, d_out, d_counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = boxes->n;
+    if (n == 0) return 0;
+    std::string deep;
+    const uint32_t stack = boxes_stack(fn, c->maxLeafDepth, &deep);
+    if (!stack) return c->fail(deep);
+    RT_HIP(c, hipSetDevice(c->device));
+    const BoxesShape bs = boxes_shape(n, k, RT_BLOCK);
+    const bool glist = stack != (uint32_t)RT_BOXES_STACK;
+    if (glist && k) {
+        if (c->boxesListBuf.bytes < bs.listBytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees lists a search in flight may be using
+        int rc = dev_alloc(c, c->boxesListBuf, bs.listBytes);
+        if (rc) return rc;
+    }
+    const BoxesArgs ba{boxes->lo, boxes->hi, n, k, (const float4*)c->objNearBuf.p, (uint4*)d_out, d_counts, (uint32_t*)c->boxesListBuf.p, (DevCounters*)c->aovCounterBuf.p};
+    if (glist) launch_boxes_overlap<RT_BOXES_STACK_DEEP, true>(c, bs.blocks, ba);
+    else launch_boxes_overlap<RT_BOXES_STACK, false>(c, bs.blocks, ba);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The host-memory form (staged): lo, hi, out, counts
+int boxes_host(rt_ctx* c, const char* fn, const RtBoxBatch* boxes, uint32_t k, RtOverlap* out, uint32_t* counts) {
+    if (!c) return -1;
+    const std::string refusal = check_boxes_query(fn, c->sc.nodes != nullptr, boxes, k, out, counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = boxes->n;
+    if (n == 0) return 0;
+    const BoxesShape bs = boxes_shape(n, k, RT_BLOCK);
+    const StagePart parts[] = {{boxes->lo, nullptr, bs.cornerBytes}, {boxes->hi, nullptr, bs.cornerBytes}, {nullptr, out, bs.outBytes}, {nullptr, counts, bs.countBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtBoxBatch dev{(const float*)d[0], (const float*)d[1], n};
+        return boxes_device(c, fn, &dev, k, (RtOverlap*)d[2], (uint32_t*)d[3]);
+    });
+}
+}  // namespace
+
+extern "C" {
+int rt_query_boxes(rt_ctx* c, const RtBoxBatch* d_boxes, uint32_t k, RtOverlap* d_out, uint32_t* d_counts) {
+    return boxes_device(c, "rt_query_boxes", d_boxes, k, d_out, d_counts);
+}
+int rt_query_boxes_host(rt_ctx* c, const RtBoxBatch* boxes, uint32_t k, RtOverlap* out, uint32_t* counts) {
+    return boxes_host(c, "rt_query_boxes_host", boxes, k, out, counts);
+}
 }  // extern "C"

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .devmem import DeviceBuffer, RtError, hip as _hip   # noqa: F401  (engine.RtError and engine._hip are where callers know them)
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtCounters, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch, RtTexel, RtTexelStats,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtBoxBatch, RtCounters, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtOverlap, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch, RtTexel, RtTexelStats,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -621,6 +621,47 @@ class Renderer:
         if sync:
             self.sync()
         return None
+
+
+    def query_boxes(self, lo, hi, k, n=None, out=None, counts=None, sync=True):
+        """Every surface that touches each closed axis-aligned box [lo, hi]: the first `k` (0..8) in index order (spheres, then
+        objects, then triangles), and how many there are (rt_query_boxes; DESIGN.md, "Box queries"). (n, 3) numpy arrays go
+        through rt_query_boxes_host and come back as (RtOverlap array of n * k records, box i's at [i * k, i * k + k)
+        (overlap_to_numpy); uint32 array of n counts); device memory, as query_within takes it, needs counts= (4 bytes per box)
+        and, with k > 0, out= (16 bytes per slot, 16-byte aligned), and returns None."""
+        k = int(k)
+        rec = C.sizeof(RtOverlap)
+        if not _on_device(lo, hi):
+            l, h = _box_arrays(lo, hi)
+            if out is not None or counts is not None or not sync:
+                raise ValueError("out=, counts= and sync=False go with device-pointer inputs")
+            batch = RtBoxBatch(l.ctypes.data, h.ctypes.data, l.shape[0])
+            res = (RtOverlap * max(l.shape[0] * k, 1))()
+            cnt = np.zeros(l.shape[0], np.uint32)
+            self._check(self._l.rt_query_boxes_host(self._h, C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data), "rt_query_boxes_host")
+            return _overlap_rows(res, l.shape[0], k), cnt
+        if counts is None:
+            raise ValueError("device-pointer inputs need counts=: device memory for the n counts")
+        n = _device_count(lo, n, counts)
+        if out is None and k > 0:
+            raise ValueError("device-pointer inputs need out=: device memory for the n * k records")
+        batch = RtBoxBatch(_device_ptr(lo, "lo", 12 * n), _device_ptr(hi, "hi", 12 * n), n)
+        self._check(self._l.rt_query_boxes(self._h, C.byref(batch), k, None if out is None else C.c_void_p(_device_ptr(out, "out", rec * n * k, floats=False)),
+                                           C.c_void_p(_device_ptr(counts, "counts", 4 * n, floats=False))), "rt_query_boxes")
+        if sync:
+            self.sync()
+        return None
+
+    def voxelize(self, lo, hi, dims):
+        """Conservative voxelisation: how many surfaces touch each cell of the grid of dims = (nx, ny, nz) cells over the box
+        [lo, hi], as a (nz, ny, nx) uint32 array. It is rt_query_boxes with k = 0 over grid_boxes(lo, hi, dims), no kernel of
+        its own. Cells are closed and neighbours share their face bit for bit, so a surface lying in a shared face belongs to
+        both cells (and one on a shared edge or corner to every cell around it): no surface inside the grid is lost between
+        cells, and the sum of the counts is not the number of surfaces."""
+        nx, ny, nz = (int(d) for d in dims)
+        cl, ch = grid_boxes(lo, hi, (nx, ny, nz))
+        _, counts = self.query_boxes(cl, ch, 0)
+        return counts.reshape(nz, ny, nx)
 
     def query_sweep(self, origins, dirs, radius, tmax=None, n=None, out=None, sync=True):
         """The first contact of a ball of `radius` whose centre moves along each ray (rt_query_sweep; DESIGN.md, "Sphere sweeps"):
@@ -1452,6 +1493,61 @@ def within_exhaustive(scene_arrays, points, radius, k):
     if _capi.lib().rt_within_exhaustive_host(C.byref(scene_arrays), C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data) != 0:
         raise RtError("rt_within_exhaustive_host refused its arguments (k > 8, NULL arrays, n >= 2^30, or indices out of range)")
     return _nearest_rows(res, p.shape[0], k), cnt
+
+
+def _box_arrays(lo, hi):
+    """Host boxes as the entry points take them: two (n, 3) float32 arrays."""
+    l = np.ascontiguousarray(lo, dtype=np.float32).reshape(-1, 3)
+    h = np.ascontiguousarray(hi, dtype=np.float32).reshape(-1, 3)
+    if l.shape[0] != h.shape[0]:
+        raise ValueError(f"hi has {h.shape[0]} corners for {l.shape[0]} boxes")
+    return l, h
+
+
+def _overlap_rows(res, n, k):
+    """The n * k records of a box query out of the (never empty) ctypes array they were written to."""
+    return (RtOverlap * (n * k)).from_buffer(res) if n * k else (RtOverlap * 0)()
+
+
+def overlap_to_numpy(recs):
+    """RtOverlap array -> dict of numpy arrays."""
+    u = np.frombuffer(recs, dtype=np.uint32).reshape(-1, 4) if len(recs) else np.zeros((0, 4), np.uint32)
+    return dict(found=u[:, 0].copy(), isSphere=u[:, 1].copy(), objectIndex=u[:, 2].copy(), triIndex=u[:, 3].copy())
+
+
+def boxes_exhaustive(scene_arrays, lo, hi, k):
+    """The definition of the box queries as a plain loop over the host arrays (rt_boxes_exhaustive_host; no GPU, no pruning):
+    `scene_arrays` is Scene.arrays(). Returns (RtOverlap array of n * k records (overlap_to_numpy), uint32 counts), as
+    Renderer.query_boxes does for numpy inputs."""
+    l, h = _box_arrays(lo, hi)
+    k = int(k)
+    batch = RtBoxBatch(l.ctypes.data, h.ctypes.data, l.shape[0])
+    res = (RtOverlap * max(l.shape[0] * k, 1))()
+    cnt = np.zeros(l.shape[0], np.uint32)
+    if _capi.lib().rt_boxes_exhaustive_host(C.byref(scene_arrays), C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data) != 0:
+        raise RtError("rt_boxes_exhaustive_host refused its arguments (k > 8, NULL arrays, n >= 2^30, or indices out of range)")
+    return _overlap_rows(res, l.shape[0], k), cnt
+
+
+def grid_boxes(lo, hi, dims):
+    """The cells of a grid of dims = (nx, ny, nz) over the box [lo, hi], as two (nx ny nz, 3) float32 arrays (lo, hi), x fastest.
+    Per axis the N + 1 edges are computed once, e_i = float32(L + i (H - L) / N) in float64 with e_0 = L and e_N = H as float32,
+    and cell i is [e_i, e_{i+1}]: neighbours share their face bit for bit."""
+    L = np.asarray(lo, dtype=np.float32).reshape(3)
+    H = np.asarray(hi, dtype=np.float32).reshape(3)
+    n = [int(d) for d in dims]
+    if len(n) != 3 or min(n) < 1:
+        raise ValueError("dims is (nx, ny, nz), each at least 1")
+    edges = []
+    for a in range(3):
+        e = (float(L[a]) + np.arange(n[a] + 1, dtype=np.float64) * (float(H[a]) - float(L[a])) / n[a]).astype(np.float32)
+        e[0], e[-1] = L[a], H[a]
+        edges.append(e)
+    z, y, x = np.meshgrid(np.arange(n[2]), np.arange(n[1]), np.arange(n[0]), indexing="ij")
+    x, y, z = x.reshape(-1), y.reshape(-1), z.reshape(-1)
+    cl = np.stack([edges[0][x], edges[1][y], edges[2][z]], axis=1).astype(np.float32)
+    ch = np.stack([edges[0][x + 1], edges[1][y + 1], edges[2][z + 1]], axis=1).astype(np.float32)
+    return np.ascontiguousarray(cl), np.ascontiguousarray(ch)
 
 
 def _sweep_arrays(origins, dirs, radius, tmax):
