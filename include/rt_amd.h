@@ -907,6 +907,58 @@ int  rt_query_boxes(rt_ctx* ctx, const RtBoxBatch* d_boxes, uint32_t k, RtOverla
 int  rt_query_boxes_host(rt_ctx* ctx, const RtBoxBatch* boxes, uint32_t k, RtOverlap* out, uint32_t* counts);
 int  rt_boxes_exhaustive_host(const RtSceneArrays* scene, const RtBoxBatch* boxes, uint32_t k, RtOverlap* out, uint32_t* counts);
 
+/* Oriented box queries ("Oriented box queries"; include/rt_obb_overlap.h states the rule, both sides compile it): the
+ * box queries for a box placed by a frame: an overlap box with a rotation, a link's bounding box, a selection volume aligned
+ * with an object or a camera, the cells of a grid in an object's own coordinates.
+ * Contract. Box i is the set { p : lo_i <= F_i p <= hi_i }, closed. F_i is the world-to-box frame: sixteen floats in
+ * RenderObject.transformMatrix's layout (column-major), frames[16 i ..], or frames[0 .. 15] for every box when sharedFrame is 1
+ * (a grid in one frame). F p is rt_xform_point(F, p) of include/rt_det_math.h in fp32; it reads twelve of the sixteen floats,
+ * the other four (m[3], m[7], m[11], m[15]) are never read. A frame and a local box, not a centre, axes and half-extents: the
+ * rule needs no inverse, an object's inverse matrix can be passed as it is (the box is then in object coordinates), and the
+ * cells of a grid in one frame share F and their face values bit for bit. F need not be orthonormal or even invertible: a
+ * singular frame is not refused, the rule applies as written.
+ * Box i is valid when the twelve frame numbers that are read are finite and lo, hi are a valid box of rt_query_boxes (six finite
+ * numbers, lo <= hi). Any other box is not searched: count 0, empty records, not counted in raysTraced.
+ * The surfaces are rt_query_nearest's; a triangle's world corners are rt_xform_point(fwd, v) in fp32 (an identity object's as
+ * they are). The member set C of a valid box:
+ *  - every triangle that rt_box_triangle(lo, hi, F a, F b, F c) keeps: rt_query_boxes' 13-axis rule on the corners taken into the
+ *    box's frame (a linear map takes triangles to triangles);
+ *  - every sphere that rt_box_sphere(lo, hi, F centre, fl(r s)) keeps, s = rt_sqrt((m[0] m[0] + m[1] m[1]) + m[2] m[2]) the
+ *    length of the frame's first column. This is the geometry of the shell exactly when the linear part of F is a rotation or
+ *    reflection times a uniform scale; for any other frame it is this formula and no more.
+ * C is a function of the box, its frame and the scene alone. Key, records, k from 0 to RT_BOXES_MAX_K, counts exact for every k
+ * and the list at a smaller k the head of the list at a larger one: all as rt_query_boxes states them, so
+ * rt_query_oriented_boxes equals rt_obbs_exhaustive_host in every byte of every record and count. With an identity frame the
+ * frame step is exact (products with 1 and 0, sums with 0), so on scenes with finite corners the answer equals rt_query_boxes'
+ * in every byte; sharedFrame = 1 equals the same matrix repeated n times in every byte.
+ * rt_query_oriented_boxes: the struct is read on the host, its arrays, d_out (16-byte aligned) and d_counts are device pointers,
+ * asynchronous on the ctx stream. rt_query_oriented_boxes_host takes host arrays, stages its five parts (frames, lo, hi, out,
+ * counts) through a ctx buffer and blocks. One kernel (k_obbs_overlap; it writes the records itself): the descent discards a
+ * subtree only when its box, taken through F (through fl(F M) for a placed object) and padded by a derived multiple of the
+ * rounding unit, lies apart from [lo, hi] on one of the box's own axes. rt_last_kernel names the search that ran:
+ * k_obbs_overlap<24, false> while the scene's deepest BVH leaf is at most 24 levels down, k_obbs_overlap<64, true> beyond (a
+ * scene deeper than 64 is refused). Counters as the box pass: boxTests (projected-box tests, the object boxes among them),
+ * triTests (triangle-rule calls), raysTraced (boxes searched), raysHit (boxes with count > 0); nothing a later render or query
+ * produces or chooses changes. It reads the tables of the scene as they are after rt_update_objects or rt_update_points.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch; (n == 0 succeeds here;) frames, lo or
+ * hi NULL ("frames, lo and hi are required"); k > RT_BOXES_MAX_K; sharedFrame > 1 ("sharedFrame = N is neither 0 nor 1");
+ * d_counts NULL, or d_out NULL with k > 0; n >= 2^30.
+ * rt_obbs_exhaustive_host: the definition as a plain loop over the host arrays: every sphere in index order, then every triangle
+ * of every object in index order, no pruning; no ctx, no GPU. -1: what rt_boxes_exhaustive_host refuses, and sharedFrame > 1.
+ * rt_object_frames_host: frames[16 i ..] = rt_mat4_inverse of the matrix of object objects[i] of the host arrays: the frame under
+ * which lo and hi are in that object's own coordinates. No ctx, no GPU. -1: a NULL argument with n > 0, an index out of range. */
+typedef struct RtObbBatch {
+    const float* frames;   /* the world-to-box matrices: 16 floats each, RenderObject.transformMatrix's layout (column-major) */
+    const float* lo;       /* n x 3, packed: the box in its frame's coordinates */
+    const float* hi;       /* n x 3 */
+    uint32_t n;
+    uint32_t sharedFrame;  /* 0: frames holds n matrices; 1: one matrix for the whole batch (a grid in one frame) */
+} RtObbBatch;
+int  rt_query_oriented_boxes(rt_ctx* ctx, const RtObbBatch* d_batch, uint32_t k, RtOverlap* d_out, uint32_t* d_counts);
+int  rt_query_oriented_boxes_host(rt_ctx* ctx, const RtObbBatch* batch, uint32_t k, RtOverlap* out, uint32_t* counts);
+int  rt_obbs_exhaustive_host(const RtSceneArrays* scene, const RtObbBatch* batch, uint32_t k, RtOverlap* out, uint32_t* counts);
+int  rt_object_frames_host(const RtSceneArrays* scene, const uint32_t* objects, uint32_t n, float* frames);
+
 /* Sphere sweeps ("Sphere sweeps"; include/rt_sweep.h states the rule, both sides compile it): a ball of radius
  * radius[i] whose centre moves along origins[i] + t dirs[i]; does it touch the scene, when and where? Sphere casts, thick rays,
  * continuous collision, the clearance of a path.

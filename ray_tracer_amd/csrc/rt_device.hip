@@ -30,6 +30,8 @@
 #include "texel_queries.h"
 #include "rt_box_overlap.hip.h"   // the kernel of the box queries; box_queries.h: their checks, the arithmetic of a batch, the stack choice
 #include "box_queries.h"
+#include "rt_obb_overlap.hip.h"   // the kernel of the oriented box queries; obb_queries.h: their checks, the arithmetic of a batch, the stack choice
+#include "obb_queries.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -2925,5 +2927,65 @@ int rt_query_boxes(rt_ctx* c, const RtBoxBatch* d_boxes, uint32_t k, RtOverlap* 
 }
 int rt_query_boxes_host(rt_ctx* c, const RtBoxBatch* boxes, uint32_t k, RtOverlap* out, uint32_t* counts) {
     return boxes_host(c, "rt_query_boxes_host", boxes, k, out, counts);
+}
+}  // extern "C"
+
+// ---- oriented box queries (obb_queries.h has the checks, the arithmetic and the stack choice; DESIGN.md, "Oriented box queries")
+namespace {
+template <int STACK, bool GLIST>
+void launch_obbs_overlap(rt_ctx* c, uint32_t blocks, const ObbsArgs& ba) {
+    hipLaunchKernelGGL((k_obbs_overlap<STACK, GLIST>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, ba);
+    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_obbs_overlap<%d, %s>", STACK, tf(GLIST));
+}
+
+// the search; it writes the records itself. The deep search's lists share boxesListBuf: the passes run one behind the other on
+// the ctx stream, and neither keeps anything in it between launches
+int obbs_device(rt_ctx* c, const char* fn, const RtObbBatch* batch, uint32_t k, RtOverlap* d_out, uint32_t* d_counts) {
+    if (!c) return -1;
+    const std::string refusal = check_obbs_query(fn, c->sc.nodes != nullptr, batch, k, d_out, d_counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = batch->n;
+    if (n == 0) return 0;
+    std::string deep;
+    const uint32_t stack = obbs_stack(fn, c->maxLeafDepth, &deep);
+    if (!stack) return c->fail(deep);
+    RT_HIP(c, hipSetDevice(c->device));
+    const ObbShape os = obbs_shape(n, k, batch->sharedFrame != 0u, RT_BLOCK);
+    const bool glist = stack != (uint32_t)RT_BOXES_STACK;
+    if (glist && k) {
+        if (c->boxesListBuf.bytes < os.listBytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees lists a search in flight may be using
+        int rc = dev_alloc(c, c->boxesListBuf, os.listBytes);
+        if (rc) return rc;
+    }
+    const ObbsArgs ba{batch->frames, batch->lo, batch->hi, n, k, batch->sharedFrame, (const float4*)c->objNearBuf.p, (uint4*)d_out, d_counts, (uint32_t*)c->boxesListBuf.p, (DevCounters*)c->aovCounterBuf.p};
+    if (glist) launch_obbs_overlap<RT_BOXES_STACK_DEEP, true>(c, os.blocks, ba);
+    else launch_obbs_overlap<RT_BOXES_STACK, false>(c, os.blocks, ba);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The host-memory form (staged): frames, lo, hi, out, counts
+int obbs_host(rt_ctx* c, const char* fn, const RtObbBatch* batch, uint32_t k, RtOverlap* out, uint32_t* counts) {
+    if (!c) return -1;
+    const std::string refusal = check_obbs_query(fn, c->sc.nodes != nullptr, batch, k, out, counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = batch->n;
+    if (n == 0) return 0;
+    const uint32_t shared = batch->sharedFrame;
+    const ObbShape os = obbs_shape(n, k, shared != 0u, RT_BLOCK);
+    const StagePart parts[] = {{batch->frames, nullptr, os.frameBytes}, {batch->lo, nullptr, os.cornerBytes}, {batch->hi, nullptr, os.cornerBytes}, {nullptr, out, os.outBytes}, {nullptr, counts, os.countBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtObbBatch dev{(const float*)d[0], (const float*)d[1], (const float*)d[2], n, shared};
+        return obbs_device(c, fn, &dev, k, (RtOverlap*)d[3], (uint32_t*)d[4]);
+    });
+}
+}  // namespace
+
+extern "C" {
+int rt_query_oriented_boxes(rt_ctx* c, const RtObbBatch* d_batch, uint32_t k, RtOverlap* d_out, uint32_t* d_counts) {
+    return obbs_device(c, "rt_query_oriented_boxes", d_batch, k, d_out, d_counts);
+}
+int rt_query_oriented_boxes_host(rt_ctx* c, const RtObbBatch* batch, uint32_t k, RtOverlap* out, uint32_t* counts) {
+    return obbs_host(c, "rt_query_oriented_boxes_host", batch, k, out, counts);
 }
 }  // extern "C"

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .devmem import DeviceBuffer, RtError, hip as _hip   # noqa: F401  (engine.RtError and engine._hip are where callers know them)
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtBoxBatch, RtCounters, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtOverlap, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch, RtTexel, RtTexelStats,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtBoxBatch, RtCounters, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtObbBatch, RtOverlap, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch, RtTexel, RtTexelStats,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -652,16 +652,53 @@ class Renderer:
             self.sync()
         return None
 
-    def voxelize(self, lo, hi, dims):
+    def voxelize(self, lo, hi, dims, frame=None):
         """Conservative voxelisation: how many surfaces touch each cell of the grid of dims = (nx, ny, nz) cells over the box
         [lo, hi], as a (nz, ny, nx) uint32 array. It is rt_query_boxes with k = 0 over grid_boxes(lo, hi, dims), no kernel of
         its own. Cells are closed and neighbours share their face bit for bit, so a surface lying in a shared face belongs to
         both cells (and one on a shared edge or corner to every cell around it): no surface inside the grid is lost between
-        cells, and the sum of the counts is not the number of surfaces."""
+        cells, and the sum of the counts is not the number of surfaces. With `frame` (16 floats, world to grid) the grid lies in
+        that frame's coordinates: rt_query_oriented_boxes with sharedFrame = 1 over the same cells, which share the frame and
+        their face values bit for bit."""
         nx, ny, nz = (int(d) for d in dims)
         cl, ch = grid_boxes(lo, hi, (nx, ny, nz))
-        _, counts = self.query_boxes(cl, ch, 0)
+        if frame is None:
+            _, counts = self.query_boxes(cl, ch, 0)
+        else:
+            _, counts = self.query_oriented_boxes(np.asarray(frame, np.float32).reshape(16), cl, ch, 0)
         return counts.reshape(nz, ny, nx)
+
+    def query_oriented_boxes(self, frames, lo, hi, k, n=None, out=None, counts=None, sync=True):
+        """Every surface that touches each closed box { p : lo <= F p <= hi } placed by its world-to-box frame F: the first `k`
+        (0..8) in index order and how many there are (rt_query_oriented_boxes; DESIGN.md, "Oriented box queries"). `frames`: (n, 16)
+        matrices in RenderObject.transformMatrix's layout (obb_frames, object_frames), or one (16,) frame that the whole batch
+        shares. numpy arrays go through rt_query_oriented_boxes_host and come back as query_boxes' pair; device memory needs
+        counts= and, with k > 0, out=, and n= where lo cannot tell, and returns None; there a tensor of 16 floats is a shared
+        frame, and an integer device pointer is taken as n frames."""
+        k = int(k)
+        rec = C.sizeof(RtOverlap)
+        if not _on_device(frames, lo, hi):
+            f, shared, l, h = _obb_arrays(frames, lo, hi)
+            if out is not None or counts is not None or not sync:
+                raise ValueError("out=, counts= and sync=False go with device-pointer inputs")
+            batch = RtObbBatch(f.ctypes.data, l.ctypes.data, h.ctypes.data, l.shape[0], shared)
+            res = (RtOverlap * max(l.shape[0] * k, 1))()
+            cnt = np.zeros(l.shape[0], np.uint32)
+            self._check(self._l.rt_query_oriented_boxes_host(self._h, C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data), "rt_query_oriented_boxes_host")
+            return _overlap_rows(res, l.shape[0], k), cnt
+        if counts is None:
+            raise ValueError("device-pointer inputs need counts=: device memory for the n counts")
+        n = _device_count(lo, n, counts)
+        if out is None and k > 0:
+            raise ValueError("device-pointer inputs need out=: device memory for the n * k records")
+        # one frame for the batch: an object of 16 floats; an integer pointer is taken as n frames
+        shared = 1 if hasattr(frames, "numel") and int(frames.numel()) == 16 and n != 1 else 0
+        batch = RtObbBatch(_device_ptr(frames, "frames", 64 if shared else 64 * n), _device_ptr(lo, "lo", 12 * n), _device_ptr(hi, "hi", 12 * n), n, shared)
+        self._check(self._l.rt_query_oriented_boxes(self._h, C.byref(batch), k, None if out is None else C.c_void_p(_device_ptr(out, "out", rec * n * k, floats=False)),
+                                                    C.c_void_p(_device_ptr(counts, "counts", 4 * n, floats=False))), "rt_query_oriented_boxes")
+        if sync:
+            self.sync()
+        return None
 
     def query_sweep(self, origins, dirs, radius, tmax=None, n=None, out=None, sync=True):
         """The first contact of a ball of `radius` whose centre moves along each ray (rt_query_sweep; DESIGN.md, "Sphere sweeps"):
@@ -1527,6 +1564,71 @@ def boxes_exhaustive(scene_arrays, lo, hi, k):
     if _capi.lib().rt_boxes_exhaustive_host(C.byref(scene_arrays), C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data) != 0:
         raise RtError("rt_boxes_exhaustive_host refused its arguments (k > 8, NULL arrays, n >= 2^30, or indices out of range)")
     return _overlap_rows(res, l.shape[0], k), cnt
+
+
+def _obb_arrays(frames, lo, hi):
+    """Host oriented boxes as the entry points take them: (n, 16) float32 frames, or (16,) with shared = 1, and _box_arrays' two."""
+    l, h = _box_arrays(lo, hi)
+    f = np.ascontiguousarray(frames, dtype=np.float32)
+    shared = 1 if f.ndim == 1 and f.size == 16 else 0
+    f = f.reshape(-1, 16)
+    if not shared and f.shape[0] != l.shape[0]:
+        raise ValueError(f"{f.shape[0]} frames for {l.shape[0]} boxes")
+    return f, shared, l, h
+
+
+def obbs_exhaustive(scene_arrays, frames, lo, hi, k):
+    """The definition of the oriented box queries as a plain loop over the host arrays (rt_obbs_exhaustive_host; no GPU, no
+    pruning): `scene_arrays` is Scene.arrays(), `frames` (n, 16) or one shared (16,). Returns what boxes_exhaustive returns."""
+    f, shared, l, h = _obb_arrays(frames, lo, hi)
+    k = int(k)
+    batch = RtObbBatch(f.ctypes.data, l.ctypes.data, h.ctypes.data, l.shape[0], shared)
+    res = (RtOverlap * max(l.shape[0] * k, 1))()
+    cnt = np.zeros(l.shape[0], np.uint32)
+    if _capi.lib().rt_obbs_exhaustive_host(C.byref(scene_arrays), C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data) != 0:
+        raise RtError("rt_obbs_exhaustive_host refused its arguments (k > 8, NULL arrays, sharedFrame > 1, n >= 2^30, or indices out of range)")
+    return _overlap_rows(res, l.shape[0], k), cnt
+
+
+def obb_frames(centres, rotations, scale=1.0):
+    """The world-to-box frames, (n, 16) float32 in RenderObject.transformMatrix's layout, of boxes whose axes are the columns of
+    `rotations` (n, 3, 3) about `centres` (n, 3): F p = scale R^T (p - centre), computed in float64 and rounded once. `scale`
+    (a number or n of them) is local units per world unit: a box [-h, h] under it has the world half-extents h / scale."""
+    c = np.asarray(centres, np.float64).reshape(-1, 3)
+    R = np.asarray(rotations, np.float64).reshape(-1, 3, 3)
+    if R.shape[0] != c.shape[0]:
+        raise ValueError(f"{R.shape[0]} rotations for {c.shape[0]} centres")
+    s = np.broadcast_to(np.asarray(scale, np.float64), (c.shape[0],))
+    A = s[:, None, None] * np.transpose(R, (0, 2, 1))                  # rows of A: the box's axes
+    t = -np.einsum("nij,nj->ni", A, c)
+    f = np.zeros((c.shape[0], 4, 4))                                   # f[n, column, row]
+    f[:, :3, :3] = np.transpose(A, (0, 2, 1))
+    f[:, 3, :3] = t
+    f[:, 3, 3] = 1.0
+    return np.ascontiguousarray(f.reshape(-1, 16).astype(np.float32))
+
+
+def object_frames(scene_arrays, objects):
+    """Each listed object's inverse matrix by rt_mat4_inverse, (n, 16) float32: under it lo and hi are in that object's own
+    coordinates (rt_object_frames_host)."""
+    idx = np.ascontiguousarray(objects, dtype=np.uint32).reshape(-1)
+    f = np.zeros((len(idx), 16), np.float32)
+    if _capi.lib().rt_object_frames_host(C.byref(scene_arrays), idx.ctypes.data, len(idx), f.ctypes.data) != 0:
+        raise RtError("rt_object_frames_host refused its arguments (an object index out of range)")
+    return f
+
+
+def frame_is_similarity(frames, tol=1e-5):
+    """Per frame: whether its linear part A is a rotation or reflection times a uniform scale within `tol`: every entry of
+    A^T A / s^2 - I is at most tol in size, s^2 = trace(A^T A) / 3 > 0. For those frames rt_obb_sphere is the geometry of the
+    shell; for the others it is its formula."""
+    f = np.asarray(frames, np.float64).reshape(-1, 4, 4)
+    A = np.transpose(f[:, :3, :3], (0, 2, 1))
+    G = np.einsum("nki,nkj->nij", A, A)
+    s2 = np.trace(G, axis1=1, axis2=2) / 3.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        off = np.abs(G / s2[:, None, None] - np.eye(3)).max(axis=(1, 2))
+    return (s2 > 0) & np.isfinite(off) & (off <= tol)
 
 
 def grid_boxes(lo, hi, dims):
