@@ -42,7 +42,8 @@
 #define RT_TE_REG_ALL 1    // k_trace_pw: ROOMY in every instantiation without phase statistics, not only in those built for five work-groups per CU (0)
 #endif
 #ifndef RT_SHADE_BLOCKS
-#define RT_SHADE_BLOCKS 5  // k_shade, k_shade_maps: work-groups per CU they are built for (__launch_bounds__): 95 registers, no spills
+#define RT_SHADE_BLOCKS 6  // k_shade, k_shade_maps, k_shade_rays, k_shade_rays_maps: work-groups per CU they are built for (__launch_bounds__): 80 registers at the most, no spills, so
+                           // that one of their waves fits a SIMD beside six 72-register waves of k_trace_pw_wide (6 x 72 + 80 = 512)
 #endif
 #ifndef RT_LEAF_PRELOAD
 #define RT_LEAF_PRELOAD 1  // trace_wave, leaf step: the second triangle's three loads kept in front of the first triangle's test, where the registers allow it
@@ -1180,8 +1181,18 @@ __global__ __launch_bounds__(RT_BLOCK, BLOCKS) void k_trace_pw(DevScene sc, Path
 // RT_HOT_PAIRS pairs fit together (launch_plan.h: wide_group_lds). One configuration, the one the big dispatches of a scene like
 // the bench frame run (launch_plan.cpp: trace_kernel_key): no overflow stack, no per-ray counters, no phase statistics, no object
 // culling; tE in a register and the leaf preload as in k_trace_pw<STACK, .., 5>.
+// Its register budget is 72, not the 80 that six waves per SIMD allow: 6 x 72 leave 80 of a SIMD's 512 registers, one wave of
+// k_shade (RT_SHADE_BLOCKS), which then runs beside the traversal instead of waiting for a work-group to end. The budget is
+// given by RT_WIDE_VGPR_REQUEST, as a launch bound cannot say it: two groups of 768 are the most a CU holds, so the compiler
+// rounds any "seven waves" back to six. For the targets with a unified register file (gfx90a and later) the compiler doubles
+// the amdgpu_num_vgpr it is given (the request counts the vector half of a file shared with the accumulation registers, of
+// which this kernel has none), so 36 asks for 72. tests/test_coresidency_budget.py reads the outcome from the code object:
+// 72 or fewer, no spill, no scratch. The figure is a fact about the compiler, not about the kernel: with another toolchain build
+// the library, read the kernel's VGPRs (tools/code_object.py), and if they are not 72 derive the request again (a compiler that
+// takes it at face value would allot 36 registers and spill, which that test refuses).
+#define RT_WIDE_VGPR_REQUEST 36
 template <int STACK, int HOT, int THREADS>
-__global__ __launch_bounds__(THREADS, 6) void k_trace_pw_wide(DevScene sc, PathState ps, TracePwArgs ta) {
+__global__ __launch_bounds__(THREADS, 6) __attribute__((amdgpu_num_vgpr(RT_WIDE_VGPR_REQUEST))) void k_trace_pw_wide(DevScene sc, PathState ps, TracePwArgs ta) {
     trace_pw_block<STACK, false, false, false, false, HOT, true, false, THREADS>(sc, ps, ta);
 }
 // The traversal of a scene that binds an alpha map (DevScene::mapFlags & RT_MAP_ALPHA): one configuration for every such scene —
@@ -1458,8 +1469,10 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
     auxMask = 0;
     rt_vec3 auxOrigin = rt_v3(0, 0, 0), auxL = auxOrigin, auxC = auxOrigin;  // probe rays of this bounce (diffuse only)
     rt_vec3 auxAlbedo = auxOrigin;                                           // ... and what the next segment needs to finish its MIS
-    float auxNdotL = 0.f, auxCosPdfL = 0.f, auxCosPdfC = 0.f;
-    float auxCosL = 0.f, auxCosC = 0.f;                                      // light_sample_pdf's cosine of the two directions
+    // dot(n, lightSample) and the cosine pdf of cosineSample. The records' other scalars are made from these and from the two
+    // directions where the records are written (light_cos of each direction; max(0, .) and the cosine pdf of lightSample), so
+    // that two registers cross the rest of the segment, not five.
+    float auxDotL = 0.f, auxCosPdfC = 0.f;
     const float4 sO = ps.rayO()[slot], sD = ps.rayD()[slot], sA = ps.att()[slot], sT = ps.total()[slot];
     // QUEUED: a sample's first segment other than the pixel's first has no record of its own, the camera ray's hit is kept in camHit
     const float4 hM = (QUEUED && fp.camReuse && (__float_as_uint(sA.w) & 0x0fffffffu) == 0u && __float_as_uint(sT.w) != 0u) ? ps.camHit()[slot]
@@ -1484,6 +1497,10 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
 
     bool done = false;       // this sample's trace() returned
     bool zeroed = false;     // ... through the NaN/negative early-out (:505)
+    // QUEUED: `total` is stored only when its bits changed. A sample that ends counts up total.w, so only a segment that goes on
+    // can leave the record as it is, and its sum is final where the hit's light has been added: compared there, once, so that the
+    // loaded record does not stay in registers to the end.
+    bool totalKept = false;
 
     if (obj != RT_HIT_NONE) {
         if (pending) {
@@ -1531,6 +1548,7 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
         rt_vec3 finalLight = direct.x == -1.f ? emission : direct;
         total = rt_add(total, rt_mul(finalLight, att));
         if (j == 0) total = rt_add(total, emission);
+        totalKept = __float_as_uint(total.x) == __float_as_uint(sT.x) && __float_as_uint(total.y) == __float_as_uint(sT.y) && __float_as_uint(total.z) == __float_as_uint(sT.z);
         if (rt_isnan(total.x) || rt_isnan(total.y) || rt_isnan(total.z) || total.x < 0.f || total.y < 0.f || total.z < 0.f) {
             done = true;
             zeroed = true;
@@ -1588,9 +1606,7 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
                 // (the four records of the unfinished MIS are written at the end, once it is known that the path goes on and that
                 // the next segment needs them)
                 auxOrigin = origin; auxL = lightSample; auxC = cosineSample; auxAlbedo = albedo;
-                auxCosL = light_cos(lightSample); auxCosC = light_cos(cosineSample);
-                auxNdotL = rt_max(0.f, rt_dot(hit.normal, lightSample));
-                auxCosPdfL = rt_max(0.f, rt_dot(lightSample, hit.normal) * RT_INV_PI);
+                auxDotL = rt_dot(hit.normal, lightSample);   // (= dot(lightSample, n) bit for bit: the products commute, the sums run x, y, z)
                 auxCosPdfC = realCosinePDF;
             }
             att = rt_mul(att, radiance);
@@ -1648,16 +1664,25 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
         alive = true;
     }
 
+    // QUEUED: the stores below index the records with a copy of the slot that the compiler cannot trace back to it. Otherwise it
+    // keeps the 64-bit addresses of rayO, rayD, att and total, which it formed for the loads at the top, in eight registers
+    // through the whole segment; this way it forms them again here, two additions each.
+    uint32_t wslot = slot;
+    if (QUEUED) asm volatile("" : "+v"(wslot));
     if (alive) {
         if (done && fp.camReuse) {
             // a new sample of the same pixel: the same camera ray, whose hit is known — no traversal this round (bit 2)
-            if (!QUEUED) ps.hit(RAY_MAIN)[slot] = ps.camHit()[slot];
+            if (!QUEUED) ps.hit(RAY_MAIN)[wslot] = ps.camHit()[wslot];
             auxMask |= 4u;
         } else {
             const float4 seed = sphere_seed(sc, ro, rd, withMask);
             if (QUEUED && seed_is_blank(seed)) auxMask |= 8u;
-            else ps.hit(RAY_MAIN)[slot] = seed;
+            else ps.hit(RAY_MAIN)[wslot] = seed;
         }
+        // the records that the probe rays' block below has no say in go out in front of it: the direction, the RNG state and the
+        // sum are off the registers while it runs
+        ps.rayD()[wslot] = mk4u(rd, state);
+        if (!QUEUED || done || !totalKept) ps.total()[wslot] = mk4u(total, samplesDone);
         if (wantAux) {
             float4 sL = sphere_seed(sc, auxOrigin, auxL, withMask), sC = sphere_seed(sc, auxOrigin, auxC, withMask);
             auxMask |= 3u;
@@ -1686,24 +1711,19 @@ __device__ __forceinline__ void shade_path(const DevScene& sc, const PathState& 
                 misW = m2;
                 wantAux = false;
             } else {
-                if (auxMask & 1u) ps.hit(RAY_NEE)[slot] = sL;     // the traversal's seed; an answered query needs no record (att.w bits 29 / 28)
-                if (auxMask & 2u) ps.hit(RAY_PROBE)[slot] = sC;
+                if (auxMask & 1u) ps.hit(RAY_NEE)[wslot] = sL;     // the traversal's seed; an answered query needs no record (att.w bits 29 / 28)
+                if (auxMask & 2u) ps.hit(RAY_PROBE)[wslot] = sC;
                 // the directions are the traversal's alone: only those of the queries that fly
-                if (auxMask & 3u) ps.auxO()[slot] = mk4(auxOrigin, 0.f);
-                if (auxMask & 1u) ps.auxDL()[slot] = mk4(auxL, 0.f);
-                if (auxMask & 2u) ps.auxDC()[slot] = mk4(auxC, 0.f);
-                ps.pendAlbedo()[slot] = mk4(auxAlbedo, auxNdotL);
-                ps.pendMis()[slot] = make_float4(auxCosL, auxCosC, auxCosPdfL, auxCosPdfC);
+                if (auxMask & 3u) ps.auxO()[wslot] = mk4(auxOrigin, 0.f);
+                if (auxMask & 1u) ps.auxDL()[wslot] = mk4(auxL, 0.f);
+                if (auxMask & 2u) ps.auxDC()[wslot] = mk4(auxC, 0.f);
+                ps.pendAlbedo()[wslot] = mk4(auxAlbedo, rt_max(0.f, auxDotL));
+                ps.pendMis()[wslot] = make_float4(light_cos(auxL), light_cos(auxC), rt_max(0.f, auxDotL * RT_INV_PI), auxCosPdfC);
             }
         }
         const uint32_t answered = wantAux ? (((auxMask & 1u) ? 0u : 0x20000000u) | ((auxMask & 2u) ? 0u : 0x10000000u)) : 0u;
-        ps.rayO()[slot] = mk4(ro, misW);
-        ps.rayD()[slot] = mk4u(rd, state);
-        ps.att()[slot] = mk4u(att, j | (wantAux ? 0x80000000u : 0u) | (specular ? 0x40000000u : 0u) | answered);
-        const float4 nT = mk4u(total, samplesDone);
-        if (!QUEUED || __float_as_uint(nT.x) != __float_as_uint(sT.x) || __float_as_uint(nT.y) != __float_as_uint(sT.y) ||
-            __float_as_uint(nT.z) != __float_as_uint(sT.z) || __float_as_uint(nT.w) != __float_as_uint(sT.w))
-            ps.total()[slot] = nT;
+        ps.rayO()[wslot] = mk4(ro, misW);
+        ps.att()[wslot] = mk4u(att, j | (wantAux ? 0x80000000u : 0u) | (specular ? 0x40000000u : 0u) | answered);
     }
 }
 
