@@ -959,6 +959,58 @@ int  rt_query_oriented_boxes_host(rt_ctx* ctx, const RtObbBatch* batch, uint32_t
 int  rt_obbs_exhaustive_host(const RtSceneArrays* scene, const RtObbBatch* batch, uint32_t k, RtOverlap* out, uint32_t* counts);
 int  rt_object_frames_host(const RtSceneArrays* scene, const uint32_t* objects, uint32_t n, float* frames);
 
+/* Triangle queries ("Triangle queries"; include/rt_tri_overlap.h states the rule, both sides compile it): every
+ * surface that a caller's triangle touches, the first k of them in index order, and how many there are: the exact narrow phase
+ * of a mesh against the scene, for a robot link, a tool, a character or a cloth.
+ * Contract. Triangle i is the closed triangle of the corners p = corners[9 i .. 9 i + 2], q = corners[9 i + 3 ..], r =
+ * corners[9 i + 6 ..]. It is valid when its nine numbers are finite; equal corners are valid. Any other triangle is not searched:
+ * count 0, empty records, not counted in raysTraced. The surfaces are rt_query_nearest's: every sphere with
+ * rt_sphere_is_surface(r), as a shell, and every triangle of every object, its world corners rt_xform_point(fwd, v) in fp32 (an
+ * identity object's corners as they are). No frontOnly, no materials, no alpha maps. Touching counts: every "separated" decision
+ * is a strict inequality, an axis that comes out zero separates nothing, and a comparison with a NaN operand is false. The member
+ * set C of a valid triangle:
+ *  - every triangle that rt_tri_triangle keeps: a separating-axis test over 17 axes in a fixed order. First the box of p, q, r
+ *    against the box of a, b, c by comparisons alone (exact). Then, with all six corners relative to the centre
+ *    fl(lo 0.5 + hi 0.5) of the query's box, the query's normal nQ, the triangle's normal nT, the nine eQi x eTj (i outer), the
+ *    three nQ x eQi and the three nT x eTj, each by projecting all six corners; the last six decide coplanar pairs. A query with
+ *    two or three equal corners is its segment or its point, except in a scene triangle's own plane, where the rule is the
+ *    formula and no more;
+ *  - every sphere that rt_tri_sphere keeps: d2min <= fl(rad rad) <= d2max, d2min = rt_point_triangle's answer at the centre, d2max
+ *    the largest corner distance. A triangle wholly inside a ball is no member.
+ * C is a function of the triangle and the scene alone: not of the visiting order, the BVH, the kernel, the stack or any knob.
+ *  - d_counts[i] = |C|, exact whatever k is.
+ *  - d_out[i * k .. i * k + k - 1]: the first min(k, |C|) members in ascending order of rt_query_boxes' key (spheres before
+ *    triangles; the lower sphere or object index; the lower triangle index), then empty records (all 0). Records as rt_query_boxes'.
+ *  - The key is total, so rt_query_triangles equals rt_tris_exhaustive_host in every byte of every record and count. Counts are
+ *    the same for every k, and the list at a smaller k is the head of the list at a larger one.
+ *  - k runs from 0 to RT_BOXES_MAX_K. k == 0: counts only, d_out may be NULL. n == 0 succeeds and does nothing.
+ * rt_query_triangles: the struct is read on the host, corners, d_out (16-byte aligned) and d_counts are device pointers,
+ * asynchronous on the ctx stream (the arrays stay valid and unchanged until the stream has passed it). rt_query_triangles_host
+ * takes host arrays, stages its three parts (corners, out, counts) through a ctx buffer and blocks. One lane per triangle, no
+ * path state, one kernel (k_tris_overlap; it writes the records itself): the descent discards a subtree whose box lies apart
+ * from the query's box (exact for an identity object, padded for a placed one, as rt_query_boxes) or, "tri_plane" 1
+ * (rt_set_tuning; the default), strictly on one side of the query's plane by more than a derived multiple of the rounding unit.
+ * rt_last_kernel names the search that ran: k_tris_overlap<24, false> while the scene's deepest BVH leaf is at most 24 levels
+ * down, k_tris_overlap<64, true> beyond (its lists live in the box queries' ctx buffer; a scene deeper than 64 is refused). The
+ * pass adds to the AOV passes' counter block: boxTests (nodes tested by box and plane, the object boxes among them), triTests
+ * (rt_tri_triangle calls), raysTraced (triangles searched), raysHit (triangles with count > 0), and changes nothing a later
+ * render or query produces or chooses. It reads the tables of the scene as they are: after rt_update_objects or
+ * rt_update_points, the moved and the refit ones.
+ * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch; (n == 0 succeeds here;) corners NULL
+ * ("corners are required"); k > RT_BOXES_MAX_K; d_counts NULL, or d_out NULL with k > 0 ("counts and, with k > 0, the output
+ * are required"); n >= 2^30.
+ * Not modelled: the segment along which two triangles cross; leaving a mesh's own neighbours out of a self-intersection check (a
+ * triangle touches itself and everything that shares a corner with it); k above 8.
+ * rt_tris_exhaustive_host: the definition as a plain loop over the host arrays: every sphere in index order, then every
+ * triangle of every object in index order, no pruning; no ctx, no GPU. -1: what rt_boxes_exhaustive_host refuses. */
+typedef struct RtTriangleBatch {
+    const float* corners;   /* n x 9, packed: p, q, r */
+    uint32_t n;
+} RtTriangleBatch;
+int  rt_query_triangles(rt_ctx* ctx, const RtTriangleBatch* d_tris, uint32_t k, RtOverlap* d_out, uint32_t* d_counts);
+int  rt_query_triangles_host(rt_ctx* ctx, const RtTriangleBatch* tris, uint32_t k, RtOverlap* out, uint32_t* counts);
+int  rt_tris_exhaustive_host(const RtSceneArrays* scene, const RtTriangleBatch* tris, uint32_t k, RtOverlap* out, uint32_t* counts);
+
 /* Sphere sweeps ("Sphere sweeps"; include/rt_sweep.h states the rule, both sides compile it): a ball of radius
  * radius[i] whose centre moves along origins[i] + t dirs[i]; does it touch the scene, when and where? Sphere casts, thick rays,
  * continuous collision, the clearance of a path.
@@ -1207,6 +1259,9 @@ int  rt_get_trace_busy_ms(rt_ctx* ctx, double* msOut);
  *                    (10..100, default 40; 0 = the parts' share as it is)
  *   "radiance_max_kslots"  rt_query_radiance: the most rays x 1024 of one piece of a batch; 0 (default) = the paths
  *                    "frames_max_mslots" allows one dispatch
+ *   "tri_plane"      rt_query_triangles: 1 (default): the descent also discards a node whose box lies strictly beside the
+ *                    query's plane; 0: by box overlap only. Same records and counts; boxTests and triTests, which count what
+ *                    the descent visited, are the one pair of counters a knob moves
  *   "trace_variant"  0 = one ray per lane (k_trace), 1 = persistent waves (k_trace_pw)
  *   "refill", "mk_refill", "chunk", "w_setup", "w_leaf", "fast_lanes", "lds_stack", "blocks_per_cu",
  *   "tile_slots", "phase_stats": traversal scheduling details, see DESIGN.md

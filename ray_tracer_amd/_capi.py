@@ -118,6 +118,10 @@ class RtObbBatch(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("lo", C.c_void_p), ("hi", C.c_void_p), ("n", C.c_uint32), ("sharedFrame", C.c_uint32)]
 
 
+class RtTriangleBatch(C.Structure):
+    _fields_ = [("corners", C.c_void_p), ("n", C.c_uint32)]
+
+
 class RtOverlap(C.Structure):
     _fields_ = [("found", C.c_uint32), ("isSphere", C.c_uint32), ("objectIndex", C.c_uint32), ("triIndex", C.c_uint32)]
 
@@ -264,6 +268,9 @@ SYMBOLS = {
     "rt_query_oriented_boxes": (C.c_int, [_vp, _P(RtObbBatch), C.c_uint32, _vp, _vp]),
     "rt_query_oriented_boxes_host": (C.c_int, [_vp, _P(RtObbBatch), C.c_uint32, _vp, _vp]),
     "rt_obbs_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtObbBatch), C.c_uint32, _vp, _vp]),
+    "rt_query_triangles": (C.c_int, [_vp, _P(RtTriangleBatch), C.c_uint32, _vp, _vp]),
+    "rt_query_triangles_host": (C.c_int, [_vp, _P(RtTriangleBatch), C.c_uint32, _vp, _vp]),
+    "rt_tris_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtTriangleBatch), C.c_uint32, _vp, _vp]),
     "rt_object_frames_host": (C.c_int, [_P(RtSceneArrays), _vp, C.c_uint32, _vp]),
     "rt_query_sweep": (C.c_int, [_vp, _P(RtSweepBatch), _vp]),
     "rt_query_sweep_host": (C.c_int, [_vp, _P(RtSweepBatch), _vp]),

@@ -33,6 +33,7 @@ TuningChange set_tuning(Tuning& t, const std::string& k, int value) {
     else if (k == "fast_share") { if (value < 0 || value > 16) return refuse("fast_share: 0..16"); t.fastShare = value; }
     else if (k == "scatter") { if (value != -1 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return refuse("scatter: -1 (auto), 0, 1, 2, 4, 8 or 16"); t.scatter = value; }
     else if (k == "fused_maps") { if (value < 0 || value > 1) return refuse("fused_maps: 0 (map scenes take the multi-kernel pipeline) or 1 (they choose as usual)"); t.fusedMaps = value; }
+    else if (k == "tri_plane") { if (value < 0 || value > 1) return refuse("tri_plane: 0 (the triangle queries descend by boxes only) or 1 (and by the query's plane)"); t.triPlane = value; }
     else if (k == "pixel_refill") { if (value < 0 || value > (int)RT_WAVE) return refuse("pixel_refill must be 0 (by ray length) .. 64"); t.pixelRefill = value; }
     else if (k == "batch_pixels") { if (value < 0 || value > (int)RT_WAVE) return refuse("batch_pixels must be 0 (auto) .. 64"); t.batchPixels = value; }
     else if (k == "batch_fixed") { if (value < 0 || value > 4096) return refuse("batch_fixed out of range"); t.batchFixed = value; }

@@ -71,6 +71,7 @@ struct Tuning {
     int pixelRefill = 0;    // fused pipeline: free lanes at which a wave reserves new pixels (64 = a block at a time, 0 = by ray length)
     int batchPixels = 0;    // fused pipeline: pixels per wave-private block (0 = chosen per launch)
     int batchFixed = 80;    // ... and the fixed part of a block's cost in the chooser, in pixel units
+    int triPlane = 1;       // rt_query_triangles: 1: the descent also discards a node that lies beside the query's plane (pruning (b)); 0: by boxes only. Same answer.
     int fusedMaps = 0;      // 1: a scene that binds an alpha, metalness or bump map may take the fused pipeline (k_render_fused_maps); 0: multi-kernel only
     int probe = 1;          // measure an unknown scene with a small dispatch before its first big one
 };

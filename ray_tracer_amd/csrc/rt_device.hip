@@ -32,6 +32,8 @@
 #include "box_queries.h"
 #include "rt_obb_overlap.hip.h"   // the kernel of the oriented box queries; obb_queries.h: their checks, the arithmetic of a batch, the stack choice
 #include "obb_queries.h"
+#include "rt_tri_overlap.hip.h"   // the kernel of the triangle queries; tri_queries.h: their checks, the arithmetic of a batch, the stack choice
+#include "tri_queries.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -2987,5 +2989,64 @@ int rt_query_oriented_boxes(rt_ctx* c, const RtObbBatch* d_batch, uint32_t k, Rt
 }
 int rt_query_oriented_boxes_host(rt_ctx* c, const RtObbBatch* batch, uint32_t k, RtOverlap* out, uint32_t* counts) {
     return obbs_host(c, "rt_query_oriented_boxes_host", batch, k, out, counts);
+}
+}  // extern "C"
+
+// ---- triangle queries (tri_queries.h has the checks, the arithmetic and the stack choice; DESIGN.md, "Triangle queries")
+namespace {
+template <int STACK, bool GLIST>
+void launch_tris_overlap(rt_ctx* c, uint32_t blocks, const TrisArgs& ta) {
+    hipLaunchKernelGGL((k_tris_overlap<STACK, GLIST>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, ta);
+    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_tris_overlap<%d, %s>", STACK, tf(GLIST));
+}
+
+// the search; it writes the records itself. The deep search's lists share boxesListBuf with the box queries: the passes run one
+// behind the other on the ctx stream, and none keeps anything in it between launches
+int tris_device(rt_ctx* c, const char* fn, const RtTriangleBatch* tris, uint32_t k, RtOverlap* d_out, uint32_t* d_counts) {
+    if (!c) return -1;
+    const std::string refusal = check_tris_query(fn, c->sc.nodes != nullptr, tris, k, d_out, d_counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = tris->n;
+    if (n == 0) return 0;
+    std::string deep;
+    const uint32_t stack = tris_stack(fn, c->maxLeafDepth, &deep);
+    if (!stack) return c->fail(deep);
+    RT_HIP(c, hipSetDevice(c->device));
+    const TrisShape ts = tris_shape(n, k, RT_BLOCK);
+    const bool glist = stack != (uint32_t)RT_BOXES_STACK;
+    if (glist && k) {
+        if (c->boxesListBuf.bytes < ts.listBytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees lists a search in flight may be using
+        int rc = dev_alloc(c, c->boxesListBuf, ts.listBytes);
+        if (rc) return rc;
+    }
+    const TrisArgs ta{tris->corners, n, k, c->tune.triPlane ? 1u : 0u, (const float4*)c->objNearBuf.p, (uint4*)d_out, d_counts, (uint32_t*)c->boxesListBuf.p, (DevCounters*)c->aovCounterBuf.p};
+    if (glist) launch_tris_overlap<RT_BOXES_STACK_DEEP, true>(c, ts.blocks, ta);
+    else launch_tris_overlap<RT_BOXES_STACK, false>(c, ts.blocks, ta);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The host-memory form (staged): corners, out, counts
+int tris_host(rt_ctx* c, const char* fn, const RtTriangleBatch* tris, uint32_t k, RtOverlap* out, uint32_t* counts) {
+    if (!c) return -1;
+    const std::string refusal = check_tris_query(fn, c->sc.nodes != nullptr, tris, k, out, counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = tris->n;
+    if (n == 0) return 0;
+    const TrisShape ts = tris_shape(n, k, RT_BLOCK);
+    const StagePart parts[] = {{tris->corners, nullptr, ts.cornerBytes}, {nullptr, out, ts.outBytes}, {nullptr, counts, ts.countBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtTriangleBatch dev{(const float*)d[0], n};
+        return tris_device(c, fn, &dev, k, (RtOverlap*)d[1], (uint32_t*)d[2]);
+    });
+}
+}  // namespace
+
+extern "C" {
+int rt_query_triangles(rt_ctx* c, const RtTriangleBatch* d_tris, uint32_t k, RtOverlap* d_out, uint32_t* d_counts) {
+    return tris_device(c, "rt_query_triangles", d_tris, k, d_out, d_counts);
+}
+int rt_query_triangles_host(rt_ctx* c, const RtTriangleBatch* tris, uint32_t k, RtOverlap* out, uint32_t* counts) {
+    return tris_host(c, "rt_query_triangles_host", tris, k, out, counts);
 }
 }  // extern "C"

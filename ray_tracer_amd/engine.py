@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .devmem import DeviceBuffer, RtError, hip as _hip   # noqa: F401  (engine.RtError and engine._hip are where callers know them)
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtBoxBatch, RtCounters, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtObbBatch, RtOverlap, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch, RtTexel, RtTexelStats,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtBoxBatch, RtCounters, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtObbBatch, RtOverlap, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch, RtTexel, RtTexelStats, RtTriangleBatch,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -699,6 +699,54 @@ class Renderer:
         if sync:
             self.sync()
         return None
+
+    def query_triangles(self, corners, k=0, n=None, out=None, counts=None, sync=True):
+        """Every surface that each closed triangle of `corners` touches: the first `k` (0..8) in index order (spheres, then
+        objects, then triangles), and how many there are (rt_query_triangles; DESIGN.md, "Triangle queries"). An (n, 9) or
+        (n, 3, 3) numpy array (p, q, r of each triangle) goes through rt_query_triangles_host and comes back as query_boxes'
+        pair; device memory, as query_boxes takes it, needs counts= (4 bytes per triangle) and, with k > 0, out= (16 bytes per
+        slot, 16-byte aligned), and n= where `corners` cannot tell (numel() // 9), and returns None."""
+        k = int(k)
+        rec = C.sizeof(RtOverlap)
+        if not _on_device(corners):
+            c = _triangle_array(corners)
+            if out is not None or counts is not None or not sync:
+                raise ValueError("out=, counts= and sync=False go with device-pointer inputs")
+            batch = RtTriangleBatch(c.ctypes.data, c.shape[0])
+            res = (RtOverlap * max(c.shape[0] * k, 1))()
+            cnt = np.zeros(c.shape[0], np.uint32)
+            self._check(self._l.rt_query_triangles_host(self._h, C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data), "rt_query_triangles_host")
+            return _overlap_rows(res, c.shape[0], k), cnt
+        if counts is None:
+            raise ValueError("device-pointer inputs need counts=: device memory for the n counts")
+        if n is None and hasattr(corners, "numel"):
+            n = int(corners.numel()) // 9
+        n = _device_count(corners, n, counts)
+        if out is None and k > 0:
+            raise ValueError("device-pointer inputs need out=: device memory for the n * k records")
+        batch = RtTriangleBatch(_device_ptr(corners, "corners", 36 * n), n)
+        self._check(self._l.rt_query_triangles(self._h, C.byref(batch), k, None if out is None else C.c_void_p(_device_ptr(out, "out", rec * n * k, floats=False)),
+                                               C.c_void_p(_device_ptr(counts, "counts", 4 * n, floats=False))), "rt_query_triangles")
+        if sync:
+            self.sync()
+        return None
+
+    def query_mesh(self, points, faces, k=0, matrix=None):
+        """query_triangles for the faces of a mesh: `points` (v, 3) float32 and `faces` (f, 3) corner indices; `matrix` (16
+        floats, RenderObject.transformMatrix's layout) places the points first, by mesh_corners' float32 restatement of
+        rt_xform_point, so that the corners are the ones a placed object of the scene would have. numpy arrays come back as
+        query_triangles' pair. Tensors on the device are gathered and placed there and come back as (records, counts): a
+        (f, k, 4) and an (f,) int32 tensor holding the RtOverlap words and the counts."""
+        c = mesh_corners(points, faces, matrix)
+        if not hasattr(c, "data_ptr"):
+            return self.query_triangles(c, k)
+        import torch
+        f = int(c.shape[0])
+        cnt = torch.zeros(max(f, 1), dtype=torch.int32, device=c.device)
+        rec = torch.zeros((max(f, 1), max(int(k), 1), 4), dtype=torch.int32, device=c.device)
+        torch.cuda.synchronize(c.device)   # the gather ran on torch's stream, the query runs on the context's
+        self.query_triangles(c, k, n=f, out=rec if int(k) else None, counts=cnt)
+        return rec[:f, :int(k)], cnt[:f]
 
     def query_sweep(self, origins, dirs, radius, tmax=None, n=None, out=None, sync=True):
         """The first contact of a ball of `radius` whose centre moves along each ray (rt_query_sweep; DESIGN.md, "Sphere sweeps"):
@@ -1564,6 +1612,46 @@ def boxes_exhaustive(scene_arrays, lo, hi, k):
     if _capi.lib().rt_boxes_exhaustive_host(C.byref(scene_arrays), C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data) != 0:
         raise RtError("rt_boxes_exhaustive_host refused its arguments (k > 8, NULL arrays, n >= 2^30, or indices out of range)")
     return _overlap_rows(res, l.shape[0], k), cnt
+
+
+def _triangle_array(corners):
+    """Host triangles as the entry points take them: an (n, 9) float32 array, p, q, r of each."""
+    c = np.ascontiguousarray(corners, dtype=np.float32)
+    if c.size % 9:
+        raise ValueError(f"corners: {c.size} numbers are not whole triangles of nine")
+    return c.reshape(-1, 9)
+
+
+def tris_exhaustive(scene_arrays, corners, k):
+    """The definition of the triangle queries as a plain loop over the host arrays (rt_tris_exhaustive_host; no GPU, no
+    pruning): `scene_arrays` is Scene.arrays(), `corners` (n, 9). Returns what boxes_exhaustive returns."""
+    c = _triangle_array(corners)
+    k = int(k)
+    batch = RtTriangleBatch(c.ctypes.data, c.shape[0])
+    res = (RtOverlap * max(c.shape[0] * k, 1))()
+    cnt = np.zeros(c.shape[0], np.uint32)
+    if _capi.lib().rt_tris_exhaustive_host(C.byref(scene_arrays), C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data) != 0:
+        raise RtError("rt_tris_exhaustive_host refused its arguments (k > 8, NULL arrays, n >= 2^30, or indices out of range)")
+    return _overlap_rows(res, c.shape[0], k), cnt
+
+
+def mesh_corners(points, faces, matrix=None):
+    """The (f, 9) float32 batch of a mesh's faces: points[faces], each point first taken through `matrix` (16 floats,
+    column-major) when given, as rt_xform_point takes it: ((m0 x + m4 y) + m8 z) + m12 in float32, one rounding an operation.
+    numpy arrays give a numpy array; torch tensors are gathered where they live, by the same expressions."""
+    if hasattr(points, "data_ptr"):
+        pts, idx = points.float().reshape(-1, 3), faces.long().reshape(-1, 3)
+    else:
+        pts, idx = np.ascontiguousarray(points, np.float32).reshape(-1, 3), np.asarray(faces, np.int64).reshape(-1, 3)
+    if matrix is not None:
+        m = [float(v) for v in np.asarray(matrix.cpu() if hasattr(matrix, "cpu") else matrix, np.float32).reshape(16)]
+        x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+        cols = [((x * m[r] + y * m[4 + r]) + z * m[8 + r]) + m[12 + r] for r in range(3)]
+        pts = cols[0].new_empty((pts.shape[0], 3)) if hasattr(pts, "data_ptr") else np.empty((pts.shape[0], 3), np.float32)
+        for r in range(3):
+            pts[:, r] = cols[r]
+    c = pts[idx].reshape(-1, 9)
+    return c.contiguous() if hasattr(c, "contiguous") else np.ascontiguousarray(c, np.float32)
 
 
 def _obb_arrays(frames, lo, hi):
