@@ -83,9 +83,13 @@ class Box:
             return F(F(F(x * y) + F(y * z)) + F(z * x))
 
 
-def build_bvh(tri_pos):
+def build_bvh(tri_pos, trace=None):
     """Returns (nodes, order): nodes = list of [minx,maxx,miny,maxy,minz,maxz,index,triCount]
-    in the reference's numbering (root 0, children in pairs), order = triangle permutation."""
+    in the reference's numbering (root 0, children in pairs), order = triangle permutation.
+    With a list as `trace`, every visited node of more than two triangles appends one record to it, in visiting order:
+    dict(node, depth, count, split, axis, splitPos, ties, tieAxes, nL, bestDefault): whether it got children, the chosen
+    axis and plane, how many (axis, candidate) pairs attained the best cost and on which axes, the size of the left side
+    after the partition (None when the node was not partitioned) and whether no cost was below the starting 1e30."""
     n = len(tri_pos)
     order = list(range(n))
     cent = centroids_of(tri_pos)
@@ -105,6 +109,7 @@ def build_bvh(tri_pos):
 
     def find_split(first, count):
         best, axis, pos = F(1e30), 0, F(0)
+        costs = []
         for a in range(3):
             cs = [cent[order[i], a] for i in range(first, first + count)]
             mn, mx = F(1e30), F(-1e30)
@@ -137,15 +142,20 @@ def build_bvh(tri_pos):
             for i in range(BINS - 1):
                 with np.errstate(over="ignore", invalid="ignore"):
                     cost = F(F(lc[i] * la[i]) + F(rc[i] * ra[i]))
+                costs.append((a, cost))
                 if cost < best:
                     axis, pos, best = a, F(mn + F(scale * F(i + 1))), cost
-        return best, axis, pos
+        return best, axis, pos, [a for a, cost in costs if cost == best]
 
     def subdivide(idx, depth):
         first, count = nodes[idx][6], nodes[idx][7]
         if count <= 2 or depth >= 64:
             return
-        best, axis, pos = find_split(first, count)
+        best, axis, pos, tied = find_split(first, count)
+        rec = dict(node=idx, depth=depth, count=count, split=False, axis=axis, splitPos=pos, ties=len(tied),
+                   tieAxes=sorted(set(tied)), nL=None, bestDefault=bool(best == F(1e30)))
+        if trace is not None:
+            trace.append(rec)
         nd = nodes[idx]
         x = F(nd[1] - nd[0]); y = F(nd[3] - nd[2]); z = F(nd[5] - nd[4])
         parent_area = F(F(F(x * y) + F(y * z)) + F(z * x))
@@ -159,8 +169,10 @@ def build_bvh(tri_pos):
                 order[i], order[j] = order[j], order[i]
                 j -= 1
         left = i - first
+        rec["nL"] = left
         if left == 0 or left == count:
             return
+        rec["split"] = True
         child = used[0]
         used[0] += 2
         set_node(child, first, left)

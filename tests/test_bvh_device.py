@@ -1,11 +1,25 @@
 """The GPU BVH builder (csrc/bvh_build.hip.h, rt_bvh_build) against the host builder of the scene half
 (itself checked against oracle/scene_ref.py): same nodes in the same numbering, same triangle order.
-A zero node bound may differ in sign (first-come on the host), so bounds are compared as floats."""
+A zero node bound may differ in sign (first-come on the host), so bounds are compared as floats.
+
+Covered: five assets behind the Cornell box; uniform blobs of 300, 69 451 and 871 414 triangles; soups of 1, 2, 3 and 7; a strip with
+equal centroids on two axes; and the edge meshes of tests/bvh_cases.py, each shown by tests/test_bvh_edges_host.py to reach its edge
+on the host: partitions that leave one side empty (nL == 0 and nL == n) in k_bvh_level and in the wide path, nodes where no cost
+is below the starting 1e30 (split at axis 0, position 0), exact ties between candidates and between axes (lattices), a level of a
+3-triangle node beside a 9000-triangle node in the wide path, a level of > 32 nodes with one of >= 1024 triangles on 64 threads,
+blobs at the launch thresholds (8192), the 2048-position chunk and node sizes of 64, 256 and 1024 +- 1, and three hooked meshes in
+one scene after the Cornell box (triIndex0 / nodeBase != 0), traced against the oracle. The device trees are also checked by
+tests/bvh_checks.py, which knows no builder. Not covered: the depth cap of 64 ("GPU BVH build")."""
 import numpy as np
 import pytest
 
+from oracle import pyoracle
 from ray_tracer_amd import engine, scenes
 from ray_tracer_amd._capi import BVHNode, Triangle
+
+import bvh_cases
+from bvh_checks import check_bvh, stats_tuple
+from util import assert_hits_equal, seeded_rays
 
 import ctypes as C
 
@@ -103,3 +117,51 @@ def test_degenerate_inputs_for_the_builder(renderer):
     host = engine.Scene(); host.add_mesh("m", pos, nrm, engine.placement(), 0)
     dev = engine.Scene(); dev.use_device_bvh(renderer); dev.add_mesh("m", pos, nrm, engine.placement(), 0)
     _same(host, dev)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(bvh_cases.CASES))
+def test_device_bvh_on_the_edge_cases(renderer, case):
+    """tests/bvh_cases.py: the conditions that make these the edges are asserted on the host tree by tests/test_bvh_edges_host.py."""
+    pos, nrm = bvh_cases.CASES[case][0]()
+    host = engine.Scene(); host.add_mesh("m", pos, nrm, engine.placement(), 0)
+    dev = engine.Scene(); dev.use_device_bvh(renderer); dev.add_mesh("m", pos, nrm, engine.placement(), 0)
+    _same(host, dev)
+    assert check_bvh(dev.numpy(), 0, 0, len(pos)) == stats_tuple(dev.last_bvh_stats())
+
+
+@pytest.mark.gpu
+def test_several_hooked_meshes_in_one_scene(renderer):
+    """Three meshes built under the hook behind the Cornell box: every one with its own triIndex0 and nodeBase, the first through
+    the wide path, the second a single given-up leaf, the third full of ties."""
+    meshes = [("blob", bvh_cases.blob(8200), engine.placement(position=(0, -0.5, 0), scale=0.6)),
+              ("one_ulp", bvh_cases.one_ulp(5), engine.placement(position=(-1.5, -0.9, 0.2), scale=0.8)),
+              ("lattice", bvh_cases.lattice(6), engine.placement(position=(0.3, -0.2, -0.9), scale=0.1))]
+
+    def build(scene):
+        scene.prepare_storage_buffers()
+        spans = []
+        for key, (pos, nrm), place in meshes:
+            before = scene.counts()
+            scene.add_mesh(key, pos, nrm, place, 0)
+            spans.append((before["bvhNodes"], before["triangles"], len(pos), stats_tuple(scene.last_bvh_stats())))
+        return spans
+
+    host = engine.Scene()
+    spans = build(host)
+    dev = engine.Scene(); dev.use_device_bvh(renderer)
+    assert build(dev) == spans
+    _same(host, dev)
+    arrays = dev.numpy()
+    roots = arrays["objects"].view(np.uint32).reshape(len(arrays["objects"]), -1)[-3:, 17]
+    for (root, first, count, stats), object_root in zip(spans, roots):
+        assert root == object_root and root > 0 and first > 0
+        assert check_bvh(arrays, root, first, count) == stats
+    o, d = seeded_rays(2048, 77)
+    renderer.upload_scene(dev)
+    g = engine.hits_to_numpy(renderer.trace_rays(o, d))
+    c = engine.hits_to_numpy(pyoracle.trace_rays(host, o, d))
+    n_objects = len(arrays["objects"])
+    for k in (3, 2, 1):  # every one of the three meshes is hit
+        assert ((c["didHit"] != 0) & (c["isSphere"] == 0) & (c["objectHitIndex"] == n_objects - k)).sum() > 0
+    assert_hits_equal(g, c)
