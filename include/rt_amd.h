@@ -999,8 +999,8 @@ int  rt_object_frames_host(const RtSceneArrays* scene, const uint32_t* objects, 
  * Refused with a message, nothing written, in this order: no uploaded scene; a NULL batch; (n == 0 succeeds here;) corners NULL
  * ("corners are required"); k > RT_BOXES_MAX_K; d_counts NULL, or d_out NULL with k > 0 ("counts and, with k > 0, the output
  * are required"); n >= 2^30.
- * Not modelled: the segment along which two triangles cross; leaving a mesh's own neighbours out of a self-intersection check (a
- * triangle touches itself and everything that shares a corner with it); k above 8.
+ * Not modelled: leaving a mesh's own neighbours out of a self-intersection check (a triangle touches itself and everything that
+ * shares a corner with it); k above 8. The segment along which two triangles cross is rt_query_cuts' answer ("Triangle cuts").
  * rt_tris_exhaustive_host: the definition as a plain loop over the host arrays: every sphere in index order, then every
  * triangle of every object in index order, no pruning; no ctx, no GPU. -1: what rt_boxes_exhaustive_host refuses. */
 typedef struct RtTriangleBatch {
@@ -1010,6 +1010,54 @@ typedef struct RtTriangleBatch {
 int  rt_query_triangles(rt_ctx* ctx, const RtTriangleBatch* d_tris, uint32_t k, RtOverlap* d_out, uint32_t* d_counts);
 int  rt_query_triangles_host(rt_ctx* ctx, const RtTriangleBatch* tris, uint32_t k, RtOverlap* out, uint32_t* counts);
 int  rt_tris_exhaustive_host(const RtSceneArrays* scene, const RtTriangleBatch* tris, uint32_t k, RtOverlap* out, uint32_t* counts);
+
+/* Triangle cuts ("Triangle cuts"; include/rt_tri_cut.h states the rule, both sides compile it): the segments along
+ * which a caller's triangle crosses the triangles of the scene, the first k of them in index order, and how many there are:
+ * intersection curves of a tool, a link or a cloth against the scene, contour lines of a cut surface, trim curves, contact lines.
+ * Contract. The batch is rt_query_triangles', and so is what makes a triangle valid; a triangle that is not valid is not
+ * searched: count 0, empty records, not counted in raysTraced. The surfaces are the scene's triangles as rt_query_triangles
+ * places them. Spheres are never members (a circle arc is not a segment). A scene triangle is a member of query i when
+ * rt_tri_cut_prepared gives the pair a cut:
+ *  - the pair passes rt_tri_triangle_prepared, so every cut member is a member of rt_query_triangles, under the same key;
+ *  - with all corners relative to the centre of the query's box, each triangle has candidate points on the other's plane: where
+ *    an edge whose ends have heights of strictly opposite sign crosses it, lo + (hi - lo) (s_lo / (s_lo - s_hi)) with the edge's
+ *    ends in the order of their coordinates (x, y, z), not of the winding, and every corner whose height is exactly 0. Three
+ *    heights of 0: the pair is coplanar and has no cut. A query with two or three equal corners has no normal, is coplanar with
+ *    everything, and has count 0;
+ *  - on the common line nQ x nT each triangle's candidates span an interval; no cut if either has no candidate or the intervals
+ *    are strictly apart; else a is the candidate of the larger lower end and b that of the smaller upper end, the query's on
+ *    equal projections, then the lower edge index;
+ *  - a, b in world coordinates fl(X + m); featA, featB: 0..2 the query's edge (p q, q r, r p) the end lies on, 3..5 the scene
+ *    triangle's (for a corner, the edge that starts at it). A cut with a non-finite number is no member; a cut of length zero
+ *    (a == b, bit for bit: the triangles touch in a point) is.
+ * The end on an edge shared by two scene triangles is the same bits in both cuts, whatever their windings, so the cuts of one
+ * query chain into polylines by comparing bits. (Not across queries: m differs.) The member set is a function of the triangle
+ * and the scene alone.
+ *  - d_counts[i]: the number of cuts, exact whatever k is.
+ *  - d_out[i * k .. i * k + k - 1]: the first min(k, count) cuts in ascending order of rt_query_boxes' key (object index, then
+ *    triangle index), then empty records (all 0). found = 1, objectIndex, triIndex as RtOverlap's, reserved = 0.
+ *  - rt_query_cuts equals rt_cuts_exhaustive_host in every byte of every record and count. Counts are the same for every k, and
+ *    the list at a smaller k is the head of the list at a larger one.
+ *  - k runs from 0 to RT_BOXES_MAX_K. k == 0: counts only, d_out may be NULL. n == 0 succeeds and does nothing.
+ * rt_query_cuts: the struct is read on the host, corners, d_out (16-byte aligned) and d_counts are device pointers, asynchronous
+ * on the ctx stream. rt_query_cuts_host takes host arrays, stages its three parts (corners, out, counts) and blocks. One lane per
+ * triangle, one kernel: k_tris_cut runs rt_query_triangles' descent with both of its prunings ("tri_plane" switches the plane's
+ * here as there), keeps keys only, and after the search computes the kept cuts again and writes each record with three 16-byte
+ * stores. rt_last_kernel names the search that ran: k_tris_cut<24, false> or k_tris_cut<64, true>, chosen as k_tris_overlap's.
+ * Counters as the triangle pass counts them: boxTests, triTests (rule calls), raysTraced (triangles searched), raysHit (triangles
+ * with a cut). Refused exactly as rt_query_triangles refuses, in its order and words, under these functions' names.
+ * Not modelled: arcs on spheres; the overlap polygon of a coplanar pair; leaving out a mesh's own neighbours (point cuts at shared
+ * corners are reported; callers filter); k above 8 (the count says when to subdivide).
+ * rt_cuts_exhaustive_host: the definition as a plain loop: every triangle of every object in index order, no pruning; no ctx, no
+ * GPU. -1: what rt_tris_exhaustive_host refuses. */
+typedef struct RtCut {            /* 48 bytes, three 16-byte stores; no member: all 0 */
+    float a[3]; uint32_t featA;   /* one end, world coordinates; the edge it lies on */
+    float b[3]; uint32_t featB;   /* the other end */
+    uint32_t found, objectIndex, triIndex, reserved;   /* reserved = 0 */
+} RtCut;
+int  rt_query_cuts(rt_ctx* ctx, const RtTriangleBatch* d_tris, uint32_t k, RtCut* d_out, uint32_t* d_counts);
+int  rt_query_cuts_host(rt_ctx* ctx, const RtTriangleBatch* tris, uint32_t k, RtCut* out, uint32_t* counts);
+int  rt_cuts_exhaustive_host(const RtSceneArrays* scene, const RtTriangleBatch* tris, uint32_t k, RtCut* out, uint32_t* counts);
 
 /* Sphere sweeps ("Sphere sweeps"; include/rt_sweep.h states the rule, both sides compile it): a ball of radius
  * radius[i] whose centre moves along origins[i] + t dirs[i]; does it touch the scene, when and where? Sphere casts, thick rays,
@@ -1259,7 +1307,7 @@ int  rt_get_trace_busy_ms(rt_ctx* ctx, double* msOut);
  *                    (10..100, default 40; 0 = the parts' share as it is)
  *   "radiance_max_kslots"  rt_query_radiance: the most rays x 1024 of one piece of a batch; 0 (default) = the paths
  *                    "frames_max_mslots" allows one dispatch
- *   "tri_plane"      rt_query_triangles: 1 (default): the descent also discards a node whose box lies strictly beside the
+ *   "tri_plane"      rt_query_triangles, rt_query_cuts: 1 (default): the descent also discards a node whose box lies strictly beside the
  *                    query's plane; 0: by box overlap only. Same records and counts; boxTests and triTests, which count what
  *                    the descent visited, are the one pair of counters a knob moves
  *   "trace_variant"  0 = one ray per lane (k_trace), 1 = persistent waves (k_trace_pw)

@@ -126,6 +126,11 @@ class RtOverlap(C.Structure):
     _fields_ = [("found", C.c_uint32), ("isSphere", C.c_uint32), ("objectIndex", C.c_uint32), ("triIndex", C.c_uint32)]
 
 
+class RtCut(C.Structure):
+    _fields_ = [("a", C.c_float * 3), ("featA", C.c_uint32), ("b", C.c_float * 3), ("featB", C.c_uint32),
+                ("found", C.c_uint32), ("objectIndex", C.c_uint32), ("triIndex", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class RtNearest(C.Structure):
     _fields_ = [("dst", C.c_float), ("found", C.c_uint32), ("isSphere", C.c_uint32), ("objectIndex", C.c_uint32),
                 ("triIndex", C.c_uint32), ("uv", C.c_float * 2), ("point", C.c_float * 3), ("_pad", C.c_uint32 * 2)]
@@ -271,6 +276,9 @@ SYMBOLS = {
     "rt_query_triangles": (C.c_int, [_vp, _P(RtTriangleBatch), C.c_uint32, _vp, _vp]),
     "rt_query_triangles_host": (C.c_int, [_vp, _P(RtTriangleBatch), C.c_uint32, _vp, _vp]),
     "rt_tris_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtTriangleBatch), C.c_uint32, _vp, _vp]),
+    "rt_query_cuts": (C.c_int, [_vp, _P(RtTriangleBatch), C.c_uint32, _vp, _vp]),
+    "rt_query_cuts_host": (C.c_int, [_vp, _P(RtTriangleBatch), C.c_uint32, _vp, _vp]),
+    "rt_cuts_exhaustive_host": (C.c_int, [_P(RtSceneArrays), _P(RtTriangleBatch), C.c_uint32, _vp, _vp]),
     "rt_object_frames_host": (C.c_int, [_P(RtSceneArrays), _vp, C.c_uint32, _vp]),
     "rt_query_sweep": (C.c_int, [_vp, _P(RtSweepBatch), _vp]),
     "rt_query_sweep_host": (C.c_int, [_vp, _P(RtSweepBatch), _vp]),

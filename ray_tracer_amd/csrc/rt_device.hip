@@ -34,6 +34,8 @@
 #include "obb_queries.h"
 #include "rt_tri_overlap.hip.h"   // the kernel of the triangle queries; tri_queries.h: their checks, the arithmetic of a batch, the stack choice
 #include "tri_queries.h"
+#include "rt_tri_cut.hip.h"   // the kernel of the cut queries; cut_queries.h: the arithmetic of a batch, the stack choice
+#include "cut_queries.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -3048,5 +3050,63 @@ int rt_query_triangles(rt_ctx* c, const RtTriangleBatch* d_tris, uint32_t k, RtO
 }
 int rt_query_triangles_host(rt_ctx* c, const RtTriangleBatch* tris, uint32_t k, RtOverlap* out, uint32_t* counts) {
     return tris_host(c, "rt_query_triangles_host", tris, k, out, counts);
+}
+}  // extern "C"
+
+// ---- cut queries (cut_queries.h has the arithmetic and the stack choice, tri_queries.h the checks; DESIGN.md, "Triangle cuts")
+namespace {
+template <int STACK, bool GLIST>
+void launch_tris_cut(rt_ctx* c, uint32_t blocks, const CutsArgs& ca) {
+    hipLaunchKernelGGL((k_tris_cut<STACK, GLIST>), dim3(blocks), dim3(RT_BLOCK), 0, c->stream, c->sc, ca);
+    snprintf(c->rep.lastKernel, sizeof c->rep.lastKernel, "k_tris_cut<%d, %s>", STACK, tf(GLIST));
+}
+
+// the search; it writes the records itself. The deep search's key lists share boxesListBuf with the box and triangle queries
+int cuts_device(rt_ctx* c, const char* fn, const RtTriangleBatch* tris, uint32_t k, RtCut* d_out, uint32_t* d_counts) {
+    if (!c) return -1;
+    const std::string refusal = check_tris_query(fn, c->sc.nodes != nullptr, tris, k, d_out, d_counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = tris->n;
+    if (n == 0) return 0;
+    std::string deep;
+    const uint32_t stack = cuts_stack(fn, c->maxLeafDepth, &deep);
+    if (!stack) return c->fail(deep);
+    RT_HIP(c, hipSetDevice(c->device));
+    const CutsShape cs = cuts_shape(n, k, RT_BLOCK);
+    const bool glist = stack != (uint32_t)RT_BOXES_STACK;
+    if (glist && k) {
+        if (c->boxesListBuf.bytes < cs.listBytes) RT_HIP(c, hipStreamSynchronize(c->stream));   // growing frees lists a search in flight may be using
+        int rc = dev_alloc(c, c->boxesListBuf, cs.listBytes);
+        if (rc) return rc;
+    }
+    const CutsArgs ca{tris->corners, n, k, c->tune.triPlane ? 1u : 0u, (const float4*)c->objNearBuf.p, (uint4*)d_out, d_counts, (uint32_t*)c->boxesListBuf.p, (DevCounters*)c->aovCounterBuf.p};
+    if (glist) launch_tris_cut<RT_BOXES_STACK_DEEP, true>(c, cs.blocks, ca);
+    else launch_tris_cut<RT_BOXES_STACK, false>(c, cs.blocks, ca);
+    RT_HIP(c, hipGetLastError());
+    return 0;
+}
+
+// The host-memory form (staged): corners, out, counts
+int cuts_host(rt_ctx* c, const char* fn, const RtTriangleBatch* tris, uint32_t k, RtCut* out, uint32_t* counts) {
+    if (!c) return -1;
+    const std::string refusal = check_tris_query(fn, c->sc.nodes != nullptr, tris, k, out, counts);
+    if (!refusal.empty()) return c->fail(refusal);
+    const uint32_t n = tris->n;
+    if (n == 0) return 0;
+    const CutsShape cs = cuts_shape(n, k, RT_BLOCK);
+    const StagePart parts[] = {{tris->corners, nullptr, cs.cornerBytes}, {nullptr, out, cs.outBytes}, {nullptr, counts, cs.countBytes}};
+    return staged(c, parts, [&](void* const* d) {
+        const RtTriangleBatch dev{(const float*)d[0], n};
+        return cuts_device(c, fn, &dev, k, (RtCut*)d[1], (uint32_t*)d[2]);
+    });
+}
+}  // namespace
+
+extern "C" {
+int rt_query_cuts(rt_ctx* c, const RtTriangleBatch* d_tris, uint32_t k, RtCut* d_out, uint32_t* d_counts) {
+    return cuts_device(c, "rt_query_cuts", d_tris, k, d_out, d_counts);
+}
+int rt_query_cuts_host(rt_ctx* c, const RtTriangleBatch* tris, uint32_t k, RtCut* out, uint32_t* counts) {
+    return cuts_host(c, "rt_query_cuts_host", tris, k, out, counts);
 }
 }  // extern "C"

@@ -54,8 +54,21 @@ __device__ __forceinline__ bool tris_node_in(TriLane& tl, bool placed, float4 f0
 }
 
 // The descent of one object's tree. placed: the object has a forward matrix (rows f0..f2) and the pad of its scale; else the
-// node boxes and the corners are used as they are.
-template <int STACK>
+// node boxes and the corners are used as they are. Pair: what a leaf does with its triangles (TriTouch here; rt_tri_cut.hip.h's
+// CutExists runs the same descent: a cut member passed rt_tri_triangle_prepared).
+struct TriTouch {
+    // the triangles [first, first + count) of a leaf of object obj against the lane's query
+    static __device__ __forceinline__ void leaf(const DevScene& sc, TriLane& tl, uint32_t obj, uint32_t first, uint32_t count, bool placed, float4 f0, float4 f1, float4 f2) {
+        for (uint32_t j = first; j < first + count; j++) {
+            rt_vec3 a = f4xyz(sc.triPos[3 * (size_t)j]), b = f4xyz(sc.triPos[3 * (size_t)j + 1]), c = f4xyz(sc.triPos[3 * (size_t)j + 2]);
+            if (placed) { a = xform_point_rows(f0, f1, f2, a); b = xform_point_rows(f0, f1, f2, b); c = xform_point_rows(f0, f1, f2, c); }
+            if (!rt_tri_triangle_prepared(&tl.t, a, b, c)) continue;
+            tl.count++;
+            tl.have = rt_box_insert(tl.list, RT_WAVE, tl.k, tl.have, rt_box_triangle_word(obj), j);
+        }
+    }
+};
+template <int STACK, typename Pair = TriTouch>
 __device__ __forceinline__ void tris_descend(const DevScene& sc, TriLane& tl, uint32_t obj, uint32_t root, uint32_t rootCnt, bool placed, float4 f0, float4 f1, float4 f2, float pad) {
     uint32_t* const stack = tl.stack;
     uint32_t sp = 0, curIdx = root, curCnt = rootCnt;
@@ -71,13 +84,7 @@ __device__ __forceinline__ void tris_descend(const DevScene& sc, TriLane& tl, ui
         }
         if (curCnt != 0) {
             tl.nTri += curCnt;
-            for (uint32_t j = curIdx; j < curIdx + curCnt; j++) {
-                rt_vec3 a = f4xyz(sc.triPos[3 * (size_t)j]), b = f4xyz(sc.triPos[3 * (size_t)j + 1]), c = f4xyz(sc.triPos[3 * (size_t)j + 2]);
-                if (placed) { a = xform_point_rows(f0, f1, f2, a); b = xform_point_rows(f0, f1, f2, b); c = xform_point_rows(f0, f1, f2, c); }
-                if (!rt_tri_triangle_prepared(&tl.t, a, b, c)) continue;
-                tl.count++;
-                tl.have = rt_box_insert(tl.list, RT_WAVE, tl.k, tl.have, rt_box_triangle_word(obj), j);
-            }
+            Pair::leaf(sc, tl, obj, curIdx, curCnt, placed, f0, f1, f2);
             have_node = false;
         } else {
             const float4* pr = sc.nodes + 2 * (size_t)curIdx;
@@ -93,6 +100,33 @@ __device__ __forceinline__ void tris_descend(const DevScene& sc, TriLane& tl, ui
                 if (cnt) leaf_from_ref(sc, w, curIdx, curCnt);
             } else have_node = false;
         }
+    }
+}
+
+// Every object of the scene for a prepared query: its box by (a) and (b), then its tree
+template <int STACK, typename Pair>
+__device__ __forceinline__ void tris_objects(const DevScene& sc, TriLane& tl, const float4* objNear) {
+    for (uint32_t obj = 0; obj < sc.objectCount; obj++) {
+        // The object's record and, below, its rows through a per-lane index, as k_boxes_overlap reads the rows: every lane
+        // reads the same numbers (threadIdx.y is 0 in this one-dimensional launch), but as vector loads into vector
+        // registers; as scalars they live through the whole descent and the scalar file overflows
+        // (tests/test_triangles_budget.py)
+        const float4* const near = rt_global(objNear) + 3 * (size_t)(obj + threadIdx.y);
+        const float4 n0 = near[0], n1 = near[1];
+        const uint4 meta = sc.objMeta[obj];
+        tl.nBox++;
+        const bool placed = (meta.w & RT_OBJ_FWD_IDENTITY) == 0u;
+        const float pad = rt_box_pad(near[2].x);
+        if (placed ? rt_box_object_apart(tl.t.lo, tl.t.hi, f4xyz(n0), f4xyz(n1), pad) : rt_box_apart(tl.t.lo, tl.t.hi, f4xyz(n0), f4xyz(n1))) continue;
+        if (tl.plane) {
+            // the object's world box, grown by the pad rt_box_object_apart grows a placed one by
+            const float g = placed ? pad : 0.f;
+            if (rt_tri_plane_apart(&tl.t, rt_v3(n0.x - g, n0.y - g, n0.z - g), rt_v3(n1.x + g, n1.y + g, n1.z + g))) continue;
+        }
+        const float4* const fwd = rt_global(sc.objFwd) + 3 * (size_t)(obj + threadIdx.y);
+        float4 f0 = make_float4(1.f, 0.f, 0.f, 0.f), f1 = make_float4(0.f, 1.f, 0.f, 0.f), f2 = make_float4(0.f, 0.f, 1.f, 0.f);
+        if (placed) { f0 = fwd[0]; f1 = fwd[1]; f2 = fwd[2]; }
+        tris_descend<STACK, Pair>(sc, tl, obj, meta.x, meta.y, placed, f0, f1, f2, pad);
     }
 }
 
@@ -125,28 +159,7 @@ __global__ __launch_bounds__(RT_BLOCK) void k_tris_overlap(DevScene sc, TrisArgs
             tl.have = rt_box_insert(tl.list, RT_WAVE, tl.k, tl.have, rt_box_sphere_word(i), 0u);
         }
         tl.t = rt_tri_prepare(p, q, r);
-        for (uint32_t obj = 0; obj < sc.objectCount; obj++) {
-            // The object's record and, below, its rows through a per-lane index, as k_boxes_overlap reads the rows: every lane
-            // reads the same numbers (threadIdx.y is 0 in this one-dimensional launch), but as vector loads into vector
-            // registers; as scalars they live through the whole descent and the scalar file overflows
-            // (tests/test_triangles_budget.py)
-            const float4* const near = rt_global(ta.objNear) + 3 * (size_t)(obj + threadIdx.y);
-            const float4 n0 = near[0], n1 = near[1];
-            const uint4 meta = sc.objMeta[obj];
-            tl.nBox++;
-            const bool placed = (meta.w & RT_OBJ_FWD_IDENTITY) == 0u;
-            const float pad = rt_box_pad(near[2].x);
-            if (placed ? rt_box_object_apart(tl.t.lo, tl.t.hi, f4xyz(n0), f4xyz(n1), pad) : rt_box_apart(tl.t.lo, tl.t.hi, f4xyz(n0), f4xyz(n1))) continue;
-            if (tl.plane) {
-                // the object's world box, grown by the pad rt_box_object_apart grows a placed one by
-                const float g = placed ? pad : 0.f;
-                if (rt_tri_plane_apart(&tl.t, rt_v3(n0.x - g, n0.y - g, n0.z - g), rt_v3(n1.x + g, n1.y + g, n1.z + g))) continue;
-            }
-            const float4* const fwd = rt_global(sc.objFwd) + 3 * (size_t)(obj + threadIdx.y);
-            float4 f0 = make_float4(1.f, 0.f, 0.f, 0.f), f1 = make_float4(0.f, 1.f, 0.f, 0.f), f2 = make_float4(0.f, 0.f, 1.f, 0.f);
-            if (placed) { f0 = fwd[0]; f1 = fwd[1]; f2 = fwd[2]; }
-            tris_descend<STACK>(sc, tl, obj, meta.x, meta.y, placed, f0, f1, f2, pad);
-        }
+        tris_objects<STACK, TriTouch>(sc, tl, ta.objNear);
     }
     if (mine) {
         ta.counts[gid] = tl.count;

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .devmem import DeviceBuffer, RtError, hip as _hip   # noqa: F401  (engine.RtError and engine._hip are where callers know them)
-from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtBoxBatch, RtCounters, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtObbBatch, RtOverlap, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch, RtTexel, RtTexelStats, RtTriangleBatch,
+from ._capi import (BVHNode, PushConstants, RayMaterial, RenderObject, RtAoParams, RtAovBuffers, RtBoxBatch, RtCounters, RtCut, RtDenoiseParams, RtHit, RtIrradianceParams, RtMeshTopology, RtNearest, RtObbBatch, RtOverlap, RtPointBatch, RtPointNormalBatch, RtRadianceParams, RtRayBatch, RtSweep, RtSweepBatch, RtTexel, RtTexelStats, RtTriangleBatch,
                     RtPlacement, RtSampleMapParams, RtSampleMapStats, RtSceneArrays, RtTemporalParams, RtTexture, Sphere, Triangle, TrianglePoint)
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
@@ -746,6 +746,53 @@ class Renderer:
         rec = torch.zeros((max(f, 1), max(int(k), 1), 4), dtype=torch.int32, device=c.device)
         torch.cuda.synchronize(c.device)   # the gather ran on torch's stream, the query runs on the context's
         self.query_triangles(c, k, n=f, out=rec if int(k) else None, counts=cnt)
+        return rec[:f, :int(k)], cnt[:f]
+
+    def query_cuts(self, corners, k=0, n=None, out=None, counts=None, sync=True):
+        """The segments along which each closed triangle of `corners` crosses the scene's triangles: the first `k` (0..8) in
+        index order (object, then triangle), and how many there are (rt_query_cuts; DESIGN.md, "Triangle cuts"). An (n, 9) or
+        (n, 3, 3) numpy array goes through rt_query_cuts_host and comes back as (RtCut array of n * k records, triangle i's at
+        [i * k, i * k + k) (cuts_to_numpy); uint32 array of n counts); device memory, as query_triangles takes it, needs counts=
+        (4 bytes per triangle) and, with k > 0, out= (48 bytes per slot, 16-byte aligned), and n= where `corners` cannot tell,
+        and returns None."""
+        k = int(k)
+        rec = C.sizeof(RtCut)
+        if not _on_device(corners):
+            c = _triangle_array(corners)
+            if out is not None or counts is not None or not sync:
+                raise ValueError("out=, counts= and sync=False go with device-pointer inputs")
+            batch = RtTriangleBatch(c.ctypes.data, c.shape[0])
+            res = (RtCut * max(c.shape[0] * k, 1))()
+            cnt = np.zeros(c.shape[0], np.uint32)
+            self._check(self._l.rt_query_cuts_host(self._h, C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data), "rt_query_cuts_host")
+            return _cut_rows(res, c.shape[0], k), cnt
+        if counts is None:
+            raise ValueError("device-pointer inputs need counts=: device memory for the n counts")
+        if n is None and hasattr(corners, "numel"):
+            n = int(corners.numel()) // 9
+        n = _device_count(corners, n, counts)
+        if out is None and k > 0:
+            raise ValueError("device-pointer inputs need out=: device memory for the n * k records")
+        batch = RtTriangleBatch(_device_ptr(corners, "corners", 36 * n), n)
+        self._check(self._l.rt_query_cuts(self._h, C.byref(batch), k, None if out is None else C.c_void_p(_device_ptr(out, "out", rec * n * k, floats=False)),
+                                          C.c_void_p(_device_ptr(counts, "counts", 4 * n, floats=False))), "rt_query_cuts")
+        if sync:
+            self.sync()
+        return None
+
+    def query_mesh_cuts(self, points, faces, k=0, matrix=None):
+        """query_cuts for the faces of a mesh, gathered and placed by mesh_corners as query_mesh gathers them. numpy arrays come
+        back as query_cuts' pair. Tensors on the device come back as (records, counts): an (f, k, 12) and an (f,) int32 tensor
+        holding the RtCut words (the end points' bits among them) and the counts."""
+        c = mesh_corners(points, faces, matrix)
+        if not hasattr(c, "data_ptr"):
+            return self.query_cuts(c, k)
+        import torch
+        f = int(c.shape[0])
+        cnt = torch.zeros(max(f, 1), dtype=torch.int32, device=c.device)
+        rec = torch.zeros((max(f, 1), max(int(k), 1), 12), dtype=torch.int32, device=c.device)
+        torch.cuda.synchronize(c.device)   # the gather ran on torch's stream, the query runs on the context's
+        self.query_cuts(c, k, n=f, out=rec if int(k) else None, counts=cnt)
         return rec[:f, :int(k)], cnt[:f]
 
     def query_sweep(self, origins, dirs, radius, tmax=None, n=None, out=None, sync=True):
@@ -1633,6 +1680,81 @@ def tris_exhaustive(scene_arrays, corners, k):
     if _capi.lib().rt_tris_exhaustive_host(C.byref(scene_arrays), C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data) != 0:
         raise RtError("rt_tris_exhaustive_host refused its arguments (k > 8, NULL arrays, n >= 2^30, or indices out of range)")
     return _overlap_rows(res, c.shape[0], k), cnt
+
+
+def _cut_rows(res, n, k):
+    """The n * k records of a cut query out of the (never empty) ctypes array they were written to."""
+    return (RtCut * (n * k)).from_buffer(res) if n * k else (RtCut * 0)()
+
+
+CUT_DTYPE = np.dtype([("a", np.float32, 3), ("featA", np.uint32), ("b", np.float32, 3), ("featB", np.uint32),
+                      ("found", np.uint32), ("objectIndex", np.uint32), ("triIndex", np.uint32), ("reserved", np.uint32)])
+
+
+def cuts_to_numpy(recs):
+    """RtCut array (or its bytes) -> a structured numpy view of CUT_DTYPE: a, featA, b, featB, found, objectIndex, triIndex,
+    reserved. A view: the end points keep their bits."""
+    return np.frombuffer(recs, dtype=CUT_DTYPE) if len(recs) else np.zeros(0, CUT_DTYPE)
+
+
+def cuts_exhaustive(scene_arrays, corners, k):
+    """The definition of the cut queries as a plain loop over the host arrays (rt_cuts_exhaustive_host; no GPU, no pruning):
+    `scene_arrays` is Scene.arrays(), `corners` (n, 9). Returns what Renderer.query_cuts returns for numpy inputs."""
+    c = _triangle_array(corners)
+    k = int(k)
+    batch = RtTriangleBatch(c.ctypes.data, c.shape[0])
+    res = (RtCut * max(c.shape[0] * k, 1))()
+    cnt = np.zeros(c.shape[0], np.uint32)
+    if _capi.lib().rt_cuts_exhaustive_host(C.byref(scene_arrays), C.byref(batch), k, C.addressof(res) if k else None, cnt.ctypes.data) != 0:
+        raise RtError("rt_cuts_exhaustive_host refused its arguments (k > 8, NULL arrays, n >= 2^30, or indices out of range)")
+    return _cut_rows(res, c.shape[0], k), cnt
+
+
+def chain_cuts(recs):
+    """Joins the cuts of ONE query (cuts_to_numpy records; those with found == 0 are left out) into polylines by end points that
+    are equal bit for bit, which is what the rule promises along the scene's edges. Returns (loops, chains): lists of lists of
+    record indices in walking order; a loop came back to where it started, a chain has two loose ends. A cut of length zero
+    is a chain of its own unless its point is an end of another cut, which it then hangs on. An end point shared by more than
+    two cuts (a scene corner in the query's plane) is joined pairwise in index order."""
+    r = np.asarray(recs)
+    idx = [int(i) for i in np.flatnonzero(r["found"] != 0)]
+    key = lambda i, end: np.ascontiguousarray(r[end][i]).view(np.uint32).tobytes()
+    ends = {}
+    for i in idx:
+        for end in ("a", "b"):
+            ends.setdefault(key(i, end), []).append((i, end))
+    link = {}   # (cut, end) -> (cut, end) across a shared point
+    for at in ends.values():
+        at = [e for e in at if not (key(e[0], "a") == key(e[0], "b") and e[1] == "b")]   # a point cut offers one end
+        for x, y in zip(at[0::2], at[1::2]):
+            if x[0] != y[0]:
+                link[x], link[y] = y, x
+    other = {"a": "b", "b": "a"}
+    seen, loops, chains = set(), [], []
+
+    def walk(i, end):
+        """from cut i, leaving through `end`: the cuts met, and whether the walk came back to i"""
+        path = []
+        while (i, end) in link:
+            i, arrive = link[(i, end)]
+            if i in seen:
+                return path, True
+            seen.add(i)
+            path.append(i)
+            end = other[arrive]
+        return path, False
+
+    for i in idx:
+        if i in seen:
+            continue
+        seen.add(i)
+        fwd, closed = walk(i, "b")
+        if closed:
+            loops.append([i] + fwd)
+            continue
+        back, _ = walk(i, "a")
+        chains.append(back[::-1] + [i] + fwd)
+    return loops, chains
 
 
 def mesh_corners(points, faces, matrix=None):
